@@ -16,10 +16,14 @@ barriers and reductions of the N > 1 path run on every bench.
 
 Prints ONE JSON line on rank 0 (contract in the task statement), with
   roofline      HBM view of the dominant kernel (algorithmic bytes / measured kernel time; the path is fp64-VALU / latency
-                bound, so `valu` carries the meaningful fraction) and
+                bound, so `valu` carries the meaningful fraction).
+A plain run sets up, warms up, times the --steps steps of the measured path and prints the line; nothing else.  `--full` adds
+every secondary measurement:
   cpu_baseline  the CPU restatement of the reference algorithm (oracle/, "port") timed on this box's host cores on a bounded
-                sample of the same workload (rank 0, N = 1 only).
-The KinoDyn legs inside the line carry their own `roofline` and `cpu_baseline` objects.
+                sample of the same workload (rank 0, N = 1 only),
+  the other batch sizes, horizons and precisions' checks, the batch-1 latencies, the KinoDyn legs (each with its own `roofline`
+  and `cpu_baseline`), per-kernel profile passes, and RCCL brought up at N = 1.
+`--dump-outputs DIR` writes what the timed path computed in its last step (dump_outputs).
 """
 import argparse
 import json
@@ -39,6 +43,7 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 FP64_VALU_PEAK_TF = 78.6    # MI355X vector fp64 peak (spec)
+DUMP_BYTES_MAX = 64_000_000  # --dump-outputs: all files together
 METRIC_SHAPE = {"solo12_trot": "Solo12 trot H=20", "solo12_mixed": "Solo12 mixed gaits (trot/bound/pace) H=20", "go2_bound": "Go2 bound H=40",
                 "solo12_trot_nominal": "Solo12 trot H=20 (nominal)"}
 
@@ -237,6 +242,24 @@ def ik_algorithmic_bytes(T, E=4):
     return 8 * (37 + 4 * E * T + 37 * (T + 1) + 18 * T)
 
 
+def dump_outputs(path, arrays, n_problems):
+    """--dump-outputs: the arrays the timed path's results() returned after its last step, one <path>/<name>.npy each, in float64
+    (integer and flag arrays convert exactly).  Arrays whose first axis has n_problems entries are per problem; when all files would
+    exceed DUMP_BYTES_MAX, the same fixed, seeded sample of problems is taken from each, its indices written as problem_index.npy."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    per_problem = [k for k, a in arrays.items() if a.ndim and a.shape[0] == n_problems]
+    budget = DUMP_BYTES_MAX - (1 << 20)        # room for the .npy headers and the arrays that are not per problem
+    if sum(a.nbytes for a in arrays.values()) > budget:
+        row = sum(arrays[k][0].nbytes for k in per_problem) + 8
+        idx = np.sort(np.random.default_rng(0).choice(n_problems, max(1, budget // row), replace=False))
+        arrays.update({k: arrays[k][idx] for k in per_problem})
+        arrays["problem_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(arrays)
+
+
 class Dist:
     """the rank bookkeeping every leg shares: barrier + synchronize brackets, MAX / SUM reductions of scalars"""
 
@@ -316,10 +339,11 @@ def summary(out):
     return s
 
 
-def kinodyn_leg(D, B, admm_iters, maxit, config="solo12_h20", steps=3, warmup=1, n_streams=3, cpu_sample=0):
+def kinodyn_leg(D, B, admm_iters, maxit, config="solo12_h20", steps=3, warmup=1, n_streams=3, cpu_sample=0, full=True, outputs=None):
     """The full KinoDynMP.optimize (centroidal ADMM + whole-body IK-DDP) over B perturbed whole-body states per GPU, device
     resident, rank r owning problems [r B, (r + 1) B).  solo12_h20: Solo12 trot, H = 20, H_ik = 10; go2_h60: BASELINE
-    config 5's shape (synthetic Go2, trot, H = 60, H_ik = 30)."""
+    config 5's shape (synthetic Go2, trot, H = 60, H_ik = 30).  full = False: the timed solves only (no IK-only timing, kernel
+    profile, multi-stream, device-built inputs or CPU passes).  outputs: a dict that receives results() of the last timed solve."""
     import dataclasses
     from bunmpc_amd import _lib, batch as bb, problems, urdf_model
     from bunmpc_amd.kinodyn_batch import KinoDynDeviceBatch
@@ -334,6 +358,29 @@ def kinodyn_leg(D, B, admm_iters, maxit, config="solo12_h20", steps=3, warmup=1,
         wb = problems.make_wb_batch(model, B, first=first)
     kb = KinoDynDeviceBatch(wb, model, device=dev, num_iters=admm_iters, maxit=maxit)
     dt = D.timed(kb.solve, steps, warmup) / steps
+    r = kb.results()
+    if outputs is not None:
+        outputs.update(r)
+    tele = D.reduce([r["ik_iters"].sum(), (r["ik_status"] != 0).sum(), (r["stats"][:, 5] != 0).sum()], "SUM")
+    it_max = D.reduce([r["ik_iters"].max()], "MAX")[0]
+    W = D.world
+    T, H = wb.ik_T, wb.dyn.H
+    abytes = (bb.algorithmic_bytes_per_solve(H, 4) + ik_algorithmic_bytes(T)) * B
+    wkey = "kinodyn %s H=%d H_ik=%d B=%d admm_iters=%d" % (config, H, T, B, admm_iters)
+    traffic, traffic_source = pmc_traffic(wkey)
+    out = {"value": W * B / dt, "unit": "KinoDynMP solves/s", "workload": "%s H=%d H_ik=%d B=%d/GPU" % (config, H, T, B),
+           "n_gpus": W, "batch": B, "global_batch": B * W, "ms_per_step": dt * 1e3, "steps": steps,
+           "ddp_iters_mean": tele[0] / (B * W), "ddp_iters_max": int(it_max), "ddp_not_converged": int(tele[1]),
+           "admm_diverged": int(tele[2]), "admm_iters_mean": float(r["stats"][:, 0].mean()), "admm_iters_cap": admm_iters,
+           "parity": "unpinned",
+           # HBM view of the whole solve (every kernel of one KinoDynMP.optimize batch): SURVEY 8d's per-solve bytes x B over the
+           # wall time of a solve; `dominant_kernel` the same bytes' IK share over that kernel's summed launches.  The path is
+           # latency / issue bound (EXPERIMENTS.md 9), so the fraction is tiny by construction.
+           "roofline": {"bound": "hbm", "achieved": abytes / dt / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": abytes / dt / 1e9 / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                        "scope": "all kernels of one batch solve", "algorithmic_bytes_per_solve_batch": abytes}}
+    if not full:
+        return out
     dt_ik = D.timed(kb.solve_ik_only, steps, 0) / steps
     # where the time of one batch solve goes: events around every kernel of the DDP loop (a separate, untimed pass)
     lib = _lib.lib()
@@ -344,9 +391,6 @@ def kinodyn_leg(D, B, admm_iters, maxit, config="solo12_h20", steps=3, warmup=1,
     prof = (5 * __import__("ctypes").c_double)()
     lib.bmpc_ik_last_profile(prof)
     kern = dict(zip(("ik_state_kernel", "ik_calcdiff_kernel", "ik_backward_kernel", "ik_forward_kernel", "other"), [float(v) for v in prof]))
-    r = kb.results()
-    tele = D.reduce([r["ik_iters"].sum(), (r["ik_status"] != 0).sum(), (r["stats"][:, 5] != 0).sum()], "SUM")
-    it_max = D.reduce([r["ik_iters"].max()], "MAX")[0]
     # n_streams batches in flight on as many HIP streams, one host thread each (bunmpc_amd/pipeline.py): the tail
     # iterations of one batch -- a few stragglers, most of the chip idle -- overlap the bulk phases of the others.
     # Whole-job throughput of a generator that keeps several batches going.
@@ -362,29 +406,13 @@ def kinodyn_leg(D, B, admm_iters, maxit, config="solo12_h20", steps=3, warmup=1,
         r2 = k.results()
         same = same and bool(np.array_equal(r2["xs"], r["xs"]) and np.array_equal(r2["ik_iters"], r["ik_iters"]))
     del kbs
-    W = D.world
-    T, H = wb.ik_T, wb.dyn.H
-    abytes = (bb.algorithmic_bytes_per_solve(H, 4) + ik_algorithmic_bytes(T)) * B
     dom = max(("ik_calcdiff_kernel", "ik_backward_kernel", "ik_forward_kernel"), key=lambda k: kern[k])
-    wkey = "kinodyn %s H=%d H_ik=%d B=%d admm_iters=%d" % (config, H, T, B, admm_iters)
-    traffic, traffic_source = pmc_traffic(wkey)
-    out = {"value": W * B / dt, "unit": "KinoDynMP solves/s", "workload": "%s H=%d H_ik=%d B=%d/GPU" % (config, H, T, B),
-           "n_gpus": W, "batch": B, "global_batch": B * W, "ms_per_step": dt * 1e3, "steps": steps,
-           "multi_stream": {"streams": n_streams, "value": W * n_streams * B / dt2, "unit": "KinoDynMP solves/s",
-                            "ms_per_round_of_batches": dt2 * 1e3, "results_equal_single_stream": same},
-           "ik_only_ms_per_step": dt_ik * 1e3, "ik_kernel_ms_per_solve": kern,
-           "ddp_iters_mean": tele[0] / (B * W), "ddp_iters_max": int(it_max), "ddp_not_converged": int(tele[1]),
-           "admm_diverged": int(tele[2]), "admm_iters_mean": float(r["stats"][:, 0].mean()), "admm_iters_cap": admm_iters,
-           "parity": "unpinned",
-           # HBM view of the whole solve (every kernel of one KinoDynMP.optimize batch): SURVEY 8d's per-solve bytes x B over the
-           # wall time of a solve; `dominant_kernel` the same bytes' IK share over that kernel's summed launches.  The path is
-           # latency / issue bound (EXPERIMENTS.md 9), so the fraction is tiny by construction.
-           "roofline": {"bound": "hbm", "achieved": abytes / dt / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": abytes / dt / 1e9 / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                        "scope": "all kernels of one batch solve", "algorithmic_bytes_per_solve_batch": abytes,
-                        "dominant_kernel": {"kernel": dom, "ms_per_solve_batch": kern[dom],
-                                            "achieved": ik_algorithmic_bytes(T) * B / (kern[dom] * 1e-3) / 1e9 if kern[dom] > 0 else None,
-                                            "algorithmic_bytes": ik_algorithmic_bytes(T) * B}}}
+    out["multi_stream"] = {"streams": n_streams, "value": W * n_streams * B / dt2, "unit": "KinoDynMP solves/s",
+                           "ms_per_round_of_batches": dt2 * 1e3, "results_equal_single_stream": same}
+    out["ik_only_ms_per_step"], out["ik_kernel_ms_per_solve"] = dt_ik * 1e3, kern
+    out["roofline"]["dominant_kernel"] = {"kernel": dom, "ms_per_solve_batch": kern[dom],
+                                          "achieved": ik_algorithmic_bytes(T) * B / (kern[dom] * 1e-3) / 1e9 if kern[dom] > 0 else None,
+                                          "algorithmic_bytes": ik_algorithmic_bytes(T) * B}
     # the inputs of the same batch built on the device from the raw states (bmpc_wb_plan_batch_device)
     if config == "solo12_h20":
         from bunmpc_amd import fk_np
@@ -512,7 +540,7 @@ def biconvex_leg(D, args):
                               "simd_busy_frac_pmc": pmc_valu_busy(wkey, wpe)}},
         "diverged": int(counts[0]), "fista_iters_per_solve": counts[1] / (B * W),
     }
-    return out, pb
+    return out, pb, res
 
 
 def other_batch_size_leg(D, args, B):
@@ -630,6 +658,11 @@ def main():
                     help="solo12_h20: Solo12 trot H=20 / H_ik=10; go2_h60: BASELINE config 5 (synthetic Go2, H=60 / H_ik=30)")
     ap.add_argument("--precision", default="f64", choices=["f64", "f32"],
                     help="f32: BASELINE config 3's mixed-precision kernel (fp32 iterates, fp64 decisions)")
+    ap.add_argument("--full", action="store_true",
+                    help="every secondary measurement as well: CPU baselines, other batch sizes / horizons, precision checks, batch-1 "
+                         "latencies, the KinoDyn legs, per-kernel profile passes, RCCL at N = 1 (the --no-* switches apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the timed path's results of its last step (rank 0's problems) as DIR/<name>.npy, float64")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -663,12 +696,12 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=dev)
         rccl = {"initialised": True, "backend": "gloo (one-device rehearsal)" if rehearsal else "nccl (RCCL)", "world": world}
-    else:
+    elif args.full:
         rccl = init_rccl_at_one(torch, dist, dev)
     if args.gpus != world and rank == 0:
         print("note: --gpus %d but WORLD_SIZE %d; using WORLD_SIZE" % (args.gpus, world), file=sys.stderr)
     D = Dist(torch, dist, dev, world, rank, rehearsal, group=dist.is_initialized())
-    cpu_ok = world == 1 and not args.no_cpu
+    cpu_ok = args.full and world == 1 and not args.no_cpu
     if cpu_ok:
         build_oracles()
     kd_batch = lambda cfg: args.kinodyn_batch or (1024 if cfg == "go2_h60" else 4096)      # noqa: E731
@@ -684,8 +717,9 @@ def main():
 
     if args.workload == "kinodyn":
         cfg = args.kinodyn_config
+        outputs = {}
         leg = kinodyn_leg(D, kd_batch(cfg), args.admm_iters, args.maxit, cfg, steps=args.steps, warmup=args.warmup,
-                          n_streams=args.kinodyn_streams, cpu_sample=kd_sample(cfg))
+                          n_streams=args.kinodyn_streams, cpu_sample=kd_sample(cfg), full=args.full, outputs=outputs)
         shape = "Go2 trot H=60 with full IK-DDP inner loop (H_ik=30)" if cfg == "go2_h60" else "Solo12 trot H=20 with full IK-DDP (H_ik=10)"
         out = {"metric": "KinoDynMP solves/sec (batch, whole node), %s, %d ADMM iters, fp64" % (shape, args.admm_iters),
                "value": leg["value"], "unit": "solves/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -698,8 +732,12 @@ def main():
             out["cpu_baseline"] = leg.pop("cpu_baseline")
             out["speedup_vs_cpu_all_cores"] = leg.pop("speedup_vs_cpu_all_cores", None)
         out["details"] = leg
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, outputs, kd_batch(cfg))
     else:
-        out, pb = biconvex_leg(D, args)
+        out, pb, outputs = biconvex_leg(D, args)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, outputs, args.batch)
         if cpu_ok:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.config, args.admm_iters, args.cpu_sample, args.maxit)
@@ -719,16 +757,16 @@ def main():
             for _ in range(3):
                 bb.solve_host(pb, num_iters=args.admm_iters, maxit=args.maxit, precision=args.precision)
             return 3 * pb.B / (time.perf_counter() - th)
-        if args.config == "solo12_trot" and args.precision == "f64":
+        if args.full and args.config == "solo12_trot" and args.precision == "f64":
             out["batch_6144"] = guarded(lambda: other_batch_size_leg(D, args, 6144))
             out["horizon_200"] = guarded(lambda: long_horizon_leg(D, args))
-        if world == 1 and not args.no_latency:
+        if args.full and world == 1 and not args.no_latency:
             lat = guarded(lambda: p50_latency(args.config, args.admm_iters))
             out["p50_latency_ms_batch1"] = lat.get("p50_ms", lat)
             out["latency_batch1"] = lat
             out["latency_kinodyn_dropin"] = guarded(kinodyn_latency)
             out["host_buffers_solves_per_s"] = guarded(host_leg)
-        if not args.no_kinodyn:
+        if args.full and not args.no_kinodyn:
             cfg = args.kinodyn_config
             out["kinodyn_full_solve"] = guarded(lambda: kinodyn_leg(D, kd_batch(cfg), args.admm_iters, args.maxit, cfg, steps=args.kinodyn_steps,
                                                                      n_streams=args.kinodyn_streams, cpu_sample=kd_sample(cfg)))

@@ -38,7 +38,8 @@ def _run_bench(extra, nproc=2):
 def test_two_rank_bench_shards_every_leg():
     from bunmpc_amd import batch as bb, problems
     B = 128
-    out = _run_bench(["--steps", "2", "--warmup", "1", "--batch", str(B), "--config", "solo12_mixed", "--kinodyn-batch", "32", "--kinodyn-steps", "1"])
+    out = _run_bench(["--full", "--steps", "2", "--warmup", "1", "--batch", str(B), "--config", "solo12_mixed", "--kinodyn-batch", "32",
+                      "--kinodyn-steps", "1"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
               "config", "roofline"):
         assert k in out, k
@@ -92,12 +93,12 @@ def test_bench_launches_its_own_ranks():
 
 
 def test_rccl_runs_at_world_size_one():
-    """A plain `python bench.py` (N = 1, no launcher) brings RCCL up with one rank on the real device and sends every leg's
+    """`python bench.py --full` (N = 1, no launcher) brings RCCL up with one rank on the real device and sends every leg's
     barrier and MAX / SUM reductions through it: the collectives of the N > 1 path have executed on this code."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "BUNMPC_BENCH_ONE_DEVICE"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "256", "--no-cpu",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--batch", "256", "--no-cpu",
                         "--no-latency", "--kinodyn-batch", "64", "--kinodyn-steps", "1", "--kinodyn-main-only"],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -108,10 +109,10 @@ def test_rccl_runs_at_world_size_one():
 
 
 def test_kinodyn_workload_line_single_rank():
-    """`--workload kinodyn`: the full KinoDynMP.optimize as the measured line, with its own roofline and cpu_baseline"""
+    """`--workload kinodyn --full`: the full KinoDynMP.optimize as the measured line, with its own roofline and cpu_baseline"""
     env = dict(os.environ)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "kinodyn", "--kinodyn-config", "go2_h60", "--kinodyn-batch", "48",
-                        "--steps", "1", "--warmup", "1"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        "--steps", "1", "--warmup", "1", "--full"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     assert "KinoDynMP" in out["metric"] and "H=60" in out["metric"] and out["dtype"] == "f64" and out["n_gpus"] == 1
@@ -121,3 +122,28 @@ def test_kinodyn_workload_line_single_rank():
     ks = out["details"]["ik_kernel_ms_per_solve"]
     assert all(ks[k] > 0 for k in ("ik_state_kernel", "ik_calcdiff_kernel", "ik_backward_kernel", "ik_forward_kernel"))
     assert np.isfinite(out["value"]) and out["value"] > 0
+
+
+def test_plain_run_times_the_headline_only_and_dumps_its_results(tmp_path):
+    """A plain run (no --full) prints the contract's fields and no secondary leg, with exactly --steps timed steps;
+    --dump-outputs writes the timed path's results of its last step: those of the same batch solved in this process."""
+    from bunmpc_amd import batch as bb, problems
+    B = 128
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", str(B),
+                        "--dump-outputs", str(tmp_path)], env=dict(os.environ), cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["higher_is_better"] is True and out["dtype"] == "f64" and out["unit"] == "solves/s" and "Solo12 trot" in out["metric"]
+    assert out["steps"] == 3 and abs(out["value"] - B * 3 / (out["ms_per_step"] * 3e-3)) <= 1e-6 * out["value"]
+    for k in ("cpu_baseline", "batch_6144", "horizon_200", "latency_batch1", "host_buffers_solves_per_s", "kinodyn_full_solve"):
+        assert k not in out, k
+    db = bb.DeviceBatch(problems.make_batch("solo12_trot", B), num_iters=10)
+    db.solve()
+    ref = db.results()
+    assert sorted(f[:-4] for f in os.listdir(tmp_path)) == sorted(ref)
+    for k, a in ref.items():
+        got = np.load(tmp_path / (k + ".npy"))
+        assert got.dtype == np.float64 and got.shape == a.shape, k
+        np.testing.assert_allclose(got, a, rtol=1e-12, atol=0, err_msg=k)

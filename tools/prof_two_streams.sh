@@ -1,11 +1,14 @@
 #!/bin/bash
-# kernel trace of the two-stream KinoDyn leg (do kernels of the two streams overlap?).  usage (GPU box): tools/prof_two_streams.sh <tag> [bench args]
+# kernel trace of the two-stream KinoDyn leg (do kernels of the two streams overlap?).  usage (GPU machine): [OUT=<dir>] tools/prof_two_streams.sh <tag> [bench args]
 tag=$1; shift
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --output-format csv -d gpurun_out/prof_$tag -o run -- python bench.py --steps 2 --warmup 1 --no-cpu --no-latency "$@" > gpurun_out/prof_$tag.log 2>&1
+cd "$(dirname "$0")/.."
+OUT=${OUT:-prof_out}
+mkdir -p $OUT
+export TMPDIR=/tmp
+rocprofv3 --kernel-trace --output-format csv -d $OUT/prof_$tag -o run -- python bench.py --full --steps 2 --warmup 1 --no-cpu --no-latency "$@" > $OUT/prof_$tag.log 2>&1
 python - <<PY
 import csv, glob, collections
-f = glob.glob("gpurun_out/prof_$tag/**/*kernel_trace.csv", recursive=True)[0]
+f = glob.glob("$OUT/prof_$tag/**/*kernel_trace.csv", recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
 print(rows[0].keys())
 q = collections.Counter(r["Queue_Id"] for r in rows)
