@@ -45,27 +45,8 @@ namespace {
 
 #include "biconvex_admm_body.h"
 
-// fp64, WPE = 1: ONE wave per SIMD.  The body holds 294 registers; capped at 256 with the FISTA iterates in registers the compiler parks
-// 63 of them in scratch memory, some inside the loops (round 2 measured that build 4 % faster at 14 x the HBM traffic, round 3 level).
-// WPE = 2 (round 4): two waves per SIMD with x_k and its image in LDS (biconvex_admm_body.h: XLDS) -- both FISTA loops free of
-// scratch accesses at 256 registers, the two waves of a SIMD covering each other's latencies.  A lone wave of this build is slower
-// than a lone wave of the other (2.30 against 1.94 ms: the LDS round trip sits on its chain), so it is taken where the batch
-// needs more waves than the chip has SIMDs and three problems per wave do not save a round (launch_biconvex_admm below):
-// B = 4096, H = 20: 3.74 against 4.02 ms.
-template <typename R, int LPP, int E, bool RAW, bool HASQF, int WPE>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void biconvex_admm_kernel(const BatchArgs a) {
-    admm_body<R, LPP, E, RAW, HASQF, false, WPE == 2>(a);
-}
-// horizons of 64 .. 255 knots: one problem per workgroup of WAVES waves (biconvex_admm_body.h: WAVES)
-template <int WAVES, bool RAW, bool HASQF, int WPE>
-__global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void biconvex_admm_wg_kernel(const BatchArgs a) {
-    admm_body<double, 64, 4, RAW, HASQF, false, WPE == 2, WAVES>(a);
-}
-// the work-stealing variant (biconvex_admm_body.h: STEAL): three problems per wave, harness form, fp64
-template <int WPE>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void biconvex_admm_steal_kernel(const BatchArgs a) {
-    admm_body<double, 21, 4, false, false, true, WPE == 2>(a);
-}
+#include "biconvex_admm_inst.h"
+
 __global__ __launch_bounds__(64) void lane_selftest_kernel(const double *in, double *out) {
     const int i = threadIdx.x;
     const double v = in[i];
@@ -83,35 +64,6 @@ __global__ __launch_bounds__(64) void lane_selftest_kernel(const double *in, dou
     out[576 + i] = (double)seg_uniform<21>(__ballot(v > 40.0) & seg_desig<21>());                  // the spread masks, as a number (< 2^63: exact up to 2^53 -- compared by bits on the host through two halves)
     out[640 + i] = (double)(unsigned)(seg_uniform<21>(__ballot(i == 16 || i == 48)) >> 32);
     out[704 + i] = (double)(unsigned)(seg_uniform<21>(__ballot(i == 16 || i == 48)) & 0xffffffffu);
-}
-
-template <typename R, int LPP, bool RAW, bool HASQF>
-hipError_t launch(const BatchArgs &a, bool two_per_simd, hipStream_t stream) {
-    const int per_wave = 64 / LPP;
-    const unsigned grid = (unsigned)((a.B + per_wave - 1) / per_wave);
-    const size_t nstate = (size_t)kSegLds + (size_t)kKnotLds * (size_t)(a.H + 1);   // X, P, F, R of one problem
-    const size_t lds = sizeof(R) * (kLdsZeros + per_wave * nstate);
-    if (sizeof(R) == sizeof(float)) return launch_biconvex_admm_f32(a, LPP, grid, lds, stream);      // biconvex_admm_f32.hip
-    if (two_per_simd) hipLaunchKernelGGL((biconvex_admm_kernel<double, LPP, 4, RAW, HASQF, 2>), dim3(grid), dim3(64), lds, stream, a);
-    else hipLaunchKernelGGL((biconvex_admm_kernel<double, LPP, 4, RAW, HASQF, 1>), dim3(grid), dim3(64), lds, stream, a);
-    return hipGetLastError();
-}
-
-template <int WAVES, bool RAW, bool HASQF, int WPE>
-hipError_t launch_wg(const BatchArgs &a, hipStream_t stream) {
-    const size_t lds = sizeof(double) * (kLdsZeros + (size_t)kSegLds + (size_t)kKnotLds * (size_t)(a.H + 1) + (size_t)WAVES * 40);
-    static std::once_flag once;      // (more than the 64 KB a kernel may take without asking, from 209 knots on)
-    static hipError_t attr = hipSuccess;
-    std::call_once(once, [] { attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&biconvex_admm_wg_kernel<WAVES, RAW, HASQF, WPE>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); });
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((biconvex_admm_wg_kernel<WAVES, RAW, HASQF, WPE>), dim3((unsigned)a.B), dim3(64 * WAVES), lds, stream, a);
-    return hipGetLastError();
-}
-template <int WAVES, int WPE>
-hipError_t launch_wg_form(const BatchArgs &a, hipStream_t stream) {
-    if (a.precision != 0) return hipErrorInvalidValue;      // (fp64 only)
-    if (!a.raw) return launch_wg<WAVES, false, false, WPE>(a, stream);
-    return a.qf ? launch_wg<WAVES, true, true, WPE>(a, stream) : launch_wg<WAVES, true, false, WPE>(a, stream);
 }
 
 // FISTA's momentum coefficients: t+ = 1 + sqrt(1 + 4 t^2)/2 (sic, fista.cpp:34), c_k = (t_k - 1)/t_{k+1} -- a function of k alone, so
@@ -155,31 +107,12 @@ int *steal_counter(hipStream_t stream) {
     if (hipMemsetAsync(c, 0, sizeof(int), stream) != hipSuccess) return nullptr;
     return c;
 }
-// the persistent grid of the work-stealing kernel: as many waves as the chip holds at once (one or two per SIMD)
-int g_steal_grid = 0;      // waves of the persistent grid (experiments, set_steal_grid below): 0 = one or two per SIMD
-hipError_t launch_steal(const BatchArgs &a, long simds, bool two_per_simd, hipStream_t stream) {
-    BatchArgs s = a;
-    s.queue = steal_counter(stream);
-    if (!s.queue) return hipErrorOutOfMemory;
-    const size_t nstate = (size_t)kSegLds + (size_t)kKnotLds * (size_t)(a.H + 1);
-    const size_t lds = sizeof(double) * (kLdsZeros + 3 * nstate);
-    const long waves = g_steal_grid > 0 ? std::min<long>(g_steal_grid, (a.B + 2) / 3) : (two_per_simd ? 2 * simds : simds);
-    if (two_per_simd) hipLaunchKernelGGL(biconvex_admm_steal_kernel<2>, dim3((unsigned)waves), dim3(64), lds, stream, s);
-    else hipLaunchKernelGGL(biconvex_admm_steal_kernel<1>, dim3((unsigned)waves), dim3(64), lds, stream, s);
-    return hipGetLastError();
-}
-
-template <int LPP>
-hipError_t launch_lpp(const BatchArgs &a, bool two_per_simd, hipStream_t stream) {
-    if (a.precision == 1) {   // fp32 arithmetic: harness form only
-        if (a.raw || LPP == 21) return hipErrorInvalidValue;
-        return launch<float, LPP == 21 ? 32 : LPP, false, false>(a, false, stream);
-    }
-    if (!a.raw) return launch<double, LPP, false, false>(a, two_per_simd, stream);
-    return a.qf ? launch<double, LPP, true, true>(a, two_per_simd, stream) : launch<double, LPP, true, false>(a, two_per_simd, stream);
-}
+int g_steal_grid = 0;      // waves of the work-stealing kernel's persistent grid (experiments, set_steal_grid below): 0 = one or two per SIMD
 
 }  // namespace
+
+hipError_t launch_admm_e4(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream) { return launch_admm<4>(a, l, stream); }
+int admm_scratch_bytes_e4() { return admm_scratch_bytes<4>(); }
 
 // Horizons of 17..21 knots: 0 = 32-lane segments (two problems per wave), 1 = 21-lane segments (three per wave), 2 (default) = whichever
 // finishes the batch sooner.  The kernel runs one wave per SIMD; a wave of three problems takes ~8 % longer than a wave of two
@@ -231,7 +164,7 @@ const char *biconvex_last_kernel_name() { return t_last_kernel; }
 
 hipError_t launch_biconvex_admm(const BatchArgs &args, int n_eff, hipStream_t stream) {
     BatchArgs a = args;
-    if (n_eff != 4 || a.H < 1 || a.H + 1 > kMaxKnots || a.B < 0 || (a.precision != 0 && a.precision != 1))
+    if ((n_eff != 2 && n_eff != 4) || a.H < 1 || a.H + 1 > kMaxKnots || a.B < 0 || (a.precision != 0 && a.precision != 1))
         return hipErrorInvalidValue;
     if (a.B == 0) return hipSuccess;
     if (a.c.maxit > kMaxFistaIters) return hipErrorInvalidValue;
@@ -244,51 +177,51 @@ hipError_t launch_biconvex_admm(const BatchArgs &args, int n_eff, hipStream_t st
         t_last_lpp = 0;
         BatchArgs al = a;
         al.exact_step_decisions = g_exact_step_decisions;
-        return launch_biconvex_latency(al, stream);
+        return launch_biconvex_latency(al, n_eff, stream);
     }
     a.cmtab = momentum_table(stream);
     if (!a.cmtab) return hipErrorOutOfMemory;
+    // the same decisions for two feet as for four, with the LDS record of the foot count (knot_lds)
+    auto go = [&](const AdmmLaunch &l) {
+        t_last_lpp = l.lpp;
+        t_last_wpe = l.w2 ? 2 : 1;
+        return n_eff == 4 ? launch_admm_e4(a, l, stream) : launch_admm_e2(a, l, stream);
+    };
     const int k = a.H + 1;
     t_last_kernel = a.precision == 1 ? "biconvex_admm_kernel_f32" : "biconvex_admm_kernel";
     t_last_wpe = 1;
-    if (k <= 16) { t_last_lpp = 16; const bool w2 = two_per_simd_pays(a, 4); t_last_wpe = w2 ? 2 : 1; return launch_lpp<16>(a, w2, stream); }
+    if (k <= 16) return go({16, two_per_simd_pays(a, 4), false, 0});
     // 17..21 knots (the headline shape): three problems per wave in 21-lane segments (fp64; the fp32 kernels keep 32-lane segments)
     if (k <= 21 && k > 16 && a.precision == 0 && three_per_wave_pays(a)) {
-        t_last_lpp = 21;
         // many ADMM iterations (the early exit makes the counts differ per problem) and more waves than the chip holds: segments that
-        // finish take the next problem (biconvex_admm_body.h: STEAL); the 32-bit offsets from the problem index must fit
-        const long S = chip_simds(), per = std::max<long>({(long)a.H * 128, 9L * (a.H + 1) * 8, a.sW_X * 8, a.sW_F * 8, a.sbounds * 8, (long)a.c.num_iters * 16});
+        // finish take the next problem (biconvex_admm_body.h: STEAL); the 32-bit offsets from the problem index must fit (the contact
+        // plan: 32 E H bytes per problem)
+        const long S = chip_simds(), per = std::max<long>({32L * n_eff * a.H, 9L * (a.H + 1) * 8, a.sW_X * 8, a.sW_F * 8, a.sbounds * 8, (long)a.c.num_iters * 16});
         if (g_work_stealing && !a.raw && a.c.num_iters >= 25 && (a.B + 2) / 3 > S && (double)a.B * (double)per < 2.0e9) {
             t_last_kernel = "biconvex_admm_steal_kernel";
             // (one wave per SIMD unless forced: measured at B = 4096, num_iters = 100: 30.7 ms; the two-waves build with grids of
             // 1024 .. 2048 waves 34.2 .. 37.3 ms -- the stealing itself already fills the gaps the second wave would)
             const bool w2 = g_two_per_simd == 1;
-            t_last_wpe = w2 ? 2 : 1;
-            return launch_steal(a, S, w2, stream);
+            // the persistent grid: as many waves as the chip holds at once (one or two per SIMD)
+            const long waves = g_steal_grid > 0 ? std::min<long>(g_steal_grid, (a.B + 2) / 3) : (w2 ? 2 * S : S);
+            a.queue = steal_counter(stream);
+            if (!a.queue) return hipErrorOutOfMemory;
+            return go({21, w2, true, waves});
         }
-        const bool w2 = two_per_simd_pays(a, 3);
-        t_last_wpe = w2 ? 2 : 1;
-        return launch_lpp<21>(a, w2, stream);
+        return go({21, two_per_simd_pays(a, 3), false, 0});
     }
     if (k > 64) {      // 65 .. 256 knots: a workgroup of two, three or four waves per problem
         t_last_kernel = "biconvex_admm_wg_kernel";
-        t_last_lpp = k <= 128 ? 128 : (k <= 192 ? 192 : 256);
+        const int lpp = k <= 128 ? 128 : (k <= 192 ? 192 : 256);
         // the two-waves-per-SIMD build when there are more waves than SIMDs -- and, for two waves per problem, when four such workgroups'
         // LDS fits a CU (at 127 knots only three do: 9.2 ms against 6.9 at B = 1024); four waves per problem: always (11.4-12.6 ms
         // against 15.9-16.8: tools/horizon_sweep.py)
-        const size_t lds_bytes = sizeof(double) * (kLdsZeros + (size_t)kSegLds + (size_t)kKnotLds * (size_t)k + (size_t)(t_last_lpp / 64) * 40);
+        const size_t lds_bytes = sizeof(double) * (kLdsZeros + (size_t)kSegLds + (size_t)knot_lds(n_eff) * (size_t)k + (size_t)(lpp / 64) * 40);
         const bool fits = k > 128 || 4 * lds_bytes <= 160 * 1024;
-        const bool w2 = g_two_per_simd == 1 || (g_two_per_simd == 2 && fits && (long)a.B * (t_last_lpp / 64) > chip_simds());
-        t_last_wpe = w2 ? 2 : 1;
-        if (k <= 128) return w2 ? launch_wg_form<2, 2>(a, stream) : launch_wg_form<2, 1>(a, stream);
-        if (k <= 192) return w2 ? launch_wg_form<3, 2>(a, stream) : launch_wg_form<3, 1>(a, stream);
-        return w2 ? launch_wg_form<4, 2>(a, stream) : launch_wg_form<4, 1>(a, stream);
+        return go({lpp, g_two_per_simd == 1 || (g_two_per_simd == 2 && fits && (long)a.B * (lpp / 64) > chip_simds()), false, 0});
     }
-    t_last_lpp = k <= 32 ? 32 : 64;
-    const bool w2 = two_per_simd_pays(a, 64 / t_last_lpp);
-    t_last_wpe = w2 ? 2 : 1;
-    if (k <= 32) return launch_lpp<32>(a, w2, stream);
-    return launch_lpp<64>(a, w2, stream);
+    const int lpp = k <= 32 ? 32 : 64;
+    return go({lpp, two_per_simd_pays(a, 64 / lpp), false, 0});
 }
 
 hipError_t launch_lane_selftest(const double *in, double *out, hipStream_t stream) {

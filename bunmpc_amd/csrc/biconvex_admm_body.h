@@ -68,19 +68,21 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
     // only its own knot's blocks (lane 0 also the x_init rows of P): HBM sees the inputs once and the
     // results once.
     // Layout: kLdsZeros zeros, then per segment the x_init rows' multipliers (kSegLds elements; lane 0 works on them) and one record
-    // per KNOT, [X 9 | P 9 | F NF | R 9] (kKnotLds = 39 elements: an odd stride, no two lanes of a segment share a bank).  Every block
+    // per KNOT, [X 9 | P 9 | F NF | R 9] (KL = knot_lds(E) = 39 elements for four feet, 33 for two: an odd stride, no two lanes of a
+    // segment share a bank; the header below -- 12 doubles and 6 ints of lane 0 -- stays kSegLds long whatever E is).  Every block
     // of a lane -- lane 0's x_init block included -- is ONE address (the record's, less kSegLds elements) plus a constant, which the
     // LDS instructions carry as their immediate offset: one address register per lane instead of one per block (with separate
     // arrays per block the two-waves build kept reloading five of them from scratch memory).  R: the affine image of the FISTA
     // loops' x_k (XLDS).
-    static_assert(9 + 9 + NF + 9 == kKnotLds && kSegLds + kKnotLds <= kLdsZeros && kSegLds >= 9, "one LDS record per knot");
+    constexpr int KL = knot_lds(E);
+    static_assert(9 + 9 + NF + 9 == KL && KL % 2 == 1 && kSegLds + KL <= kLdsZeros && kSegLds >= 9 && 12 + 6 / 2 <= kSegLds, "one LDS record per knot");
     R *zeros = reinterpret_cast<R *>(lds_raw);      // what a lane without a knot reads for x_k (XLDS)
-    R *Sg = zeros + kLdsZeros + (long)seg * (kSegLds + (long)(H + 1) * kKnotLds) + (long)t * kKnotLds;
+    R *Sg = zeros + kLdsZeros + (long)seg * (kSegLds + (long)(H + 1) * KL) + (long)t * KL;
     R *PIg = Sg, *Xg = Sg + kSegLds, *Pg = Xg + 9, *Fg = Xg + 18, *Rg = Xg + 18 + NF;      // (PIg: lane 0's only)
     const R *Szr = rvalid ? Sg : zeros, *Szk = kvalid ? Sg : zeros;
     const R *Fz = Szr + kSegLds + 18, *RFz = Szr + kSegLds + 18 + NF, *Xz = Szk + kSegLds, *RXz = Szk + kSegLds + 18 + NF;
     // knot t <-> t +- 1 and the sums over a problem's knots: within the wave by DPP, across a workgroup's waves (MW) through LDS
-    double *const xch = reinterpret_cast<double *>(zeros) + kLdsZeros + kSegLds + (long)(H + 1) * kKnotLds;      // MW: [2][WAVES][9] next, [2][WAVES][9] previous, [2][WAVES][2] sums
+    double *const xch = reinterpret_cast<double *>(zeros) + kLdsZeros + kSegLds + (long)(H + 1) * KL;      // MW: [2][WAVES][9] next, [2][WAVES][9] previous, [2][WAVES][2] sums
     int par_n = 0, par_p = 0, par_s = 0;
     auto shift_next = [&](const auto &v, auto &o) {      // o = v of knot t + 1 (0 behind the last lane)
         constexpr int N = (int)(sizeof(v) / sizeof(v[0]));
@@ -165,7 +167,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
     // the ADMM loop it was itself kept in scratch memory)
     auto header = [&]() {
         const int sg = (int)(opaque_copy((unsigned)lane) / (unsigned)LPP);
-        return reinterpret_cast<double *>(zeros) + kLdsZeros + (long)(sg < 64 / LPP ? sg : 0) * (kSegLds + (long)(H + 1) * kKnotLds);
+        return reinterpret_cast<double *>(zeros) + kLdsZeros + (long)(sg < 64 / LPP ? sg : 0) * (kSegLds + (long)(H + 1) * KL);
     };
     auto lds_fence = [&]() { asm volatile("" ::: "memory"); };       // (the compiler may not carry a parked value past this in a register)
     auto park_x = [&]() {      // before the force loop: everything the motion step and the end of the ADMM iteration work on

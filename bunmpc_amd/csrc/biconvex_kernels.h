@@ -53,20 +53,35 @@ struct BatchArgs {
 };
 
 constexpr int kStats = 6;
-constexpr int kKnotLds = 39;           // LDS elements per knot of a problem (biconvex_admm_body.h: X 9, P 9, F 12, R 9)
+// LDS elements per knot of a problem (biconvex_admm_body.h: X 9, P 9, F 3E, R 9): 39 for four feet, 33 for two -- odd strides, so no
+// two lanes of a segment share a bank (an odd E would make it even: only E = 2 and 4 are built)
+constexpr int knot_lds(int E) { return 27 + 3 * E; }
 constexpr int kSegLds = 15;            // ... and per problem in front of its knots (the x_init rows' multipliers, 9; XLDS: step constants, violation, counters)
 constexpr int kLdsZeros = 54;          // zeros in LDS in front of all that (lanes without a knot read them)
 constexpr int kMaxFistaIters = 4096;  // length of the momentum table (one per device, momentum_table below; the one-problem-per-wave kernel keeps its own in LDS: 32 KB + <= 30 KB of iterates < 64 KB)
 constexpr int kMaxKnots = 256; // H + 1 <= 256: one knot per lane, one problem per <= 64 lanes of a wave, or (65 .. 256 knots) per workgroup of 2 / 4 waves
 
 // Launch the batched ADMM kernel on `stream`.  Returns hipSuccess or the launch error;
-// hipErrorInvalidValue for unsupported shapes (n_eff != 4, H + 1 > 64).
+// hipErrorInvalidValue for unsupported shapes (n_eff not 2 or 4, H + 1 > 256).
 hipError_t launch_biconvex_admm(const BatchArgs &a, int n_eff, hipStream_t stream);
 
-// The one-problem-per-wave mapping (biconvex_latency.hip): fp64, n_eff = 4, H + 1 <= 21.  launch_biconvex_admm takes it for
+// The kernel launch_biconvex_admm chose for a batch (it sets a.cmtab and, for the work-stealing kernel, a.queue first)
+struct AdmmLaunch {
+    int lpp;             // lanes per problem 16 / 21 / 32 / 64, or 128 / 192 / 256: one problem per workgroup of 2 / 3 / 4 waves
+    bool w2;             // the two-waves-per-SIMD build
+    bool steal;          // the work-stealing kernel (lpp 21, harness form, fp64)
+    long steal_waves;    // ... its persistent grid
+};
+// ... launched by the instantiations of one foot count: biconvex_admm.hip (E = 4), biconvex_admm_e2.hip (E = 2)
+hipError_t launch_admm_e4(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream);
+hipError_t launch_admm_e2(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream);
+int admm_scratch_bytes_e4();      // largest private-segment bytes per lane over the fp64 batch, workgroup and work-stealing kernels, -1 on error
+int admm_scratch_bytes_e2();
+
+// The one-problem-per-wave mapping (biconvex_latency.hip): fp64, n_eff = 2 or 4, H + 1 <= 21.  launch_biconvex_admm takes it for
 // batches of at most latency_mapping_max_batch() problems that fit.
 bool latency_mapping_fits(const BatchArgs &a, int n_eff);
-hipError_t launch_biconvex_latency(const BatchArgs &a, hipStream_t stream);
+hipError_t launch_biconvex_latency(const BatchArgs &a, int n_eff, hipStream_t stream);
 int set_latency_mapping_max_batch(int max_batch);   // returns the old value
 int set_three_per_wave(int mode);                    // 21-lane segments for 17..21 knots: 0 never, 1 always, 2 when it pays (default); returns the old value
 int set_two_waves_per_simd(int mode);               // the two-waves-per-SIMD build of the fp64 batch kernel: 0 never, 1 always, 2 when it pays (default); returns the old value
@@ -76,11 +91,13 @@ int set_work_stealing(int on);                       // the segment-level work-s
 int biconvex_last_lanes_per_problem();               // of the calling host thread's latest launch: 16 / 21 / 32 / 64, 0 = one problem per wave
 int set_exact_step_decisions(int on);                // ... takes every step decision from the fp64 sums; returns the old value
 
-// fp32 instantiations (biconvex_admm_f32.hip); called by launch_biconvex_admm with the lanes per problem (16 / 32 / 64), the grid
-// and the LDS bytes it has worked out
+// fp32 instantiations (biconvex_admm_f32.hip: E = 4, biconvex_admm_f32_e2.hip: E = 2); called by launch_biconvex_admm with the
+// lanes per problem (16 / 32 / 64), the grid and the LDS bytes it has worked out
 hipError_t launch_biconvex_admm_f32(const BatchArgs &a, int lpp, unsigned grid, size_t lds, hipStream_t stream);
+hipError_t launch_biconvex_admm_f32_e2(const BatchArgs &a, int lpp, unsigned grid, size_t lds, hipStream_t stream);
 
 int biconvex_admm_f32_scratch_bytes();    // private-segment bytes per lane of the fp32 kernels (hipFuncGetAttributes), -1 on error
+int biconvex_admm_f32_e2_scratch_bytes();
 
 // Lane-exchange self test (DPP shifts and segment sums used by the kernel).
 // out must hold 12*64 doubles.

@@ -2,9 +2,9 @@
 // time of a solve is the length of its dependent instruction chain and not the number of problems in flight.  Same
 // algorithm, same algebra and the same reference lines as biconvex_admm.hip (see the header there); what differs is how
 // one problem is spread over the 64 lanes:
-//   * force step   lane = 32 h + t : knot t (t < H <= 20), feet 2h and 2h + 1.  The 6 x 12 block of A_x of a knot is the sum
-//                  of the two halves' 6 x 6 blocks: v_permlane32_swap adds them, after which both lanes of a knot hold the
-//                  same six residual rows.
+//   * force step   lane = 32 h + t : knot t (t < H <= 20), feet E/2 h .. E/2 h + E/2 - 1 (four feet: 2h, 2h + 1; two feet: h).
+//                  The 6 x 3E block of A_x of a knot is the sum of the two halves' 6 x 3E/2 blocks: v_permlane32_swap adds
+//                  them, after which both lanes of a knot hold the same six residual rows.
 //   * motion step  lane = 21 g + t : knot t (t <= H), component group g = CoM / velocity / angular momentum (three of the
 //                  nine components each; lane 63 idles).  Knot t +- 1 of the same group sits in the neighbouring lane (DPP
 //                  wave shifts, as in the batch kernel; the lane before a group's first knot is the previous group's knot 20,
@@ -13,7 +13,7 @@
 //                  and their transposes -- fetch three doubles from one other lane through ds_bpermute and enter as a
 //                  per-lane 3 x 3 pattern a f_k + b f_{k+1} + c f_{k+2} whose coefficients are zero where a group has no
 //                  such term.
-// A wave therefore executes 6 of the 12 force components and 3 of the 9 state components per instruction stream instead of
+// A wave therefore executes 3E/2 of the 3E force components and 3 of the 9 state components per instruction stream instead of
 // all of them: ~2.3x fewer vector instructions per FISTA iteration than one knot per lane, at 40 / 63 busy lanes.  With one
 // problem per wave every decision is wave-uniform (scalar branches, no lane masks), the iterates of the problem rest in LDS
 // between phases, and nothing crosses waves.
@@ -35,13 +35,15 @@ __device__ __forceinline__ double bperm(double v, int src_lane_bytes) {
     return __hiloint2double(hi, lo);
 }
 
-template <bool RAW, bool HASQF>
+template <int E, bool RAW, bool HASQF>
 __global__ __launch_bounds__(64) void biconvex_latency_kernel(const BatchArgs a) {
+    static_assert(E == 2 || E == 4, "E / 2 feet per half-wave");
+    constexpr int NH = E / 2, NL = 3 * NH;      // feet and force components per lane (force step)
     extern __shared__ double lds_raw[];
     const int lane = threadIdx.x;
     const int H = a.H, maxit = a.c.maxit;
     const long pb = blockIdx.x;
-    const long nx = 9L * (H + 1), nf = 12L * H;
+    const long nx = 9L * (H + 1), nf = 3L * E * H;
     double *cmtab = lds_raw;                                   // [maxit]
     double *Xs = cmtab + ((maxit + 1) & ~1), *Ps = Xs + nx, *Fs = Ps + nx;     // iterates of the problem between phases
     const double m = a.c.m, rho = a.c.rho, mu = a.c.mu, beta = a.c.beta, tol = a.c.tol, exit_tol = a.c.exit_tol;
@@ -80,16 +82,16 @@ __global__ __launch_bounds__(64) void biconvex_latency_kernel(const BatchArgs a)
     for (int it = 0; it < a.c.num_iters && alive; ++it) {
         // =================================================================== F step: lane = (half fh, knot ft)
         {
-            const double *cg = a.cnt_plan + ((pb * H + (fvalid ? ft : 0)) * 4 + 2 * fh) * 4;     // feet 2 fh, 2 fh + 1 of the knot
+            const double *cg = a.cnt_plan + ((pb * H + (fvalid ? ft : 0)) * E + NH * fh) * 4;     // feet NH fh .. NH fh + NH - 1 of the knot
             const double dt = fvalid ? a.dt[pb * H + ft] : 0.0;
-            double an[2], sp[2][3], wf[6], qf[HASQF ? 6 : 1];
-            UNROLL for (int n = 0; n < 2; ++n) {
+            double an[NH], sp[NH][3], wf[NL], qf[HASQF ? NL : 1];
+            UNROLL for (int n = 0; n < NH; ++n) {
                 const double c = fvalid ? cg[4 * n] : 0.0;
                 an[n] = c * (dt / m);
                 UNROLL for (int k = 0; k < 3; ++k) sp[n][k] = fvalid ? c * (Xs[9 * ft + k] - cg[4 * n + 1 + k]) * dt : 0.0;
             }
-            const long fo = 12L * ft + 6 * fh;
-            UNROLL for (int j = 0; j < 6; ++j) {
+            const long fo = 3L * E * ft + NL * fh;
+            UNROLL for (int j = 0; j < NL; ++j) {
                 wf[j] = fvalid ? (RAW ? a.Qf[pb * nf + fo + j] : a.W_F[pb * a.sW_F + fo + j]) : 0.0;
                 if (HASQF) qf[j] = fvalid ? 0.5 * a.qf[pb * nf + fo + j] : 0.0;
             }
@@ -100,10 +102,10 @@ __global__ __launch_bounds__(64) void biconvex_latency_kernel(const BatchArgs a)
                 if (k == 2) bx += kGravity * dt;
                 bpk[k] = fvalid ? (-bx + Ps[9 * ft + 3 + k]) : 0.0;
             }
-            // u = A v + bPk on rows 9t+3..8: this half's two feet, then the other half's share
-            auto applyA = [&](const double (&v)[6], double (&u)[6]) {
+            // u = A v + bPk on rows 9t+3..8: this half's feet, then the other half's share
+            auto applyA = [&](const double (&v)[NL], double (&u)[6]) {
                 double s[6] = {0, 0, 0, 0, 0, 0};
-                UNROLL for (int n = 0; n < 2; ++n) {
+                UNROLL for (int n = 0; n < NH; ++n) {
                     const double vx = v[3 * n], vy = v[3 * n + 1], vz = v[3 * n + 2];
                     s[0] += an[n] * vx; s[1] += an[n] * vy; s[2] += an[n] * vz;
                     s[3] += sp[n][2] * vy - sp[n][1] * vz;
@@ -112,23 +114,25 @@ __global__ __launch_bounds__(64) void biconvex_latency_kernel(const BatchArgs a)
                 }
                 UNROLL for (int k = 0; k < 6; ++k) u[k] = swap32_sum(s[k]) + bpk[k];
             };
-            double xa[6], xb[6], y[6], ra[6], rb[6], ry[6];
-            UNROLL for (int j = 0; j < 6; ++j) { xa[j] = fvalid ? Fs[fo + j] : 0.0; y[j] = xa[j]; }
+            double xa[NL], xb[NL], y[NL], ra[6], rb[6], ry[6];
+            UNROLL for (int j = 0; j < NL; ++j) { xa[j] = fvalid ? Fs[fo + j] : 0.0; y[j] = xa[j]; }
             applyA(y, ry);
             UNROLL for (int k = 0; k < 6; ++k) ra[k] = ry[k];
             const double mu2 = mu * mu, imu = 1.0 / (mu * mu + 1.0);
-            // the fp32 shortcut of the step decisions (banded_decisions) presumes sums of non-negative terms
-            const bool banded_f = !a.exact_step_decisions && rho >= 0.0 && !__any(wf[0] < 0 || wf[1] < 0 || wf[2] < 0 || wf[3] < 0 || wf[4] < 0 || wf[5] < 0);
+            // the fp32 shortcut of the step decisions (banded_decisions) presumes sums of non-negative terms (every weight of the lane)
+            bool wneg = false;
+            UNROLL for (int j = 0; j < NL; ++j) wneg = wneg || wf[j] < 0;
+            const bool banded_f = !a.exact_step_decisions && rho >= 0.0 && !__any(wneg);
             double invL = 2.0 * (1.0 / L_f);      // the gradient is carried as half of itself (biconvex_admm.hip)
             const double e2w = fh == 0 ? rho : 0.0;   // the residual rows are held twice: counted once
             bool act = true;
-            auto iterate = [&](const double (&xo)[6], const double (&ro)[6], double (&xn)[6], double (&rn)[6], int i) {
+            auto iterate = [&](const double (&xo)[NL], const double (&ro)[6], double (&xn)[NL], double (&rn)[6], int i) {
                 const double cm = cmtab[i];
                 bool done;
                 for (;;) {      // backtracking (fista.cpp:8-26)
-                    double fr[6];
+                    double fr[NL];
                     bool cone_any = false;
-                    UNROLL for (int n = 0; n < 2; ++n) {
+                    UNROLL for (int n = 0; n < NH; ++n) {
                         const double zx = an[n] * ry[0] - sp[n][2] * ry[4] + sp[n][1] * ry[5];
                         const double zy = an[n] * ry[1] + sp[n][2] * ry[3] - sp[n][0] * ry[5];
                         const double zz = an[n] * ry[2] - sp[n][1] * ry[3] + sp[n][0] * ry[4];
@@ -149,7 +153,7 @@ __global__ __launch_bounds__(64) void biconvex_latency_kernel(const BatchArgs a)
                         xn[3 * n + 2] = keep * fz;
                     }
                     if (__any(cone_any)) {   // cone branch (fista.cpp:64-68); skipped while no lane needs it
-                        UNROLL for (int n = 0; n < 2; ++n) {
+                        UNROLL for (int n = 0; n < NH; ++n) {
                             const double s = fma(fr[3 * n], fr[3 * n], fr[3 * n + 1] * fr[3 * n + 1]);
                             const double fz = fr[3 * n + 2];
                             const bool zero = (s * mu < -fz) || (fz < 0);
@@ -162,7 +166,7 @@ __global__ __launch_bounds__(64) void biconvex_latency_kernel(const BatchArgs a)
                     }
                     applyA(xn, rn);
                     double g2 = 0, cv = 0, e2 = 0;
-                    UNROLL for (int j = 0; j < 6; ++j) {
+                    UNROLL for (int j = 0; j < NL; ++j) {
                         const double d = xn[j] - y[j];
                         g2 = fma(d, d, g2);
                         cv = fma(wf[j] * d, d, cv);
@@ -188,8 +192,8 @@ __global__ __launch_bounds__(64) void biconvex_latency_kernel(const BatchArgs a)
                     invL = 2.0 * (1.0 / L_f);
                 }
                 done = __any(done);
-                if ((done || i == maxit - 1) && fvalid) { UNROLL for (int j = 0; j < 6; ++j) Fs[fo + j] = xn[j]; }
-                UNROLL for (int j = 0; j < 6; ++j) y[j] = fma(cm, xn[j] - xo[j], xn[j]);
+                if ((done || i == maxit - 1) && fvalid) { UNROLL for (int j = 0; j < NL; ++j) Fs[fo + j] = xn[j]; }
+                UNROLL for (int j = 0; j < NL; ++j) y[j] = fma(cm, xn[j] - xo[j], xn[j]);
                 UNROLL for (int k = 0; k < 6; ++k) ry[k] = fma(cm, rn[k] - ro[k], rn[k]);
                 ++it_f;
                 act = !done;
@@ -205,19 +209,19 @@ __global__ __launch_bounds__(64) void biconvex_latency_kernel(const BatchArgs a)
         // =================================================================== X step: lane = (group xg, knot xt)
         {
             const int tq = rvalid ? xt : 0;
-            const double *cg = a.cnt_plan + (pb * H + tq) * 16;
+            const double *cg = a.cnt_plan + (pb * H + tq) * (4 * E);
             const double dt = rvalid ? a.dt[pb * H + xt] : 0.0;
             const double dtp = (xg < 3 && xt >= 1 && xt <= H) ? a.dt[pb * H + xt - 1] : 0.0;
-            double c[4], r[4][3];
-            UNROLL for (int n = 0; n < 4; ++n) {
+            double c[E], r[E][3];
+            UNROLL for (int n = 0; n < E; ++n) {
                 c[n] = rvalid ? cg[4 * n] : 0.0;
                 UNROLL for (int k = 0; k < 3; ++k) r[n][k] = rvalid ? cg[4 * n + 1 + k] : 0.0;
             }
             // A_f / b_f entries of this knot from the new forces (centroidal.cpp:86-127)
             double SX = 0, SY = 0, SZ = 0, b3 = 0, b4 = 0, b5 = 0, b6 = 0, b7 = 0, b8 = 0;
-            UNROLL for (int n = 0; n < 4; ++n) {
-                const double fx = rvalid ? Fs[12 * xt + 3 * n] : 0.0, fy = rvalid ? Fs[12 * xt + 3 * n + 1] : 0.0,
-                             fz = rvalid ? Fs[12 * xt + 3 * n + 2] : 0.0;
+            UNROLL for (int n = 0; n < E; ++n) {
+                const double fx = rvalid ? Fs[3 * E * xt + 3 * n] : 0.0, fy = rvalid ? Fs[3 * E * xt + 3 * n + 1] : 0.0,
+                             fz = rvalid ? Fs[3 * E * xt + 3 * n + 2] : 0.0;
                 SX += c[n] * fx * dt; SY += c[n] * fy * dt; SZ += c[n] * fz * dt;
                 b3 += -c[n] * fx * dt / m; b4 += -c[n] * fy * dt / m; b5 += -c[n] * fz * dt / m;
                 b6 += (c[n] * fy * r[n][2] - c[n] * fz * r[n][1]) * dt;
@@ -248,11 +252,11 @@ __global__ __launch_bounds__(64) void biconvex_latency_kernel(const BatchArgs a)
                 }
                 // create_bound_constraints (biconvex.cpp:27-55): CoM box around the feet
                 double csum = 0;
-                UNROLL for (int n = 0; n < 4; ++n) csum += c[n];
+                UNROLL for (int n = 0; n < E; ++n) csum += c[n];
                 const bool bounded = rvalid && xg == 0 && csum > 0;
                 UNROLL for (int k = 0; k < 3; ++k) {
                     double mx = r[0][k], mn = r[0][k];
-                    UNROLL for (int n = 1; n < 4; ++n) { mx = fmax(mx, r[n][k]); mn = fmin(mn, r[n][k]); }
+                    UNROLL for (int n = 1; n < E; ++n) { mx = fmax(mx, r[n][k]); mn = fmin(mn, r[n][k]); }
                     lb[k] = bounded ? mx + a.bounds[pb * a.sbounds + 6L * xt + k] : -INFINITY;
                     ub[k] = bounded ? mn + a.bounds[pb * a.sbounds + 6L * xt + 3 + k] : INFINITY;
                 }
@@ -403,23 +407,29 @@ __global__ __launch_bounds__(64) void biconvex_latency_kernel(const BatchArgs a)
     }
 }
 
-template <bool RAW, bool HASQF>
+template <int E, bool RAW, bool HASQF>
 hipError_t launch(const BatchArgs &a, hipStream_t stream) {
-    const size_t nstate = 2 * 9 * (size_t)(a.H + 1) + 12 * (size_t)a.H;
+    const size_t nstate = 2 * 9 * (size_t)(a.H + 1) + 3 * E * (size_t)a.H;
     const size_t lds = sizeof(double) * ((((size_t)a.c.maxit + 1) & ~(size_t)1) + nstate);
-    hipLaunchKernelGGL((biconvex_latency_kernel<RAW, HASQF>), dim3((unsigned)a.B), dim3(64), lds, stream, a);
+    hipLaunchKernelGGL((biconvex_latency_kernel<E, RAW, HASQF>), dim3((unsigned)a.B), dim3(64), lds, stream, a);
     return hipGetLastError();
+}
+template <int E>
+hipError_t launch_form(const BatchArgs &a, hipStream_t stream) {
+    if (!a.raw) return launch<E, false, false>(a, stream);
+    return a.qf ? launch<E, true, true>(a, stream) : launch<E, true, false>(a, stream);
 }
 
 }  // namespace
 
 bool latency_mapping_fits(const BatchArgs &a, int n_eff) {
-    return n_eff == 4 && a.precision == 0 && a.H >= 1 && a.H + 1 <= kLatKnots && a.B >= 1;
+    return (n_eff == 2 || n_eff == 4) && a.precision == 0 && a.H >= 1 && a.H + 1 <= kLatKnots && a.B >= 1;
 }
 
-hipError_t launch_biconvex_latency(const BatchArgs &a, hipStream_t stream) {
-    if (!a.raw) return launch<false, false>(a, stream);
-    return a.qf ? launch<true, true>(a, stream) : launch<true, false>(a, stream);
+hipError_t launch_biconvex_latency(const BatchArgs &a, int n_eff, hipStream_t stream) {
+    if (n_eff == 2) return launch_form<2>(a, stream);
+    if (n_eff == 4) return launch_form<4>(a, stream);
+    return hipErrorInvalidValue;
 }
 
 }  // namespace bunmpc

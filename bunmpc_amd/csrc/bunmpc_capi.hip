@@ -68,7 +68,7 @@ bunmpc::BatchArgs to_args(const bmpc_batch_t &d) {
 int check_batch(const bmpc_batch_t *d) {
     if (!d) return fail(BMPC_BAD_ARG, "null batch descriptor");
     if (d->B < 0 || d->n_col < 1) return fail(BMPC_BAD_ARG, "B < 0 or n_col < 1");
-    if (d->n_eff != 4) return fail(BMPC_BAD_ARG, "only n_eff == 4 is built");
+    if (d->n_eff != 2 && d->n_eff != 4) return fail(BMPC_BAD_ARG, "n_eff must be 2 or 4: the centroidal kernels are built for n_eff in {2, 4}");
     if (d->n_col + 1 > bunmpc::kMaxKnots)
         return fail(BMPC_BAD_ARG, "n_col + 1 > 256 knots is not supported (one knot per lane, at most four waves per problem)");
     if (d->n_col + 1 > 64 && d->precision != 0) return fail(BMPC_BAD_ARG, "n_col + 1 > 64 knots: fp64 only");
@@ -150,6 +150,11 @@ int bmpc_biconvex_last_lanes_per_problem(void) { return bunmpc::biconvex_last_la
 int bmpc_set_latency_mapping_max_batch(int max_batch) { return bunmpc::set_latency_mapping_max_batch(max_batch); }
 int bmpc_set_exact_step_decisions(int on) { return bunmpc::set_exact_step_decisions(on); }
 int bmpc_biconvex_fp32_scratch_bytes(void) { return bunmpc::biconvex_admm_f32_scratch_bytes(); }
+int bmpc_biconvex_kernel_scratch_bytes(int n_eff, int precision) {
+    if ((n_eff != 2 && n_eff != 4) || (precision != 0 && precision != 1)) { fail(BMPC_BAD_ARG, "n_eff must be 2 or 4, precision 0 or 1"); return -1; }
+    if (precision == 1) return n_eff == 4 ? bunmpc::biconvex_admm_f32_scratch_bytes() : bunmpc::biconvex_admm_f32_e2_scratch_bytes();
+    return n_eff == 4 ? bunmpc::admm_scratch_bytes_e4() : bunmpc::admm_scratch_bytes_e2();
+}
 const char *bmpc_last_error(void) { return g_err.c_str(); }
 
 int bmpc_device_count(int *count) {

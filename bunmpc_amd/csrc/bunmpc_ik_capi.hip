@@ -800,6 +800,7 @@ void bmpc_ik_layout_trace(int n_col, long *offset, int *iters, int *width) {   /
 int bmpc_kinodyn_solve_batch_device(const bmpc_kinodyn_batch_t *d, void *hip_stream) {
     if (!d || !d->x || !d->ik.model) return ik_fail(BMPC_BAD_ARG, "null KinoDyn batch descriptor");
     if (d->dyn.B != d->ik.B || d->ik.n_col > d->dyn.n_col) return ik_fail(BMPC_BAD_ARG, "inconsistent batch sizes / horizons");
+    if (d->dyn.n_eff != 4) return ik_fail(BMPC_BAD_ARG, "KinoDynMP: n_eff must be 4 (the whole-body model is a 12-joint quadruped)");
     if (d->dyn.B == 0) return BMPC_OK;
     auto *model = const_cast<bmpc_model *>(d->ik.model);
     if (int rc = model->upload()) return rc;
@@ -814,6 +815,7 @@ int bmpc_kinodyn_solve_batch_device(const bmpc_kinodyn_batch_t *d, void *hip_str
 // ------------------------------------------------------------------- KinoDynMP ----
 bmpc_kinodyn_t *bmpc_kinodyn_create(const bmpc_model_t *model, double m, int n_eff, int dyn_col, int ik_col) {
     if (!model || ik_col < 1 || ik_col > dyn_col) { ik_fail(BMPC_BAD_ARG, "bad KinoDynMP arguments"); return nullptr; }
+    if (n_eff != 4) { ik_fail(BMPC_BAD_ARG, "KinoDynMP: n_eff must be 4 (the whole-body model is a 12-joint quadruped)"); return nullptr; }
     auto *h = new bmpc_kinodyn;
     h->model = model; h->m = m; h->n_eff = n_eff; h->dyn_col = dyn_col; h->ik_col = ik_col;
     h->dyn = bmpc_biconvex_create(m, dyn_col, n_eff);

@@ -8,7 +8,8 @@ batch axis.  Follows, without importing it,
   iterative_supervised_learning/examples/motions/cyclic/solo12_{trot,bound,jump}.py (gait constants)
 at the centroidal level: the robot state enters only through CoM / foot positions
 (no pinocchio), exactly as SURVEY.md 8d defines configs 1-4.  Go2 and "pace" do not
-exist in the reference: those sets are synthetic (documented in DESIGN.md).
+exist in the reference: those sets are synthetic (documented in DESIGN.md), as is the biped
+(BIPED, BIPED_GAITS, make_batch("biped_walk")): two feet, n_eff = 2.
 """
 from dataclasses import dataclass, field, replace
 
@@ -30,7 +31,7 @@ class GaitParams:
     gait_horizon: float
     W_X: np.ndarray
     W_X_ter: np.ndarray
-    W_F: np.ndarray            # (12,) one knot: 4 feet x 3
+    W_F: np.ndarray            # (3E,) one knot: E feet x 3
     nom_ht: float
     rho: float = 5e4
     gait_dt: float = 0.05
@@ -47,8 +48,8 @@ class GaitParams:
 class RobotParams:
     name: str
     mass: float
-    feet_xy: np.ndarray        # (4,2) nominal foot xy (FL,FR,HL,HR)
-    offsets_xy: np.ndarray     # (4,2) hip-minus-com offsets after rounding and +-0.04 widening
+    feet_xy: np.ndarray        # (E,2) nominal foot xy (FL,FR,HL,HR; a biped: L,R)
+    offsets_xy: np.ndarray     # (E,2) hip-minus-com offsets after rounding and +-0.04 widening
     com_height: float
 
 
@@ -88,6 +89,32 @@ PACE = GaitParams(
     TROT.W_X.copy(), TROT.W_X_ter.copy(), TROT.W_F.copy(), 0.2)
 GAITS = {"trot": TROT, "bound": BOUND, "jump": JUMP, "pace": PACE}
 
+# synthetic biped, Bolt-sized (the reference's IK examples target bipeds; its centroidal demo runs n_eff = 2): 1.3 kg, CoM at
+# 0.30 m, feet (L, R) 0.08 m either side of the CoM, hips above them.  Not a robot description: numbers of the right size only.
+BIPED = RobotParams(
+    "biped", 1.3,
+    np.array([[0.0, 0.08], [0.0, -0.08]]),
+    np.array([[0.0, 0.08], [0.0, -0.08]]),
+    0.30)
+# biped gaits, trot's state weights and timing (0.05 s knots, 20 per plan), forces 2 feet x 3:
+#   walk   each foot 60 % on the ground, half a period apart: two double-support phases per period
+#   stand  both feet always on the ground
+#   hop    both feet together, 60 % stance, then a flight phase of 0.2 s
+BIPED_WALK = GaitParams(
+    "biped_walk", 0.5, (0.6, 0.6), (0.0, 0.5), 2.0,
+    TROT.W_X.copy(), TROT.W_X_ter.copy(), np.array(2 * [1e1, 1e1, 1e1]), 0.30, step_ht=0.05)
+BIPED_STAND = GaitParams(
+    "biped_stand", 0.5, (1.0, 1.0), (0.0, 0.0), 2.0,
+    TROT.W_X.copy(), TROT.W_X_ter.copy(), np.array(2 * [1e1, 1e1, 1e1]), 0.30, step_ht=0.0)
+BIPED_HOP = GaitParams(
+    "biped_hop", 0.5, (0.6, 0.6), (0.0, 0.0), 2.0,
+    TROT.W_X.copy(), TROT.W_X_ter.copy(), np.array(2 * [1e1, 1e1, 1.5e1]), 0.30, step_ht=0.05)
+BIPED_GAITS = {"walk": BIPED_WALK, "stand": BIPED_STAND, "hop": BIPED_HOP}
+# friction coefficient of the biped batches: 10, as for the synthetic Go2.  With the reference's mu = 1 the CPU oracle solves the
+# biped_walk problems without NaN, but its squared-norm "SoC" projection (fista.cpp:52-70) inflates the forces of long solves: at 100
+# ADMM iterations up to 174 N on a 1.3 kg robot, against 24 N with mu = 5 or 10 (256 problems; ten iterations: the same 15 N for all).
+BIPED_MU = 10.0
+
 
 # ---------------------------------------------------------------- gait phase ---
 def gait_phi(t, period, offset):
@@ -116,9 +143,10 @@ def contact_plan(gait, robot, H, t0, com_xy, z_height, feet0, v_des, w_des, hip_
     noise), vectorised over the batch.
       t0 (B,), com_xy (B,2) already rounded, z_height (B,), feet0 (B,4,3) already rounded,
       v_des (B,3) in the yaw frame (yaw = 0 here, R = I), w_des (B,)
-    returns cnt_plan (B,H,4,4), swing_time (B,H,4), dt (B,H)."""
+    E feet, as many as the gait has (4 for the quadrupeds, 2 for the biped; feet0 (B,E,3))
+    returns cnt_plan (B,H,E,4), swing_time (B,H,E), dt (B,H)."""
     B = t0.shape[0]
-    E = 4
+    E = len(gait.stance_percent)
     gdt = gait.gait_dt
     cnt = np.zeros((B, H, E, 4))
     swing = np.zeros((B, H, E))
@@ -255,12 +283,17 @@ def make_batch(config, B, first=0, seed=None, H=None):
                              parameter a Go2 user would have to change (set_friction_coefficient,
                              biconvex.hpp:131)
       "solo12_mixed"         config 4 trot/bound/pace with per-problem weights, H = 20
+      "biped_walk"           synthetic biped (BIPED, n_eff = 2), walk / hop mix with per-problem weights (W_F: 6 per knot),
+                             H = 20, mu = BIPED_MU; draws as "solo12_trot"
     `first` = absolute index of problem 0 (for rank sharding)."""
-    cfg_index = {"solo12_trot_nominal": 1, "solo12_trot": 2, "go2_bound": 3, "solo12_mixed": 4}[config]
+    cfg_index = {"solo12_trot_nominal": 1, "solo12_trot": 2, "go2_bound": 3, "solo12_mixed": 4, "biped_walk": 6}[config]
     seed = BASE_SEED + cfg_index if seed is None else seed
-    robot = GO2 if config == "go2_bound" else SOLO12
-    E = 4
-    if config == "solo12_mixed":
+    robot = GO2 if config == "go2_bound" else (BIPED if config == "biped_walk" else SOLO12)
+    E = robot.feet_xy.shape[0]
+    if config == "biped_walk":
+        gaits = [BIPED_WALK, BIPED_HOP]
+        H = BIPED_WALK.horizon if H is None else H
+    elif config == "solo12_mixed":
         gaits = [TROT, BOUND, PACE]
         H = 20 if H is None else H
     elif config == "go2_bound":
@@ -287,7 +320,7 @@ def make_batch(config, B, first=0, seed=None, H=None):
         x_init[:, 0:3] += nrm[:, 0:3] * np.array([0.02, 0.02, 0.01])
         x_init[:, 3:6] += nrm[:, 3:6] * 0.1
         x_init[:, 6:9] += nrm[:, 6:9] * 0.02
-        feet0[:, :, 0:2] += 0.01 * nrm[:, 9:17].reshape(B, E, 2)
+        feet0[:, :, 0:2] += 0.01 * nrm[:, 9:9 + 2 * E].reshape(B, E, 2)
     feet0_raw = feet0.copy()
     feet0 = np.round(feet0, 3)                       # :215 np.round(oMf.translation, 3)
     com_xy = np.round(x_init[:, 0:2], 3)             # :164
@@ -316,7 +349,7 @@ def make_batch(config, B, first=0, seed=None, H=None):
         W_F = np.stack([np.tile(gaits[k].W_F, H) for k in gid])
     bounds = np.tile(BOUNDS_TILE, (H, 1))[None]
     return Batch(config, B, H, E, robot.mass, gaits[0].rho, cnt, dt, x_init, X_nom, X_ter,
-                 W_X, W_X_ter, W_F, bounds, swing, gid, 10.0 if config == "go2_bound" else 1.0,
+                 W_X, W_X_ter, W_F, bounds, swing, gid, {"go2_bound": 10.0, "biped_walk": BIPED_MU}.get(config, 1.0),
                  dict(seed=seed, first=first, t0=t0, v_des=v_des, gaits=[g.name for g in gaits], gait_objs=gaits, robot=robot,
                       feet0_raw=feet0_raw, w_des=w_des))
 

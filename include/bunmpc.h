@@ -116,7 +116,7 @@ int bmpc_biconvex_set_robot_mass(bmpc_biconvex_t *h, double m);
  *       the solve's discrete path per ADMM iteration, what the prefix-parity tests compare with the CPU oracle's
  *   A caller built against an older header must zero-initialise the whole struct (bmpc_batch_defaults does) and check
  *   bmpc_batch_struct_size() == sizeof(bmpc_batch_t).
- *   Shapes: n_eff = 4; n_col + 1 <= 256 knots (up to 64: 4 / 3 / 2 / 1 problems per wave, fp64 or fp32 iterates; 65 .. 256: one
+ *   Shapes: n_eff in {2, 4}; n_col + 1 <= 256 knots (up to 64: 4 / 3 / 2 / 1 problems per wave, fp64 or fp32 iterates; 65 .. 256: one
  *   problem per workgroup of two .. four waves, fp64 -- the horizons of the reference's examples/analysis/solve_times_test.py).
  */
 typedef struct {
@@ -190,6 +190,10 @@ int bmpc_set_exact_step_decisions(int on);
  * the build is set up for (bunmpc_amd/build.py: their translation unit is compiled without the SLP vectoriser); a compiler that
  * spills again shows up here, and in 4x the HBM traffic. */
 int bmpc_biconvex_fp32_scratch_bytes(void);
+/* The largest scratch (private-segment) bytes per lane over the batch-kernel instantiations of one foot count (n_eff 2 or 4) and
+ * precision (0: fp64 -- one knot per lane at every lanes-per-problem and build, one problem per workgroup, work stealing; 1: fp32),
+ * as the loaded code object reports them; -1 (BMPC_BAD_ARG) for another n_eff or precision, or on error. */
+int bmpc_biconvex_kernel_scratch_bytes(int n_eff, int precision);
 /* symbol-name prefix of the kernel that serves (n_col, raw), for profiles */
 const char *bmpc_biconvex_kernel_name(int n_col, int raw);
 /* which kernel the calling host thread's latest batch solve was dispatched to: "biconvex_latency_kernel" (one problem per wave),
@@ -345,6 +349,7 @@ int bmpc_ik_centroidal_state_device(const bmpc_model_t *model, const double *x, 
 /* biconvex_mpc_cpp.KinoDynMP ---------------------------------------------------------
  * srcpy/motion_planner/biconvex.cpp:55-63 over src/motion_planner/kino_dyn.cpp */
 typedef struct bmpc_kinodyn bmpc_kinodyn_t;
+/* n_eff must be 4 here and in bmpc_kinodyn_solve_batch_device (BMPC_BAD_ARG otherwise): the IK model is a 12-joint quadruped */
 bmpc_kinodyn_t *bmpc_kinodyn_create(const bmpc_model_t *model, double m, int n_eff, int dyn_col, int ik_col); /* :56 */
 void bmpc_kinodyn_destroy(bmpc_kinodyn_t *h);
 bmpc_biconvex_t *bmpc_kinodyn_return_dyn(bmpc_kinodyn_t *h);      /* borrowed, owned by h           :57 */

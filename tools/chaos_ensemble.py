@@ -24,6 +24,7 @@ from tests import util                    # noqa: E402
 CASES = [("solo12_mixed", "solo12_mixed", 4096, None, 64, 10),
          ("go2_bound_h40", "go2_bound", 4096, 40, 64, 10),
          ("solo12_trot_n100", "solo12_trot", 4096, None, 64, 100),
+         ("biped_walk", "biped_walk", 4096, None, 64, 10),        # n_eff = 2 (walk / hop: hop's flight phases may leave the common path, as go2_bound's do)
          # the centroidal part of the reference's own call kd.optimize(q, v, 100, 1) (abstract_cyclic_gen.py:663) on the whole-body
          # batch of bench.py's KinoDyn legs: x_init = centroidal state of (q, v) by the CPU twin (kino_dyn.cpp:42)
          ("kinodyn_solo12_n100", "wb:solo12", 4096, None, 64, 100)]
