@@ -94,6 +94,7 @@ _SIGS = {
     "bmpc_batch_struct_size": (_I, []),
     "bmpc_set_latency_mapping_max_batch": (_I, [_I]),
     "bmpc_set_exact_step_decisions": (_I, [_I]),
+    "bmpc_set_certified_steps": (_I, [_I]),
     "bmpc_biconvex_fp32_scratch_bytes": (_I, []),
     "bmpc_biconvex_kernel_scratch_bytes": (_I, [_I, _I]),
     "bmpc_last_error": (C.c_char_p, []),

@@ -156,6 +156,8 @@ static int g_latency_max_batch = 1024;
 int set_latency_mapping_max_batch(int max_batch) { const int old = g_latency_max_batch; g_latency_max_batch = max_batch; return old; }
 static int g_exact_step_decisions = 0;
 int set_exact_step_decisions(int on) { const int old = g_exact_step_decisions; g_exact_step_decisions = on; return old; }
+static int g_certified_steps = 1;
+int set_certified_steps(int on) { const int old = g_certified_steps; g_certified_steps = on; return old; }
 // which kernel the calling host thread's latest launch_biconvex_admm took (tests of the default dispatch; profiles)
 static thread_local const char *t_last_kernel = "";
 static thread_local int t_last_lpp = 0;       // lanes per problem of that launch (0: the one-problem-per-wave kernel)
@@ -181,6 +183,7 @@ hipError_t launch_biconvex_admm(const BatchArgs &args, int n_eff, hipStream_t st
     }
     a.cmtab = momentum_table(stream);
     if (!a.cmtab) return hipErrorOutOfMemory;
+    a.certified_steps = g_certified_steps != 0;
     // the same decisions for two feet as for four, with the LDS record of the foot count (knot_lds)
     auto go = [&](const AdmmLaunch &l) {
         t_last_lpp = l.lpp;

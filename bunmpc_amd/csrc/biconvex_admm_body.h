@@ -38,6 +38,13 @@
 // neighbour wave's edge lane picks them up), the segment sums are the waves' sums added in wave order by every wave (same bits
 // everywhere, so every decision stays workgroup-uniform and the barriers sit in uniform control flow); buffers alternate between
 // two copies, so one barrier per exchange is enough.  Everything else is the one-wave code.
+// Step certificate of the force step: margin eta of the test  bound <= (L/2)(1 - eta), and the factor of the
+// |d|^2 floor below which the certified loop hands a step to the tested one: 2 (|a| + |b|)^2 <= 2|a|^2 + 2|b|^2, noise <= 2^-40 of
+// the images' scale (2^-53: a few ulp per image, with room for the iterates to grow within the phase), (5 / eta)^2 from the margin's
+// split.
+constexpr double kCertEta = 1.0 / 64.0;
+constexpr double kCertFloor = 2.0 * 25.0 / (kCertEta * kCertEta) * 0x1p-80;
+
 template <typename R, int LPP, int E, bool RAW, bool HASQF, bool STEAL = false, bool XLDS = false, int WAVES = 1>
 __device__ __forceinline__ void admm_body(const BatchArgs &a) {
     constexpr bool MW = WAVES > 1;
@@ -117,6 +124,41 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
             s0 = t0; s1 = t1;
             par_s ^= 1;
         }
+    };
+    auto sum1 = [&](double &s0) {      // one of them, with sum2's bits for it
+        seg_sum1<LPP>(s0);
+        if (MW) {
+            double *buf = xch + 4 * WAVES * 9 + par_s * (WAVES * 2);
+            if (lane == 0) buf[2 * wv] = s0;
+            __syncthreads();
+            double t0 = buf[0];
+            UNROLL for (int w = 1; w < WAVES; ++w) t0 += buf[2 * w];
+            s0 = t0;
+            par_s ^= 1;
+        }
+    };
+    // The step certificate of a force phase: every lane of every live problem found its scaled Gershgorin row test
+    // (`ok`) true -- then no step of the phase's FISTA loop can fail the backtracking test, and the loop runs without it.  Wave-
+    // (MW: workgroup-) uniform.
+    constexpr bool CAN_CERT = sizeof(R) == sizeof(double);      // (fp32: the image noise does make the test fire, see the force step)
+    auto certify = [&](bool ok, mask_t live) -> bool {
+        if (!CAN_CERT || !a.certified_steps) return false;
+        if (!MW) return (__ballot(!ok) & live) == 0;
+        double f = ok ? 0.0 : 1.0;
+        sum1(f);
+        return __ballot(f != 0.0) == 0;
+    };
+    // ... and below which |d|^2 a certified loop hands the step to the tested one: the images A y + bPk are carried through the
+    // momentum step, so rn - ry = A d + noise of a few ulp of the images; the certificate's margin absorbs the noise only while |d| is
+    // not far below it.  s2: the lane's |bPk|^2 + (T / rho)|x_0|^2 (T / rho bounds |||A|||^2); the floor is the largest over the wave's
+    // live problems (a scalar).
+    auto cert_floor = [&](double s2, double Lh, mask_t live) {
+        sum1(s2);
+        const double f = lanes(live) ? s2 * kCertFloor * ((double)rho / Lh) : 0.0;
+        constexpr int NS = LPP == 21 ? 3 : 64 / LPP;
+        double m = 0.0;
+        UNROLL for (int k = 0; k < NS; ++k) m = fmax(m, lane_bcast(f, LPP == 21 ? 16 * (k + 1) : k * LPP));
+        return m;
     };
     // Global arrays are addressed as a WAVE-UNIFORM base (the block of the wave's first problem: scalar registers) plus a 32-bit
     // per-lane byte offset (problem within the wave, knot): `global_load v, v_off, s[base]`.  A 64-bit pointer per lane and array
@@ -302,6 +344,35 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
                             : ldz<R>(a.W_F + wave0 * a.sW_F, 8u * (sl_ * (unsigned)a.sW_F + (unsigned)NF * tr) + ph, j, rvalid);
                 if (HASQF) qf[j] = R(0.5) * ldz<R>(a.qf + wave0 * nf, o.F + ph, j, rvalid);
             }
+            // the step certificate: M = W + rho A_x'A_x is block-diagonal per knot; with dg = diag(M), u = |A| dg, v = |A|' u the lane's
+            // rows pass if W_j dg_j + rho v_j <= T dg_j (tools/certify_rate.py restates this)
+            bool cert = false;
+            double floor2 = 0.0;
+            if (CAN_CERT && a.certified_steps) {
+                const double Lh0 = (double)L_f * 0.5, T = Lh0 * (1.0 - kCertEta);
+                double dg[NF], u[6] = {0, 0, 0, 0, 0, 0}, x2 = 0.0, b2 = 0.0;
+                UNROLL for (int n = 0; n < E; ++n) {
+                    const double a0 = fabs((double)an[n]), s0 = (double)sp[n][0], s1 = (double)sp[n][1], s2 = (double)sp[n][2];
+                    const double q = a0 * a0 + s0 * s0 + s1 * s1 + s2 * s2;
+                    dg[3 * n] = (double)wf[3 * n] + (double)rho * (q - s0 * s0);
+                    dg[3 * n + 1] = (double)wf[3 * n + 1] + (double)rho * (q - s1 * s1);
+                    dg[3 * n + 2] = (double)wf[3 * n + 2] + (double)rho * (q - s2 * s2);
+                    UNROLL for (int k = 0; k < 3; ++k) u[k] += a0 * dg[3 * n + k];
+                    u[3] += fabs(s2) * dg[3 * n + 1] + fabs(s1) * dg[3 * n + 2];
+                    u[4] += fabs(s0) * dg[3 * n + 2] + fabs(s2) * dg[3 * n];
+                    u[5] += fabs(s1) * dg[3 * n] + fabs(s0) * dg[3 * n + 1];
+                }
+                bool ok = true;
+                UNROLL for (int n = 0; n < E; ++n) {
+                    const double a0 = fabs((double)an[n]), s0 = fabs((double)sp[n][0]), s1 = fabs((double)sp[n][1]), s2 = fabs((double)sp[n][2]);
+                    const double v[3] = {a0 * u[0] + s2 * u[4] + s1 * u[5], a0 * u[1] + s2 * u[3] + s0 * u[5], a0 * u[2] + s1 * u[3] + s0 * u[4]};
+                    UNROLL for (int k = 0; k < 3; ++k) ok = ok && (double)wf[3 * n + k] * dg[3 * n + k] + (double)rho * v[k] <= T * dg[3 * n + k];
+                }
+                if (rvalid) { UNROLL for (int j = 0; j < NF; ++j) x2 += (double)Fg[j] * (double)Fg[j]; }      // (x_0: the F block)
+                UNROLL for (int k = 0; k < 6; ++k) b2 += (double)bpk[k] * (double)bpk[k];
+                cert = certify(ok, alive);
+                if (cert) floor2 = cert_floor(b2 + (T / (double)rho) * x2, Lh0, alive);
+            }
             // u = A v + bPk on rows 9t+3..8
             auto applyA = [&](const R (&v)[NF], R (&u)[6]) {
                 R s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0;
@@ -329,7 +400,8 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
             mask_t act = alive;
             // one FISTA iteration: reads x from xo/ro, leaves x_{k+1} in xn/rn, advances y/ry (XLDS: x_k from LDS, x_{k+1} to LDS;
             // the four arrays are then no more than the iteration's temporaries)
-            auto iterate = [&](const R (&xo_reg)[NF], const R (&ro_reg)[6], R (&xn)[NF], R (&rn)[6], int i) {
+            auto iterate = [&](const R (&xo_reg)[NF], const R (&ro_reg)[6], R (&xn)[NF], R (&rn)[6], int i, auto certc) {
+                constexpr bool CERT = decltype(certc)::value;      // the certified loop (see `cert`): no backtracking test unless |d| is tiny
                 const R cm = (R)cmtab[i];
                 R xo[NF], ro[6];
                 if (!XLDS) {
@@ -376,6 +448,9 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
                     }
                     applyA(xn, rn);
                     R g2 = 0, cv = 0, e2 = 0, dv[NF];
+                    if (CERT) {
+                        UNROLL for (int j = 0; j < NF; ++j) { const R d = xn[j] - y[j]; g2 = fmaR(d, d, g2); }
+                    } else {
                     UNROLL for (int j = 0; j < NF; ++j) {
                         const R d = xn[j] - y[j];
                         dv[j] = d;
@@ -400,22 +475,27 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
                         e2 = s0 * s0 + s1 * s1 + s2 * s2 + s3 * s3 + s4 * s4 + s5 * s5;
                     }
                     cv = fmaR(rho, e2, cv);
+                    }
                     if (XLDS) {     // x_k and its image come in while the sums are reduced (unconditional: lanes without a knot read zeros)
                         UNROLL for (int j = 0; j < NF; ++j) xo[j] = Fz[j];
                         UNROLL for (int k = 0; k < 6; ++k) ro[k] = RFz[k];
                     }
                     double g2s = (double)g2, cvs = (double)cv;
-                    sum2(g2s, cvs);
+                    if (CERT) {
+                        sum1(g2s);
+                        // a live problem's step below the floor: nothing of this iteration is kept, the tested loop runs it again
+                        if ((seg_uniform<LPP>(__ballot(g2s < floor2) & seg_desig<LPP>()) & act) != 0) return false;
+                    } else sum2(g2s, cvs);
                     // fista.cpp:14-17: G = sqrt(g2); retry if cv > (L/2) G*G; done if G < tol.  G*G and g2
                     // differ by a few ulp, so outside a 1e-14 relative band the sqrt cannot change either
                     // decision; inside it the reference expression is evaluated as written.
                     const double Lh = (double)L_f * 0.5, rhs = Lh * g2s;
-                    mask_t bt = __ballot(cvs > rhs);
+                    mask_t bt = CERT ? mask_t(0) : __ballot(cvs > rhs);      // (certified: cvs <= rhs whatever the step)
                     done = __ballot(g2s < tol2);
-                    const mask_t edge = __ballot((fabs(cvs - rhs) <= 1e-14 * rhs) || (fabs(g2s - tol2) <= 1e-14 * tol2)) & seg_desig<LPP>();
+                    const mask_t edge = __ballot((!CERT && fabs(cvs - rhs) <= 1e-14 * rhs) || (fabs(g2s - tol2) <= 1e-14 * tol2)) & seg_desig<LPP>();
                     if (edge != 0) {
                         const double Gn = sqrt(g2s);
-                        bt = __ballot(cvs > Lh * (Gn * Gn));
+                        if (!CERT) bt = __ballot(cvs > Lh * (Gn * Gn));
                         done = __ballot(Gn < tol);
                     }
                     bt = seg_uniform<LPP>(bt);      // (LPP = 21: the sums live at three lanes; their decisions go to their segments)
@@ -443,12 +523,24 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
                 }
                 it_f += lanes(act) ? 1 : 0;
                 act &= ~done;
+                return true;
             };
-            for (int i = 0; i < maxit; i += 2) {
-                if (act == 0) break;
-                iterate(xa, ra, xb, rb, i);
-                if (i + 1 >= maxit || act == 0) break;
-                iterate(xb, rb, xa, ra, i + 1);
+            // the certified loop, if the phase has its certificate, then the tested one from the iteration the first left undone (the
+            // last maxit: none); iteration i reads x_k from xa when i is even, so an odd start first moves x_k there
+            auto loop = [&](int i0, auto certc) {
+                for (int i = i0; i < maxit; i += 2) {
+                    if (act == 0) break;
+                    if (!iterate(xa, ra, xb, rb, i, certc)) return i;
+                    if (i + 1 >= maxit || act == 0) break;
+                    if (!iterate(xb, rb, xa, ra, i + 1, certc)) return i + 1;
+                }
+                return maxit;
+            };
+            int i0 = 0;
+            if constexpr (CAN_CERT) { if (cert) i0 = loop(0, std::true_type{}); }
+            if (i0 < maxit) {
+                if (!XLDS && (i0 & 1)) { UNROLL for (int j = 0; j < NF; ++j) xa[j] = xb[j]; UNROLL for (int k = 0; k < 6; ++k) ra[k] = rb[k]; }
+                loop(i0, std::false_type{});
             }
         }
 

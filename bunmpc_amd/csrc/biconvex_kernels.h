@@ -2,6 +2,7 @@
 // (bunmpc_capi.hip) and the batched centroidal ADMM kernel (biconvex_admm.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 namespace bunmpc {
 
@@ -38,6 +39,7 @@ struct BatchArgs {
     int B, H, raw, cold_start;
     int precision;   // 0: fp64 arithmetic; 1: fp32 iterates with fp64 decisions (harness form only)
     int exact_step_decisions;   // 1: the one-problem-per-wave kernel skips the fp32 shortcut of its step decisions (tests)
+    int certified_steps;        // (set by the launcher) 1: fp64 batch kernels skip the backtracking test in phases whose step is certified
     double L0_x, L0_f;
     SolverConsts c;
     const double *cnt_plan, *dt, *x_init;
@@ -90,6 +92,7 @@ int set_steal_grid(int waves);                       // waves of the work-steali
 int set_work_stealing(int on);                       // the segment-level work-stealing kernel for num_iters >= 25 (default on); returns the old value
 int biconvex_last_lanes_per_problem();               // of the calling host thread's latest launch: 16 / 21 / 32 / 64, 0 = one problem per wave
 int set_exact_step_decisions(int on);                // ... takes every step decision from the fp64 sums; returns the old value
+int set_certified_steps(int on);                     // the fp64 batch kernels' per-phase step certificate (default on); returns the old value
 
 // fp32 instantiations (biconvex_admm_f32.hip: E = 4, biconvex_admm_f32_e2.hip: E = 2); called by launch_biconvex_admm with the
 // lanes per problem (16 / 32 / 64), the grid and the LDS bytes it has worked out

@@ -79,6 +79,16 @@ __device__ __forceinline__ void seg21_sum2(double &a, double &b, bool is_p) {
     a = dpp_bcast15(pa) + qa;
     b = dpp_bcast15(pb) + qb;
 }
+// ... the sum of a alone: seg21_sum2's operations on a, hence its bits (valid at the designated lanes only)
+__device__ __forceinline__ void seg21_sum1(double &a, bool is_p) {
+    double pa = is_p ? a : 0.0, qa = is_p ? 0.0 : a;
+    double t0, t1;
+    t0 = dpp_mov<DPP_QUAD_XOR1>(pa); t1 = dpp_mov<DPP_QUAD_XOR1>(qa); pa += t0; qa += t1;
+    t0 = dpp_mov<DPP_QUAD_XOR2>(pa); t1 = dpp_mov<DPP_QUAD_XOR2>(qa); pa += t0; qa += t1;
+    t0 = dpp_mov<DPP_ROW_HALF_MIRROR>(pa); t1 = dpp_mov<DPP_ROW_HALF_MIRROR>(qa); pa += t0; qa += t1;
+    t0 = dpp_mov<DPP_ROW_MIRROR>(pa); t1 = dpp_mov<DPP_ROW_MIRROR>(qa); pa += t0; qa += t1;
+    a = dpp_bcast15(pa) + qa;
+}
 // value of v at lane `src` (compile-time constant), wave-uniform
 __device__ __forceinline__ double lane_bcast(double v, int src) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
@@ -141,6 +151,13 @@ __device__ __forceinline__ void seg_sum2(double &a, double &b) {
         a = __hiloint2double(x1[0], x0[0]) + __hiloint2double(x1[1], x0[1]);
         b = __hiloint2double(y1[0], y0[0]) + __hiloint2double(y1[1], y0[1]);
     }
+}
+
+// One segment sum with the bits of seg_sum2's first (or second) sum: valid where seg_sum2's are (LPP = 21: the designated lanes)
+template <int LPP>
+__device__ __forceinline__ void seg_sum1(double &a) {
+    if (LPP == 21) { seg21_sum1(a, seg21_is_p((int)(threadIdx.x & 63))); return; }
+    a = seg_sum<LPP>(a);
 }
 
 // The two decisions of a FISTA step -- retry (cv > (L/2) g2) and exit (g2 < tol^2) -- from WAVE sums of g2 and cv taken in fp32:

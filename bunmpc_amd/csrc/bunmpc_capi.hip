@@ -149,6 +149,7 @@ int bmpc_biconvex_last_waves_per_simd(void) { return bunmpc::biconvex_last_waves
 int bmpc_biconvex_last_lanes_per_problem(void) { return bunmpc::biconvex_last_lanes_per_problem(); }
 int bmpc_set_latency_mapping_max_batch(int max_batch) { return bunmpc::set_latency_mapping_max_batch(max_batch); }
 int bmpc_set_exact_step_decisions(int on) { return bunmpc::set_exact_step_decisions(on); }
+int bmpc_set_certified_steps(int on) { return bunmpc::set_certified_steps(on); }
 int bmpc_biconvex_fp32_scratch_bytes(void) { return bunmpc::biconvex_admm_f32_scratch_bytes(); }
 int bmpc_biconvex_kernel_scratch_bytes(int n_eff, int precision) {
     if ((n_eff != 2 && n_eff != 4) || (precision != 0 && precision != 1)) { fail(BMPC_BAD_ARG, "n_eff must be 2 or 4, precision 0 or 1"); return -1; }

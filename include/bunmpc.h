@@ -186,6 +186,11 @@ int bmpc_biconvex_last_waves_per_simd(void);
  * expression otherwise.  on = 1: always from the fp64 sums (a test switch: results must be bit-identical either way).
  * Returns the old value. */
 int bmpc_set_exact_step_decisions(int on);
+/* The fp64 batch kernels skip FISTA's backtracking test for a whole force step (one ADMM iteration's force-QP loop) of a wave whose
+ * live problems all carry a certificate that the test cannot fire: a diagonally scaled Gershgorin bound of the step's Hessian
+ * below (L/2)(1 - 2^-6).  on = 0: every step is tested (a test switch: results must be
+ * bit-identical either way).  Default 1.  Returns the old value. */
+int bmpc_set_certified_steps(int on);
 /* Scratch (private-segment) bytes per lane of the fp32 kernels as the loaded code object reports them, -1 on error.  0 is what
  * the build is set up for (bunmpc_amd/build.py: their translation unit is compiled without the SLP vectoriser); a compiler that
  * spills again shows up here, and in 4x the HBM traffic. */

@@ -1,0 +1,151 @@
+"""How often the centroidal kernel's per-phase step certificate holds (biconvex_admm_body.h: `cert`).
+The kernel applies it to the force step; the motion step's bound is restated here as a measurement (DESIGN.md says why the kernel
+does not use it yet).
+
+FISTA's backtracking test retries a step iff d'(Q + rho A'A) d > (L/2)|d|^2.  Where a diagonally scaled Gershgorin bound of
+M = Q + rho A'A is below (L/2)(1 - eta), no d can make it retry, so the kernel runs that phase's FISTA loop without the test.  This
+is the numpy restatement of the bound the kernel evaluates per lane (knot), with |A| in place of A:
+
+    dg = diag(M)  (Q_ii + rho * column norms^2 of A),   u = |A| dg,   v = |A|' u,
+    lane certified  iff  Q_ii dg_i + rho v_i <= (L/2)(1 - eta) dg_i  for every component i of the knot,
+
+which bounds max_i sum_j |M_ij| dg_j / dg_i >= lambda_max(M) (D^-1 M D has M's spectrum).  The force step's A_x is block-diagonal
+per knot; the motion step's A_f couples knot t with t + 1 (dg of the next knot, u of the previous one).  The x_init rows are lane 0's
++rho on Q, as the kernel folds them.
+
+    python tools/certify_rate.py [--B 512] [--configs solo12_trot,...]
+
+re-solves the batch with num_iters = k (the C oracle, matrix-free variant) for every ADMM boundary k and reports the fraction of
+certified (problem, phase) pairs: the force phase of ADMM iteration k + 1 sees X after k iterations, its motion phase F after k + 1.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ETA = 2.0 ** -6      # the kernel's margin (biconvex_admm_body.h: kCertEta)
+
+
+def force_bound_terms(cnt, dt, m, X, W_F, rho):
+    """cnt [B][H][E][4], dt [B][H], X [B][9 (H + 1)], W_F [B][3 E H] -> (lhs, dg) [B][H][3E]: lane-wise Q_ii dg_i + rho v_i and dg_i."""
+    B, H, E, _ = cnt.shape
+    c = cnt[..., 0]
+    r = cnt[..., 1:4]
+    Xk = X.reshape(B, H + 1, 9)[:, :H, 0:3]
+    an = np.abs(c * (dt / m)[..., None])                                           # [B][H][E]
+    sp = c[..., None] * (Xk[:, :, None, :] - r) * dt[..., None, None]              # [B][H][E][3]
+    w = W_F.reshape(B, H, E, 3)
+    s2 = (sp * sp).sum(-1, keepdims=True)
+    dg = w + rho * (an[..., None] ** 2 + s2 - sp * sp)                              # column norms^2 of A_x
+    a = np.abs(sp)
+    u = np.empty((B, H, 6))
+    u[..., 0:3] = (an[..., None] * dg).sum(2)
+    u[..., 3] = (a[..., 2] * dg[..., 1] + a[..., 1] * dg[..., 2]).sum(2)
+    u[..., 4] = (a[..., 0] * dg[..., 2] + a[..., 2] * dg[..., 0]).sum(2)
+    u[..., 5] = (a[..., 1] * dg[..., 0] + a[..., 0] * dg[..., 1]).sum(2)
+    v = an[..., None] * u[:, :, None, 0:3]
+    v[..., 0] += a[..., 2] * u[:, :, None, 4] + a[..., 1] * u[:, :, None, 5]
+    v[..., 1] += a[..., 2] * u[:, :, None, 3] + a[..., 0] * u[:, :, None, 5]
+    v[..., 2] += a[..., 1] * u[:, :, None, 3] + a[..., 0] * u[:, :, None, 4]
+    return (w * dg + rho * v).reshape(B, H, 3 * E), dg.reshape(B, H, 3 * E)
+
+
+def motion_bound_terms(cnt, dt, F, Qx, rho):
+    """cnt [B][H][E][4], dt [B][H], F [B][3 E H], Qx [B][9 (H + 1)] (diagonal) -> (lhs, dg) [B][H + 1][9]."""
+    B, H, E, _ = cnt.shape
+    c = cnt[..., 0]
+    f = F.reshape(B, H, E, 3)
+    S = (c[..., None] * f * dt[..., None, None]).sum(2)                            # [B][H][3]: SX, SY, SZ
+    a = np.zeros((B, H + 1, 3))
+    a[:, :H] = np.abs(S)
+    ax, ay, az = a[..., 0], a[..., 1], a[..., 2]
+    dtk = np.zeros((B, H + 1)); dtk[:, :H] = dt
+    dtp = np.zeros((B, H + 1)); dtp[:, 1:] = dt                                    # dt of knot t - 1
+    has_row = np.zeros((B, H + 1, 1)); has_row[:, :H] = 1.0                         # row-block t exists (t < H)
+    has_prev = np.ones((B, H + 1, 1)); has_prev[:, 0] = 0.0
+    Q = Qx.reshape(B, H + 1, 9).copy()
+    Q[:, 0] += rho                                                                  # the x_init rows
+    coln = has_row * np.ones(9) + has_prev * np.ones(9)                             # the 1 / -1 of D_t / U_{t-1}
+    coln[..., 0] += ay ** 2 + az ** 2
+    coln[..., 1] += ax ** 2 + az ** 2
+    coln[..., 2] += ax ** 2 + ay ** 2
+    coln[..., 3:6] += dtp[..., None] ** 2
+    dg = Q + rho * coln
+    dgn = np.zeros_like(dg); dgn[:, :H] = dg[:, 1:]                                  # dg of knot t + 1
+    u = dg + dgn
+    u[..., 0:3] += dtk[..., None] * dgn[..., 3:6]
+    u[..., 6] += az * dg[..., 1] + ay * dg[..., 2]
+    u[..., 7] += az * dg[..., 0] + ax * dg[..., 2]
+    u[..., 8] += ay * dg[..., 0] + ax * dg[..., 1]
+    u *= has_row
+    up = np.zeros_like(u); up[:, 1:] = u[:, :H]                                      # u of row-block t - 1
+    v = u + up
+    v[..., 3:6] += dtp[..., None] * up[..., 0:3]
+    v[..., 0] += az * u[..., 7] + ay * u[..., 8]
+    v[..., 1] += az * u[..., 6] + ax * u[..., 8]
+    v[..., 2] += ay * u[..., 6] + ax * u[..., 7]
+    return Q * dg + rho * v, dg
+
+
+def bound_from_terms(lhs, dg):
+    """the scaled Gershgorin bound of lambda_max(M) per problem: max_i lhs_i / dg_i"""
+    return (lhs / dg).reshape(lhs.shape[0], -1).max(1)
+
+
+def certified(lhs, dg, L, eta=ETA):
+    """per problem: every lane's test lhs_i <= (L/2)(1 - eta) dg_i"""
+    T = (np.asarray(L, np.float64) * 0.5 * (1.0 - eta)).reshape(-1, *([1] * (lhs.ndim - 1)))
+    return np.all(lhs <= T * dg, axis=tuple(range(1, lhs.ndim)))
+
+
+def _costs(batch):
+    from oracle import oracle_c
+    B, H = batch.B, batch.H
+    Qx = np.empty((B, 9 * (H + 1)))
+    for b in range(B):
+        sb = 0 if batch.W_X.shape[0] == 1 else b
+        Qx[b], _ = oracle_c.create_cost_X(batch.W_X[sb], batch.W_X_ter[sb], batch.X_ter[b], batch.X_nom[b])
+    W_F = np.broadcast_to(batch.W_F, (B, batch.W_F.shape[1]))
+    return Qx, W_F
+
+
+def rates(batch, num_iters=10):
+    from oracle import oracle_c
+    Qx, W_F = _costs(batch)
+    X0, F0, _ = batch.warm_start()
+    states = [(X0, F0, np.full(batch.B, 2.25e6), np.full(batch.B, 506.25))]
+    for k in range(1, num_iters + 1):
+        o = oracle_c.solve_batch(batch, num_iters=k, fast=True)
+        states.append((o["X"], o["F"], o["L_x"], o["L_f"]))
+    nf = nm = 0
+    worst_f = worst_m = 0.0
+    for k in range(num_iters):
+        X, _, _, Lf = states[k]
+        _, F, Lx, _ = states[k + 1]
+        lf, df = force_bound_terms(batch.cnt_plan, batch.dt, batch.m, X, W_F, batch.rho)
+        lm, dm = motion_bound_terms(batch.cnt_plan, batch.dt, F, Qx, batch.rho)
+        nf += int(certified(lf, df, Lf).sum())
+        nm += int(certified(lm, dm, Lx).sum())
+        worst_f = max(worst_f, float((bound_from_terms(lf, df) / (0.5 * Lf)).max()))
+        worst_m = max(worst_m, float((bound_from_terms(lm, dm) / (0.5 * Lx)).max()))
+    n = num_iters * batch.B
+    return dict(force=nf / n, motion=nm / n, force_bound_over_half_L=worst_f, motion_bound_over_half_L=worst_m)
+
+
+def main():
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from bunmpc_amd import problems
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--B", type=int, default=512)
+    ap.add_argument("--num-iters", type=int, default=10)
+    ap.add_argument("--configs", default="solo12_trot,solo12_mixed,go2_bound,biped_walk")
+    args = ap.parse_args()
+    for cfg in args.configs.split(","):
+        r = rates(problems.make_batch(cfg, args.B), args.num_iters)
+        print(f"{cfg:14s} B={args.B}  certified phases: force {100 * r['force']:6.2f} %  motion {100 * r['motion']:6.2f} %   "
+              f"max bound / (L/2): force {r['force_bound_over_half_L']:.4f}  motion {r['motion_bound_over_half_L']:.4f}")
+
+
+if __name__ == "__main__":
+    main()
