@@ -174,12 +174,11 @@ hipError_t launch_biconvex_admm(const BatchArgs &args, int n_eff, hipStream_t st
     for (long stride : {a.sW_X, a.sW_X_ter, a.sW_F, a.sbounds})
         if (stride < 0 || stride > (1L << 26)) return hipErrorInvalidValue;
     // few problems, short horizon: one problem per wave (the chain of a solve is ~2.3x shorter; biconvex_latency.hip)
+    a.exact_step_decisions = g_exact_step_decisions;      // (every kernel with the fp32 shortcut of its step decisions)
     if (a.B <= g_latency_max_batch && latency_mapping_fits(a, n_eff)) {
         t_last_kernel = "biconvex_latency_kernel";
         t_last_lpp = 0;
-        BatchArgs al = a;
-        al.exact_step_decisions = g_exact_step_decisions;
-        return launch_biconvex_latency(al, n_eff, stream);
+        return launch_biconvex_latency(a, n_eff, stream);
     }
     a.cmtab = momentum_table(stream);
     if (!a.cmtab) return hipErrorOutOfMemory;

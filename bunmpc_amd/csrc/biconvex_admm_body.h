@@ -160,6 +160,33 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
         UNROLL for (int k = 0; k < NS; ++k) m = fmax(m, lane_bcast(f, LPP == 21 ? 16 * (k + 1) : k * LPP));
         return m;
     };
+    // fp32 step decisions: a FISTA step takes retry (cv > (L/2) g2), exit (g2 < tol^2) and, in the certified
+    // force loop, the floor test (g2 < floor2) from fp32 segment sums (seg_sum2_f32: 12 instead of 30 instructions at 32 lanes) when
+    // for every live problem of the wave both comparisons are clear of their thresholds by kBand relative and the g2 sum lies in
+    // [1e-24, 1e30]; the fp32 sums are within 5e-7 of the exact ones there, so each such decision is the one the fp64 sums make.
+    // Otherwise the wave runs the fp64 sums and the reference expression, as it did without the shortcut.  The bound holds for sums of
+    // non-negative terms: a phase takes the shortcut only with rho >= 0 and no negative weight in the wave (`banded`), and never under
+    // bmpc_set_exact_step_decisions(1).  One instantiation takes it: the two-waves-per-SIMD build of the 32-lane, four-feet kernel in
+    // the harness form -- the benchmark's kernel, the one whose gain (3.37 -> 3.30 ms), unchanged iterates and unchanged registers and
+    // scratch (40 bytes per lane, none inside the loops) were checked.  In the other single-wave builds the same
+    // source moved the compiler's register allocation (scratch of the 16- / 21-lane and two-feet kernels 40 -> 116, 32 -> 100, 8 -> 76
+    // bytes per lane, reloads inside the FISTA loops), the rounding of the iterates (two feet, 21 lanes) or the time (the work-stealing
+    // kernel, 27.6 -> 29.6 ms): they keep the fp64 sums, as do the workgroup kernels (MW) and the fp32 kernel.
+    constexpr bool BAND = !MW && !STEAL && XLDS && !RAW && LPP == 32 && E == 4 && sizeof(R) == sizeof(double);
+    constexpr double kBand = 1e-5;
+    // (1 - kBand) x and (1 + kBand) x as floats, wave-uniform (scalar registers): thresholds that need no range check, g2 is confined
+    auto band_u = [](double x, float &lo, float &hi) {
+        lo = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint((float)(x * (1.0 - kBand)))));
+        hi = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint((float)(x * (1.0 + kBand)))));
+    };
+    // ... of a step constant L/2, per lane: NaN (no comparison clear) outside [1e-3, 1e30], where the products could leave fp32's range
+    auto band_L = [](double Lh, float &lo, float &hi) {
+        const bool in = Lh >= 1e-3 && Lh <= 1e30;
+        lo = in ? (float)(Lh * (1.0 - kBand)) : __builtin_nanf("");
+        hi = in ? (float)(Lh * (1.0 + kBand)) : __builtin_nanf("");
+    };
+    float t2lo = 0.0f, t2hi = 0.0f;
+    if constexpr (BAND) band_u(tol * tol, t2lo, t2hi);
     // Global arrays are addressed as a WAVE-UNIFORM base (the block of the wave's first problem: scalar registers) plus a 32-bit
     // per-lane byte offset (problem within the wave, knot): `global_load v, v_off, s[base]`.  A 64-bit pointer per lane and array
     // -- what `a.X + pb * nx + 9 * t` makes -- held some thirty vector registers over both FISTA loops, and they were what the
@@ -397,6 +424,15 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
             const R mu2 = mu * mu, imu = R(1) / (mu * mu + R(1));
             const double tol2 = tol * tol;
             R invL = R(2) * (R(1) / L_f);      // 2 / L, see above
+            mask_t banded = 0;      // the fp32 step decisions (see BAND): all ones or 0 (a mask: a bool here would live in a vector register)
+            float Llo = 0.0f, Lhi = 0.0f, flo = 0.0f, fhi = 0.0f;
+            if constexpr (BAND) if (!a.exact_step_decisions) {
+                bool wneg = false;
+                UNROLL for (int j = 0; j < NF; ++j) wneg = wneg || wf[j] < R(0);
+                banded = rho >= R(0) && __ballot(wneg) == 0 ? ~mask_t(0) : mask_t(0);
+                band_L((double)L_f * 0.5, Llo, Lhi);
+                band_u(floor2, flo, fhi);
+            }
             mask_t act = alive;
             // one FISTA iteration: reads x from xo/ro, leaves x_{k+1} in xn/rn, advances y/ry (XLDS: x_k from LDS, x_{k+1} to LDS;
             // the four arrays are then no more than the iteration's temporaries)
@@ -480,23 +516,64 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
                         UNROLL for (int j = 0; j < NF; ++j) xo[j] = Fz[j];
                         UNROLL for (int k = 0; k < 6; ++k) ro[k] = RFz[k];
                     }
-                    double g2s = (double)g2, cvs = (double)cv;
-                    if (CERT) {
-                        sum1(g2s);
-                        // a live problem's step below the floor: nothing of this iteration is kept, the tested loop runs it again
-                        if ((seg_uniform<LPP>(__ballot(g2s < floor2) & seg_desig<LPP>()) & act) != 0) return false;
-                    } else sum2(g2s, cvs);
-                    // fista.cpp:14-17: G = sqrt(g2); retry if cv > (L/2) G*G; done if G < tol.  G*G and g2
-                    // differ by a few ulp, so outside a 1e-14 relative band the sqrt cannot change either
-                    // decision; inside it the reference expression is evaluated as written.
-                    const double Lh = (double)L_f * 0.5, rhs = Lh * g2s;
-                    mask_t bt = CERT ? mask_t(0) : __ballot(cvs > rhs);      // (certified: cvs <= rhs whatever the step)
-                    done = __ballot(g2s < tol2);
-                    const mask_t edge = __ballot((!CERT && fabs(cvs - rhs) <= 1e-14 * rhs) || (fabs(g2s - tol2) <= 1e-14 * tol2)) & seg_desig<LPP>();
-                    if (edge != 0) {
-                        const double Gn = sqrt(g2s);
-                        if (!CERT) bt = __ballot(cvs > Lh * (Gn * Gn));
-                        done = __ballot(Gn < tol);
+                    mask_t bt;
+                    if constexpr (BAND) {      // (the other instantiations compile the code below the `else` alone, as before the shortcut)
+                        bt = 0;      // (certified: cvs <= rhs whatever the step)
+                        mask_t unclear = ~mask_t(0);      // designated lanes of live problems whose fp32 decisions are not clear
+                        if (banded != 0) {      // the fp32 decisions, if every live problem's are clear (see BAND)
+                            float gf = (float)g2, cf = (float)cv;
+                            if (CERT) seg_sum1_f32<LPP>(gf);
+                            else seg_sum2_f32<LPP>(gf, cf);
+                            const mask_t yes = CERT ? __ballot(gf < flo) : __ballot(cf > gf * Lhi);
+                            const mask_t no = CERT ? __ballot(gf > fhi) : __ballot(cf < gf * Llo);
+                            const mask_t dyes = __ballot(gf < t2lo), dno = __ballot(gf > t2hi);
+                            const mask_t clear = (yes | no) & (dyes | dno) & __ballot(gf >= 1e-24f) & __ballot(gf <= 1e30f);
+                            unclear = ~clear & seg_desig<LPP>() & act;
+                            if (unclear == 0) {
+                                if (CERT && (seg_uniform<LPP>(yes & seg_desig<LPP>()) & act) != 0) return false;      // (see below)
+                                if (!CERT) bt = yes;
+                                done = dyes;
+                            }
+                        }
+                        if (unclear != 0) {
+                            double g2s = (double)g2, cvs = (double)cv;
+                            if (CERT) {
+                                sum1(g2s);
+                                // a live problem's step below the floor: nothing of this iteration is kept, the tested loop runs it again
+                                if ((seg_uniform<LPP>(__ballot(g2s < floor2) & seg_desig<LPP>()) & act) != 0) return false;
+                            } else sum2(g2s, cvs);
+                            // fista.cpp:14-17: G = sqrt(g2); retry if cv > (L/2) G*G; done if G < tol.  G*G and g2
+                            // differ by a few ulp, so outside a 1e-14 relative band the sqrt cannot change either
+                            // decision; inside it the reference expression is evaluated as written.
+                            const double Lh = (double)L_f * 0.5, rhs = Lh * g2s;
+                            if (!CERT) bt = __ballot(cvs > rhs);
+                            done = __ballot(g2s < tol2);
+                            const mask_t edge = __ballot((!CERT && fabs(cvs - rhs) <= 1e-14 * rhs) || (fabs(g2s - tol2) <= 1e-14 * tol2)) & seg_desig<LPP>();
+                            if (edge != 0) {
+                                const double Gn = sqrt(g2s);
+                                if (!CERT) bt = __ballot(cvs > Lh * (Gn * Gn));
+                                done = __ballot(Gn < tol);
+                            }
+                        }
+                    } else {
+                        double g2s = (double)g2, cvs = (double)cv;
+                        if (CERT) {
+                            sum1(g2s);
+                            // a live problem's step below the floor: nothing of this iteration is kept, the tested loop runs it again
+                            if ((seg_uniform<LPP>(__ballot(g2s < floor2) & seg_desig<LPP>()) & act) != 0) return false;
+                        } else sum2(g2s, cvs);
+                        // fista.cpp:14-17: G = sqrt(g2); retry if cv > (L/2) G*G; done if G < tol.  G*G and g2
+                        // differ by a few ulp, so outside a 1e-14 relative band the sqrt cannot change either
+                        // decision; inside it the reference expression is evaluated as written.
+                        const double Lh = (double)L_f * 0.5, rhs = Lh * g2s;
+                        bt = CERT ? mask_t(0) : __ballot(cvs > rhs);      // (certified: cvs <= rhs whatever the step)
+                        done = __ballot(g2s < tol2);
+                        const mask_t edge = __ballot((!CERT && fabs(cvs - rhs) <= 1e-14 * rhs) || (fabs(g2s - tol2) <= 1e-14 * tol2)) & seg_desig<LPP>();
+                        if (edge != 0) {
+                            const double Gn = sqrt(g2s);
+                            if (!CERT) bt = __ballot(cvs > Lh * (Gn * Gn));
+                            done = __ballot(Gn < tol);
+                        }
                     }
                     bt = seg_uniform<LPP>(bt);      // (LPP = 21: the sums live at three lanes; their decisions go to their segments)
                     done = seg_uniform<LPP>(done);
@@ -509,6 +586,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
                     if (bt == 0) break;
                     if (lanes(bt)) { L_f *= beta; ++bt_f; }
                     invL = R(2) * (R(1) / L_f);
+                    if constexpr (BAND) if (banded != 0) band_L((double)L_f * 0.5, Llo, Lhi);
                 }
                 if (!XLDS) {
                     const mask_t last = act & (i == maxit - 1 ? ~mask_t(0) : done) & rvalid_m;
@@ -653,6 +731,14 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
             const double tol2 = tol * tol;
             if (PARK) load_xloop();
             R invL = R(2) * (R(1) / L_x);
+            mask_t banded = 0;      // (see the force step)
+            float Llo = 0.0f, Lhi = 0.0f;
+            if constexpr (BAND) if (!a.exact_step_decisions) {
+                bool wneg = false;
+                UNROLL for (int l = 0; l < 9; ++l) wneg = wneg || qd[l] < R(0);
+                banded = rho >= R(0) && __ballot(wneg) == 0 ? ~mask_t(0) : mask_t(0);
+                band_L((double)L_x * 0.5, Llo, Lhi);
+            }
             mask_t act = alive;
             auto iterate = [&](const R (&xo_reg)[9], const R (&ro_reg)[9], R (&xn)[9], R (&rn)[9], int i) {
                 const R cm = (R)cmtab[i];
@@ -688,16 +774,44 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
                     }
                     cv = fmaR(rho, e2, cv);
                     if (XLDS) { UNROLL for (int l = 0; l < 9; ++l) { xo[l] = Xz[l]; ro[l] = RXz[l]; } }      // (see the force step)
-                    double g2s = (double)g2, cvs = (double)cv;
-                    sum2(g2s, cvs);
-                    const double Lh = (double)L_x * 0.5, rhs = Lh * g2s;   // see the force loop for the sqrt-free form
-                    mask_t bt = __ballot(cvs > rhs);
-                    done = __ballot(g2s < tol2);
-                    const mask_t edge = __ballot((fabs(cvs - rhs) <= 1e-14 * rhs) || (fabs(g2s - tol2) <= 1e-14 * tol2)) & seg_desig<LPP>();
-                    if (edge != 0) {
-                        const double Gn = sqrt(g2s);
-                        bt = __ballot(cvs > Lh * (Gn * Gn));
-                        done = __ballot(Gn < tol);
+                    mask_t bt;
+                    if constexpr (BAND) {
+                        mask_t unclear = ~mask_t(0);
+                        bt = 0;
+                        if (banded != 0) {      // the fp32 decisions, if every live problem's are clear (see the force step)
+                            float gf = (float)g2, cf = (float)cv;
+                            seg_sum2_f32<LPP>(gf, cf);
+                            const mask_t yes = __ballot(cf > gf * Lhi), no = __ballot(cf < gf * Llo);
+                            const mask_t dyes = __ballot(gf < t2lo), dno = __ballot(gf > t2hi);
+                            const mask_t clear = (yes | no) & (dyes | dno) & __ballot(gf >= 1e-24f) & __ballot(gf <= 1e30f);
+                            unclear = ~clear & seg_desig<LPP>() & act;
+                            if (unclear == 0) { bt = yes; done = dyes; }
+                        }
+                        if (unclear != 0) {
+                            double g2s = (double)g2, cvs = (double)cv;
+                            sum2(g2s, cvs);
+                            const double Lh = (double)L_x * 0.5, rhs = Lh * g2s;   // see the force loop for the sqrt-free form
+                            bt = __ballot(cvs > rhs);
+                            done = __ballot(g2s < tol2);
+                            const mask_t edge = __ballot((fabs(cvs - rhs) <= 1e-14 * rhs) || (fabs(g2s - tol2) <= 1e-14 * tol2)) & seg_desig<LPP>();
+                            if (edge != 0) {
+                                const double Gn = sqrt(g2s);
+                                bt = __ballot(cvs > Lh * (Gn * Gn));
+                                done = __ballot(Gn < tol);
+                            }
+                        }
+                    } else {
+                        double g2s = (double)g2, cvs = (double)cv;
+                        sum2(g2s, cvs);
+                        const double Lh = (double)L_x * 0.5, rhs = Lh * g2s;   // see the force loop for the sqrt-free form
+                        bt = __ballot(cvs > rhs);
+                        done = __ballot(g2s < tol2);
+                        const mask_t edge = __ballot((fabs(cvs - rhs) <= 1e-14 * rhs) || (fabs(g2s - tol2) <= 1e-14 * tol2)) & seg_desig<LPP>();
+                        if (edge != 0) {
+                            const double Gn = sqrt(g2s);
+                            bt = __ballot(cvs > Lh * (Gn * Gn));
+                            done = __ballot(Gn < tol);
+                        }
                     }
                     bt = seg_uniform<LPP>(bt);      // (LPP = 21: the sums live at three lanes; their decisions go to their segments)
                     done = seg_uniform<LPP>(done);
@@ -707,6 +821,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
                     if (bt == 0) break;
                     if (lanes(bt)) { L_x *= beta; ++bt_x; }
                     invL = R(2) * (R(1) / L_x);
+                    if constexpr (BAND) if (banded != 0) band_L((double)L_x * 0.5, Llo, Lhi);
                 }
                 if (!XLDS) {
                     const mask_t last = act & (i == maxit - 1 ? ~mask_t(0) : done) & kvalid_m;

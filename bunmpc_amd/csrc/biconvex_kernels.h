@@ -38,7 +38,7 @@ struct SolverConsts {
 struct BatchArgs {
     int B, H, raw, cold_start;
     int precision;   // 0: fp64 arithmetic; 1: fp32 iterates with fp64 decisions (harness form only)
-    int exact_step_decisions;   // 1: the one-problem-per-wave kernel skips the fp32 shortcut of its step decisions (tests)
+    int exact_step_decisions;   // (set by the launcher) 1: the kernels with the fp32 shortcut of their step decisions skip it (tests)
     int certified_steps;        // (set by the launcher) 1: fp64 batch kernels skip the backtracking test in phases whose step is certified
     double L0_x, L0_f;
     SolverConsts c;
@@ -91,7 +91,7 @@ int biconvex_last_waves_per_simd();                  // of the calling host thre
 int set_steal_grid(int waves);                       // waves of the work-stealing kernel's persistent grid (experiments; 0 = what the chip holds); returns the old value
 int set_work_stealing(int on);                       // the segment-level work-stealing kernel for num_iters >= 25 (default on); returns the old value
 int biconvex_last_lanes_per_problem();               // of the calling host thread's latest launch: 16 / 21 / 32 / 64, 0 = one problem per wave
-int set_exact_step_decisions(int on);                // ... takes every step decision from the fp64 sums; returns the old value
+int set_exact_step_decisions(int on);                // every step decision from the fp64 sums, in every centroidal kernel; returns the old value
 int set_certified_steps(int on);                     // the fp64 batch kernels' per-phase step certificate (default on); returns the old value
 
 // fp32 instantiations (biconvex_admm_f32.hip: E = 4, biconvex_admm_f32_e2.hip: E = 2); called by launch_biconvex_admm with the

@@ -160,6 +160,44 @@ __device__ __forceinline__ void seg_sum1(double &a) {
     a = seg_sum<LPP>(a);
 }
 
+// ---- fp32 segment sums for the step decisions of the batch kernel (biconvex_admm_body.h: `banded`).  seg_sum2's butterfly on floats:
+// each add takes its partner through DPP (one v_add_f32 with the move fused into it: no v_mov_b32_dpp), each permlane swap moves one
+// dword per value instead of two.  Fixed order of additions, so every lane of a segment holds the same bits.  Conversion (2^-24) and
+// at most six adds (2^-24 each) on non-negative terms: within 5e-7 of the exact sum, relative.  Power-of-two
+// segments only (the 21-lane kernels keep the fp64 sums).
+// the two sums of a and b over the LPP-lane segment (valid where seg_sum2's are)
+template <int LPP>
+__device__ __forceinline__ void seg_sum2_f32(float &a, float &b) {
+    static_assert(LPP == 16 || LPP == 32 || LPP == 64, "power-of-two segments");
+    a += dpp_mov<DPP_QUAD_XOR1>(a); b += dpp_mov<DPP_QUAD_XOR1>(b);
+    a += dpp_mov<DPP_QUAD_XOR2>(a); b += dpp_mov<DPP_QUAD_XOR2>(b);
+    a += dpp_mov<DPP_ROW_HALF_MIRROR>(a); b += dpp_mov<DPP_ROW_HALF_MIRROR>(b);
+    a += dpp_mov<DPP_ROW_MIRROR>(a); b += dpp_mov<DPP_ROW_MIRROR>(b);
+    if (LPP >= 32) {
+        auto x = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(a), false, false);
+        auto y = __builtin_amdgcn_permlane16_swap(__float_as_uint(b), __float_as_uint(b), false, false);
+        a = __uint_as_float(x[0]) + __uint_as_float(x[1]);
+        b = __uint_as_float(y[0]) + __uint_as_float(y[1]);
+    }
+    if (LPP >= 64) {
+        auto x = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(a), false, false);
+        auto y = __builtin_amdgcn_permlane32_swap(__float_as_uint(b), __float_as_uint(b), false, false);
+        a = __uint_as_float(x[0]) + __uint_as_float(x[1]);
+        b = __uint_as_float(y[0]) + __uint_as_float(y[1]);
+    }
+}
+// ... of a alone (seg_sum2_f32's operations on a, hence its bits)
+template <int LPP>
+__device__ __forceinline__ void seg_sum1_f32(float &a) {
+    static_assert(LPP == 16 || LPP == 32 || LPP == 64, "power-of-two segments");
+    a += dpp_mov<DPP_QUAD_XOR1>(a);
+    a += dpp_mov<DPP_QUAD_XOR2>(a);
+    a += dpp_mov<DPP_ROW_HALF_MIRROR>(a);
+    a += dpp_mov<DPP_ROW_MIRROR>(a);
+    if (LPP >= 32) { auto x = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(a), false, false); a = __uint_as_float(x[0]) + __uint_as_float(x[1]); }
+    if (LPP >= 64) { auto x = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(a), false, false); a = __uint_as_float(x[0]) + __uint_as_float(x[1]); }
+}
+
 // The two decisions of a FISTA step -- retry (cv > (L/2) g2) and exit (g2 < tol^2) -- from WAVE sums of g2 and cv taken in fp32:
 // 4 DPP-fused v_add_f32 per value, one v_permlane16_swap that leaves the sums of g2 in rows 0 / 2 and of cv in rows 1 / 3, one
 // v_permlane32_swap, two v_readlane: 19 instructions against the 36 of the fp64 butterfly (seg_sum2<64>).  The fp32 sums of

@@ -181,10 +181,11 @@ int bmpc_set_two_waves_per_simd(int mode);
 int bmpc_biconvex_last_lanes_per_problem(void);
 /* ... and the waves per SIMD its kernel was built for (1 or 2) */
 int bmpc_biconvex_last_waves_per_simd(void);
-/* The one-problem-per-wave kernel takes the two decisions of a FISTA step (retry, fista.cpp:16; exit, fista.cpp:29) from fp32
- * wave sums whenever both comparisons are clear of their thresholds by 1e-5 relative, from the fp64 sums and the reference
- * expression otherwise.  on = 1: always from the fp64 sums (a test switch: results must be bit-identical either way).
- * Returns the old value. */
+/* Two centroidal kernels take the decisions of a FISTA step (retry, fista.cpp:16; exit, fista.cpp:29) from fp32 sums whenever every
+ * comparison of the wave's live problems is clear of its threshold by 1e-5 relative, from the fp64 sums and the reference expression
+ * otherwise: the one-problem-per-wave kernel, and the two-waves-per-SIMD build of the batch kernel at 32 lanes per problem, four feet,
+ * harness form (the benchmark's kernel).  Every other kernel always uses the fp64 sums.  on = 1: those two as well
+ * (a test switch: results must be bit-identical either way).  Returns the old value. */
 int bmpc_set_exact_step_decisions(int on);
 /* The fp64 batch kernels skip FISTA's backtracking test for a whole force step (one ADMM iteration's force-QP loop) of a wave whose
  * live problems all carry a certificate that the test cannot fire: a diagonally scaled Gershgorin bound of the step's Hessian

@@ -1,0 +1,140 @@
+#!/usr/bin/env python3
+"""Vector instructions per loop of one kernel in a hipcc -S listing.  Every innermost loop (a block range closed by a backward branch:
+the FISTA iteration bodies) with the vector (VALU) instructions it holds in all -- DPP moves, permlanes, readlanes and conversions included,
+memory and scalar instructions not -- and the same on the cheapest path through the body (from its head to its back edge: an
+iteration that takes none of the branches it can skip -- the cone step, the retry bookkeeping, the fp64 fall-back of the step
+decisions), with that path's fp64 arithmetic (v_fma_f64, v_fmac_f64, v_mul_f64, v_add_f64), DPP moves, DPP-fused operations and
+permlanes.  Also the kernel's registers, scratch and static LDS as the compiler reports them.
+
+    python tools/loop_valu.py LISTING.s KERNEL_SUBSTRING [--through RE] [--blocks]
+    python tools/loop_valu.py --compile bunmpc_amd/csrc/biconvex_admm.hip KERNEL_SUBSTRING [--through RE] [--blocks]
+        (--compile: device code of the unit with bunmpc_amd/build.py's flags for it; --through RE: the cheapest path that runs an
+        instruction matching RE, e.g. 'permlane' for an iteration that reduces its sums -- in fp32 where it can)
+
+The headline kernel: 'biconvex_admm_kernelIdLi32ELi4ELb0ELb0ELi2E' (biconvex_admm_kernel<double, 32, 4, false, false, 2>)."""
+import collections
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F64 = ("v_fma_f64", "v_fmac_f64", "v_mul_f64", "v_add_f64")
+NOT_VALU = ("global_", "buffer_", "flat_", "scratch_", "ds_", "s_")
+
+
+def compile_listing(src):
+    sys.path.insert(0, ROOT)
+    from bunmpc_amd import build
+    out = os.path.join(tempfile.mkdtemp(), os.path.basename(src) + ".s")
+    cmd = [build.HIPCC] + build.FLAGS + build.FILE_FLAGS.get(os.path.basename(src), []) + \
+          ["--cuda-device-only", "-S", "-I", os.path.join(ROOT, "include"), src, "-o", out]
+    subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
+    return out
+
+
+def is_valu(mn):
+    return mn.startswith("v_") and not mn.startswith(NOT_VALU)
+
+
+def base(mn):
+    return re.sub(r"_(e32|e64|dpp|sdwa)$", "", mn)
+
+
+def blocks_of(body):
+    """basic blocks [(label, first line, [(mnemonic, text)])] in listing order: a label starts one, a branch ends one (the code behind
+    a conditional branch is a block of its own, named label+n)"""
+    out, cur, n = [], ("entry", 0, []), 0
+    for i, l in enumerate(body):
+        m = re.match(r"^(\.LBB\d+_\d+):", l)
+        if m:
+            out.append(cur)
+            cur, n = (m.group(1), i, []), 0
+            continue
+        t = l.split(";")[0].strip()
+        if t and not t.startswith("."):
+            if cur[2] and cur[2][-1][0].startswith(("s_branch", "s_cbranch")):
+                out.append(cur)
+                n += 1
+                cur = ("%s+%d" % (cur[0].split("+")[0], n), i, [])
+            cur[2].append((t.split()[0], t))
+    out.append(cur)
+    return out
+
+
+def resources(lines, end):
+    """the compiler's kernel-info comments after the function"""
+    res = {}
+    for l in lines[end:end + 40]:
+        m = re.match(r"; (TotalNumSgprs|NumVgprs|NumAgprs|ScratchSize|Occupancy|LDSByteSize): (\d+)", l)
+        if m:
+            res[m.group(1)] = int(m.group(2))
+    return res
+
+
+def main():
+    argv = sys.argv[1:]
+    through = argv[argv.index("--through") + 1] if "--through" in argv else None
+    if through:
+        del argv[argv.index("--through"):argv.index("--through") + 2]
+    args = [a for a in argv if not a.startswith("--")]
+    listing = compile_listing(args[0]) if "--compile" in sys.argv else args[0]
+    lines = open(listing).read().split("\n")
+    start = next(i for i, l in enumerate(lines) if args[1] in l and re.match(r"^[A-Za-z_][\w.]*:", l))
+    end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
+    body = lines[start:end]
+    name = body[0].split(":")[0]
+    res = resources(lines, end)
+    print(name)
+    print("  vgpr %s  agpr %s  sgpr %s  scratch %s B/lane  static LDS %s B  occupancy %s" % tuple(
+        res.get(k) for k in ("NumVgprs", "NumAgprs", "TotalNumSgprs", "ScratchSize", "LDSByteSize", "Occupancy")))
+    blocks = blocks_of(body)
+    index = {b[0]: k for k, b in enumerate(blocks)}
+    edges = [(k, index[t.split()[-1]], mn) for k, (_, _, ins) in enumerate(blocks) for mn, t in ins
+             if mn.startswith(("s_branch", "s_cbranch")) and t.split()[-1] in index]
+    loops = sorted({(dst, src) for src, dst, _ in edges if dst <= src})
+    inner = [(a, b) for a, b in loops if not any((c, d) != (a, b) and a <= c and d <= b for c, d in loops)]
+    nvalu = [sum(1 for mn, _ in blk[2] if is_valu(mn)) for blk in blocks]
+    for a, b in inner:
+        # the cheapest way through the body: from the head to the block of the back edge along forward edges (fall-through or branch)
+        succ = {k: set() for k in range(a, b + 1)}
+        for k in range(a, b):
+            ins = blocks[k][2]
+            if not (ins and ins[-1][0] == "s_branch"):
+                succ[k].add(k + 1)
+        for src, dst, _ in edges:
+            if a <= src < dst <= b:
+                succ[src].add(dst)
+        # (--through RE: the cheapest path that executes an instruction matching RE -- the segment sums: 'permlane')
+        has = [bool(through) and any(re.search(through, t) for _, t in blk[2]) for blk in blocks]
+        cost, prev = {(a, has[a] or not through): (nvalu[a], None)}, {}
+        for k in range(a, b + 1):
+            for seen in (False, True):
+                if (k, seen) in cost:
+                    for n in succ[k]:
+                        st = (n, seen or has[n])
+                        c = cost[(k, seen)][0] + nvalu[n]
+                        if st not in cost or c < cost[st][0]:
+                            cost[st] = (c, (k, seen))
+        path, st = [], (b, True)
+        while st is not None and (b, True) in cost:
+            path.append(st[0])
+            st = cost[st][1]
+        hot = [(mn, t) for k in path for mn, t in blocks[k][2]]
+        f64 = collections.Counter(base(mn) for mn, _ in hot if base(mn) in F64)
+        dpp_mov = sum(1 for mn, t in hot if mn.startswith("v_mov_b32") and re.search(r"quad_perm|row_|wave_", t))
+        dpp_op = sum(1 for mn, t in hot if is_valu(mn) and not mn.startswith("v_mov_b32") and re.search(r"quad_perm|row_", t))
+        perm = sum(1 for mn, _ in hot if mn.startswith("v_permlane"))
+        last = blocks[b + 1][1] if b + 1 < len(blocks) else len(body)
+        print("  loop %s..%s (listing lines %d..%d): VALU %d in all, %d on the cheapest path | on it: %s, DPP moves %d, DPP-fused ops %d, "
+              "permlanes %d" % (blocks[a][0], blocks[b][0], start + blocks[a][1] + 1, start + last, sum(nvalu[a:b + 1]),
+                                sum(1 for mn, _ in hot if is_valu(mn)), " ".join("%s %d" % (f, f64[f]) for f in F64), dpp_mov, dpp_op, perm))
+        if "--blocks" in sys.argv:
+            for k in range(a, b + 1):
+                br = [t for mn, t in blocks[k][2] if mn.startswith(("s_branch", "s_cbranch"))]
+                print("    %-14s %-4s VALU %4d  %s" % (blocks[k][0], "path" if k in path else "", nvalu[k], "; ".join(br)))
+
+
+if __name__ == "__main__":
+    main()
