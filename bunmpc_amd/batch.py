@@ -26,6 +26,19 @@ def _stride(a):
     return 0 if a.shape[0] == 1 else int(np.prod(a.shape[1:]))
 
 
+def _block_cost(B, H, E, Qx_blk, Qf_blk, put):
+    """bmpc_block_cost_t of Qx_blk (1 or B, H + 1, 9, 9) / Qf_blk (1 or B, H, 3E, 3E), either None; put(array) -> its address"""
+    c = _lib.BlockCost()
+    for name, a, shape in (("Qx_blk", Qx_blk, (H + 1, 9, 9)), ("Qf_blk", Qf_blk, (H, 3 * E, 3 * E))):
+        if a is None:
+            continue
+        if a.shape[1:] != shape or a.shape[0] not in (1, B):
+            raise ValueError("%s: expected shape (1 or %d, %d, %d, %d), got %s" % ((name, B) + shape + (tuple(a.shape),)))
+        setattr(c, name, put(a))
+        setattr(c, "s" + name, _stride(a))
+    return c
+
+
 def algorithmic_bytes_per_solve(H, E=4, per_problem_weights=False):
     """inputs (4E+10)H+18 doubles, outputs 18(H+1)+3EH+1 doubles
     (+ 9+9+3E+6+3 doubles when weights are per problem)."""
@@ -37,12 +50,14 @@ def algorithmic_bytes_per_solve(H, E=4, per_problem_weights=False):
 
 class DeviceBatch:
     """A problems.Batch resident on one GPU, harness form (the kernel applies create_cost_X /
-    create_cost_F / create_bound_constraints itself)."""
+    create_cost_F / create_bound_constraints itself) or, with raw=, the raw form."""
 
     def __init__(self, batch, device="cuda", num_iters=10, maxit=150, tol=1e-5, exit_tol=1e-3,
-                 beta=1.5, mu=None, keep_hist=False, precision="f64", plan=None):
+                 beta=1.5, mu=None, keep_hist=False, precision="f64", plan=None, raw=None):
         """plan: a plan_batch.DevicePlan whose tensors (cnt_plan, dt, X_nom, X_ter, x_init) are used in place of the
-        batch's host arrays -- inputs built on the GPU never leave HBM"""
+        batch's host arrays -- inputs built on the GPU never leave HBM.
+        raw: dict(Qx, qx, lbx, ubx, Qf[, qf][, Qx_blk][, Qf_blk]) -- the raw cost / bound form (solve_host explains it); with
+        Qx_blk / Qf_blk the per-knot block costs, through bmpc_biconvex_solve_batch_blocks_device"""
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("DeviceBatch needs a GPU: no CPU fallback exists for the solve")
@@ -62,7 +77,19 @@ class DeviceBatch:
         else:
             assert plan.B == B and plan.H == H
             self.t = dict(cnt_plan=plan.cnt_plan, dt=plan.dt, x_init=plan.inp["x_init"], X_nom=plan.X_nom, X_ter=plan.X_ter)
-        self.t.update(W_X=up(batch.W_X), W_X_ter=up(batch.W_X_ter), W_F=up(batch.W_F), bounds=up(batch.bounds))
+        self.blocks = None
+        if raw is None:
+            self.t.update(W_X=up(batch.W_X), W_X_ter=up(batch.W_X_ter), W_F=up(batch.W_F), bounds=up(batch.bounds))
+        else:
+            for k in ("X_nom", "X_ter"):
+                del self.t[k]
+            for k in ("Qx", "qx", "lbx", "ubx", "Qf", "qf"):
+                if raw.get(k) is not None and not (k in ("Qx", "Qf") and raw.get(k + "_blk") is not None):
+                    assert np.shape(raw[k]) == (B, 3 * E * H if k in ("Qf", "qf") else 9 * (H + 1)), k
+                    self.t[k] = up(raw[k])
+            self.tb = {k: up(raw[k]) for k in ("Qx_blk", "Qf_blk") if raw.get(k) is not None}
+            if self.tb:
+                self.blocks = _block_cost(B, H, E, self.tb.get("Qx_blk"), self.tb.get("Qf_blk"), lambda t: t.data_ptr())
         self.X = torch.empty((B, 9 * (H + 1)), dtype=f64, device=self.device)
         self.F = torch.empty((B, 3 * E * H), dtype=f64, device=self.device)
         self.P = torch.empty((B, 9 * (H + 1)), dtype=f64, device=self.device)
@@ -78,12 +105,13 @@ class DeviceBatch:
         _lib.lib().bmpc_batch_defaults(C.byref(d))
         _solver_fields(d, batch, num_iters, maxit, tol, exit_tol, beta, mu)
         d.precision = {"f64": 0, "f32": 1}[precision]
-        d.raw = 0
+        d.raw = 0 if raw is None else 1
         d.cold_start = 1
         for k, v in self.t.items():
             setattr(d, k, v.data_ptr())
-        d.sW_X, d.sW_X_ter = _stride(batch.W_X), _stride(batch.W_X_ter)
-        d.sW_F, d.sbounds = _stride(batch.W_F), _stride(batch.bounds)
+        if raw is None:
+            d.sW_X, d.sW_X_ter = _stride(batch.W_X), _stride(batch.W_X_ter)
+            d.sW_F, d.sbounds = _stride(batch.W_F), _stride(batch.bounds)
         d.X, d.F, d.P = self.X.data_ptr(), self.F.data_ptr(), self.P.data_ptr()
         d.L_x, d.L_f = self.L_x.data_ptr(), self.L_f.data_ptr()
         d.dyn_viol, d.stats = self.dyn_viol.data_ptr(), self.stats.data_ptr()
@@ -120,7 +148,10 @@ class DeviceBatch:
         if self.hist is not None:      # rows of ADMM iterations that do not run keep their NaN / -1
             self.hist.fill_(float("nan"))
             self.trace.fill_(-1)
-        _lib.check(_lib.lib().bmpc_biconvex_solve_batch_device(C.byref(self.desc), C.c_void_p(stream)))
+        if self.blocks is not None:
+            _lib.check(_lib.lib().bmpc_biconvex_solve_batch_blocks_device(C.byref(self.desc), C.byref(self.blocks), C.c_void_p(stream)))
+        else:
+            _lib.check(_lib.lib().bmpc_biconvex_solve_batch_device(C.byref(self.desc), C.c_void_p(stream)))
 
     def results(self):
         self.torch.cuda.synchronize(self.device)
@@ -137,7 +168,9 @@ def solve_host(batch, num_iters=10, maxit=150, tol=1e-5, exit_tol=1e-3, beta=1.5
                warm=None, L_x=None, L_f=None, raw=None, keep_hist=False, precision="f64"):
     """numpy in / numpy out through bmpc_biconvex_solve_batch_host (copies in, one launch,
     copies out).  warm = (X, F, P) or None for a cold start.  raw = dict(Qx,qx,lbx,ubx,Qf[,qf])
-    switches to the raw cost/bound form."""
+    switches to the raw cost/bound form; with Qx_blk (1 or B, H + 1, 9, 9) and / or Qf_blk (1 or B, H, 3E, 3E) in it that side's
+    cost is block-diagonal per knot (symmetric blocks; a leading dimension of 1: shared by the batch) and its Qx / Qf may be left
+    out (bmpc_biconvex_solve_batch_blocks_host)."""
     B, H, E = batch.B, batch.H, batch.E
     nx, nf = 9 * (H + 1), 3 * E * H
     keep = []
@@ -161,7 +194,11 @@ def solve_host(batch, num_iters=10, maxit=150, tol=1e-5, exit_tol=1e-3, beta=1.5
         d.sW_F, d.sbounds = _stride(batch.W_F), _stride(batch.bounds)
     else:
         d.raw = 1
+        blocks = _block_cost(B, H, E, *(None if raw.get(k) is None else f64(raw[k]) for k in ("Qx_blk", "Qf_blk")),
+                             put=lambda a: a.ctypes.data)
         for k in ("Qx", "qx", "lbx", "ubx", "Qf"):
+            if raw.get(k) is None and k in ("Qx", "Qf") and raw.get(k + "_blk") is not None:
+                continue
             a = f64(raw[k])
             assert a.shape == (B, nf if k == "Qf" else nx), k
             setattr(d, k, a.ctypes.data)
@@ -183,7 +220,10 @@ def solve_host(batch, num_iters=10, maxit=150, tol=1e-5, exit_tol=1e-3, beta=1.5
     trace = np.full((B, max(num_iters, 1), 4), -1, dtype=np.int32) if keep_hist else None
     d.hist = hist.ctypes.data if keep_hist else None
     d.trace = trace.ctypes.data if keep_hist else None
-    _lib.check(_lib.lib().bmpc_biconvex_solve_batch_host(C.byref(d)))
+    if raw is not None and (blocks.Qx_blk or blocks.Qf_blk):
+        _lib.check(_lib.lib().bmpc_biconvex_solve_batch_blocks_host(C.byref(d), C.byref(blocks)))
+    else:
+        _lib.check(_lib.lib().bmpc_biconvex_solve_batch_host(C.byref(d)))
     out = dict(X=X, F=F, P=P, L_x=Lx, L_f=Lf, dyn_viol=viol, stats=stats.astype(np.int64))
     if keep_hist:
         out["hist"] = hist

@@ -3,9 +3,13 @@
 (same method names, argument meaning and print-and-continue error behaviour), backed by
 the C-ABI in include/bunmpc.h; `optimize` runs the gfx950 ADMM kernel.
 
-Differences that are deliberate and visible: `set_cost_x/f` accept only a diagonal Q (the
-only form the reference's own callers build); wrong sizes raise ValueError instead of
-reading out of bounds."""
+`set_cost_x/f` take what the reference's take -- a 1-D diagonal, a dense square matrix or a scipy.sparse matrix -- and classify it
+by structure: a diagonal goes the diagonal way (as before), a matrix that is block-diagonal per knot (9 x 9 blocks for X,
+3 n_eff x 3 n_eff for F) and exactly symmetric goes to the block-cost kernel (fp64, n_col + 1 <= 64 knots).
+
+Differences that are deliberate and visible: a Q that couples different knots, or an asymmetric one (the reference's gradient 2 Q y
+and its acceptance test agree for symmetric Q only), raises ValueError naming the first offending (row, col); wrong sizes raise
+ValueError instead of reading out of bounds."""
 import ctypes as C
 
 import numpy as np
@@ -20,25 +24,42 @@ def _vec(a, n, name):
     return a
 
 
-def _diag_of(Q, n, name):
+def classify_cost(Q, n, k, name):
+    """What set_cost_x / set_cost_f do with Q (n x n, knots of k variables): ("diag", d [n]) or ("blocks", blk [n / k][k][k]).
+    ValueError for a matrix that is not square of size n, has a non-zero outside its knots' blocks, or is not exactly symmetric."""
     if hasattr(Q, "tocoo"):  # scipy sparse
         coo = Q.tocoo()
         if coo.shape != (n, n):
             raise ValueError("%s: expected a %dx%d matrix" % (name, n, n))
-        off = coo.row != coo.col
-        if np.any(coo.data[off] != 0):
-            raise ValueError("%s: only diagonal Q is supported" % name)
+        nz = coo.data != 0
+        row, col, val = coo.row[nz].astype(np.int64), coo.col[nz].astype(np.int64), np.asarray(coo.data[nz], dtype=np.float64)
+    else:
+        Q = np.asarray(Q, dtype=np.float64)
+        if Q.ndim == 1:
+            return "diag", _vec(Q, n, name)
+        if Q.shape != (n, n):
+            raise ValueError("%s: expected a %dx%d matrix" % (name, n, n))
+        row, col = np.nonzero(Q)
+        val = Q[row, col]
+    order = np.lexsort((col, row))
+    row, col, val = row[order], col[order], val[order]
+    if np.all(row == col):
         d = np.zeros(n)
-        np.add.at(d, coo.row[~off], coo.data[~off])
-        return d
-    Q = np.asarray(Q, dtype=np.float64)
-    if Q.ndim == 1:
-        return _vec(Q, n, name)
-    if Q.shape != (n, n):
-        raise ValueError("%s: expected a %dx%d matrix" % (name, n, n))
-    if np.any(Q - np.diag(np.diag(Q)) != 0):
-        raise ValueError("%s: only diagonal Q is supported" % name)
-    return np.ascontiguousarray(np.diag(Q))
+        np.add.at(d, row, val)
+        return "diag", d
+    wide = row // k != col // k
+    if np.any(wide):
+        i = int(np.argmax(wide))
+        raise ValueError("%s: entry (%d, %d) couples knots %d and %d: only per-knot %dx%d blocks are supported"
+                         % (name, row[i], col[i], row[i] // k, col[i] // k, k, k))
+    blk = np.zeros((n // k, k, k))
+    np.add.at(blk, (row // k, row % k, col % k), val)      # (a sparse matrix may list an entry twice: they add up)
+    asym = blk != blk.transpose(0, 2, 1)
+    if np.any(asym):
+        t, r, c = (int(v[0]) for v in np.nonzero(asym))
+        raise ValueError("%s: entry (%d, %d) differs from (%d, %d): Q must be exactly symmetric (it is not symmetrised here)"
+                         % (name, t * k + r, t * k + c, t * k + c, t * k + r))
+    return "blocks", blk
 
 
 class BiconvexMP:
@@ -92,12 +113,16 @@ class BiconvexMP:
         return out
 
     def set_cost_x(self, Q_x, q_x):
-        Q, q = _diag_of(Q_x, self.nx, "Q_x"), _vec(q_x, self.nx, "q_x")
-        _lib.check(self._lib.bmpc_biconvex_set_cost_x(self._h, Q.ctypes.data, q.ctypes.data))
+        kind, Q = classify_cost(Q_x, self.nx, 9, "Q_x")
+        q = _vec(q_x, self.nx, "q_x")
+        fn = self._lib.bmpc_biconvex_set_cost_x if kind == "diag" else self._lib.bmpc_biconvex_set_cost_x_blocks
+        _lib.check(fn(self._h, Q.ctypes.data, q.ctypes.data))
 
     def set_cost_f(self, Q_f, q_f):
-        Q, q = _diag_of(Q_f, self.nf, "Q_f"), _vec(q_f, self.nf, "q_f")
-        _lib.check(self._lib.bmpc_biconvex_set_cost_f(self._h, Q.ctypes.data, q.ctypes.data))
+        kind, Q = classify_cost(Q_f, self.nf, 3 * self.n_eff, "Q_f")
+        q = _vec(q_f, self.nf, "q_f")
+        fn = self._lib.bmpc_biconvex_set_cost_f if kind == "diag" else self._lib.bmpc_biconvex_set_cost_f_blocks
+        _lib.check(fn(self._h, Q.ctypes.data, q.ctypes.data))
 
     def create_cost_X(self, W_X, W_X_ter, X_ter, X_nom):
         a = [_vec(W_X, self.nx - 9, "W_X"), _vec(W_X_ter, 9, "W_X_ter"), _vec(X_ter, 9, "X_ter"),

@@ -226,6 +226,27 @@ hipError_t launch_biconvex_admm(const BatchArgs &args, int n_eff, hipStream_t st
     return go({lpp, two_per_simd_pays(a, 64 / lpp), false, 0});
 }
 
+// Block costs (BlockArgs): the block kernel at every batch size and num_iters -- never the one-problem-per-wave, work-stealing or
+// two-waves kernels, which hold diagonal weights only.  The lanes per problem are chosen as above.
+hipError_t launch_biconvex_admm_blocks(const BatchArgs &args, const BlockArgs &q, int n_eff, hipStream_t stream) {
+    BatchArgs a = args;
+    if ((n_eff != 2 && n_eff != 4) || a.H < 1 || a.H + 1 > 64 || a.B < 0 || a.precision != 0 || !a.raw) return hipErrorInvalidValue;
+    if (a.B == 0) return hipSuccess;
+    if (a.c.maxit > kMaxFistaIters) return hipErrorInvalidValue;
+    for (long stride : {q.sQx_blk, q.sQf_blk})
+        if (stride < 0 || stride > (1L << 26)) return hipErrorInvalidValue;
+    a.exact_step_decisions = g_exact_step_decisions;      // (no effect: these kernels always take the fp64 sums)
+    a.certified_steps = 0;                                 // (... and test every step)
+    a.cmtab = momentum_table(stream);
+    if (!a.cmtab) return hipErrorOutOfMemory;
+    const int k = a.H + 1;
+    const int lpp = k <= 16 ? 16 : (k <= 21 && three_per_wave_pays(a) ? 21 : (k <= 32 ? 32 : 64));
+    t_last_kernel = "biconvex_admm_bq_kernel";
+    t_last_lpp = lpp;
+    t_last_wpe = 1;
+    return n_eff == 4 ? launch_admm_bq_e4(a, q, lpp, stream) : launch_admm_bq_e2(a, q, lpp, stream);
+}
+
 hipError_t launch_lane_selftest(const double *in, double *out, hipStream_t stream) {
     hipLaunchKernelGGL(lane_selftest_kernel, dim3(1), dim3(64), 0, stream, in, out);
     return hipGetLastError();

@@ -45,8 +45,19 @@
 constexpr double kCertEta = 1.0 / 64.0;
 constexpr double kCertFloor = 2.0 * 25.0 / (kCertEta * kCertEta) * 0x1p-80;
 
-template <typename R, int LPP, int E, bool RAW, bool HASQF, bool STEAL = false, bool XLDS = false, int WAVES = 1>
-__device__ __forceinline__ void admm_body(const BatchArgs &a) {
+// BQ (per-knot block-diagonal costs: raw form, fp64, one wave per SIMD): a lane holds its knot's SYMMETRIC block -- the upper triangle,
+// 45 values for X, 3E (3E + 1) / 2 for F -- where the other instantiations hold the knot's diagonal weights, loaded once per phase like
+// them.  Q y is a lane-local mat-vec and d'Q d a lane-local quadratic form, both accumulated row by row with the columns in increasing
+// index, in every lanes-per-problem mapping alike (only the segment sums differ between mappings, as without blocks); the chains start
+// from the terms the diagonal code adds its product to, so a block that holds a diagonal alone (exact zeros beside it) gives the
+// diagonal code's bits.  No step certificate (its Gershgorin rows assume a diagonal W) and no fp32 step decisions: every step is tested
+// on the fp64 sums.  Every BQ line is under `if constexpr`: the other instantiations compile what they compiled without it.
+// sym_index: where element (r, c) of a symmetric n x n block sits in its packed upper triangle (rows one after the other)
+constexpr int sym_index(int n, int r, int c) { return r <= c ? r * n - r * (r - 1) / 2 + (c - r) : c * n - c * (c - 1) / 2 + (r - c); }
+
+template <typename R, int LPP, int E, bool RAW, bool HASQF, bool STEAL = false, bool XLDS = false, int WAVES = 1, bool BQ = false>
+__device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &bq = BlockArgs{}) {
+    static_assert(!BQ || (RAW && !STEAL && !XLDS && WAVES == 1 && sizeof(R) == sizeof(double)), "block costs: raw form, fp64, one wave per problem, one wave per SIMD");
     constexpr bool MW = WAVES > 1;
     static_assert(!MW || (LPP == 64 && !STEAL && sizeof(R) == sizeof(double)), "several waves per problem: fp64, one problem per workgroup");
     constexpr bool PARK = XLDS && !MW;      // (the LDS header is written by lane 0 and read by the whole problem: across waves that would take barriers)
@@ -140,7 +151,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
     // The step certificate of a force phase: every lane of every live problem found its scaled Gershgorin row test
     // (`ok`) true -- then no step of the phase's FISTA loop can fail the backtracking test, and the loop runs without it.  Wave-
     // (MW: workgroup-) uniform.
-    constexpr bool CAN_CERT = sizeof(R) == sizeof(double);      // (fp32: the image noise does make the test fire, see the force step)
+    constexpr bool CAN_CERT = sizeof(R) == sizeof(double) && !BQ;      // (BQ: the rows below assume a diagonal W; fp32: the image noise does make the test fire, see the force step)
     auto certify = [&](bool ok, mask_t live) -> bool {
         if (!CAN_CERT || !a.certified_steps) return false;
         if (!MW) return (__ballot(!ok) & live) == 0;
@@ -366,10 +377,28 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
             // scaling by two is exact in binary floating point, so every iterate has the bits of the reference's
             // y - g/L, and the doubled copies of the weights (2 Q, 2 rho) need no registers.
             R wf[NF], qf[HASQF ? NF : 1];
+            constexpr int NW = BQ ? NF * (NF + 1) / 2 : 1;
+            [[maybe_unused]] R Wb[NW];      // BQ: the knot's block, its upper triangle (sym_index)
+            if constexpr (BQ) {
+                UNROLL for (int j = 0; j < NF; ++j) {
+                    wf[j] = R(0);      // (unused)
+                    if (HASQF) qf[j] = R(0.5) * ldz<R>(a.qf + wave0 * nf, o.F + ph, j, rvalid);
+                }
+                if (bq.Qf_blk) {
+                    const unsigned oB = 8u * (sl_ * (unsigned)bq.sQf_blk + (unsigned)(NF * NF) * tr) + ph;
+                    UNROLL for (int r = 0; r < NF; ++r) {
+                        UNROLL for (int cc = r; cc < NF; ++cc) Wb[sym_index(NF, r, cc)] = ldz<R>(bq.Qf_blk + wave0 * bq.sQf_blk, oB, r * NF + cc, rvalid);
+                    }
+                } else {      // this side has its diagonal only: the block with exact zeros beside it
+                    UNROLL for (int k = 0; k < NW; ++k) Wb[k] = R(0);
+                    UNROLL for (int j = 0; j < NF; ++j) Wb[sym_index(NF, j, j)] = ldz<R>(a.Qf + wave0 * nf, o.F + ph, j, rvalid);
+                }
+            } else {
             UNROLL for (int j = 0; j < NF; ++j) {
                 wf[j] = RAW ? ldz<R>(a.Qf + wave0 * nf, o.F + ph, j, rvalid)
                             : ldz<R>(a.W_F + wave0 * a.sW_F, 8u * (sl_ * (unsigned)a.sW_F + (unsigned)NF * tr) + ph, j, rvalid);
                 if (HASQF) qf[j] = R(0.5) * ldz<R>(a.qf + wave0 * nf, o.F + ph, j, rvalid);
+            }
             }
             // the step certificate: M = W + rho A_x'A_x is block-diagonal per knot; with dg = diag(M), u = |A| dg, v = |A|' u the lane's
             // rows pass if W_j dg_j + rho v_j <= T dg_j (tools/certify_rate.py restates this)
@@ -455,8 +484,18 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
                         const R zx = an[n] * ry[0] - sp[n][2] * ry[4] + sp[n][1] * ry[5];
                         const R zy = an[n] * ry[1] + sp[n][2] * ry[3] - sp[n][0] * ry[5];
                         const R zz = an[n] * ry[2] - sp[n][1] * ry[3] + sp[n][0] * ry[4];
-                        R gx = fmaR(wf[3 * n], y[3 * n], rho * zx), gy = fmaR(wf[3 * n + 1], y[3 * n + 1], rho * zy),
-                          gz = fmaR(wf[3 * n + 2], y[3 * n + 2], rho * zz);
+                        R gx, gy, gz;
+                        if constexpr (BQ) {      // rows 3n .. 3n + 2 of W y, added to rho A'(A y + bPk) column by column
+                            gx = rho * zx; gy = rho * zy; gz = rho * zz;
+                            UNROLL for (int j = 0; j < NF; ++j) {
+                                gx = fmaR(Wb[sym_index(NF, 3 * n, j)], y[j], gx);
+                                gy = fmaR(Wb[sym_index(NF, 3 * n + 1, j)], y[j], gy);
+                                gz = fmaR(Wb[sym_index(NF, 3 * n + 2, j)], y[j], gz);
+                            }
+                        } else {
+                            gx = fmaR(wf[3 * n], y[3 * n], rho * zx); gy = fmaR(wf[3 * n + 1], y[3 * n + 1], rho * zy);
+                            gz = fmaR(wf[3 * n + 2], y[3 * n + 2], rho * zz);
+                        }
                         if (HASQF) { gx += qf[3 * n]; gy += qf[3 * n + 1]; gz += qf[3 * n + 2]; }
                         fr[3 * n] = fmaR(-gx, invL, y[3 * n]);
                         fr[3 * n + 1] = fmaR(-gy, invL, y[3 * n + 1]);
@@ -491,7 +530,14 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
                         const R d = xn[j] - y[j];
                         dv[j] = d;
                         g2 = fmaR(d, d, g2);
-                        cv = fmaR(wf[j] * d, d, cv);
+                        if constexpr (!BQ) cv = fmaR(wf[j] * d, d, cv);
+                    }
+                    if constexpr (BQ) {      // d'W d, row by row
+                        UNROLL for (int r = 0; r < NF; ++r) {
+                            R wd = Wb[sym_index(NF, r, 0)] * dv[0];
+                            UNROLL for (int j = 1; j < NF; ++j) wd = fmaR(Wb[sym_index(NF, r, j)], dv[j], wd);
+                            cv = fmaR(wd, dv[r], cv);
+                        }
                     }
                     if (sizeof(R) == sizeof(double)) {
                         UNROLL for (int k = 0; k < 6; ++k) { const R e = rn[k] - ry[k]; e2 = fmaR(e, e, e2); }
@@ -659,7 +705,8 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
             R qd[9], q[9], lb[NB], ub[NB];
             if (RAW) {
                 UNROLL for (int l = 0; l < 9; ++l) {
-                    qd[l] = ldz<R>(a.Qx + wave0 * nx, o.X + ph, l, kvalid);
+                    if constexpr (BQ) qd[l] = R(0);      // (unused)
+                    else qd[l] = ldz<R>(a.Qx + wave0 * nx, o.X + ph, l, kvalid);
                     q[l] = R(0.5) * ldz<R>(a.qx + wave0 * nx, o.X + ph, l, kvalid);     // q/2
                 }
                 UNROLL for (int l = 0; l < NB; ++l) {
@@ -704,6 +751,19 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
                 const R bpi = l0 ? (pi[l] - xi) : R(0);
                 qd[l] += l0 ? rho : R(0);
                 q[l] = fmaR(rho, bpi, q[l]);
+            }
+            [[maybe_unused]] R Qb[BQ ? 45 : 1];      // BQ: the knot's block, its upper triangle (sym_index), lane 0's with rho on its diagonal
+            if constexpr (BQ) {
+                if (bq.Qx_blk) {
+                    const unsigned oB = 8u * (sl_ * (unsigned)bq.sQx_blk + 81u * tk) + ph;
+                    UNROLL for (int r = 0; r < 9; ++r) {
+                        UNROLL for (int cc = r; cc < 9; ++cc) Qb[sym_index(9, r, cc)] = ldz<R>(bq.Qx_blk + wave0 * bq.sQx_blk, oB, r * 9 + cc, kvalid);
+                    }
+                } else {      // this side has its diagonal only: the block with exact zeros beside it
+                    UNROLL for (int k = 0; k < 45; ++k) Qb[k] = R(0);
+                    UNROLL for (int l = 0; l < 9; ++l) Qb[sym_index(9, l, l)] = ldz<R>(a.Qx + wave0 * nx, o.X + ph, l, kvalid);
+                }
+                UNROLL for (int l = 0; l < 9; ++l) Qb[sym_index(9, l, l)] += l0 ? rho : R(0);
             }
             UNROLL for (int l = 0; l < NB; ++l) {   // quieted once, so the clamp is a bare min/max pair
                 lb[l] = __builtin_canonicalize(lb[l]);
@@ -757,7 +817,9 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
                         z[1] += SX * ry[8] - SZ * ry[6];
                         z[2] += SY * ry[6] - SX * ry[7];
                         UNROLL for (int l = 0; l < 9; ++l) {
-                            const R g = fmaR(qd[l], y[l], fmaR(rho, z[l], q[l]));
+                            R g = fmaR(rho, z[l], q[l]);
+                            if constexpr (BQ) { UNROLL for (int j = 0; j < 9; ++j) g = fmaR(Qb[sym_index(9, l, j)], y[j], g); }      // row l of Q y, column by column
+                            else g = fmaR(qd[l], y[l], g);
                             R v = fmaR(-g, invL, y[l]);
                             if (l < NB) v = clamp_box(v, lb[l], ub[l]);
                             xn[l] = v;
@@ -765,12 +827,21 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a) {
                     }
                     applyA(xn, rn);
                     R g2 = 0, cv = 0, e2 = 0;
+                    [[maybe_unused]] R dx[BQ ? 9 : 1];
                     UNROLL for (int l = 0; l < 9; ++l) {
                         const R d = xn[l] - y[l];
                         const R e = rn[l] - ry[l];
                         g2 = fmaR(d, d, g2);
-                        cv = fmaR(qd[l] * d, d, cv);
+                        if constexpr (BQ) dx[l] = d;
+                        else cv = fmaR(qd[l] * d, d, cv);
                         e2 = fmaR(e, e, e2);
+                    }
+                    if constexpr (BQ) {      // d'Q d, row by row
+                        UNROLL for (int r = 0; r < 9; ++r) {
+                            R qdr = Qb[sym_index(9, r, 0)] * dx[0];
+                            UNROLL for (int j = 1; j < 9; ++j) qdr = fmaR(Qb[sym_index(9, r, j)], dx[j], qdr);
+                            cv = fmaR(qdr, dx[r], cv);
+                        }
                     }
                     cv = fmaR(rho, e2, cv);
                     if (XLDS) { UNROLL for (int l = 0; l < 9; ++l) { xo[l] = Xz[l]; ro[l] = RXz[l]; } }      // (see the force step)

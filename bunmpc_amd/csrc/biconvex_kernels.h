@@ -54,6 +54,15 @@ struct BatchArgs {
     int *queue;      // (set by the launcher) the work-stealing kernel's device counter: problems handed out beyond the first per segment
 };
 
+// Per-knot block-diagonal costs (bmpc_block_cost_t): the knot's symmetric block in place of its diagonal weights, raw form, fp64, one
+// knot per lane (biconvex_admm_body.h: BQ).  Row-major full blocks; a side whose pointer is null takes BatchArgs' diagonal (Qx / Qf), which
+// the kernel spreads into a block with exact zeros beside it.  Strides in doubles, 0 = one set of blocks shared by the batch.
+struct BlockArgs {
+    const double *Qx_blk;   // [.][H + 1][9][9]
+    const double *Qf_blk;   // [.][H][3E][3E]
+    long sQx_blk, sQf_blk;
+};
+
 constexpr int kStats = 6;
 // LDS elements per knot of a problem (biconvex_admm_body.h: X 9, P 9, F 3E, R 9): 39 for four feet, 33 for two -- odd strides, so no
 // two lanes of a segment share a bank (an odd E would make it even: only E = 2 and 4 are built)
@@ -79,6 +88,14 @@ hipError_t launch_admm_e4(const BatchArgs &a, const AdmmLaunch &l, hipStream_t s
 hipError_t launch_admm_e2(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream);
 int admm_scratch_bytes_e4();      // largest private-segment bytes per lane over the fp64 batch, workgroup and work-stealing kernels, -1 on error
 int admm_scratch_bytes_e2();
+// The block-cost kernels (biconvex_admm_bq.hip: E = 4, biconvex_admm_bq_e2.hip: E = 2): lpp 16 / 21 / 32 / 64, one wave per SIMD
+hipError_t launch_admm_bq_e4(const BatchArgs &a, const BlockArgs &q, int lpp, hipStream_t stream);
+hipError_t launch_admm_bq_e2(const BatchArgs &a, const BlockArgs &q, int lpp, hipStream_t stream);
+int admm_bq_scratch_bytes_e4();      // largest private-segment bytes per lane over them, -1 on error
+int admm_bq_scratch_bytes_e2();
+// ... and their dispatch: every batch size and num_iters goes to them (never the one-problem-per-wave, work-stealing or two-waves
+// kernels).  hipErrorInvalidValue unless raw, fp64, n_eff 2 or 4 and H + 1 <= 64 (the C-ABI refuses those with a message first).
+hipError_t launch_biconvex_admm_blocks(const BatchArgs &a, const BlockArgs &q, int n_eff, hipStream_t stream);
 
 // The one-problem-per-wave mapping (biconvex_latency.hip): fp64, n_eff = 2 or 4, H + 1 <= 21.  launch_biconvex_admm takes it for
 // batches of at most latency_mapping_max_batch() problems that fit.

@@ -65,7 +65,8 @@ bunmpc::BatchArgs to_args(const bmpc_batch_t &d) {
     return a;
 }
 
-int check_batch(const bmpc_batch_t *d) {
+// x_blk / f_blk: that side's cost comes as blocks (bmpc_block_cost_t), its diagonal is not needed
+int check_batch(const bmpc_batch_t *d, bool x_blk = false, bool f_blk = false) {
     if (!d) return fail(BMPC_BAD_ARG, "null batch descriptor");
     if (d->B < 0 || d->n_col < 1) return fail(BMPC_BAD_ARG, "B < 0 or n_col < 1");
     if (d->n_eff != 2 && d->n_eff != 4) return fail(BMPC_BAD_ARG, "n_eff must be 2 or 4: the centroidal kernels are built for n_eff in {2, 4}");
@@ -80,7 +81,7 @@ int check_batch(const bmpc_batch_t *d) {
     if (!d->cnt_plan || !d->dt || !d->x_init || !d->X || !d->F || !d->P || !d->L_x || !d->L_f)
         return fail(BMPC_BAD_ARG, "missing required array");
     if (d->raw) {
-        if (!d->Qx || !d->qx || !d->lbx || !d->ubx || !d->Qf)
+        if ((!d->Qx && !x_blk) || !d->qx || !d->lbx || !d->ubx || (!d->Qf && !f_blk))
             return fail(BMPC_BAD_ARG, "raw form needs Qx, qx, lbx, ubx, Qf");
     } else {
         if (!d->W_X || !d->W_X_ter || !d->W_F || !d->bounds || !d->X_nom || !d->X_ter)
@@ -91,6 +92,39 @@ int check_batch(const bmpc_batch_t *d) {
             if (stride < 0 || stride > (1L << 26)) return fail(BMPC_BAD_ARG, "batch stride of a weight / bounds array is negative or above 2^26 doubles");
     }
     return BMPC_OK;
+}
+
+bool has_blocks(const bmpc_block_cost_t *c) { return c && (c->Qx_blk || c->Qf_blk); }
+
+// a batch with block costs: what the block kernels are built for, then the batch itself
+int check_blocks(const bmpc_batch_t *d, const bmpc_block_cost_t *c) {
+    if (!d) return fail(BMPC_BAD_ARG, "null batch descriptor");
+    if (d->precision != 0) return fail(BMPC_BAD_ARG, "block costs (Qx_blk / Qf_blk) are built for fp64 only: precision must be 0");
+    if (!d->raw) return fail(BMPC_BAD_ARG, "block costs (Qx_blk / Qf_blk) are built for the raw form only: raw must be 1");
+    if (d->n_col + 1 > 64) return fail(BMPC_BAD_ARG, "block costs (Qx_blk / Qf_blk) are built for n_col + 1 <= 64 knots only (one problem per wave segment)");
+    if (int rc = check_batch(d, c->Qx_blk != nullptr, c->Qf_blk != nullptr)) return rc;
+    const long need_x = 81L * (d->n_col + 1), need_f = 9L * d->n_eff * d->n_eff * d->n_col;
+    if ((c->Qx_blk && (c->sQx_blk < 0 || c->sQx_blk > (1L << 26) || (c->sQx_blk != 0 && c->sQx_blk < need_x))) ||
+        (c->Qf_blk && (c->sQf_blk < 0 || c->sQf_blk > (1L << 26) || (c->sQf_blk != 0 && c->sQf_blk < need_f))))
+        return fail(BMPC_BAD_ARG, "batch stride of a block array must be 0 (shared) or between one problem's blocks and 2^26 doubles");
+    return BMPC_OK;
+}
+
+// blocks [n][k][k] on the host: the first asymmetric pair, if any
+int check_symmetric(const double *blk, size_t n, int k, const char *what) {
+    for (size_t i = 0; i < n; ++i)
+        for (int r = 0; r < k; ++r)
+            for (int c = r + 1; c < k; ++c)
+                if (blk[(i * k + r) * k + c] != blk[(i * k + c) * k + r])
+                    return fail(BMPC_BAD_ARG, std::string(what) + ": block " + std::to_string(i) + " is not symmetric at (" + std::to_string(r) + ", " + std::to_string(c) + ")");
+    return BMPC_OK;
+}
+
+bunmpc::BlockArgs to_block_args(const bmpc_block_cost_t &c) {
+    bunmpc::BlockArgs q;
+    q.Qx_blk = c.Qx_blk; q.Qf_blk = c.Qf_blk;
+    q.sQx_blk = c.Qx_blk ? c.sQx_blk : 0; q.sQf_blk = c.Qf_blk ? c.sQf_blk : 0;
+    return q;
 }
 
 }  // namespace
@@ -125,6 +159,8 @@ struct bmpc_biconvex {
     // problem data (problem.hpp): diagonal Q, q, bounds
     std::vector<double> Qx, qx, lbx, ubx, Qf, qf, lbf, ubf;
     bool qf_nonzero = false;
+    // per-knot blocks of Q (set_cost_x_blocks / set_cost_f_blocks); empty: that side has its diagonal
+    std::vector<double> Qx_blk, Qf_blk;
     // iterates
     std::vector<double> X, F, P;
     std::vector<double> rot;  // set_rotation_matrix_f: stored, unused (as in the reference)
@@ -151,6 +187,11 @@ int bmpc_set_latency_mapping_max_batch(int max_batch) { return bunmpc::set_laten
 int bmpc_set_exact_step_decisions(int on) { return bunmpc::set_exact_step_decisions(on); }
 int bmpc_set_certified_steps(int on) { return bunmpc::set_certified_steps(on); }
 int bmpc_biconvex_fp32_scratch_bytes(void) { return bunmpc::biconvex_admm_f32_scratch_bytes(); }
+int bmpc_block_cost_struct_size(void) { return (int)sizeof(bmpc_block_cost_t); }
+int bmpc_biconvex_block_kernel_scratch_bytes(int n_eff) {
+    if (n_eff != 2 && n_eff != 4) { fail(BMPC_BAD_ARG, "n_eff must be 2 or 4"); return -1; }
+    return n_eff == 4 ? bunmpc::admm_bq_scratch_bytes_e4() : bunmpc::admm_bq_scratch_bytes_e2();
+}
 int bmpc_biconvex_kernel_scratch_bytes(int n_eff, int precision) {
     if ((n_eff != 2 && n_eff != 4) || (precision != 0 && precision != 1)) { fail(BMPC_BAD_ARG, "n_eff must be 2 or 4, precision 0 or 1"); return -1; }
     if (precision == 1) return n_eff == 4 ? bunmpc::biconvex_admm_f32_scratch_bytes() : bunmpc::biconvex_admm_f32_e2_scratch_bytes();
@@ -445,11 +486,32 @@ int bmpc_biconvex_return_b_f(bmpc_biconvex_t *h, const double *F, const double *
 int bmpc_biconvex_set_cost_x(bmpc_biconvex_t *h, const double *Q, const double *q) {
     H_CHECK(Q, q);
     h->Qx.assign(Q, Q + h->nx()); h->qx.assign(q, q + h->nx());
+    h->Qx_blk.clear();
+    return BMPC_OK;
+}
+int bmpc_biconvex_set_cost_x_blocks(bmpc_biconvex_t *h, const double *Q_blk, const double *q) {
+    H_CHECK(Q_blk, q);
+    if (int rc = check_symmetric(Q_blk, (size_t)h->n_col + 1, 9, "set_cost_x_blocks")) return rc;
+    h->Qx_blk.assign(Q_blk, Q_blk + (size_t)81 * (h->n_col + 1));
+    for (int i = 0; i < h->nx(); ++i) h->Qx[i] = Q_blk[(size_t)(i / 9) * 81 + (size_t)(i % 9) * 10];      // (the diagonal, for whoever reads Qx)
+    h->qx.assign(q, q + h->nx());
+    return BMPC_OK;
+}
+int bmpc_biconvex_set_cost_f_blocks(bmpc_biconvex_t *h, const double *Q_blk, const double *q) {
+    H_CHECK(Q_blk, q);
+    const int k = 3 * h->n_eff;
+    if (int rc = check_symmetric(Q_blk, (size_t)h->n_col, k, "set_cost_f_blocks")) return rc;
+    h->Qf_blk.assign(Q_blk, Q_blk + (size_t)k * k * h->n_col);
+    for (int i = 0; i < h->nf(); ++i) h->Qf[i] = Q_blk[(size_t)(i / k) * k * k + (size_t)(i % k) * (k + 1)];
+    h->qf.assign(q, q + h->nf());
+    h->qf_nonzero = false;
+    for (double v : h->qf) if (v != 0.0) h->qf_nonzero = true;
     return BMPC_OK;
 }
 int bmpc_biconvex_set_cost_f(bmpc_biconvex_t *h, const double *Q, const double *q) {
     H_CHECK(Q, q);
     h->Qf.assign(Q, Q + h->nf()); h->qf.assign(q, q + h->nf());
+    h->Qf_blk.clear();
     h->qf_nonzero = false;
     for (double v : h->qf) if (v != 0.0) h->qf_nonzero = true;
     return BMPC_OK;
@@ -463,11 +525,13 @@ int bmpc_biconvex_create_cost_X(bmpc_biconvex_t *h, const double *W_X, const dou
         h->Qx[i] = W_X_ter[i - nv + 9];
         h->qx[i] = -2 * (X_ter[i - nv + 9] * W_X_ter[i - nv + 9]);
     }
+    h->Qx_blk.clear();
     return BMPC_OK;
 }
 int bmpc_biconvex_create_cost_F(bmpc_biconvex_t *h, const double *W_F) {  // biconvex.cpp:74-78
     H_CHECK(W_F);
     h->Qf.assign(W_F, W_F + h->nf());
+    h->Qf_blk.clear();
     return BMPC_OK;
 }
 int bmpc_biconvex_set_bounds_x(bmpc_biconvex_t *h, const double *lb, const double *ub) {
@@ -580,12 +644,15 @@ int bmpc_biconvex_optimize(bmpc_biconvex_t *h, const double *x_init, int num_ite
     const size_t o_cnt = take(cnt.size()), o_dt = take(H), o_xi = take(9), o_Qx = take(nx), o_qx = take(nx),
                  o_lb = take(nx), o_ub = take(nx), o_Qf = take(nf), o_qf = take(nf), o_X = take(nx),
                  o_F = take(nf), o_P = take(nx), o_L = take(2), o_viol = take(1), o_hist = take(nh);
+    const size_t o_end = off, o_Qxb = take(h->Qx_blk.size()), o_Qfb = take(h->Qf_blk.size());      // (blocks: behind what comes back)
     std::vector<double> stage(off, 0.0);
     auto put = [&](size_t o, const double *src, size_t n) { std::memcpy(stage.data() + o, src, sizeof(double) * n); };
     put(o_cnt, cnt.data(), cnt.size()); put(o_dt, h->dt.data(), H); put(o_xi, x_init, 9);
     put(o_Qx, h->Qx.data(), nx); put(o_qx, h->qx.data(), nx); put(o_lb, h->lbx.data(), nx); put(o_ub, h->ubx.data(), nx);
     put(o_Qf, h->Qf.data(), nf); put(o_qf, h->qf.data(), nf);
     put(o_X, h->X.data(), nx); put(o_F, h->F.data(), nf); put(o_P, h->P.data(), nx);
+    if (!h->Qx_blk.empty()) put(o_Qxb, h->Qx_blk.data(), h->Qx_blk.size());
+    if (!h->Qf_blk.empty()) put(o_Qfb, h->Qf_blk.data(), h->Qf_blk.size());
     stage[o_L] = h->L_x; stage[o_L + 1] = h->L_f;
     HIP_TRY(h->dbuf.ensure(sizeof(double) * off));
     HIP_TRY(h->dstats.ensure(sizeof(int) * bunmpc::kStats));
@@ -602,9 +669,18 @@ int bmpc_biconvex_optimize(bmpc_biconvex_t *h, const double *x_init, int num_ite
     b.qf = h->qf_nonzero ? d + o_qf : nullptr;
     b.X = d + o_X; b.F = d + o_F; b.P = d + o_P; b.L_x = d + o_L; b.L_f = d + o_L + 1;
     b.dyn_viol = d + o_viol; b.hist = d + o_hist; b.stats = static_cast<int *>(h->dstats.p);
-    if (int rc = check_batch(&b)) return rc;
-    HIP_TRY(bunmpc::launch_biconvex_admm(to_args(b), E, nullptr));
-    HIP_TRY(hipMemcpy(stage.data() + o_X, d + o_X, sizeof(double) * (off - o_X), hipMemcpyDeviceToHost));
+    bmpc_block_cost_t blk;
+    std::memset(&blk, 0, sizeof(blk));
+    if (!h->Qx_blk.empty()) blk.Qx_blk = d + o_Qxb;
+    if (!h->Qf_blk.empty()) blk.Qf_blk = d + o_Qfb;
+    if (has_blocks(&blk)) {
+        if (int rc = check_blocks(&b, &blk)) return rc;
+        HIP_TRY(bunmpc::launch_biconvex_admm_blocks(to_args(b), to_block_args(blk), E, nullptr));
+    } else {
+        if (int rc = check_batch(&b)) return rc;
+        HIP_TRY(bunmpc::launch_biconvex_admm(to_args(b), E, nullptr));
+    }
+    HIP_TRY(hipMemcpy(stage.data() + o_X, d + o_X, sizeof(double) * (o_end - o_X), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(h->last_stats, h->dstats.p, sizeof(int) * bunmpc::kStats, hipMemcpyDeviceToHost));
     std::memcpy(h->X.data(), stage.data() + o_X, sizeof(double) * nx);
     std::memcpy(h->F.data(), stage.data() + o_F, sizeof(double) * nf);
@@ -635,20 +711,46 @@ int bmpc_biconvex_solve_batch_device(const bmpc_batch_t *d, void *hip_stream) {
     return BMPC_OK;
 }
 
-int bmpc_biconvex_solve_batch_host(const bmpc_batch_t *d) {
-    if (int rc = check_batch(d)) return rc;
+int bmpc_biconvex_solve_batch_blocks_device(const bmpc_batch_t *d, const bmpc_block_cost_t *c, void *hip_stream) {
+    if (!has_blocks(c)) return bmpc_biconvex_solve_batch_device(d, hip_stream);
+    if (int rc = check_blocks(d, c)) return rc;
+    HIP_TRY(bunmpc::launch_biconvex_admm_blocks(to_args(*d), to_block_args(*c), d->n_eff, static_cast<hipStream_t>(hip_stream)));
+    return BMPC_OK;
+}
+
+int bmpc_biconvex_solve_batch_host(const bmpc_batch_t *d) { return bmpc_biconvex_solve_batch_blocks_host(d, nullptr); }
+
+int bmpc_biconvex_solve_batch_blocks_host(const bmpc_batch_t *d, const bmpc_block_cost_t *c) {
+    const bool blocks = has_blocks(c);
+    if (int rc = blocks ? check_blocks(d, c) : check_batch(d)) return rc;
     const size_t B = (size_t)d->B, H = (size_t)d->n_col, E = (size_t)d->n_eff;
     const size_t nx = 9 * (H + 1), nf = 3 * E * H;
     if (B == 0) return BMPC_OK;
     bmpc_batch_t b = *d;
+    bmpc_block_cost_t cb;
+    std::memset(&cb, 0, sizeof(cb));
+    if (blocks) cb = *c;
     struct In { const double **slot; size_t n; };
     struct Out { double **slot; double *host; size_t n; };
     auto rows = [&](long stride) { return stride == 0 ? (size_t)1 : B; };
     std::vector<In> ins = {{&b.cnt_plan, B * H * E * 4}, {&b.dt, B * H}, {&b.x_init, B * 9}};
     if (d->raw) {
-        ins.push_back({&b.Qx, B * nx}); ins.push_back({&b.qx, B * nx});
+        if (cb.Qx_blk) {
+            const size_t n = (rows(cb.sQx_blk) - 1) * (size_t)cb.sQx_blk + 81 * (H + 1);
+            for (size_t i = 0; i < rows(cb.sQx_blk); ++i)
+                if (int rc = check_symmetric(cb.Qx_blk + i * (size_t)cb.sQx_blk, H + 1, 9, "Qx_blk")) return rc;
+            ins.push_back({&cb.Qx_blk, n});
+            b.Qx = nullptr;
+        } else ins.push_back({&b.Qx, B * nx});
+        ins.push_back({&b.qx, B * nx});
         ins.push_back({&b.lbx, B * nx}); ins.push_back({&b.ubx, B * nx});
-        ins.push_back({&b.Qf, B * nf});
+        if (cb.Qf_blk) {
+            const size_t kk = 9 * E * E, n = (rows(cb.sQf_blk) - 1) * (size_t)cb.sQf_blk + kk * H;
+            for (size_t i = 0; i < rows(cb.sQf_blk); ++i)
+                if (int rc = check_symmetric(cb.Qf_blk + i * (size_t)cb.sQf_blk, H, 3 * (int)E, "Qf_blk")) return rc;
+            ins.push_back({&cb.Qf_blk, n});
+            b.Qf = nullptr;
+        } else ins.push_back({&b.Qf, B * nf});
         if (d->qf) ins.push_back({&b.qf, B * nf});
     } else {
         ins.push_back({&b.W_X, (rows(d->sW_X) - 1) * (size_t)d->sW_X + 9 * H});
@@ -686,7 +788,8 @@ int bmpc_biconvex_solve_batch_host(const bmpc_batch_t *d) {
         HIP_TRY(hipMemcpy(tbuf.p, d->trace, sizeof(int) * ntrace, hipMemcpyHostToDevice));
         b.trace = static_cast<int *>(tbuf.p);
     }
-    HIP_TRY(bunmpc::launch_biconvex_admm(to_args(b), d->n_eff, nullptr));
+    if (blocks) HIP_TRY(bunmpc::launch_biconvex_admm_blocks(to_args(b), to_block_args(cb), d->n_eff, nullptr));
+    else HIP_TRY(bunmpc::launch_biconvex_admm(to_args(b), d->n_eff, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     for (auto &o : outs) HIP_TRY(hipMemcpy(o.host, *o.slot, sizeof(double) * o.n, hipMemcpyDeviceToHost));
     if (d->stats) HIP_TRY(hipMemcpy(d->stats, sbuf.p, sizeof(int) * bunmpc::kStats * B, hipMemcpyDeviceToHost));

@@ -261,6 +261,50 @@ class Batch:
                      None if self.gait_id is None else self.gait_id[lo:hi], self.mu, dict(self.meta))
 
 
+def block_costs(Qx, qx, Qf, E, yaw, lam=0.25):
+    """Per-knot block costs from a batch's diagonal raw arrays Qx, qx (B, 9 (H + 1)) and Qf (B, 3 E H): what a heading-aligned cost
+    and a force-distribution term look like (tests, tools/block_cost_bench.py).
+      * every 3-vector's weights w become R diag(w) R' with R the rotation about z by the problem's yaw (B,) [rad];
+      * F gains lam * mean(w of the knot) * kron(Laplacian_E, I_3): the sum over pairs of feet of |f_n - f_m|^2.
+    Both parts are positive semi-definite by construction, which is asserted (eigvalsh(block).min() >= -1e-12 eigvalsh(block).max()).
+    qx follows the rotated Q: q = -2 Q x_ref with x_ref the reference the diagonal pair (Qx, qx) encodes.
+    Returns dict(Qx_blk (B, H + 1, 9, 9), Qf_blk (B, H, 3E, 3E), qx (B, 9 (H + 1)))."""
+    Qx, qx, Qf = (np.asarray(a, dtype=np.float64) for a in (Qx, qx, Qf))
+    B, K, H = Qx.shape[0], Qx.shape[1] // 9, Qf.shape[1] // (3 * E)
+    yaw = np.broadcast_to(np.asarray(yaw, dtype=np.float64), (B,))
+    Qx_blk, Qf_blk, q = np.zeros((B, K, 9, 9)), np.zeros((B, H, 3 * E, 3 * E)), np.zeros((B, 9 * K))
+    lap = np.kron(E * np.eye(E) - np.ones((E, E)), np.eye(3))
+    for i in range(B):
+        c, s = np.cos(yaw[i]), np.sin(yaw[i])
+        R = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+        for t in range(K):
+            w = Qx[i, 9 * t:9 * t + 9]
+            for g in range(3):
+                Qx_blk[i, t, 3 * g:3 * g + 3, 3 * g:3 * g + 3] = R @ np.diag(w[3 * g:3 * g + 3]) @ R.T
+        for t in range(H):
+            w = Qf[i, 3 * E * t:3 * E * t + 3 * E]
+            for n in range(E):
+                Qf_blk[i, t, 3 * n:3 * n + 3, 3 * n:3 * n + 3] = R @ np.diag(w[3 * n:3 * n + 3]) @ R.T
+            Qf_blk[i, t] += lam * w.mean() * lap
+        x_ref = -0.5 * qx[i] / np.where(Qx[i] != 0, Qx[i], 1.0)
+        q[i] = -2.0 * np.einsum("tab,tb->ta", (Qx_blk[i] + Qx_blk[i].transpose(0, 2, 1)) / 2, x_ref.reshape(K, 9)).reshape(-1)
+    Qx_blk = (Qx_blk + Qx_blk.transpose(0, 1, 3, 2)) / 2      # exactly symmetric
+    Qf_blk = (Qf_blk + Qf_blk.transpose(0, 1, 3, 2)) / 2
+    for blk in (Qx_blk, Qf_blk):
+        ev = np.linalg.eigvalsh(blk)
+        assert np.all(ev.min(axis=-1) >= -1e-12 * ev.max(axis=-1)), "block cost is not positive semi-definite"
+    return dict(Qx_blk=Qx_blk, Qf_blk=Qf_blk, qx=q)
+
+
+def block_diag_matrix(blk):
+    """The square matrix whose diagonal blocks are blk (n, k, k), dense: what set_cost_x / set_cost_f take"""
+    n, k, _ = blk.shape
+    Q = np.zeros((n * k, n * k))
+    for t in range(n):
+        Q[t * k:(t + 1) * k, t * k:(t + 1) * k] = blk[t]
+    return Q
+
+
 def _draws(seed, first, B, n):
     """Per-problem independent streams: problem b always sees the same numbers whatever the
     batch size or the rank that generates it (SeedSequence.spawn keyed by absolute index)."""

@@ -203,8 +203,37 @@ int bmpc_biconvex_kernel_scratch_bytes(int n_eff, int precision);
 /* symbol-name prefix of the kernel that serves (n_col, raw), for profiles */
 const char *bmpc_biconvex_kernel_name(int n_col, int raw);
 /* which kernel the calling host thread's latest batch solve was dispatched to: "biconvex_latency_kernel" (one problem per wave),
- * "biconvex_admm_kernel" or "biconvex_admm_kernel_f32" (one knot per lane); "" before the first solve */
+ * "biconvex_admm_kernel" or "biconvex_admm_kernel_f32" (one knot per lane), "biconvex_admm_bq_kernel" (block costs); "" before the first solve */
 const char *bmpc_biconvex_last_kernel_name(void);
+
+/* Per-knot block-diagonal costs (additive) --------------------------------------------------------------------------------
+ * The reference's set_cost_x / set_cost_f take a sparse matrix (biconvex.hpp:54-60) and ProblemData uses all of it
+ * (problem.cpp:31-56).  Here Q may be block-diagonal per knot: a symmetric 9 x 9 block per knot for X, a symmetric 3E x 3E block per
+ * knot for F -- weights in a rotated frame, terms that couple the feet of a knot, CoM position-velocity coupling.  Blocks are
+ * row-major and must be symmetric (the gradient 2 Q y and the test's (y1 + y0)'Q d agree for symmetric Q only; the host entry
+ * points check it, the device entry point cannot).  Anything that couples different knots cannot be expressed.
+ * Either pointer may be NULL: that side uses the batch descriptor's diagonal (d->Qx / d->Qf, which the other side then does not
+ * need).  With both NULL the calls are the plain ones.  Strides in doubles: 0 = one set of blocks shared by the batch, otherwise at
+ * least one problem's blocks and at most 2^26.
+ * Built for: raw form (raw = 1), fp64 (precision = 0), n_col + 1 <= 64 knots, n_eff in {2, 4}; anything else is BMPC_BAD_ARG with a
+ * message that names the limit.  Such a batch runs "biconvex_admm_bq_kernel" (one knot per lane, 16 / 21 / 32 / 64 lanes per
+ * problem, one wave per SIMD) at every batch size and num_iters; every FISTA step is tested on fp64 sums (no step certificate, no
+ * fp32 step decisions), so bmpc_set_certified_steps, bmpc_set_exact_step_decisions, bmpc_set_work_stealing and
+ * bmpc_set_two_waves_per_simd do not touch it. */
+typedef struct {
+    const double *Qx_blk; long sQx_blk;   /* [.][n_col+1][9][9] */
+    const double *Qf_blk; long sQf_blk;   /* [.][n_col][3E][3E] */
+} bmpc_block_cost_t;
+int bmpc_block_cost_struct_size(void);       /* sizeof(bmpc_block_cost_t), to catch binding drift */
+int bmpc_biconvex_solve_batch_blocks_device(const bmpc_batch_t *d, const bmpc_block_cost_t *c, void *hip_stream);
+int bmpc_biconvex_solve_batch_blocks_host(const bmpc_batch_t *d, const bmpc_block_cost_t *c);
+/* The handle's cost as blocks: Q_blk [n_col+1][9][9] / [n_col][3E][3E], q as in set_cost_x / set_cost_f.  optimize then takes the
+ * block kernel while either side has blocks; bmpc_biconvex_set_cost_x / _f (or create_cost_X / _F) return that side to its diagonal. */
+int bmpc_biconvex_set_cost_x_blocks(bmpc_biconvex_t *h, const double *Q_blk, const double *q);
+int bmpc_biconvex_set_cost_f_blocks(bmpc_biconvex_t *h, const double *Q_blk, const double *q);
+/* The largest scratch (private-segment) bytes per lane over the block-cost kernels of one foot count (n_eff 2 or 4), as the loaded
+ * code object reports them; -1 for another n_eff, or on error.  (bmpc_biconvex_kernel_scratch_bytes covers the other kernels.) */
+int bmpc_biconvex_block_kernel_scratch_bytes(int n_eff);
 
 /* rigid-body model -------------------------------------------------------------------
  * What pinocchio::urdf::buildModel(urdf, JointModelFreeFlyer()) yields (inverse_kinematics.cpp:10,
