@@ -30,6 +30,11 @@ class Batch(C.Structure):
                                            "L_x", "L_f", "dyn_viol", "hist", "stats", "trace")])
 
 
+class BandCost(C.Structure):
+    """bmpc_band_cost_t"""
+    _fields_ = [("Qx_off", C.c_void_p), ("sQx_off", C.c_long), ("Qf_off", C.c_void_p), ("sQf_off", C.c_long)]
+
+
 class BlockCost(C.Structure):
     """bmpc_block_cost_t"""
     _fields_ = [("Qx_blk", C.c_void_p), ("sQx_blk", C.c_long), ("Qf_blk", C.c_void_p), ("sQf_blk", C.c_long)]
@@ -160,6 +165,12 @@ _SIGS = {
     "bmpc_biconvex_set_cost_x_blocks": (_I, [_P, _P, _P]),
     "bmpc_biconvex_set_cost_f_blocks": (_I, [_P, _P, _P]),
     "bmpc_biconvex_block_kernel_scratch_bytes": (_I, [_I]),
+    "bmpc_band_cost_struct_size": (_I, []),
+    "bmpc_biconvex_solve_batch_band_device": (_I, [_P, _P, _P]),
+    "bmpc_biconvex_solve_batch_band_host": (_I, [_P, _P]),
+    "bmpc_biconvex_set_cost_x_band": (_I, [_P, _P, _P, _P]),
+    "bmpc_biconvex_set_cost_f_band": (_I, [_P, _P, _P, _P]),
+    "bmpc_biconvex_band_kernel_scratch_bytes": (_I, [_I]),
     "bmpc_biconvex_kernel_name": (C.c_char_p, [_I, _I]),
     "bmpc_biconvex_last_kernel_name": (C.c_char_p, []),
     "bmpc_plan_batch_device": (_I, [_P, _P]),
@@ -279,6 +290,8 @@ def lib():
             raise ImportError("bmpc_batch_t layout differs between include/bunmpc.h and bunmpc_amd/_lib.py")
         if handle.bmpc_block_cost_struct_size() != C.sizeof(BlockCost):
             raise ImportError("bmpc_block_cost_t layout differs between include/bunmpc.h and bunmpc_amd/_lib.py")
+        if handle.bmpc_band_cost_struct_size() != C.sizeof(BandCost):
+            raise ImportError("bmpc_band_cost_t layout differs between include/bunmpc.h and bunmpc_amd/_lib.py")
         if handle.bmpc_ik_batch_struct_size() != C.sizeof(IkBatch):
             raise ImportError("bmpc_ik_batch_t layout differs between include/bunmpc.h and bunmpc_amd/_lib.py")
         _lib = handle

@@ -39,6 +39,20 @@ def _block_cost(B, H, E, Qx_blk, Qf_blk, put):
     return c
 
 
+def _band_cost(B, H, E, Qx_off, Qf_off, put):
+    """bmpc_band_cost_t of Qx_off (1 or B, H, 9) / Qf_off (1 or B, H - 1, 3E), either None; put(array) -> its address"""
+    c = _lib.BandCost()
+    for name, a, shape in (("Qx_off", Qx_off, (H, 9)), ("Qf_off", Qf_off, (H - 1, 3 * E))):
+        if a is None:
+            continue
+        if a.shape[1:] != shape or a.shape[0] not in (1, B):
+            raise ValueError("%s: expected shape (1 or %d, %d, %d), got %s" % ((name, B) + shape + (tuple(a.shape),)))
+        if a.size:      # (H = 1: no pair of force knots)
+            setattr(c, name, put(a))
+            setattr(c, "s" + name, _stride(a))
+    return c
+
+
 def algorithmic_bytes_per_solve(H, E=4, per_problem_weights=False):
     """inputs (4E+10)H+18 doubles, outputs 18(H+1)+3EH+1 doubles
     (+ 9+9+3E+6+3 doubles when weights are per problem)."""
@@ -57,7 +71,8 @@ class DeviceBatch:
         """plan: a plan_batch.DevicePlan whose tensors (cnt_plan, dt, X_nom, X_ter, x_init) are used in place of the
         batch's host arrays -- inputs built on the GPU never leave HBM.
         raw: dict(Qx, qx, lbx, ubx, Qf[, qf][, Qx_blk][, Qf_blk]) -- the raw cost / bound form (solve_host explains it); with
-        Qx_blk / Qf_blk the per-knot block costs, through bmpc_biconvex_solve_batch_blocks_device"""
+        Qx_blk / Qf_blk the per-knot block costs, through bmpc_biconvex_solve_batch_blocks_device; with Qx_off / Qf_off the costs
+        between neighbouring knots, through bmpc_biconvex_solve_batch_band_device"""
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("DeviceBatch needs a GPU: no CPU fallback exists for the solve")
@@ -78,6 +93,7 @@ class DeviceBatch:
             assert plan.B == B and plan.H == H
             self.t = dict(cnt_plan=plan.cnt_plan, dt=plan.dt, x_init=plan.inp["x_init"], X_nom=plan.X_nom, X_ter=plan.X_ter)
         self.blocks = None
+        self.band = None
         if raw is None:
             self.t.update(W_X=up(batch.W_X), W_X_ter=up(batch.W_X_ter), W_F=up(batch.W_F), bounds=up(batch.bounds))
         else:
@@ -90,6 +106,11 @@ class DeviceBatch:
             self.tb = {k: up(raw[k]) for k in ("Qx_blk", "Qf_blk") if raw.get(k) is not None}
             if self.tb:
                 self.blocks = _block_cost(B, H, E, self.tb.get("Qx_blk"), self.tb.get("Qf_blk"), lambda t: t.data_ptr())
+            self.tk = {k: up(raw[k]) for k in ("Qx_off", "Qf_off") if raw.get(k) is not None}
+            if self.tk:
+                if self.tb:
+                    raise ValueError("Qx_off / Qf_off (costs between neighbouring knots) cannot be combined with Qx_blk / Qf_blk (per-knot blocks)")
+                self.band = _band_cost(B, H, E, self.tk.get("Qx_off"), self.tk.get("Qf_off"), lambda t: t.data_ptr())
         self.X = torch.empty((B, 9 * (H + 1)), dtype=f64, device=self.device)
         self.F = torch.empty((B, 3 * E * H), dtype=f64, device=self.device)
         self.P = torch.empty((B, 9 * (H + 1)), dtype=f64, device=self.device)
@@ -150,6 +171,8 @@ class DeviceBatch:
             self.trace.fill_(-1)
         if self.blocks is not None:
             _lib.check(_lib.lib().bmpc_biconvex_solve_batch_blocks_device(C.byref(self.desc), C.byref(self.blocks), C.c_void_p(stream)))
+        elif self.band is not None:
+            _lib.check(_lib.lib().bmpc_biconvex_solve_batch_band_device(C.byref(self.desc), C.byref(self.band), C.c_void_p(stream)))
         else:
             _lib.check(_lib.lib().bmpc_biconvex_solve_batch_device(C.byref(self.desc), C.c_void_p(stream)))
 
@@ -170,7 +193,9 @@ def solve_host(batch, num_iters=10, maxit=150, tol=1e-5, exit_tol=1e-3, beta=1.5
     copies out).  warm = (X, F, P) or None for a cold start.  raw = dict(Qx,qx,lbx,ubx,Qf[,qf])
     switches to the raw cost/bound form; with Qx_blk (1 or B, H + 1, 9, 9) and / or Qf_blk (1 or B, H, 3E, 3E) in it that side's
     cost is block-diagonal per knot (symmetric blocks; a leading dimension of 1: shared by the batch) and its Qx / Qf may be left
-    out (bmpc_biconvex_solve_batch_blocks_host)."""
+    out (bmpc_biconvex_solve_batch_blocks_host).  With Qx_off (1 or B, H, 9) and / or Qf_off (1 or B, H - 1, 3E) in it, Q has the
+    weight off[t][i] between component i of knots t and t + 1 beside its diagonal Qx / Qf -- force-rate and momentum-rate costs
+    (bmpc_biconvex_solve_batch_band_host); not together with blocks."""
     B, H, E = batch.B, batch.H, batch.E
     nx, nf = 9 * (H + 1), 3 * E * H
     keep = []
@@ -196,6 +221,10 @@ def solve_host(batch, num_iters=10, maxit=150, tol=1e-5, exit_tol=1e-3, beta=1.5
         d.raw = 1
         blocks = _block_cost(B, H, E, *(None if raw.get(k) is None else f64(raw[k]) for k in ("Qx_blk", "Qf_blk")),
                              put=lambda a: a.ctypes.data)
+        band = _band_cost(B, H, E, *(None if raw.get(k) is None else f64(raw[k]) for k in ("Qx_off", "Qf_off")),
+                          put=lambda a: a.ctypes.data)
+        if (band.Qx_off or band.Qf_off) and (blocks.Qx_blk or blocks.Qf_blk):
+            raise ValueError("Qx_off / Qf_off (costs between neighbouring knots) cannot be combined with Qx_blk / Qf_blk (per-knot blocks)")
         for k in ("Qx", "qx", "lbx", "ubx", "Qf"):
             if raw.get(k) is None and k in ("Qx", "Qf") and raw.get(k + "_blk") is not None:
                 continue
@@ -222,6 +251,8 @@ def solve_host(batch, num_iters=10, maxit=150, tol=1e-5, exit_tol=1e-3, beta=1.5
     d.trace = trace.ctypes.data if keep_hist else None
     if raw is not None and (blocks.Qx_blk or blocks.Qf_blk):
         _lib.check(_lib.lib().bmpc_biconvex_solve_batch_blocks_host(C.byref(d), C.byref(blocks)))
+    elif raw is not None and (band.Qx_off or band.Qf_off):
+        _lib.check(_lib.lib().bmpc_biconvex_solve_batch_band_host(C.byref(d), C.byref(band)))
     else:
         _lib.check(_lib.lib().bmpc_biconvex_solve_batch_host(C.byref(d)))
     out = dict(X=X, F=F, P=P, L_x=Lx, L_f=Lf, dyn_viol=viol, stats=stats.astype(np.int64))

@@ -5,9 +5,12 @@ the C-ABI in include/bunmpc.h; `optimize` runs the gfx950 ADMM kernel.
 
 `set_cost_x/f` take what the reference's take -- a 1-D diagonal, a dense square matrix or a scipy.sparse matrix -- and classify it
 by structure: a diagonal goes the diagonal way (as before), a matrix that is block-diagonal per knot (9 x 9 blocks for X,
-3 n_eff x 3 n_eff for F) and exactly symmetric goes to the block-cost kernel (fp64, n_col + 1 <= 64 knots).
+3 n_eff x 3 n_eff for F) and exactly symmetric goes to the block-cost kernel (fp64, n_col + 1 <= 64 knots), and a diagonal plus
+entries between the SAME component of NEIGHBOURING knots (force-rate, momentum-rate terms D'R D) goes to the band-cost kernel (same
+limits).
 
-Differences that are deliberate and visible: a Q that couples different knots, or an asymmetric one (the reference's gradient 2 Q y
+Differences that are deliberate and visible: a Q that couples knots in any other way (other components, knots further apart, or
+coupling next to full per-knot blocks), or an asymmetric one (the reference's gradient 2 Q y
 and its acceptance test agree for symmetric Q only), raises ValueError naming the first offending (row, col); wrong sizes raise
 ValueError instead of reading out of bounds."""
 import ctypes as C
@@ -25,8 +28,11 @@ def _vec(a, n, name):
 
 
 def classify_cost(Q, n, k, name):
-    """What set_cost_x / set_cost_f do with Q (n x n, knots of k variables): ("diag", d [n]) or ("blocks", blk [n / k][k][k]).
-    ValueError for a matrix that is not square of size n, has a non-zero outside its knots' blocks, or is not exactly symmetric."""
+    """What set_cost_x / set_cost_f do with Q (n x n, knots of k variables): ("diag", d [n]), ("blocks", blk [n / k][k][k]) or
+    ("band", (diag [n / k][k], off [n / k - 1][k])) -- a diagonal plus Q[(t, i), (t + 1, i)] = Q[(t + 1, i), (t, i)] = off[t][i].
+    ValueError for a matrix that is not square of size n, has a non-zero outside its knots' blocks that is not on the diagonal of a
+    neighbouring-knot block (the first such (row, col) in row-major order is named), is not exactly symmetric, or has coupling
+    between knots next to per-knot blocks that are not diagonal."""
     if hasattr(Q, "tocoo"):  # scipy sparse
         coo = Q.tocoo()
         if coo.shape != (n, n):
@@ -49,9 +55,29 @@ def classify_cost(Q, n, k, name):
         return "diag", d
     wide = row // k != col // k
     if np.any(wide):
-        i = int(np.argmax(wide))
-        raise ValueError("%s: entry (%d, %d) couples knots %d and %d: only per-knot %dx%d blocks are supported"
-                         % (name, row[i], col[i], row[i] // k, col[i] // k, k, k))
+        bad = wide & (np.abs(row - col) != k)
+        if np.any(bad):
+            i = int(np.argmax(bad))
+            raise ValueError("%s: entry (%d, %d) couples knots %d and %d: beside per-knot %dx%d blocks only the same component of "
+                             "neighbouring knots may be coupled (entries (r, r + %d))"
+                             % (name, row[i], col[i], row[i] // k, col[i] // k, k, k, k))
+        up, lo = np.zeros(n - k), np.zeros(n - k)
+        sel = wide & (col > row)
+        np.add.at(up, row[sel], val[sel])
+        sel = wide & (col < row)
+        np.add.at(lo, col[sel], val[sel])
+        if np.any(up != lo):
+            r = int(np.argmax(up != lo))
+            raise ValueError("%s: entry (%d, %d) differs from (%d, %d): Q must be exactly symmetric (it is not symmetrised here)"
+                             % (name, r, r + k, r + k, r))
+        inner = ~wide & (row != col)
+        if np.any(inner):
+            i = int(np.argmax(inner))
+            raise ValueError("%s: entry (%d, %d) lies beside the diagonal of its knot's block while other entries couple neighbouring "
+                             "knots: coupling between knots needs diagonal per-knot weights" % (name, row[i], col[i]))
+        d = np.zeros(n)
+        np.add.at(d, row[~wide], val[~wide])
+        return "band", (d.reshape(n // k, k), up.reshape(n // k - 1, k))
     blk = np.zeros((n // k, k, k))
     np.add.at(blk, (row // k, row % k, col % k), val)      # (a sparse matrix may list an entry twice: they add up)
     asym = blk != blk.transpose(0, 2, 1)
@@ -115,12 +141,20 @@ class BiconvexMP:
     def set_cost_x(self, Q_x, q_x):
         kind, Q = classify_cost(Q_x, self.nx, 9, "Q_x")
         q = _vec(q_x, self.nx, "q_x")
+        if kind == "band":
+            diag, off = (np.ascontiguousarray(a) for a in Q)
+            _lib.check(self._lib.bmpc_biconvex_set_cost_x_band(self._h, diag.ctypes.data, off.ctypes.data, q.ctypes.data))
+            return
         fn = self._lib.bmpc_biconvex_set_cost_x if kind == "diag" else self._lib.bmpc_biconvex_set_cost_x_blocks
         _lib.check(fn(self._h, Q.ctypes.data, q.ctypes.data))
 
     def set_cost_f(self, Q_f, q_f):
         kind, Q = classify_cost(Q_f, self.nf, 3 * self.n_eff, "Q_f")
         q = _vec(q_f, self.nf, "q_f")
+        if kind == "band":
+            diag, off = (np.ascontiguousarray(a) for a in Q)
+            _lib.check(self._lib.bmpc_biconvex_set_cost_f_band(self._h, diag.ctypes.data, off.ctypes.data, q.ctypes.data))
+            return
         fn = self._lib.bmpc_biconvex_set_cost_f if kind == "diag" else self._lib.bmpc_biconvex_set_cost_f_blocks
         _lib.check(fn(self._h, Q.ctypes.data, q.ctypes.data))
 

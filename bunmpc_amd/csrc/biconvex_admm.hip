@@ -247,6 +247,29 @@ hipError_t launch_biconvex_admm_blocks(const BatchArgs &args, const BlockArgs &q
     return n_eff == 4 ? launch_admm_bq_e4(a, q, lpp, stream) : launch_admm_bq_e2(a, q, lpp, stream);
 }
 
+// Costs that couple neighbouring knots (BandArgs): their kernel at every batch size and num_iters, as block batches go to theirs.  None
+// of the dispatch switches reaches it: every step is tested on the fp64 sums, one wave per SIMD, no work stealing.
+hipError_t launch_biconvex_admm_band(const BatchArgs &args, const BandArgs &q, int n_eff, hipStream_t stream) {
+    BatchArgs a = args;
+    if ((n_eff != 2 && n_eff != 4) || a.H < 1 || a.H + 1 > 64 || a.B < 0 || a.precision != 0 || !a.raw) return hipErrorInvalidValue;
+    if (a.B == 0) return hipSuccess;
+    if (a.c.maxit > kMaxFistaIters) return hipErrorInvalidValue;
+    for (long stride : {q.sQx_off, q.sQf_off})
+        if (stride < 0 || stride > (1L << 26)) return hipErrorInvalidValue;
+    BandArgs b = q;
+    if (a.H < 2) { b.Qf_off = nullptr; b.sQf_off = 0; }      // (one force knot: no pair)
+    a.exact_step_decisions = g_exact_step_decisions;      // (no effect: these kernels always take the fp64 sums)
+    a.certified_steps = 0;                                 // (... and test every step)
+    a.cmtab = momentum_table(stream);
+    if (!a.cmtab) return hipErrorOutOfMemory;
+    const int k = a.H + 1;
+    const int lpp = k <= 16 ? 16 : (k <= 21 && three_per_wave_pays(a) ? 21 : (k <= 32 ? 32 : 64));
+    t_last_kernel = "biconvex_admm_kq_kernel";
+    t_last_lpp = lpp;
+    t_last_wpe = 1;
+    return n_eff == 4 ? launch_admm_kq_e4(a, b, lpp, stream) : launch_admm_kq_e2(a, b, lpp, stream);
+}
+
 hipError_t launch_lane_selftest(const double *in, double *out, hipStream_t stream) {
     hipLaunchKernelGGL(lane_selftest_kernel, dim3(1), dim3(64), 0, stream, in, out);
     return hipGetLastError();

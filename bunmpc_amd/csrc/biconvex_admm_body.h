@@ -55,9 +55,21 @@ constexpr double kCertFloor = 2.0 * 25.0 / (kCertEta * kCertEta) * 0x1p-80;
 // sym_index: where element (r, c) of a symmetric n x n block sits in its packed upper triangle (rows one after the other)
 constexpr int sym_index(int n, int r, int c) { return r <= c ? r * n - r * (r - 1) / 2 + (c - r) : c * n - c * (c - 1) / 2 + (r - c); }
 
-template <typename R, int LPP, int E, bool RAW, bool HASQF, bool STEAL = false, bool XLDS = false, int WAVES = 1, bool BQ = false>
-__device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &bq = BlockArgs{}) {
+// KQ (costs that couple neighbouring knots -- force-rate and momentum-rate terms D'R D, D the first difference over knots: raw form,
+// fp64, one wave per SIMD, diagonal per-knot weights): beside its knot's diagonal weights a lane holds the weights `off` between its
+// knot t and knot t + 1, component by component (9 for X, 3E for F; exactly zero in the last knot's lane and in lanes without a knot)
+// and those of the pair (t - 1, t), fetched from the previous lane once per phase.  (Q y)_t = diag_t y_t + off_{t-1} y_{t-1} + off_t y_{t+1}
+// and d'Q d = sum_t diag_t d_t^2 + 2 off_t d_t d_{t+1} (lane t owns the pair): the neighbour lanes' y come by the wave shifts the motion
+// step already uses for A_f -- in the force step they are its first exchange between knots -- and d_{t+1} likewise, once per trial of a
+// step.  What a shift brings across the end of a segment is removed by keep_if, not
+// by its zero weight: NaN x 0 is NaN, and a diverged problem's NaNs stay its own.  The coupling products are added behind the diagonal
+// code's own term, so zero weights follow the diagonal kernel's path.  No step certificate (W + rho A_x'A_x is no longer block-diagonal
+// per knot) and no fp32 step decisions.  Every KQ operation is under `if constexpr` (its few declarations beside them are dead in the
+// other instantiations): those compile to the instructions they compiled to without it.
+template <typename R, int LPP, int E, bool RAW, bool HASQF, bool STEAL = false, bool XLDS = false, int WAVES = 1, bool BQ = false, bool KQ = false>
+__device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &bq = BlockArgs{}, const BandArgs &kq = BandArgs{}) {
     static_assert(!BQ || (RAW && !STEAL && !XLDS && WAVES == 1 && sizeof(R) == sizeof(double)), "block costs: raw form, fp64, one wave per problem, one wave per SIMD");
+    static_assert(!KQ || (RAW && !BQ && !STEAL && !XLDS && WAVES == 1 && sizeof(R) == sizeof(double)), "neighbour-knot costs: raw form, diagonal per-knot weights, fp64, one wave per problem, one wave per SIMD");
     constexpr bool MW = WAVES > 1;
     static_assert(!MW || (LPP == 64 && !STEAL && sizeof(R) == sizeof(double)), "several waves per problem: fp64, one problem per workgroup");
     constexpr bool PARK = XLDS && !MW;      // (the LDS header is written by lane 0 and read by the whole problem: across waves that would take barriers)
@@ -151,7 +163,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
     // The step certificate of a force phase: every lane of every live problem found its scaled Gershgorin row test
     // (`ok`) true -- then no step of the phase's FISTA loop can fail the backtracking test, and the loop runs without it.  Wave-
     // (MW: workgroup-) uniform.
-    constexpr bool CAN_CERT = sizeof(R) == sizeof(double) && !BQ;      // (BQ: the rows below assume a diagonal W; fp32: the image noise does make the test fire, see the force step)
+    constexpr bool CAN_CERT = sizeof(R) == sizeof(double) && !BQ && !KQ;      // (BQ, KQ: the rows below assume a diagonal W; fp32: the image noise does make the test fire, see the force step)
     auto certify = [&](bool ok, mask_t live) -> bool {
         if (!CAN_CERT || !a.certified_steps) return false;
         if (!MW) return (__ballot(!ok) & live) == 0;
@@ -400,6 +412,19 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                 if (HASQF) qf[j] = R(0.5) * ldz<R>(a.qf + wave0 * nf, o.F + ph, j, rvalid);
             }
             }
+            // KQ: the weights between knots t and t + 1 (of) and t - 1 and t (ofp); a lane's place decides which neighbours it has
+            [[maybe_unused]] R of[KQ ? NF : 1], ofp[KQ ? NF : 1];
+            [[maybe_unused]] const int fnm = pvalid && t + 1 < H ? -1 : 0, fpm = rvalid && t >= 1 ? -1 : 0;
+            if constexpr (KQ) {
+                if (kq.Qf_off) {
+                    const unsigned oB = 8u * (sl_ * (unsigned)kq.sQf_off + (unsigned)NF * (unsigned)(t + 1 < H ? t : (H >= 2 ? H - 2 : 0))) + ph;
+                    UNROLL for (int j = 0; j < NF; ++j) of[j] = ldz<R>(kq.Qf_off + wave0 * kq.sQf_off, oB, j, fnm != 0);
+                } else {
+                    UNROLL for (int j = 0; j < NF; ++j) of[j] = R(0);
+                }
+                shift_prev(of, ofp);
+                UNROLL for (int j = 0; j < NF; ++j) ofp[j] = keep_if(ofp[j], fpm);
+            }
             // the step certificate: M = W + rho A_x'A_x is block-diagonal per knot; with dg = diag(M), u = |A| dg, v = |A|' u the lane's
             // rows pass if W_j dg_j + rho v_j <= T dg_j (tools/certify_rate.py restates this)
             bool cert = false;
@@ -476,6 +501,14 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                 mask_t done;
                 mask_t pend = act;
                 for (;;) {  // backtracking (fista.cpp:8-26); segments that accepted recompute the same values
+                    // KQ: y of knots t - 1 and t + 1 (fetched per trial: nearly every step takes one, and held across the retry loop they
+                    // would sit in accumulation registers)
+                    [[maybe_unused]] R yp[KQ ? NF : 1], yn[KQ ? NF : 1];
+                    if constexpr (KQ) {
+                        shift_prev(y, yp);
+                        shift_next(y, yn);
+                        UNROLL for (int j = 0; j < NF; ++j) { yp[j] = keep_if(yp[j], fpm); yn[j] = keep_if(yn[j], fnm); }
+                    }
                     // g/2 = Q y + q/2 + rho A^T (A y + bPk)          (problem.cpp:36-38,54-56), the step y - (2/L) g/2 and the
                     // "SoC" projection exactly as fista.cpp:52-70 writes it (zeroing by a 0 / 1 factor: one select per foot)
                     unsigned long long anycone = 0;     // lanes with a force on the cone branch, as a scalar mask
@@ -495,6 +528,10 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                         } else {
                             gx = fmaR(wf[3 * n], y[3 * n], rho * zx); gy = fmaR(wf[3 * n + 1], y[3 * n + 1], rho * zy);
                             gz = fmaR(wf[3 * n + 2], y[3 * n + 2], rho * zz);
+                            if constexpr (KQ) {
+                                gx = fmaR(ofp[3 * n], yp[3 * n], gx); gy = fmaR(ofp[3 * n + 1], yp[3 * n + 1], gy); gz = fmaR(ofp[3 * n + 2], yp[3 * n + 2], gz);
+                                gx = fmaR(of[3 * n], yn[3 * n], gx); gy = fmaR(of[3 * n + 1], yn[3 * n + 1], gy); gz = fmaR(of[3 * n + 2], yn[3 * n + 2], gz);
+                            }
                         }
                         if (HASQF) { gx += qf[3 * n]; gy += qf[3 * n + 1]; gz += qf[3 * n + 2]; }
                         fr[3 * n] = fmaR(-gx, invL, y[3 * n]);
@@ -531,6 +568,12 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                         dv[j] = d;
                         g2 = fmaR(d, d, g2);
                         if constexpr (!BQ) cv = fmaR(wf[j] * d, d, cv);
+                    }
+                    if constexpr (KQ) {      // the pairs (t, t + 1): 2 off_t d_t d_{t+1}, summed on their own so that ONE keep_if removes what came
+                        R dn[NF], cp = 0;    // across the end of the segment
+                        shift_next(dv, dn);
+                        UNROLL for (int j = 0; j < NF; ++j) cp = fmaR((of[j] + of[j]) * dv[j], dn[j], cp);
+                        cv += keep_if(cp, fnm);
                     }
                     if constexpr (BQ) {      // d'W d, row by row
                         UNROLL for (int r = 0; r < NF; ++r) {
@@ -765,15 +808,30 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                 }
                 UNROLL for (int l = 0; l < 9; ++l) Qb[sym_index(9, l, l)] += l0 ? rho : R(0);
             }
+            // KQ: the weights between knots t and t + 1 (ox) and t - 1 and t (oxp)
+            [[maybe_unused]] R ox[KQ ? 9 : 1], oxp[KQ ? 9 : 1];
+            [[maybe_unused]] const int xpm = kvalid && t >= 1 ? -1 : 0;
+            if constexpr (KQ) {
+                if (kq.Qx_off) {
+                    const unsigned oB = 8u * (sl_ * (unsigned)kq.sQx_off + 9u * tr) + ph;
+                    UNROLL for (int l = 0; l < 9; ++l) ox[l] = ldz<R>(kq.Qx_off + wave0 * kq.sQx_off, oB, l, rvalid);
+                } else {
+                    UNROLL for (int l = 0; l < 9; ++l) ox[l] = R(0);
+                }
+                shift_prev(ox, oxp);
+                UNROLL for (int l = 0; l < 9; ++l) oxp[l] = keep_if(oxp[l], xpm);
+            }
             UNROLL for (int l = 0; l < NB; ++l) {   // quieted once, so the clamp is a bare min/max pair
                 lb[l] = __builtin_canonicalize(lb[l]);
                 ub[l] = __builtin_canonicalize(ub[l]);
             }
             const int rmask = rvalid ? -1 : 0;      // row-block mask: lanes t >= H own no dynamics rows
             // u = A_f v + bPk on row-block t; vn = v of knot t+1
+            [[maybe_unused]] R vnx[KQ ? 9 : 1];      // KQ: what applyA fetched last from knot t + 1
             auto applyA = [&](const R (&v)[9], R (&u)[9]) {
                 R vn[9];
                 shift_next(v, vn);
+                if constexpr (KQ) { UNROLL for (int l = 0; l < 9; ++l) vnx[l] = vn[l]; }
                 R w[9];
                 UNROLL for (int l = 0; l < 9; ++l) w[l] = v[l] - vn[l];
                 UNROLL for (int k = 0; k < 3; ++k) w[k] += dt * vn[3 + k];
@@ -807,6 +865,12 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                 mask_t done;
                 mask_t pend = act;
                 for (;;) {
+                    [[maybe_unused]] R yp[KQ ? 9 : 1], yn[KQ ? 9 : 1];      // KQ: y of knots t - 1 and t + 1 (per trial, see the force step)
+                    if constexpr (KQ) {
+                        shift_prev(y, yp);
+                        shift_next(y, yn);
+                        UNROLL for (int l = 0; l < 9; ++l) { yp[l] = keep_if(yp[l], xpm); yn[l] = keep_if(yn[l], rmask); }
+                    }
                     {   // half gradient Q y + q/2 + rho A_f^T (A_f y + bPk), step, box projection (fista.cpp:10); inside the retry
                         // loop like the force step's
                         R z[9], wp[9];
@@ -820,6 +884,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                             R g = fmaR(rho, z[l], q[l]);
                             if constexpr (BQ) { UNROLL for (int j = 0; j < 9; ++j) g = fmaR(Qb[sym_index(9, l, j)], y[j], g); }      // row l of Q y, column by column
                             else g = fmaR(qd[l], y[l], g);
+                            if constexpr (KQ) { g = fmaR(oxp[l], yp[l], g); g = fmaR(ox[l], yn[l], g); }
                             R v = fmaR(-g, invL, y[l]);
                             if (l < NB) v = clamp_box(v, lb[l], ub[l]);
                             xn[l] = v;
@@ -828,12 +893,15 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                     applyA(xn, rn);
                     R g2 = 0, cv = 0, e2 = 0;
                     [[maybe_unused]] R dx[BQ ? 9 : 1];
+                    [[maybe_unused]] R cp = 0;      // KQ: the pairs (t, t + 1), 2 off_t d_t d_{t+1}, summed on their own (see the force step)
                     UNROLL for (int l = 0; l < 9; ++l) {
                         const R d = xn[l] - y[l];
                         const R e = rn[l] - ry[l];
                         g2 = fmaR(d, d, g2);
                         if constexpr (BQ) dx[l] = d;
                         else cv = fmaR(qd[l] * d, d, cv);
+                        // KQ: d_{t+1} = xn_{t+1} - y_{t+1} from what applyA fetched (the neighbour lane's bits where that lane is the problem's)
+                        if constexpr (KQ) cp = fmaR((ox[l] + ox[l]) * d, vnx[l] - yn[l], cp);
                         e2 = fmaR(e, e, e2);
                     }
                     if constexpr (BQ) {      // d'Q d, row by row
@@ -843,6 +911,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                             cv = fmaR(qdr, dx[r], cv);
                         }
                     }
+                    if constexpr (KQ) cv += keep_if(cp, rmask);
                     cv = fmaR(rho, e2, cv);
                     if (XLDS) { UNROLL for (int l = 0; l < 9; ++l) { xo[l] = Xz[l]; ro[l] = RXz[l]; } }      // (see the force step)
                     mask_t bt;

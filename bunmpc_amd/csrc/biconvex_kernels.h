@@ -63,6 +63,15 @@ struct BlockArgs {
     long sQx_blk, sQf_blk;
 };
 
+// Costs that couple neighbouring knots (bmpc_band_cost_t): Q[(t, i), (t + 1, i)] = Q[(t + 1, i), (t, i)] = off[t][i] beside BatchArgs'
+// diagonal (Qx / Qf) -- force-rate and momentum-rate terms.  Raw form, fp64, one knot per lane (biconvex_admm_body.h: KQ).  A side whose
+// pointer is null has no coupling.  Strides in doubles, 0 = one set of weights shared by the batch.
+struct BandArgs {
+    const double *Qx_off;   // [.][H][9]
+    const double *Qf_off;   // [.][H - 1][3E]
+    long sQx_off, sQf_off;
+};
+
 constexpr int kStats = 6;
 // LDS elements per knot of a problem (biconvex_admm_body.h: X 9, P 9, F 3E, R 9): 39 for four feet, 33 for two -- odd strides, so no
 // two lanes of a segment share a bank (an odd E would make it even: only E = 2 and 4 are built)
@@ -96,6 +105,13 @@ int admm_bq_scratch_bytes_e2();
 // ... and their dispatch: every batch size and num_iters goes to them (never the one-problem-per-wave, work-stealing or two-waves
 // kernels).  hipErrorInvalidValue unless raw, fp64, n_eff 2 or 4 and H + 1 <= 64 (the C-ABI refuses those with a message first).
 hipError_t launch_biconvex_admm_blocks(const BatchArgs &a, const BlockArgs &q, int n_eff, hipStream_t stream);
+
+// The neighbour-knot-cost kernels (biconvex_admm_kq.hip: E = 4, biconvex_admm_kq_e2.hip: E = 2) and their dispatch, as for the block kernels
+hipError_t launch_admm_kq_e4(const BatchArgs &a, const BandArgs &q, int lpp, hipStream_t stream);
+hipError_t launch_admm_kq_e2(const BatchArgs &a, const BandArgs &q, int lpp, hipStream_t stream);
+int admm_kq_scratch_bytes_e4();      // largest private-segment bytes per lane over them, -1 on error
+int admm_kq_scratch_bytes_e2();
+hipError_t launch_biconvex_admm_band(const BatchArgs &a, const BandArgs &q, int n_eff, hipStream_t stream);
 
 // The one-problem-per-wave mapping (biconvex_latency.hip): fp64, n_eff = 2 or 4, H + 1 <= 21.  launch_biconvex_admm takes it for
 // batches of at most latency_mapping_max_batch() problems that fit.

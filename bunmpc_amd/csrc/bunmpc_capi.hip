@@ -127,6 +127,29 @@ bunmpc::BlockArgs to_block_args(const bmpc_block_cost_t &c) {
     return q;
 }
 
+bool has_band(const bmpc_band_cost_t *c) { return c && (c->Qx_off || c->Qf_off); }
+
+// a batch with costs between neighbouring knots: what the band kernels are built for, then the batch itself
+int check_band(const bmpc_batch_t *d, const bmpc_band_cost_t *c) {
+    if (!d) return fail(BMPC_BAD_ARG, "null batch descriptor");
+    if (d->precision != 0) return fail(BMPC_BAD_ARG, "costs between neighbouring knots (Qx_off / Qf_off) are built for fp64 only: precision must be 0");
+    if (!d->raw) return fail(BMPC_BAD_ARG, "costs between neighbouring knots (Qx_off / Qf_off) are built for the raw form only: raw must be 1");
+    if (d->n_col + 1 > 64) return fail(BMPC_BAD_ARG, "costs between neighbouring knots (Qx_off / Qf_off) are built for n_col + 1 <= 64 knots only (one problem per wave segment)");
+    if (int rc = check_batch(d)) return rc;
+    const long need_x = 9L * d->n_col, need_f = 3L * d->n_eff * (d->n_col - 1);
+    if ((c->Qx_off && (c->sQx_off < 0 || c->sQx_off > (1L << 26) || (c->sQx_off != 0 && c->sQx_off < need_x))) ||
+        (c->Qf_off && (c->sQf_off < 0 || c->sQf_off > (1L << 26) || (c->sQf_off != 0 && c->sQf_off < need_f))))
+        return fail(BMPC_BAD_ARG, "batch stride of a coupling array (Qx_off / Qf_off) must be 0 (shared) or between one problem's weights and 2^26 doubles");
+    return BMPC_OK;
+}
+
+bunmpc::BandArgs to_band_args(const bmpc_band_cost_t &c) {
+    bunmpc::BandArgs q;
+    q.Qx_off = c.Qx_off; q.Qf_off = c.Qf_off;
+    q.sQx_off = c.Qx_off ? c.sQx_off : 0; q.sQf_off = c.Qf_off ? c.sQf_off : 0;
+    return q;
+}
+
 }  // namespace
 
 namespace bunmpc {
@@ -161,6 +184,9 @@ struct bmpc_biconvex {
     bool qf_nonzero = false;
     // per-knot blocks of Q (set_cost_x_blocks / set_cost_f_blocks); empty: that side has its diagonal
     std::vector<double> Qx_blk, Qf_blk;
+    // weights between neighbouring knots (set_cost_x_band / set_cost_f_band); has_*_off false: that side has none
+    std::vector<double> Qx_off, Qf_off;
+    bool has_x_off = false, has_f_off = false;
     // iterates
     std::vector<double> X, F, P;
     std::vector<double> rot;  // set_rotation_matrix_f: stored, unused (as in the reference)
@@ -188,6 +214,11 @@ int bmpc_set_exact_step_decisions(int on) { return bunmpc::set_exact_step_decisi
 int bmpc_set_certified_steps(int on) { return bunmpc::set_certified_steps(on); }
 int bmpc_biconvex_fp32_scratch_bytes(void) { return bunmpc::biconvex_admm_f32_scratch_bytes(); }
 int bmpc_block_cost_struct_size(void) { return (int)sizeof(bmpc_block_cost_t); }
+int bmpc_band_cost_struct_size(void) { return (int)sizeof(bmpc_band_cost_t); }
+int bmpc_biconvex_band_kernel_scratch_bytes(int n_eff) {
+    if (n_eff != 2 && n_eff != 4) { fail(BMPC_BAD_ARG, "n_eff must be 2 or 4"); return -1; }
+    return n_eff == 4 ? bunmpc::admm_kq_scratch_bytes_e4() : bunmpc::admm_kq_scratch_bytes_e2();
+}
 int bmpc_biconvex_block_kernel_scratch_bytes(int n_eff) {
     if (n_eff != 2 && n_eff != 4) { fail(BMPC_BAD_ARG, "n_eff must be 2 or 4"); return -1; }
     return n_eff == 4 ? bunmpc::admm_bq_scratch_bytes_e4() : bunmpc::admm_bq_scratch_bytes_e2();
@@ -487,12 +518,32 @@ int bmpc_biconvex_set_cost_x(bmpc_biconvex_t *h, const double *Q, const double *
     H_CHECK(Q, q);
     h->Qx.assign(Q, Q + h->nx()); h->qx.assign(q, q + h->nx());
     h->Qx_blk.clear();
+    h->has_x_off = false;
+    return BMPC_OK;
+}
+int bmpc_biconvex_set_cost_x_band(bmpc_biconvex_t *h, const double *Q_diag, const double *Q_off, const double *q) {
+    H_CHECK(Q_diag, q);
+    h->Qx.assign(Q_diag, Q_diag + h->nx()); h->qx.assign(q, q + h->nx());
+    h->Qx_blk.clear();
+    h->has_x_off = Q_off != nullptr;
+    if (Q_off) h->Qx_off.assign(Q_off, Q_off + (size_t)9 * h->n_col);
+    return BMPC_OK;
+}
+int bmpc_biconvex_set_cost_f_band(bmpc_biconvex_t *h, const double *Q_diag, const double *Q_off, const double *q) {
+    H_CHECK(Q_diag, q);
+    h->Qf.assign(Q_diag, Q_diag + h->nf()); h->qf.assign(q, q + h->nf());
+    h->Qf_blk.clear();
+    h->has_f_off = Q_off != nullptr && h->n_col > 1;
+    if (h->has_f_off) h->Qf_off.assign(Q_off, Q_off + (size_t)3 * h->n_eff * (h->n_col - 1));
+    h->qf_nonzero = false;
+    for (double v : h->qf) if (v != 0.0) h->qf_nonzero = true;
     return BMPC_OK;
 }
 int bmpc_biconvex_set_cost_x_blocks(bmpc_biconvex_t *h, const double *Q_blk, const double *q) {
     H_CHECK(Q_blk, q);
     if (int rc = check_symmetric(Q_blk, (size_t)h->n_col + 1, 9, "set_cost_x_blocks")) return rc;
     h->Qx_blk.assign(Q_blk, Q_blk + (size_t)81 * (h->n_col + 1));
+    h->has_x_off = false;
     for (int i = 0; i < h->nx(); ++i) h->Qx[i] = Q_blk[(size_t)(i / 9) * 81 + (size_t)(i % 9) * 10];      // (the diagonal, for whoever reads Qx)
     h->qx.assign(q, q + h->nx());
     return BMPC_OK;
@@ -502,6 +553,7 @@ int bmpc_biconvex_set_cost_f_blocks(bmpc_biconvex_t *h, const double *Q_blk, con
     const int k = 3 * h->n_eff;
     if (int rc = check_symmetric(Q_blk, (size_t)h->n_col, k, "set_cost_f_blocks")) return rc;
     h->Qf_blk.assign(Q_blk, Q_blk + (size_t)k * k * h->n_col);
+    h->has_f_off = false;
     for (int i = 0; i < h->nf(); ++i) h->Qf[i] = Q_blk[(size_t)(i / k) * k * k + (size_t)(i % k) * (k + 1)];
     h->qf.assign(q, q + h->nf());
     h->qf_nonzero = false;
@@ -512,6 +564,7 @@ int bmpc_biconvex_set_cost_f(bmpc_biconvex_t *h, const double *Q, const double *
     H_CHECK(Q, q);
     h->Qf.assign(Q, Q + h->nf()); h->qf.assign(q, q + h->nf());
     h->Qf_blk.clear();
+    h->has_f_off = false;
     h->qf_nonzero = false;
     for (double v : h->qf) if (v != 0.0) h->qf_nonzero = true;
     return BMPC_OK;
@@ -526,12 +579,14 @@ int bmpc_biconvex_create_cost_X(bmpc_biconvex_t *h, const double *W_X, const dou
         h->qx[i] = -2 * (X_ter[i - nv + 9] * W_X_ter[i - nv + 9]);
     }
     h->Qx_blk.clear();
+    h->has_x_off = false;
     return BMPC_OK;
 }
 int bmpc_biconvex_create_cost_F(bmpc_biconvex_t *h, const double *W_F) {  // biconvex.cpp:74-78
     H_CHECK(W_F);
     h->Qf.assign(W_F, W_F + h->nf());
     h->Qf_blk.clear();
+    h->has_f_off = false;
     return BMPC_OK;
 }
 int bmpc_biconvex_set_bounds_x(bmpc_biconvex_t *h, const double *lb, const double *ub) {
@@ -628,6 +683,11 @@ int bmpc_biconvex_last_stats(const bmpc_biconvex_t *h, int *stats6) {
 // BiConvexMP::optimize (biconvex.cpp:80-120) as one B = 1 launch of the batched kernel.
 int bmpc_biconvex_optimize(bmpc_biconvex_t *h, const double *x_init, int num_iters) {
     H_CHECK(x_init);
+    if ((h->has_x_off || h->has_f_off) && (!h->Qx_blk.empty() || !h->Qf_blk.empty()))
+        return fail(BMPC_BAD_ARG, "the handle carries costs between neighbouring knots (set_cost_x_band / set_cost_f_band) and per-knot blocks "
+                                  "(set_cost_x_blocks / set_cost_f_blocks): coupling between knots needs diagonal per-knot weights on both sides");
+    if ((h->has_x_off || h->has_f_off) && h->n_col + 1 > 64)
+        return fail(BMPC_BAD_ARG, "costs between neighbouring knots (Qx_off / Qf_off) are built for n_col + 1 <= 64 knots only (one problem per wave segment)");
     if (int rc = need_plan(h)) return rc;
     if (num_iters < 0) return fail(BMPC_BAD_ARG, "num_iters < 0");
     const int H = h->n_col, E = h->n_eff, nx = h->nx(), nf = h->nf();
@@ -645,6 +705,7 @@ int bmpc_biconvex_optimize(bmpc_biconvex_t *h, const double *x_init, int num_ite
                  o_lb = take(nx), o_ub = take(nx), o_Qf = take(nf), o_qf = take(nf), o_X = take(nx),
                  o_F = take(nf), o_P = take(nx), o_L = take(2), o_viol = take(1), o_hist = take(nh);
     const size_t o_end = off, o_Qxb = take(h->Qx_blk.size()), o_Qfb = take(h->Qf_blk.size());      // (blocks: behind what comes back)
+    const size_t o_Qxo = take(h->has_x_off ? h->Qx_off.size() : 0), o_Qfo = take(h->has_f_off ? h->Qf_off.size() : 0);
     std::vector<double> stage(off, 0.0);
     auto put = [&](size_t o, const double *src, size_t n) { std::memcpy(stage.data() + o, src, sizeof(double) * n); };
     put(o_cnt, cnt.data(), cnt.size()); put(o_dt, h->dt.data(), H); put(o_xi, x_init, 9);
@@ -653,6 +714,8 @@ int bmpc_biconvex_optimize(bmpc_biconvex_t *h, const double *x_init, int num_ite
     put(o_X, h->X.data(), nx); put(o_F, h->F.data(), nf); put(o_P, h->P.data(), nx);
     if (!h->Qx_blk.empty()) put(o_Qxb, h->Qx_blk.data(), h->Qx_blk.size());
     if (!h->Qf_blk.empty()) put(o_Qfb, h->Qf_blk.data(), h->Qf_blk.size());
+    if (h->has_x_off) put(o_Qxo, h->Qx_off.data(), h->Qx_off.size());
+    if (h->has_f_off) put(o_Qfo, h->Qf_off.data(), h->Qf_off.size());
     stage[o_L] = h->L_x; stage[o_L + 1] = h->L_f;
     HIP_TRY(h->dbuf.ensure(sizeof(double) * off));
     HIP_TRY(h->dstats.ensure(sizeof(int) * bunmpc::kStats));
@@ -673,7 +736,14 @@ int bmpc_biconvex_optimize(bmpc_biconvex_t *h, const double *x_init, int num_ite
     std::memset(&blk, 0, sizeof(blk));
     if (!h->Qx_blk.empty()) blk.Qx_blk = d + o_Qxb;
     if (!h->Qf_blk.empty()) blk.Qf_blk = d + o_Qfb;
-    if (has_blocks(&blk)) {
+    bmpc_band_cost_t band;
+    std::memset(&band, 0, sizeof(band));
+    if (h->has_x_off) band.Qx_off = d + o_Qxo;
+    if (h->has_f_off) band.Qf_off = d + o_Qfo;
+    if (has_band(&band)) {
+        if (int rc = check_band(&b, &band)) return rc;
+        HIP_TRY(bunmpc::launch_biconvex_admm_band(to_args(b), to_band_args(band), E, nullptr));
+    } else if (has_blocks(&blk)) {
         if (int rc = check_blocks(&b, &blk)) return rc;
         HIP_TRY(bunmpc::launch_biconvex_admm_blocks(to_args(b), to_block_args(blk), E, nullptr));
     } else {
@@ -718,11 +788,27 @@ int bmpc_biconvex_solve_batch_blocks_device(const bmpc_batch_t *d, const bmpc_bl
     return BMPC_OK;
 }
 
-int bmpc_biconvex_solve_batch_host(const bmpc_batch_t *d) { return bmpc_biconvex_solve_batch_blocks_host(d, nullptr); }
+int bmpc_biconvex_solve_batch_band_device(const bmpc_batch_t *d, const bmpc_band_cost_t *c, void *hip_stream) {
+    if (!has_band(c)) return bmpc_biconvex_solve_batch_device(d, hip_stream);
+    if (int rc = check_band(d, c)) return rc;
+    HIP_TRY(bunmpc::launch_biconvex_admm_band(to_args(*d), to_band_args(*c), d->n_eff, static_cast<hipStream_t>(hip_stream)));
+    return BMPC_OK;
+}
 
-int bmpc_biconvex_solve_batch_blocks_host(const bmpc_batch_t *d, const bmpc_block_cost_t *c) {
-    const bool blocks = has_blocks(c);
-    if (int rc = blocks ? check_blocks(d, c) : check_batch(d)) return rc;
+namespace {
+int solve_batch_host(const bmpc_batch_t *d, const bmpc_block_cost_t *c, const bmpc_band_cost_t *kc);
+}
+int bmpc_biconvex_solve_batch_host(const bmpc_batch_t *d) { return solve_batch_host(d, nullptr, nullptr); }
+int bmpc_biconvex_solve_batch_blocks_host(const bmpc_batch_t *d, const bmpc_block_cost_t *c) { return solve_batch_host(d, c, nullptr); }
+int bmpc_biconvex_solve_batch_band_host(const bmpc_batch_t *d, const bmpc_band_cost_t *c) { return solve_batch_host(d, nullptr, c); }
+
+}  // extern "C"
+
+namespace {
+// the host entry points: arrays to the device, one launch, results back (c: per-knot blocks, kc: costs between neighbouring knots; at most one of them)
+int solve_batch_host(const bmpc_batch_t *d, const bmpc_block_cost_t *c, const bmpc_band_cost_t *kc) {
+    const bool blocks = has_blocks(c), band = has_band(kc);
+    if (int rc = blocks ? check_blocks(d, c) : (band ? check_band(d, kc) : check_batch(d))) return rc;
     const size_t B = (size_t)d->B, H = (size_t)d->n_col, E = (size_t)d->n_eff;
     const size_t nx = 9 * (H + 1), nf = 3 * E * H;
     if (B == 0) return BMPC_OK;
@@ -730,6 +816,10 @@ int bmpc_biconvex_solve_batch_blocks_host(const bmpc_batch_t *d, const bmpc_bloc
     bmpc_block_cost_t cb;
     std::memset(&cb, 0, sizeof(cb));
     if (blocks) cb = *c;
+    bmpc_band_cost_t kb;
+    std::memset(&kb, 0, sizeof(kb));
+    if (band) kb = *kc;
+    if (H < 2) kb.Qf_off = nullptr;      // (one force knot: no pair)
     struct In { const double **slot; size_t n; };
     struct Out { double **slot; double *host; size_t n; };
     auto rows = [&](long stride) { return stride == 0 ? (size_t)1 : B; };
@@ -752,6 +842,8 @@ int bmpc_biconvex_solve_batch_blocks_host(const bmpc_batch_t *d, const bmpc_bloc
             b.Qf = nullptr;
         } else ins.push_back({&b.Qf, B * nf});
         if (d->qf) ins.push_back({&b.qf, B * nf});
+        if (kb.Qx_off) ins.push_back({&kb.Qx_off, (rows(kb.sQx_off) - 1) * (size_t)kb.sQx_off + 9 * H});
+        if (kb.Qf_off) ins.push_back({&kb.Qf_off, (rows(kb.sQf_off) - 1) * (size_t)kb.sQf_off + 3 * E * (H - 1)});
     } else {
         ins.push_back({&b.W_X, (rows(d->sW_X) - 1) * (size_t)d->sW_X + 9 * H});
         ins.push_back({&b.W_X_ter, (rows(d->sW_X_ter) - 1) * (size_t)d->sW_X_ter + 9});
@@ -789,6 +881,7 @@ int bmpc_biconvex_solve_batch_blocks_host(const bmpc_batch_t *d, const bmpc_bloc
         b.trace = static_cast<int *>(tbuf.p);
     }
     if (blocks) HIP_TRY(bunmpc::launch_biconvex_admm_blocks(to_args(b), to_block_args(cb), d->n_eff, nullptr));
+    else if (has_band(&kb)) HIP_TRY(bunmpc::launch_biconvex_admm_band(to_args(b), to_band_args(kb), d->n_eff, nullptr));
     else HIP_TRY(bunmpc::launch_biconvex_admm(to_args(b), d->n_eff, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     for (auto &o : outs) HIP_TRY(hipMemcpy(o.host, *o.slot, sizeof(double) * o.n, hipMemcpyDeviceToHost));
@@ -796,6 +889,9 @@ int bmpc_biconvex_solve_batch_blocks_host(const bmpc_batch_t *d, const bmpc_bloc
     if (d->trace) HIP_TRY(hipMemcpy(d->trace, tbuf.p, sizeof(int) * ntrace, hipMemcpyDeviceToHost));
     return BMPC_OK;
 }
+}  // namespace
+
+extern "C" {
 
 const char *bmpc_biconvex_kernel_name(int n_col, int raw) { return bunmpc::biconvex_kernel_name(n_col, raw); }
 const char *bmpc_biconvex_last_kernel_name(void) { return bunmpc::biconvex_last_kernel_name(); }

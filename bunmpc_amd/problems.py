@@ -305,6 +305,39 @@ def block_diag_matrix(blk):
     return Q
 
 
+def rate_costs(Qx, Qf, E, lam_x, lam_f):
+    """Costs between neighbouring knots from a batch's diagonal raw arrays Qx (B, 9 (H + 1)) and Qf (B, 3 E H): a force-rate term
+    sum_t (F_{t+1} - F_t)' R_f[t] (F_{t+1} - F_t) with R_f[t] = lam_f * Qf[t], t = 0 .. H - 2, and the same difference on X with
+    R_x[t] = lam_x * Qx[t], t = 0 .. H - 1, the three CoM-position components set to 0 (a rate cost on velocity and angular momentum:
+    CoM acceleration, momentum rate).  Each is D' R D with D the first difference over the knots: diag[t] += R[t - 1] + R[t],
+    off[t] = -R[t] (tests, tools/band_cost_bench.py).
+    Returns dict(Qx (B, 9 (H + 1)), Qx_off (B, H, 9), Qf (B, 3 E H), Qf_off (B, H - 1, 3 E))."""
+    Qx, Qf = (np.asarray(a, dtype=np.float64) for a in (Qx, Qf))
+    B, K, H = Qx.shape[0], Qx.shape[1] // 9, Qf.shape[1] // (3 * E)
+    dx, df = Qx.reshape(B, K, 9).copy(), Qf.reshape(B, H, 3 * E).copy()
+    Rx, Rf = lam_x * dx[:, :-1], lam_f * df[:, :-1]
+    Rx[:, :, :3] = 0.0
+    dx[:, :-1] += Rx
+    dx[:, 1:] += Rx
+    df[:, :-1] += Rf
+    df[:, 1:] += Rf
+    return dict(Qx=dx.reshape(B, -1), Qx_off=-Rx, Qf=df.reshape(B, -1), Qf_off=-Rf)
+
+
+def band_matrix(diag, off):
+    """The square matrix with diag (n k values) on its diagonal and off (n - 1, k) between the same components of neighbouring
+    knots, Q[(t, i), (t + 1, i)] = Q[(t + 1, i), (t, i)] = off[t][i], dense: what set_cost_x / set_cost_f take"""
+    off = np.asarray(off, dtype=np.float64)
+    k = off.shape[1]
+    diag = np.asarray(diag, dtype=np.float64).reshape(-1)
+    assert diag.size == (off.shape[0] + 1) * k
+    Q = np.diag(diag)
+    i = np.arange(off.size)
+    Q[i, i + k] = off.reshape(-1)
+    Q[i + k, i] = off.reshape(-1)
+    return Q
+
+
 def _draws(seed, first, B, n):
     """Per-problem independent streams: problem b always sees the same numbers whatever the
     batch size or the rank that generates it (SeedSequence.spawn keyed by absolute index)."""

@@ -203,7 +203,8 @@ int bmpc_biconvex_kernel_scratch_bytes(int n_eff, int precision);
 /* symbol-name prefix of the kernel that serves (n_col, raw), for profiles */
 const char *bmpc_biconvex_kernel_name(int n_col, int raw);
 /* which kernel the calling host thread's latest batch solve was dispatched to: "biconvex_latency_kernel" (one problem per wave),
- * "biconvex_admm_kernel" or "biconvex_admm_kernel_f32" (one knot per lane), "biconvex_admm_bq_kernel" (block costs); "" before the first solve */
+ * "biconvex_admm_kernel" or "biconvex_admm_kernel_f32" (one knot per lane), "biconvex_admm_bq_kernel" (block costs),
+ * "biconvex_admm_kq_kernel" (costs between neighbouring knots); "" before the first solve */
 const char *bmpc_biconvex_last_kernel_name(void);
 
 /* Per-knot block-diagonal costs (additive) --------------------------------------------------------------------------------
@@ -234,6 +235,38 @@ int bmpc_biconvex_set_cost_f_blocks(bmpc_biconvex_t *h, const double *Q_blk, con
 /* The largest scratch (private-segment) bytes per lane over the block-cost kernels of one foot count (n_eff 2 or 4), as the loaded
  * code object reports them; -1 for another n_eff, or on error.  (bmpc_biconvex_kernel_scratch_bytes covers the other kernels.) */
 int bmpc_biconvex_block_kernel_scratch_bytes(int n_eff);
+
+/* Costs between neighbouring knots ("band" costs, additive) -----------------------------------------------------------------
+ * A force-rate term sum_t (F_{t+1} - F_t)' R_t (F_{t+1} - F_t), or the same difference on rows of X (CoM acceleration, momentum
+ * rate), is D' R D with D the first difference over the knots: a Q that is block-tridiagonal over the knots with DIAGONAL
+ * off-diagonal blocks.  That class is taken here:
+ *     Q[(t, i), (t, i)]     = the per-knot diagonal, d->Qx / d->Qf as ever
+ *     Q[(t, i), (t + 1, i)] = Q[(t + 1, i), (t, i)] = off[t][i]        (any sign; Q = diag + D' R D: diag[t] += R[t-1] + R[t], off[t] = -R[t])
+ * Either pointer may be NULL: that side has no coupling.  With c NULL or both pointers NULL the calls are the plain ones.  Strides
+ * in doubles: 0 = one set of weights shared by the batch, otherwise at least one problem's weights and at most 2^26.
+ * Not expressible: off-diagonal blocks that are not diagonal, coupling beyond the next knot, and coupling together with per-knot
+ * blocks (bmpc_block_cost_t) on either side.
+ * Built for: raw form (raw = 1), fp64 (precision = 0), n_col + 1 <= 64 knots, n_eff in {2, 4}; anything else is BMPC_BAD_ARG with a
+ * message that names the limit.  Such a batch runs "biconvex_admm_kq_kernel" (one knot per lane, 16 / 21 / 32 / 64 lanes per
+ * problem, one wave per SIMD) at every batch size and num_iters; every FISTA step is tested on fp64 sums (no step certificate, no
+ * fp32 step decisions), so bmpc_set_certified_steps, bmpc_set_exact_step_decisions, bmpc_set_work_stealing and
+ * bmpc_set_two_waves_per_simd do not touch it. */
+typedef struct {
+    const double *Qx_off; long sQx_off;   /* [.][n_col][9]        weight between knots t and t + 1 of X */
+    const double *Qf_off; long sQf_off;   /* [.][n_col - 1][3E]   ... of F                              */
+} bmpc_band_cost_t;
+int bmpc_band_cost_struct_size(void);        /* sizeof(bmpc_band_cost_t), to catch binding drift */
+int bmpc_biconvex_solve_batch_band_device(const bmpc_batch_t *d, const bmpc_band_cost_t *c, void *hip_stream);
+int bmpc_biconvex_solve_batch_band_host(const bmpc_batch_t *d, const bmpc_band_cost_t *c);
+/* The handle's cost with coupling: Q_diag [n_col+1][9] / [n_col][3E] and q as in set_cost_x / set_cost_f, Q_off [n_col][9] /
+ * [n_col-1][3E] (NULL: none).  optimize then takes the band kernel while either side has coupling; bmpc_biconvex_set_cost_x / _f
+ * (or create_cost_X / _F) return that side to its diagonal.  A handle that carries coupling on one side and blocks on either is
+ * refused by optimize (BMPC_BAD_ARG). */
+int bmpc_biconvex_set_cost_x_band(bmpc_biconvex_t *h, const double *Q_diag, const double *Q_off, const double *q);
+int bmpc_biconvex_set_cost_f_band(bmpc_biconvex_t *h, const double *Q_diag, const double *Q_off, const double *q);
+/* The largest scratch (private-segment) bytes per lane over the band-cost kernels of one foot count (n_eff 2 or 4), as the loaded
+ * code object reports them; -1 for another n_eff, or on error. */
+int bmpc_biconvex_band_kernel_scratch_bytes(int n_eff);
 
 /* rigid-body model -------------------------------------------------------------------
  * What pinocchio::urdf::buildModel(urdf, JointModelFreeFlyer()) yields (inverse_kinematics.cpp:10,
