@@ -40,6 +40,12 @@ class BlockCost(C.Structure):
     _fields_ = [("Qx_blk", C.c_void_p), ("sQx_blk", C.c_long), ("Qf_blk", C.c_void_p), ("sQf_blk", C.c_long)]
 
 
+class LaunchPlan(C.Structure):
+    """bmpc_launch_plan_t"""
+    _fields_ = [("status", C.c_int), ("lanes_per_problem", C.c_int), ("waves_per_simd", C.c_int), ("steal", C.c_int), ("steal_waves", C.c_long),
+                ("kernel", C.c_char_p)]
+
+
 class GaitParams(C.Structure):
     """bmpc_gait_params_t"""
     _fields_ = [("gait_period", C.c_double), ("gait_dt", C.c_double), ("gait_horizon", C.c_double), ("nom_ht", C.c_double),
@@ -173,6 +179,7 @@ _SIGS = {
     "bmpc_biconvex_band_kernel_scratch_bytes": (_I, [_I]),
     "bmpc_biconvex_kernel_name": (C.c_char_p, [_I, _I]),
     "bmpc_biconvex_last_kernel_name": (C.c_char_p, []),
+    "bmpc_biconvex_plan_launch": (_I, [_P, _I, C.c_long, _P]),
     "bmpc_plan_batch_device": (_I, [_P, _P]),
     "bmpc_wb_plan_batch_device": (_I, [_P, _P]),
     "bmpc_interp_batch_device": (_I, [_P, _P]),

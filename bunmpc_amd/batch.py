@@ -26,31 +26,33 @@ def _stride(a):
     return 0 if a.shape[0] == 1 else int(np.prod(a.shape[1:]))
 
 
-def _block_cost(B, H, E, Qx_blk, Qf_blk, put):
-    """bmpc_block_cost_t of Qx_blk (1 or B, H + 1, 9, 9) / Qf_blk (1 or B, H, 3E, 3E), either None; put(array) -> its address"""
-    c = _lib.BlockCost()
-    for name, a, shape in (("Qx_blk", Qx_blk, (H + 1, 9, 9)), ("Qf_blk", Qf_blk, (H, 3 * E, 3 * E))):
+_COMBINED = "Qx_off / Qf_off (costs between neighbouring knots) cannot be combined with Qx_blk / Qf_blk (per-knot blocks)"
+
+
+def _cost_ext(kind, B, H, E, x, f, put):
+    """bmpc_block_cost_t (kind "blk") of Qx_blk (1 or B, H + 1, 9, 9) / Qf_blk (1 or B, H, 3E, 3E), or bmpc_band_cost_t (kind "off") of
+    Qx_off (1 or B, H, 9) / Qf_off (1 or B, H - 1, 3E); either array None.  put(array) -> its address.  None without an array."""
+    shapes = {"blk": ((H + 1, 9, 9), (H, 3 * E, 3 * E)), "off": ((H, 9), (H - 1, 3 * E))}[kind]
+    c = _lib.BlockCost() if kind == "blk" else _lib.BandCost()
+    for name, a, shape in (("Qx_" + kind, x, shapes[0]), ("Qf_" + kind, f, shapes[1])):
         if a is None:
             continue
         if a.shape[1:] != shape or a.shape[0] not in (1, B):
-            raise ValueError("%s: expected shape (1 or %d, %d, %d, %d), got %s" % ((name, B) + shape + (tuple(a.shape),)))
-        setattr(c, name, put(a))
-        setattr(c, "s" + name, _stride(a))
-    return c
-
-
-def _band_cost(B, H, E, Qx_off, Qf_off, put):
-    """bmpc_band_cost_t of Qx_off (1 or B, H, 9) / Qf_off (1 or B, H - 1, 3E), either None; put(array) -> its address"""
-    c = _lib.BandCost()
-    for name, a, shape in (("Qx_off", Qx_off, (H, 9)), ("Qf_off", Qf_off, (H - 1, 3 * E))):
-        if a is None:
-            continue
-        if a.shape[1:] != shape or a.shape[0] not in (1, B):
-            raise ValueError("%s: expected shape (1 or %d, %d, %d), got %s" % ((name, B) + shape + (tuple(a.shape),)))
-        if a.size:      # (H = 1: no pair of force knots)
+            raise ValueError("%s: expected shape (1 or %d, %s), got %s" % (name, B, ", ".join("%d" % n for n in shape), tuple(a.shape)))
+        if a.size:      # (band costs at H = 1: no pair of force knots)
             setattr(c, name, put(a))
             setattr(c, "s" + name, _stride(a))
-    return c
+    return c if getattr(c, "Qx_" + kind) or getattr(c, "Qf_" + kind) else None
+
+
+def _launch(desc, blocks, band, stream=None):
+    """the solve call of the batch's cost shape: on `stream` with device arrays, or (None) the host call"""
+    lib, where = _lib.lib(), "host" if stream is None else "device"
+    tail = () if stream is None else (C.c_void_p(stream),)
+    for kind, cost in (("blocks_", blocks), ("band_", band)):
+        if cost is not None:
+            return _lib.check(getattr(lib, "bmpc_biconvex_solve_batch_" + kind + where)(C.byref(desc), C.byref(cost), *tail))
+    return _lib.check(getattr(lib, "bmpc_biconvex_solve_batch_" + where)(C.byref(desc), *tail))
 
 
 def algorithmic_bytes_per_solve(H, E=4, per_problem_weights=False):
@@ -104,13 +106,11 @@ class DeviceBatch:
                     assert np.shape(raw[k]) == (B, 3 * E * H if k in ("Qf", "qf") else 9 * (H + 1)), k
                     self.t[k] = up(raw[k])
             self.tb = {k: up(raw[k]) for k in ("Qx_blk", "Qf_blk") if raw.get(k) is not None}
-            if self.tb:
-                self.blocks = _block_cost(B, H, E, self.tb.get("Qx_blk"), self.tb.get("Qf_blk"), lambda t: t.data_ptr())
             self.tk = {k: up(raw[k]) for k in ("Qx_off", "Qf_off") if raw.get(k) is not None}
-            if self.tk:
-                if self.tb:
-                    raise ValueError("Qx_off / Qf_off (costs between neighbouring knots) cannot be combined with Qx_blk / Qf_blk (per-knot blocks)")
-                self.band = _band_cost(B, H, E, self.tk.get("Qx_off"), self.tk.get("Qf_off"), lambda t: t.data_ptr())
+            self.blocks = _cost_ext("blk", B, H, E, self.tb.get("Qx_blk"), self.tb.get("Qf_blk"), lambda t: t.data_ptr())
+            if self.tb and self.tk:
+                raise ValueError(_COMBINED)
+            self.band = _cost_ext("off", B, H, E, self.tk.get("Qx_off"), self.tk.get("Qf_off"), lambda t: t.data_ptr())
         self.X = torch.empty((B, 9 * (H + 1)), dtype=f64, device=self.device)
         self.F = torch.empty((B, 3 * E * H), dtype=f64, device=self.device)
         self.P = torch.empty((B, 9 * (H + 1)), dtype=f64, device=self.device)
@@ -169,12 +169,7 @@ class DeviceBatch:
         if self.hist is not None:      # rows of ADMM iterations that do not run keep their NaN / -1
             self.hist.fill_(float("nan"))
             self.trace.fill_(-1)
-        if self.blocks is not None:
-            _lib.check(_lib.lib().bmpc_biconvex_solve_batch_blocks_device(C.byref(self.desc), C.byref(self.blocks), C.c_void_p(stream)))
-        elif self.band is not None:
-            _lib.check(_lib.lib().bmpc_biconvex_solve_batch_band_device(C.byref(self.desc), C.byref(self.band), C.c_void_p(stream)))
-        else:
-            _lib.check(_lib.lib().bmpc_biconvex_solve_batch_device(C.byref(self.desc), C.c_void_p(stream)))
+        _launch(self.desc, self.blocks, self.band, stream)
 
     def results(self):
         self.torch.cuda.synchronize(self.device)
@@ -205,6 +200,7 @@ def solve_host(batch, num_iters=10, maxit=150, tol=1e-5, exit_tol=1e-3, beta=1.5
         keep.append(a)
         return a
 
+    blocks = band = None
     d = _lib.Batch()
     _lib.lib().bmpc_batch_defaults(C.byref(d))
     _solver_fields(d, batch, num_iters, maxit, tol, exit_tol, beta, mu)
@@ -219,12 +215,10 @@ def solve_host(batch, num_iters=10, maxit=150, tol=1e-5, exit_tol=1e-3, beta=1.5
         d.sW_F, d.sbounds = _stride(batch.W_F), _stride(batch.bounds)
     else:
         d.raw = 1
-        blocks = _block_cost(B, H, E, *(None if raw.get(k) is None else f64(raw[k]) for k in ("Qx_blk", "Qf_blk")),
-                             put=lambda a: a.ctypes.data)
-        band = _band_cost(B, H, E, *(None if raw.get(k) is None else f64(raw[k]) for k in ("Qx_off", "Qf_off")),
-                          put=lambda a: a.ctypes.data)
-        if (band.Qx_off or band.Qf_off) and (blocks.Qx_blk or blocks.Qf_blk):
-            raise ValueError("Qx_off / Qf_off (costs between neighbouring knots) cannot be combined with Qx_blk / Qf_blk (per-knot blocks)")
+        blocks, band = (_cost_ext(kind, B, H, E, *(None if raw.get(k) is None else f64(raw[k]) for k in ("Qx_" + kind, "Qf_" + kind)),
+                                  put=lambda a: a.ctypes.data) for kind in ("blk", "off"))
+        if blocks is not None and band is not None:
+            raise ValueError(_COMBINED)
         for k in ("Qx", "qx", "lbx", "ubx", "Qf"):
             if raw.get(k) is None and k in ("Qx", "Qf") and raw.get(k + "_blk") is not None:
                 continue
@@ -249,12 +243,7 @@ def solve_host(batch, num_iters=10, maxit=150, tol=1e-5, exit_tol=1e-3, beta=1.5
     trace = np.full((B, max(num_iters, 1), 4), -1, dtype=np.int32) if keep_hist else None
     d.hist = hist.ctypes.data if keep_hist else None
     d.trace = trace.ctypes.data if keep_hist else None
-    if raw is not None and (blocks.Qx_blk or blocks.Qf_blk):
-        _lib.check(_lib.lib().bmpc_biconvex_solve_batch_blocks_host(C.byref(d), C.byref(blocks)))
-    elif raw is not None and (band.Qx_off or band.Qf_off):
-        _lib.check(_lib.lib().bmpc_biconvex_solve_batch_band_host(C.byref(d), C.byref(band)))
-    else:
-        _lib.check(_lib.lib().bmpc_biconvex_solve_batch_host(C.byref(d)))
+    _launch(d, blocks, band)
     out = dict(X=X, F=F, P=P, L_x=Lx, L_f=Lf, dyn_viol=viol, stats=stats.astype(np.int64))
     if keep_hist:
         out["hist"] = hist

@@ -77,44 +77,62 @@ __global__ void momentum_table_kernel(double *tab, int n) {
         tk = tk1;
     }
 }
-const double *momentum_table(hipStream_t stream) {
-    static std::mutex lock;
-    static double *tab[16] = {};
+// What a process keeps per device: the momentum table, the work-stealing launches' counters and the chip's size.  (The raised LDS limit
+// of a workgroup kernel is per device too: launch_wg, biconvex_admm_inst.h.)
+struct DeviceState {
+    double *momentum = nullptr;
+    int *steal_ring = nullptr;       // 64 counters, one per launch in flight (a launch zeroes its own on its stream in front of the kernel;
+    unsigned steal_next = 0;         // with 64 a counter comes round again only after 63 later launches on this device)
+    long simds = 0;
+};
+std::mutex g_device_lock;
+// ... of the current device; call with g_device_lock held.  nullptr on error or beyond 16 devices.
+DeviceState *device_state() {
+    static DeviceState state[16];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-    std::lock_guard<std::mutex> hold(lock);
-    if (!tab[dev]) {
+    return &state[dev];
+}
+long device_simds() {
+    std::lock_guard<std::mutex> hold(g_device_lock);
+    DeviceState *d = device_state();
+    if (d && d->simds) return d->simds;
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    if (d) d->simds = 4 * cus;
+    return 4 * cus;
+}
+const double *momentum_table(hipStream_t stream) {
+    std::lock_guard<std::mutex> hold(g_device_lock);
+    DeviceState *d = device_state();
+    if (!d) return nullptr;
+    if (!d->momentum) {
         double *t = nullptr;
         if (hipMalloc(reinterpret_cast<void **>(&t), kMaxFistaIters * sizeof(double)) != hipSuccess) return nullptr;
         hipLaunchKernelGGL(momentum_table_kernel, dim3(1), dim3(1), 0, stream, t, kMaxFistaIters);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { (void)hipFree(t); return nullptr; }      // (once per device: later launches on any stream find it filled)
-        tab[dev] = t;
+        d->momentum = t;
     }
-    return tab[dev];
+    return d->momentum;
 }
-
-// Device counters of the work-stealing launches: a ring of 64 per device, one per launch in flight (a launch zeroes its own on its
-// stream in front of the kernel; with 64 a counter comes round again only after 63 later launches of this process)
 int *steal_counter(hipStream_t stream) {
-    static std::mutex lock;
-    static int *ring[16] = {};
-    static unsigned next = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-    std::lock_guard<std::mutex> hold(lock);
-    if (!ring[dev] && hipMalloc(reinterpret_cast<void **>(&ring[dev]), 64 * sizeof(int)) != hipSuccess) { ring[dev] = nullptr; return nullptr; }
-    int *c = ring[dev] + (next++ % 64);
+    std::lock_guard<std::mutex> hold(g_device_lock);
+    DeviceState *d = device_state();
+    if (!d) return nullptr;
+    if (!d->steal_ring && hipMalloc(reinterpret_cast<void **>(&d->steal_ring), 64 * sizeof(int)) != hipSuccess) { d->steal_ring = nullptr; return nullptr; }
+    int *c = d->steal_ring + (d->steal_next++ % 64);
     if (hipMemsetAsync(c, 0, sizeof(int), stream) != hipSuccess) return nullptr;
     return c;
 }
-int g_steal_grid = 0;      // waves of the work-stealing kernel's persistent grid (experiments, set_steal_grid below): 0 = one or two per SIMD
 
-}  // namespace
+DispatchKnobs g_knobs;
+// of the calling host thread's latest launch_biconvex_admm (tests of the default dispatch; profiles)
+thread_local const char *t_last_kernel = "";
+thread_local int t_last_lpp = 0, t_last_wpe = 1;
 
-hipError_t launch_admm_e4(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream) { return launch_admm<4>(a, l, stream); }
-int admm_scratch_bytes_e4() { return admm_scratch_bytes<4>(); }
+int set_knob(int &knob, int value) { const int old = knob; knob = value; return old; }
 
-// Horizons of 17..21 knots: 0 = 32-lane segments (two problems per wave), 1 = 21-lane segments (three per wave), 2 (default) = whichever
+// Horizons of 17..21 knots: 32-lane segments (two problems per wave) or 21-lane segments (three per wave), whichever
 // finishes the batch sooner.  The kernel runs one wave per SIMD; a wave of three problems takes ~8 % longer than a wave of two
 // (the segment sums cost more), so three per wave wins whenever it needs fewer ROUNDS of waves over the chip's SIMDs -- at
 // B = 4096 on an MI355X (1024 SIMDs) both need two rounds, 1366 waves or 2048, and two per wave is the faster one; at B = 3072 or
@@ -122,152 +140,123 @@ int admm_scratch_bytes_e4() { return admm_scratch_bytes<4>(); }
 // (num_iters well above ten: the ADMM's early exit, biconvex.cpp:111-114, makes the iteration counts differ per problem and the
 // scheduler backfills; measured at num_iters = 100, B = 4096: 31 -> 28 ms).  (Tried and dropped: B = 4096 as one round of three per
 // wave for 3072 problems + the one-problem-per-wave kernel for the other 1024 -- 2.29 + 1.7 ms, level with 2 x 2.02 ms.)
-int set_steal_grid(int waves) { const int old = g_steal_grid; g_steal_grid = waves; return old; }
-static int g_three_per_wave = 2;
-int set_three_per_wave(int on) { const int old = g_three_per_wave; g_three_per_wave = on; return old; }
-static long chip_simds() {
-    static int simds = 0;
-    if (simds == 0) {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        simds = 4 * cus;
-    }
-    return simds;
-}
-static bool three_per_wave_pays(const BatchArgs &a) {
-    if (g_three_per_wave != 2) return g_three_per_wave != 0;
-    const long simds = chip_simds(), w3 = (a.B + 2) / 3, w2 = (a.B + 1) / 2;
+bool three_per_wave_pays(const BatchArgs &a, long simds, const DispatchKnobs &kn) {
+    if (kn.three_per_wave != 2) return kn.three_per_wave != 0;
+    const long w3 = (a.B + 2) / 3, w2 = (a.B + 1) / 2;
     return (w3 + simds - 1) / simds < (w2 + simds - 1) / simds || a.c.num_iters >= 25;
 }
-// Two waves per SIMD (the XLDS build): 0 never, 1 whenever the kernel exists for the shape (16 / 32 / 64 lanes per problem, fp64),
-// 2 (default) where it is the faster one: the batch needs more waves than the chip has SIMDs.  Results do not depend on it.
-static int g_two_per_simd = 2;
-int set_two_waves_per_simd(int mode) { const int old = g_two_per_simd; g_two_per_simd = mode; return old; }
-static bool two_per_simd_pays(const BatchArgs &a, int per_wave) {
-    if (a.precision != 0 || g_two_per_simd == 0) return false;
-    if (g_two_per_simd == 1) return true;
-    return (a.B + per_wave - 1) / per_wave > chip_simds();
+// Two waves per SIMD (the XLDS build) where it is the faster one: the batch needs more waves than the chip has SIMDs.  Results do not
+// depend on it.
+bool two_per_simd_pays(const BatchArgs &a, int per_wave, long simds, const DispatchKnobs &kn) {
+    if (a.precision != 0 || kn.two_per_simd == 0) return false;
+    if (kn.two_per_simd == 1) return true;
+    return (a.B + per_wave - 1) / per_wave > simds;
 }
-static thread_local int t_last_wpe = 1;
+
+}  // namespace
+
+const AdmmUnit &admm_unit_e4() {
+    static const AdmmUnit unit = {launch_admm<4>, admm_scratch_bytes<4>};
+    return unit;
+}
+const AdmmUnit &admm_unit(CostShape shape, int precision, int n_eff) {
+    const bool four = n_eff == 4;
+    if (shape == kBlocks) return four ? admm_unit_bq_e4() : admm_unit_bq_e2();
+    if (shape == kBand) return four ? admm_unit_kq_e4() : admm_unit_kq_e2();
+    if (precision == 1) return four ? admm_unit_f32_e4() : admm_unit_f32_e2();
+    return four ? admm_unit_e4() : admm_unit_e2();
+}
+
+int set_steal_grid(int waves) { return set_knob(g_knobs.steal_grid, waves); }
+int set_three_per_wave(int on) { return set_knob(g_knobs.three_per_wave, on); }
+int set_two_waves_per_simd(int mode) { return set_knob(g_knobs.two_per_simd, mode); }
+int set_work_stealing(int on) { return set_knob(g_knobs.work_stealing, on); }
+int set_latency_mapping_max_batch(int max_batch) { return set_knob(g_knobs.latency_max_batch, max_batch); }
+int set_exact_step_decisions(int on) { return set_knob(g_knobs.exact_step_decisions, on); }
+int set_certified_steps(int on) { return set_knob(g_knobs.certified_steps, on); }
 int biconvex_last_waves_per_simd() { return t_last_wpe; }
-static int g_work_stealing = 1;       // 0: never the work-stealing kernel (tests: results must not depend on it)
-int set_work_stealing(int on) { const int old = g_work_stealing; g_work_stealing = on; return old; }
-static int g_latency_max_batch = 1024;
-int set_latency_mapping_max_batch(int max_batch) { const int old = g_latency_max_batch; g_latency_max_batch = max_batch; return old; }
-static int g_exact_step_decisions = 0;
-int set_exact_step_decisions(int on) { const int old = g_exact_step_decisions; g_exact_step_decisions = on; return old; }
-static int g_certified_steps = 1;
-int set_certified_steps(int on) { const int old = g_certified_steps; g_certified_steps = on; return old; }
-// which kernel the calling host thread's latest launch_biconvex_admm took (tests of the default dispatch; profiles)
-static thread_local const char *t_last_kernel = "";
-static thread_local int t_last_lpp = 0;       // lanes per problem of that launch (0: the one-problem-per-wave kernel)
 int biconvex_last_lanes_per_problem() { return t_last_lpp; }
 const char *biconvex_last_kernel_name() { return t_last_kernel; }
 
-hipError_t launch_biconvex_admm(const BatchArgs &args, int n_eff, hipStream_t stream) {
-    BatchArgs a = args;
-    if ((n_eff != 2 && n_eff != 4) || a.H < 1 || a.H + 1 > kMaxKnots || a.B < 0 || (a.precision != 0 && a.precision != 1))
-        return hipErrorInvalidValue;
-    if (a.B == 0) return hipSuccess;
-    if (a.c.maxit > kMaxFistaIters) return hipErrorInvalidValue;
-    // the kernels address a wave's problems by 32-bit byte offsets from the wave's first problem (at most four problems)
-    for (long stride : {a.sW_X, a.sW_X_ter, a.sW_F, a.sbounds})
-        if (stride < 0 || stride > (1L << 26)) return hipErrorInvalidValue;
-    // few problems, short horizon: one problem per wave (the chain of a solve is ~2.3x shorter; biconvex_latency.hip)
-    a.exact_step_decisions = g_exact_step_decisions;      // (every kernel with the fp32 shortcut of its step decisions)
-    if (a.B <= g_latency_max_batch && latency_mapping_fits(a, n_eff)) {
-        t_last_kernel = "biconvex_latency_kernel";
-        t_last_lpp = 0;
-        return launch_biconvex_latency(a, n_eff, stream);
-    }
-    a.cmtab = momentum_table(stream);
-    if (!a.cmtab) return hipErrorOutOfMemory;
-    a.certified_steps = g_certified_steps != 0;
-    // the same decisions for two feet as for four, with the LDS record of the foot count (knot_lds)
-    auto go = [&](const AdmmLaunch &l) {
-        t_last_lpp = l.lpp;
-        t_last_wpe = l.w2 ? 2 : 1;
-        return n_eff == 4 ? launch_admm_e4(a, l, stream) : launch_admm_e2(a, l, stream);
-    };
+// Which kernel a batch gets.  Block and band costs: their own kernels at every batch size and num_iters -- never the
+// one-problem-per-wave, work-stealing, workgroup or two-waves kernels, which hold diagonal weights only -- with every step tested on
+// the fp64 sums; the lanes per problem are chosen as for diagonal costs.
+LaunchPlan plan_launch(const BatchArgs &a, CostShape shape, int n_eff, long simds, const DispatchKnobs &kn) {
+    LaunchPlan p = {hipErrorInvalidValue, nullptr, {0, false, false, 0, {}}, false, a.certified_steps};
+    const bool diag = shape == kDiag;
     const int k = a.H + 1;
-    t_last_kernel = a.precision == 1 ? "biconvex_admm_kernel_f32" : "biconvex_admm_kernel";
-    t_last_wpe = 1;
-    if (k <= 16) return go({16, two_per_simd_pays(a, 4), false, 0});
+    const bool built = diag ? k <= kMaxKnots && (a.precision == 0 || a.precision == 1)
+                            : (shape == kBlocks || shape == kBand) && k <= 64 && a.precision == 0 && a.raw;      // (blocks / band: raw form, fp64, one problem per wave segment)
+    if ((n_eff != 2 && n_eff != 4) || a.H < 1 || a.B < 0 || !built) return p;
+    if (a.B == 0) { p.status = hipSuccess; return p; }
+    if (a.c.maxit > kMaxFistaIters) return p;
+    // the kernels address a wave's problems by 32-bit byte offsets from the wave's first problem (at most four problems)
+    if (diag)
+        for (long stride : {a.sW_X, a.sW_X_ter, a.sW_F, a.sbounds})
+            if (stride < 0 || stride > (1L << 26)) return p;
+    p.status = hipSuccess;
+    // few problems, short horizon: one problem per wave (the chain of a solve is ~2.3x shorter; biconvex_latency.hip)
+    if (diag && a.B <= kn.latency_max_batch && latency_mapping_fits(a, n_eff)) {
+        p.kernel = "biconvex_latency_kernel";
+        p.latency = true;
+        return p;
+    }
+    p.certified_steps = diag && kn.certified_steps != 0;
+    p.kernel = shape == kBlocks ? "biconvex_admm_bq_kernel" : (shape == kBand ? "biconvex_admm_kq_kernel" : (a.precision == 1 ? "biconvex_admm_kernel_f32" : "biconvex_admm_kernel"));
+    // the same decisions for two feet as for four, with the LDS record of the foot count (knot_lds)
+    auto segments = [&](int lpp) { p.l.lpp = lpp; p.l.w2 = diag && two_per_simd_pays(a, 64 / lpp, simds, kn); return p; };
+    if (k <= 16) return segments(16);
     // 17..21 knots (the headline shape): three problems per wave in 21-lane segments (fp64; the fp32 kernels keep 32-lane segments)
-    if (k <= 21 && k > 16 && a.precision == 0 && three_per_wave_pays(a)) {
+    if (k <= 21 && a.precision == 0 && three_per_wave_pays(a, simds, kn)) {
         // many ADMM iterations (the early exit makes the counts differ per problem) and more waves than the chip holds: segments that
         // finish take the next problem (biconvex_admm_body.h: STEAL); the 32-bit offsets from the problem index must fit (the contact
         // plan: 32 E H bytes per problem)
-        const long S = chip_simds(), per = std::max<long>({32L * n_eff * a.H, 9L * (a.H + 1) * 8, a.sW_X * 8, a.sW_F * 8, a.sbounds * 8, (long)a.c.num_iters * 16});
-        if (g_work_stealing && !a.raw && a.c.num_iters >= 25 && (a.B + 2) / 3 > S && (double)a.B * (double)per < 2.0e9) {
-            t_last_kernel = "biconvex_admm_steal_kernel";
+        const long per = std::max<long>({32L * n_eff * a.H, 9L * (a.H + 1) * 8, a.sW_X * 8, a.sW_F * 8, a.sbounds * 8, (long)a.c.num_iters * 16});
+        if (diag && kn.work_stealing && !a.raw && a.c.num_iters >= 25 && (a.B + 2) / 3 > simds && (double)a.B * (double)per < 2.0e9) {
+            p.kernel = "biconvex_admm_steal_kernel";
             // (one wave per SIMD unless forced: measured at B = 4096, num_iters = 100: 30.7 ms; the two-waves build with grids of
             // 1024 .. 2048 waves 34.2 .. 37.3 ms -- the stealing itself already fills the gaps the second wave would)
-            const bool w2 = g_two_per_simd == 1;
+            const bool w2 = kn.two_per_simd == 1;
             // the persistent grid: as many waves as the chip holds at once (one or two per SIMD)
-            const long waves = g_steal_grid > 0 ? std::min<long>(g_steal_grid, (a.B + 2) / 3) : (w2 ? 2 * S : S);
-            a.queue = steal_counter(stream);
-            if (!a.queue) return hipErrorOutOfMemory;
-            return go({21, w2, true, waves});
+            p.l = {21, w2, true, kn.steal_grid > 0 ? std::min<long>(kn.steal_grid, (a.B + 2) / 3) : (w2 ? 2 * simds : simds), {}};
+            return p;
         }
-        return go({21, two_per_simd_pays(a, 3), false, 0});
+        return segments(21);
     }
     if (k > 64) {      // 65 .. 256 knots: a workgroup of two, three or four waves per problem
-        t_last_kernel = "biconvex_admm_wg_kernel";
+        p.kernel = "biconvex_admm_wg_kernel";
         const int lpp = k <= 128 ? 128 : (k <= 192 ? 192 : 256);
         // the two-waves-per-SIMD build when there are more waves than SIMDs -- and, for two waves per problem, when four such workgroups'
         // LDS fits a CU (at 127 knots only three do: 9.2 ms against 6.9 at B = 1024); four waves per problem: always (11.4-12.6 ms
         // against 15.9-16.8: tools/horizon_sweep.py)
-        const size_t lds_bytes = sizeof(double) * (kLdsZeros + (size_t)kSegLds + (size_t)knot_lds(n_eff) * (size_t)k + (size_t)(lpp / 64) * 40);
-        const bool fits = k > 128 || 4 * lds_bytes <= 160 * 1024;
-        return go({lpp, g_two_per_simd == 1 || (g_two_per_simd == 2 && fits && (long)a.B * (lpp / 64) > chip_simds()), false, 0});
+        const bool fits = k > 128 || 4 * launch_lds_bytes(sizeof(double), 1, n_eff, a.H, (size_t)(lpp / 64) * 40) <= 160 * 1024;
+        p.l = {lpp, kn.two_per_simd == 1 || (kn.two_per_simd == 2 && fits && (long)a.B * (lpp / 64) > simds), false, 0, {}};
+        return p;
     }
-    const int lpp = k <= 32 ? 32 : 64;
-    return go({lpp, two_per_simd_pays(a, 64 / lpp), false, 0});
+    return segments(k <= 32 ? 32 : 64);
 }
+LaunchPlan plan_launch(const BatchArgs &a, CostShape shape, int n_eff, long simds) { return plan_launch(a, shape, n_eff, simds, g_knobs); }
 
-// Block costs (BlockArgs): the block kernel at every batch size and num_iters -- never the one-problem-per-wave, work-stealing or
-// two-waves kernels, which hold diagonal weights only.  The lanes per problem are chosen as above.
-hipError_t launch_biconvex_admm_blocks(const BatchArgs &args, const BlockArgs &q, int n_eff, hipStream_t stream) {
-    BatchArgs a = args;
-    if ((n_eff != 2 && n_eff != 4) || a.H < 1 || a.H + 1 > 64 || a.B < 0 || a.precision != 0 || !a.raw) return hipErrorInvalidValue;
-    if (a.B == 0) return hipSuccess;
-    if (a.c.maxit > kMaxFistaIters) return hipErrorInvalidValue;
-    for (long stride : {q.sQx_blk, q.sQf_blk})
+hipError_t launch_biconvex_admm(const BatchArgs &args, const CostArgs &cost, int n_eff, hipStream_t stream) {
+    LaunchPlan p = plan_launch(args, cost.shape, n_eff, device_simds(), g_knobs);
+    if (p.status != hipSuccess || !p.kernel) return p.status;
+    for (long stride : {cost.sx, cost.sf})
         if (stride < 0 || stride > (1L << 26)) return hipErrorInvalidValue;
-    a.exact_step_decisions = g_exact_step_decisions;      // (no effect: these kernels always take the fp64 sums)
-    a.certified_steps = 0;                                 // (... and test every step)
+    BatchArgs a = args;
+    a.exact_step_decisions = g_knobs.exact_step_decisions;      // (every kernel with the fp32 shortcut of its step decisions; none with block or band costs)
+    a.certified_steps = p.certified_steps;
+    t_last_kernel = p.kernel;
+    t_last_lpp = p.l.lpp;
+    // (the one-problem-per-wave kernel leaves the record of the waves per SIMD what the launch before it set: tests compare whole
+    // (name, lanes, waves) records between consecutive launches, and bmpc_biconvex_plan_launch reports 0 for such a plan)
+    if (p.latency) return launch_biconvex_latency(a, n_eff, stream);
+    t_last_wpe = p.l.w2 ? 2 : 1;
     a.cmtab = momentum_table(stream);
     if (!a.cmtab) return hipErrorOutOfMemory;
-    const int k = a.H + 1;
-    const int lpp = k <= 16 ? 16 : (k <= 21 && three_per_wave_pays(a) ? 21 : (k <= 32 ? 32 : 64));
-    t_last_kernel = "biconvex_admm_bq_kernel";
-    t_last_lpp = lpp;
-    t_last_wpe = 1;
-    return n_eff == 4 ? launch_admm_bq_e4(a, q, lpp, stream) : launch_admm_bq_e2(a, q, lpp, stream);
-}
-
-// Costs that couple neighbouring knots (BandArgs): their kernel at every batch size and num_iters, as block batches go to theirs.  None
-// of the dispatch switches reaches it: every step is tested on the fp64 sums, one wave per SIMD, no work stealing.
-hipError_t launch_biconvex_admm_band(const BatchArgs &args, const BandArgs &q, int n_eff, hipStream_t stream) {
-    BatchArgs a = args;
-    if ((n_eff != 2 && n_eff != 4) || a.H < 1 || a.H + 1 > 64 || a.B < 0 || a.precision != 0 || !a.raw) return hipErrorInvalidValue;
-    if (a.B == 0) return hipSuccess;
-    if (a.c.maxit > kMaxFistaIters) return hipErrorInvalidValue;
-    for (long stride : {q.sQx_off, q.sQf_off})
-        if (stride < 0 || stride > (1L << 26)) return hipErrorInvalidValue;
-    BandArgs b = q;
-    if (a.H < 2) { b.Qf_off = nullptr; b.sQf_off = 0; }      // (one force knot: no pair)
-    a.exact_step_decisions = g_exact_step_decisions;      // (no effect: these kernels always take the fp64 sums)
-    a.certified_steps = 0;                                 // (... and test every step)
-    a.cmtab = momentum_table(stream);
-    if (!a.cmtab) return hipErrorOutOfMemory;
-    const int k = a.H + 1;
-    const int lpp = k <= 16 ? 16 : (k <= 21 && three_per_wave_pays(a) ? 21 : (k <= 32 ? 32 : 64));
-    t_last_kernel = "biconvex_admm_kq_kernel";
-    t_last_lpp = lpp;
-    t_last_wpe = 1;
-    return n_eff == 4 ? launch_admm_kq_e4(a, b, lpp, stream) : launch_admm_kq_e2(a, b, lpp, stream);
+    if (p.l.steal && !(a.queue = steal_counter(stream))) return hipErrorOutOfMemory;
+    p.l.cost = cost;
+    if (cost.shape == kBand && a.H < 2) { p.l.cost.f = nullptr; p.l.cost.sf = 0; }      // (one force knot: no pair)
+    return admm_unit(cost.shape, a.precision, n_eff).launch(a, p.l, stream);
 }
 
 hipError_t launch_lane_selftest(const double *in, double *out, hipStream_t stream) {
@@ -278,7 +267,7 @@ hipError_t launch_lane_selftest(const double *in, double *out, hipStream_t strea
 const char *biconvex_kernel_name(int H, int raw) {
     (void)raw;
     const int k = H + 1;
-    return k <= 16 ? "biconvex_admm_kernel<double, 16" : (k <= 21 && g_three_per_wave == 1 ? "biconvex_admm_kernel<double, 21" : (k <= 32 ? "biconvex_admm_kernel<double, 32" : "biconvex_admm_kernel<double, 64"));
+    return k <= 16 ? "biconvex_admm_kernel<double, 16" : (k <= 21 && g_knobs.three_per_wave == 1 ? "biconvex_admm_kernel<double, 21" : (k <= 32 ? "biconvex_admm_kernel<double, 32" : "biconvex_admm_kernel<double, 64"));
 }
 
 }  // namespace bunmpc

@@ -1,16 +1,20 @@
-// The block-cost instantiations of the batched centroidal ADMM for TWO feet (bipeds): see biconvex_admm_bq.hip.
+// The block-cost instantiations of the batched centroidal ADMM for TWO feet: biconvex_admm_bq.hip's kernels with E = 2, built with the
+// same flags (bunmpc_amd/build.py).
 #include "biconvex_kernels.h"
+#include <mutex>
 
 namespace bunmpc {
 namespace {
 
 #include "biconvex_lanes.h"
 #include "biconvex_admm_body.h"
-#include "biconvex_admm_bq_inst.h"
+#include "biconvex_admm_inst.h"
 
 }  // namespace
 
-hipError_t launch_admm_bq_e2(const BatchArgs &a, const BlockArgs &q, int lpp, hipStream_t stream) { return launch_admm_bq<2>(a, q, lpp, stream); }
-int admm_bq_scratch_bytes_e2() { return admm_bq_scratch_bytes<2>(); }
+const AdmmUnit &admm_unit_bq_e2() {
+    static const AdmmUnit unit = {launch_bq<2>, bq_scratch_bytes<2>};
+    return unit;
+}
 
 }  // namespace bunmpc

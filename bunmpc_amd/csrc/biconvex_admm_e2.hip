@@ -1,9 +1,8 @@
 // The fp64 instantiations of the batched centroidal ADMM for TWO feet (bipeds): the same kernels as biconvex_admm.hip instantiates
 // for four (biconvex_admm_inst.h), in a translation unit of their own so that both build in parallel with the same flags
-// (bunmpc_amd/build.py).  A knot's LDS record is 33 doubles instead of 39 (knot_lds); launch_biconvex_admm (biconvex_admm.hip) decides
+// (bunmpc_amd/build.py).  A knot's LDS record is 33 doubles instead of 39 (knot_lds); plan_launch (biconvex_admm.hip) decides
 // which kernel a batch gets, for both foot counts alike.
 #include "biconvex_kernels.h"
-#include <algorithm>
 #include <mutex>
 
 namespace bunmpc {
@@ -15,7 +14,9 @@ namespace {
 
 }  // namespace
 
-hipError_t launch_admm_e2(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream) { return launch_admm<2>(a, l, stream); }
-int admm_scratch_bytes_e2() { return admm_scratch_bytes<2>(); }
+const AdmmUnit &admm_unit_e2() {
+    static const AdmmUnit unit = {launch_admm<2>, admm_scratch_bytes<2>};
+    return unit;
+}
 
 }  // namespace bunmpc

@@ -7,8 +7,8 @@
 // spilled to scratch memory under the cap of 256 that two waves per SIMD need (345 MB of HBM traffic per launch against 75 MB of
 // inputs and results; profiles/r02_pmc_hbm_cfg3.txt).  Without the packing the body takes 200-212 registers: no scratch, and
 // Go2 H = 40, B = 4096 goes 7.09 -> 6.02 ms.  (The fp64 kernels are ~0.5 % faster WITH the vectoriser, hence the split.)
+// Its scratch bytes (AdmmUnit::scratch_bytes) being 0 is the point of this file.
 #include "biconvex_kernels.h"
-#include <algorithm>
 #include <mutex>
 
 namespace bunmpc {
@@ -16,15 +16,13 @@ namespace {
 
 #include "biconvex_lanes.h"
 #include "biconvex_admm_body.h"
-#include "biconvex_admm_inst.h"      // (biconvex_admm_kernel_f32)
+#include "biconvex_admm_inst.h"
 
 }  // namespace
 
-hipError_t launch_biconvex_admm_f32(const BatchArgs &a, int lpp, unsigned grid, size_t lds, hipStream_t stream) {
-    return launch_f32<4>(a, lpp, grid, lds, stream);
+const AdmmUnit &admm_unit_f32_e4() {
+    static const AdmmUnit unit = {launch_f32<4>, f32_scratch_bytes<4>};
+    return unit;
 }
-
-// private-segment (scratch) bytes per lane of the fp32 instantiations, the largest of the three: 0 is the point of this file
-int biconvex_admm_f32_scratch_bytes() { return f32_scratch_bytes<4>(); }
 
 }  // namespace bunmpc

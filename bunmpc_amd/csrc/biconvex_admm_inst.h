@@ -1,9 +1,12 @@
 // The kernels of the batched centroidal ADMM and their launches, templated on the number of feet E.  Included inside the anonymous
-// namespace of one translation unit per foot count and precision (after biconvex_lanes.h and biconvex_admm_body.h):
-//   biconvex_admm.hip        fp64, E = 4        biconvex_admm_f32.hip      fp32, E = 4
-//   biconvex_admm_e2.hip     fp64, E = 2        biconvex_admm_f32_e2.hip   fp32, E = 2
-// so that every unit is built with its own flags (bunmpc_amd/build.py) and the units build in parallel.  Which kernel a batch gets is
-// decided once, for every E, by launch_biconvex_admm (biconvex_admm.hip).
+// namespace of one translation unit per cost shape, precision and foot count (after biconvex_lanes.h and biconvex_admm_body.h), each
+// of which instantiates its own launch and exports it as one AdmmUnit (biconvex_kernels.h):
+//   biconvex_admm.hip        fp64, E = 4   launch_admm        biconvex_admm_f32.hip      fp32, E = 4   launch_f32
+//   biconvex_admm_e2.hip     fp64, E = 2                      biconvex_admm_f32_e2.hip   fp32, E = 2
+//   biconvex_admm_bq.hip     blocks, E = 4   launch_bq        biconvex_admm_kq.hip       band, E = 4   launch_kq
+//   biconvex_admm_bq_e2.hip  blocks, E = 2                    biconvex_admm_kq_e2.hip    band, E = 2
+// so that every unit is built with its own flags (bunmpc_amd/build.py), the units build in parallel and one feature's kernels cannot
+// disturb another's code object.  Which kernel a batch gets is decided once, for every unit, by plan_launch (biconvex_admm.hip).
 #pragma once
 
 // fp64, WPE = 1: ONE wave per SIMD.  The body holds 294 registers; capped at 256 with the FISTA iterates in registers the compiler parks
@@ -34,30 +37,63 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     admm_body<float, LPP, E, false, false>(a);
 }
 
-// LDS of one problem: the x_init rows' multipliers and the header, then one record per knot (X, P, F, R)
-template <int E>
-size_t problem_lds(int H) { return (size_t)kSegLds + (size_t)knot_lds(E) * (size_t)(H + 1); }
+// Per-knot block costs (biconvex_admm_body.h: BQ).  Raw form, fp64, one wave per SIMD: the force phase holds the knot's 3E x 3E block
+// (78 values at four feet) beside what the diagonal kernel holds, the motion phase its 9 x 9 block (45).
+template <int LPP, int E, bool HASQF>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void biconvex_admm_bq_kernel(const BatchArgs a, const BlockArgs q) {
+    admm_body<double, LPP, E, true, HASQF, false, false, 1, true>(a, q);
+}
+// Costs between neighbouring knots (biconvex_admm_body.h: KQ).  Raw form, fp64, one wave per SIMD: beside what the diagonal kernel holds
+// a phase keeps the coupling weights of its knot's two pairs (2 x 3E or 2 x 9 values) and, over a FISTA iteration, its two neighbours' y.
+template <int LPP, int E, bool HASQF>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void biconvex_admm_kq_kernel(const BatchArgs a, const BandArgs q) {
+    admm_body<double, LPP, E, true, HASQF, false, false, 1, false, true>(a, BlockArgs{}, q);
+}
 
-template <typename R, int LPP, int E, bool RAW, bool HASQF>
-hipError_t launch(const BatchArgs &a, bool two_per_simd, hipStream_t stream) {
-    const int per_wave = 64 / LPP;
-    const unsigned grid = (unsigned)((a.B + per_wave - 1) / per_wave);
-    const size_t lds = sizeof(R) * (kLdsZeros + per_wave * problem_lds<E>(a.H));
-    if (sizeof(R) == sizeof(float))      // biconvex_admm_f32.hip, biconvex_admm_f32_e2.hip
-        return E == 4 ? launch_biconvex_admm_f32(a, LPP, grid, lds, stream) : launch_biconvex_admm_f32_e2(a, LPP, grid, lds, stream);
-    if (two_per_simd) hipLaunchKernelGGL((biconvex_admm_kernel<double, LPP, E, RAW, HASQF, 2>), dim3(grid), dim3(64), lds, stream, a);
-    else hipLaunchKernelGGL((biconvex_admm_kernel<double, LPP, E, RAW, HASQF, 1>), dim3(grid), dim3(64), lds, stream, a);
+// The one switch over the lanes per problem: f(std::integral_constant<int, LPP>) of the plan's lpp.  A launch names the values its unit
+// instantiates with `if constexpr` and refuses the others.
+template <typename F>
+hipError_t with_lpp(int lpp, F &&f) {
+    switch (lpp) {
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 21: return f(std::integral_constant<int, 21>{});
+        case 32: return f(std::integral_constant<int, 32>{});
+        case 64: return f(std::integral_constant<int, 64>{});
+        case 128: return f(std::integral_constant<int, 128>{});
+        case 192: return f(std::integral_constant<int, 192>{});
+        case 256: return f(std::integral_constant<int, 256>{});
+        default: return hipErrorInvalidValue;
+    }
+}
+// a kernel of 64 / LPP problems per wave over the batch, with its arguments
+template <int LPP, int E, typename K, typename... A>
+hipError_t launch_segments(K kernel, size_t elem, const BatchArgs &a, hipStream_t stream, const A &...args) {
+    hipLaunchKernelGGL(kernel, dim3(launch_grid(a.B, 64 / LPP)), dim3(64), launch_lds_bytes(elem, 64 / LPP, E, a.H), stream, a, args...);
     return hipGetLastError();
+}
+
+template <int LPP, int E, bool RAW, bool HASQF>
+hipError_t launch(const BatchArgs &a, bool two_per_simd, hipStream_t stream) {
+    if (two_per_simd) return launch_segments<LPP, E>(biconvex_admm_kernel<double, LPP, E, RAW, HASQF, 2>, sizeof(double), a, stream);
+    return launch_segments<LPP, E>(biconvex_admm_kernel<double, LPP, E, RAW, HASQF, 1>, sizeof(double), a, stream);
 }
 
 template <int E, int WAVES, bool RAW, bool HASQF, int WPE>
 hipError_t launch_wg(const BatchArgs &a, hipStream_t stream) {
-    const size_t lds = sizeof(double) * (kLdsZeros + problem_lds<E>(a.H) + (size_t)WAVES * 40);
-    static std::once_flag once;      // (more than the 64 KB a kernel may take without asking, from 209 knots on)
-    static hipError_t attr = hipSuccess;
-    std::call_once(once, [] { attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&biconvex_admm_wg_kernel<E, WAVES, RAW, HASQF, WPE>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); });
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((biconvex_admm_wg_kernel<E, WAVES, RAW, HASQF, WPE>), dim3((unsigned)a.B), dim3(64 * WAVES), lds, stream, a);
+    // more than the 64 KB a kernel may take without asking, from 209 knots on: raised once per device and instantiation
+    static std::mutex lock;
+    static bool raised[16] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return hipErrorInvalidDevice;
+    {
+        std::lock_guard<std::mutex> hold(lock);
+        if (!raised[dev]) {
+            const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&biconvex_admm_wg_kernel<E, WAVES, RAW, HASQF, WPE>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+            if (attr != hipSuccess) return attr;
+            raised[dev] = true;
+        }
+    }
+    hipLaunchKernelGGL((biconvex_admm_wg_kernel<E, WAVES, RAW, HASQF, WPE>), dim3(launch_grid(a.B, 1)), dim3(64 * WAVES), launch_lds_bytes(sizeof(double), 1, E, a.H, (size_t)WAVES * 40), stream, a);
     return hipGetLastError();
 }
 template <int E, int WAVES, int WPE>
@@ -67,39 +103,56 @@ hipError_t launch_wg_form(const BatchArgs &a, hipStream_t stream) {
     return a.qf ? launch_wg<E, WAVES, true, true, WPE>(a, stream) : launch_wg<E, WAVES, true, false, WPE>(a, stream);
 }
 
-// the persistent grid of the work-stealing kernel (a.queue: its device counter, set by the caller)
-template <int E>
-hipError_t launch_steal(const BatchArgs &a, long waves, bool two_per_simd, hipStream_t stream) {
-    const size_t lds = sizeof(double) * (kLdsZeros + 3 * problem_lds<E>(a.H));
-    if (two_per_simd) hipLaunchKernelGGL((biconvex_admm_steal_kernel<E, 2>), dim3((unsigned)waves), dim3(64), lds, stream, a);
-    else hipLaunchKernelGGL((biconvex_admm_steal_kernel<E, 1>), dim3((unsigned)waves), dim3(64), lds, stream, a);
-    return hipGetLastError();
-}
-
-template <int LPP, int E>
-hipError_t launch_lpp(const BatchArgs &a, bool two_per_simd, hipStream_t stream) {
-    if (a.precision == 1) {   // fp32 arithmetic: harness form only
-        if (a.raw || LPP == 21) return hipErrorInvalidValue;
-        return launch<float, LPP == 21 ? 32 : LPP, E, false, false>(a, false, stream);
-    }
-    if (!a.raw) return launch<double, LPP, E, false, false>(a, two_per_simd, stream);
-    return a.qf ? launch<double, LPP, E, true, true>(a, two_per_simd, stream) : launch<double, LPP, E, true, false>(a, two_per_simd, stream);
-}
-
-// the launch launch_biconvex_admm decided on
+// the launch plan_launch decided on, fp64 with diagonal costs: batch kernel, workgroup kernel, or the persistent grid of the
+// work-stealing kernel (a.queue: its device counter, set by the caller)
 template <int E>
 hipError_t launch_admm(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream) {
-    if (l.steal) return launch_steal<E>(a, l.steal_waves, l.w2, stream);
-    switch (l.lpp) {
-        case 16: return launch_lpp<16, E>(a, l.w2, stream);
-        case 21: return launch_lpp<21, E>(a, l.w2, stream);
-        case 32: return launch_lpp<32, E>(a, l.w2, stream);
-        case 64: return launch_lpp<64, E>(a, l.w2, stream);
-        case 128: return l.w2 ? launch_wg_form<E, 2, 2>(a, stream) : launch_wg_form<E, 2, 1>(a, stream);
-        case 192: return l.w2 ? launch_wg_form<E, 3, 2>(a, stream) : launch_wg_form<E, 3, 1>(a, stream);
-        case 256: return l.w2 ? launch_wg_form<E, 4, 2>(a, stream) : launch_wg_form<E, 4, 1>(a, stream);
-        default: return hipErrorInvalidValue;
+    if (a.precision != 0) return hipErrorInvalidValue;
+    if (l.steal) {
+        const size_t lds = launch_lds_bytes(sizeof(double), 3, E, a.H);
+        if (l.w2) hipLaunchKernelGGL((biconvex_admm_steal_kernel<E, 2>), dim3((unsigned)l.steal_waves), dim3(64), lds, stream, a);
+        else hipLaunchKernelGGL((biconvex_admm_steal_kernel<E, 1>), dim3((unsigned)l.steal_waves), dim3(64), lds, stream, a);
+        return hipGetLastError();
     }
+    return with_lpp(l.lpp, [&](auto lanes) {
+        constexpr int LPP = decltype(lanes)::value;
+        if constexpr (LPP > 64) return l.w2 ? launch_wg_form<E, LPP / 64, 2>(a, stream) : launch_wg_form<E, LPP / 64, 1>(a, stream);
+        else if (!a.raw) return launch<LPP, E, false, false>(a, l.w2, stream);
+        else return a.qf ? launch<LPP, E, true, true>(a, l.w2, stream) : launch<LPP, E, true, false>(a, l.w2, stream);
+    });
+}
+// ... fp32 (the units built without the SLP vectoriser): harness form, 16 / 32 / 64 lanes per problem
+template <int E>
+hipError_t launch_f32(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream) {
+    if (a.precision != 1 || a.raw) return hipErrorInvalidValue;
+    return with_lpp(l.lpp, [&](auto lanes) {
+        constexpr int LPP = decltype(lanes)::value;
+        if constexpr (LPP == 16 || LPP == 32 || LPP == 64) return launch_segments<LPP, E>(biconvex_admm_kernel_f32<LPP, E>, sizeof(float), a, stream);
+        else return hipErrorInvalidValue;
+    });
+}
+// ... block costs and costs between neighbouring knots: raw form, fp64, at most 64 lanes per problem
+template <int E>
+hipError_t launch_bq(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream) {
+    if (!a.raw || a.precision != 0 || a.H + 1 > l.lpp) return hipErrorInvalidValue;
+    const BlockArgs q = {l.cost.x, l.cost.f, l.cost.sx, l.cost.sf};
+    return with_lpp(l.lpp, [&](auto lanes) {
+        constexpr int LPP = decltype(lanes)::value;
+        if constexpr (LPP > 64) return hipErrorInvalidValue;
+        else return a.qf ? launch_segments<LPP, E>(biconvex_admm_bq_kernel<LPP, E, true>, sizeof(double), a, stream, q)
+                         : launch_segments<LPP, E>(biconvex_admm_bq_kernel<LPP, E, false>, sizeof(double), a, stream, q);
+    });
+}
+template <int E>
+hipError_t launch_kq(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream) {
+    if (!a.raw || a.precision != 0 || a.H + 1 > l.lpp) return hipErrorInvalidValue;
+    const BandArgs q = {l.cost.x, l.cost.f, l.cost.sx, l.cost.sf};
+    return with_lpp(l.lpp, [&](auto lanes) {
+        constexpr int LPP = decltype(lanes)::value;
+        if constexpr (LPP > 64) return hipErrorInvalidValue;
+        else return a.qf ? launch_segments<LPP, E>(biconvex_admm_kq_kernel<LPP, E, true>, sizeof(double), a, stream, q)
+                         : launch_segments<LPP, E>(biconvex_admm_kq_kernel<LPP, E, false>, sizeof(double), a, stream, q);
+    });
 }
 
 // private-segment (scratch) bytes per lane, the largest over the kernels listed
@@ -136,15 +189,15 @@ int admm_scratch_bytes() {
     }
     return worst;
 }
-
-// fp32 (the units built without the SLP vectoriser)
-template <int E>
-hipError_t launch_f32(const BatchArgs &a, int lpp, unsigned grid, size_t lds, hipStream_t stream) {
-    if (lpp == 16) hipLaunchKernelGGL((biconvex_admm_kernel_f32<16, E>), dim3(grid), dim3(64), lds, stream, a);
-    else if (lpp == 32) hipLaunchKernelGGL((biconvex_admm_kernel_f32<32, E>), dim3(grid), dim3(64), lds, stream, a);
-    else if (lpp == 64) hipLaunchKernelGGL((biconvex_admm_kernel_f32<64, E>), dim3(grid), dim3(64), lds, stream, a);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
 template <int E>
 int f32_scratch_bytes() { return max_scratch_bytes(&biconvex_admm_kernel_f32<16, E>, &biconvex_admm_kernel_f32<32, E>, &biconvex_admm_kernel_f32<64, E>); }
+template <int E>
+int bq_scratch_bytes() {
+    return max_scratch_bytes(&biconvex_admm_bq_kernel<16, E, false>, &biconvex_admm_bq_kernel<16, E, true>, &biconvex_admm_bq_kernel<21, E, false>, &biconvex_admm_bq_kernel<21, E, true>,
+                             &biconvex_admm_bq_kernel<32, E, false>, &biconvex_admm_bq_kernel<32, E, true>, &biconvex_admm_bq_kernel<64, E, false>, &biconvex_admm_bq_kernel<64, E, true>);
+}
+template <int E>
+int kq_scratch_bytes() {
+    return max_scratch_bytes(&biconvex_admm_kq_kernel<16, E, false>, &biconvex_admm_kq_kernel<16, E, true>, &biconvex_admm_kq_kernel<21, E, false>, &biconvex_admm_kq_kernel<21, E, true>,
+                             &biconvex_admm_kq_kernel<32, E, false>, &biconvex_admm_kq_kernel<32, E, true>, &biconvex_admm_kq_kernel<64, E, false>, &biconvex_admm_kq_kernel<64, E, true>);
+}

@@ -81,39 +81,69 @@ constexpr int kLdsZeros = 54;          // zeros in LDS in front of all that (lan
 constexpr int kMaxFistaIters = 4096;  // length of the momentum table (one per device, momentum_table below; the one-problem-per-wave kernel keeps its own in LDS: 32 KB + <= 30 KB of iterates < 64 KB)
 constexpr int kMaxKnots = 256; // H + 1 <= 256: one knot per lane, one problem per <= 64 lanes of a wave, or (65 .. 256 knots) per workgroup of 2 / 4 waves
 
-// Launch the batched ADMM kernel on `stream`.  Returns hipSuccess or the launch error;
-// hipErrorInvalidValue for unsupported shapes (n_eff not 2 or 4, H + 1 > 256).
-hipError_t launch_biconvex_admm(const BatchArgs &a, int n_eff, hipStream_t stream);
+// Which Q a batch has beside BatchArgs' diagonal (Qx / Qf), and that Q's arrays: BlockArgs' for kBlocks, BandArgs' for kBand, x = the
+// motion side (Qx_blk / Qx_off), f = the force side
+enum CostShape { kDiag = 0, kBlocks = 1, kBand = 2 };
+struct CostArgs {
+    CostShape shape = kDiag;
+    const double *x = nullptr, *f = nullptr;
+    long sx = 0, sf = 0;
+};
 
-// The kernel launch_biconvex_admm chose for a batch (it sets a.cmtab and, for the work-stealing kernel, a.queue first)
+// LDS bytes of a workgroup that holds per_wg problems of H + 1 knots in elements of elem bytes: the zeros, then per problem the
+// x_init rows' multipliers and the header and one record per knot (X, P, F, R), then `extra` elements -- and the workgroups of a batch
+constexpr size_t launch_lds_bytes(size_t elem, int per_wg, int E, int H, size_t extra = 0) {
+    return elem * (kLdsZeros + (size_t)per_wg * ((size_t)kSegLds + (size_t)knot_lds(E) * (size_t)(H + 1)) + extra);
+}
+constexpr unsigned launch_grid(int B, int per_wg) { return (unsigned)((B + per_wg - 1) / per_wg); }
+
+// The kernel a batch gets.  Set by plan_launch, except the cost arrays: launch_biconvex_admm adds those.
 struct AdmmLaunch {
-    int lpp;             // lanes per problem 16 / 21 / 32 / 64, or 128 / 192 / 256: one problem per workgroup of 2 / 3 / 4 waves
+    int lpp;             // lanes per problem 16 / 21 / 32 / 64, or 128 / 192 / 256: one problem per workgroup of 2 / 3 / 4 waves; 0: the one-problem-per-wave kernel
     bool w2;             // the two-waves-per-SIMD build
     bool steal;          // the work-stealing kernel (lpp 21, harness form, fp64)
     long steal_waves;    // ... its persistent grid
+    CostArgs cost;
 };
-// ... launched by the instantiations of one foot count: biconvex_admm.hip (E = 4), biconvex_admm_e2.hip (E = 2)
-hipError_t launch_admm_e4(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream);
-hipError_t launch_admm_e2(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream);
-int admm_scratch_bytes_e4();      // largest private-segment bytes per lane over the fp64 batch, workgroup and work-stealing kernels, -1 on error
-int admm_scratch_bytes_e2();
-// The block-cost kernels (biconvex_admm_bq.hip: E = 4, biconvex_admm_bq_e2.hip: E = 2): lpp 16 / 21 / 32 / 64, one wave per SIMD
-hipError_t launch_admm_bq_e4(const BatchArgs &a, const BlockArgs &q, int lpp, hipStream_t stream);
-hipError_t launch_admm_bq_e2(const BatchArgs &a, const BlockArgs &q, int lpp, hipStream_t stream);
-int admm_bq_scratch_bytes_e4();      // largest private-segment bytes per lane over them, -1 on error
-int admm_bq_scratch_bytes_e2();
-// ... and their dispatch: every batch size and num_iters goes to them (never the one-problem-per-wave, work-stealing or two-waves
-// kernels).  hipErrorInvalidValue unless raw, fp64, n_eff 2 or 4 and H + 1 <= 64 (the C-ABI refuses those with a message first).
-hipError_t launch_biconvex_admm_blocks(const BatchArgs &a, const BlockArgs &q, int n_eff, hipStream_t stream);
+// The instantiations of one cost shape, precision and foot count: one translation unit each (biconvex_admm_inst.h lists them).
+// launch: the launch plan_launch decided on (a.cmtab and, for the work-stealing kernel, a.queue set); scratch_bytes: the largest
+// private-segment bytes per lane over the unit's kernels, -1 on error
+struct AdmmUnit {
+    hipError_t (*launch)(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream);
+    int (*scratch_bytes)();
+};
+const AdmmUnit &admm_unit_e4(), &admm_unit_e2(), &admm_unit_f32_e4(), &admm_unit_f32_e2(), &admm_unit_bq_e4(), &admm_unit_bq_e2(), &admm_unit_kq_e4(), &admm_unit_kq_e2();
+// ... of a combination the caller has validated: n_eff 2 or 4, precision 0 or 1 (blocks / band: 0)
+const AdmmUnit &admm_unit(CostShape shape, int precision, int n_eff);
 
-// The neighbour-knot-cost kernels (biconvex_admm_kq.hip: E = 4, biconvex_admm_kq_e2.hip: E = 2) and their dispatch, as for the block kernels
-hipError_t launch_admm_kq_e4(const BatchArgs &a, const BandArgs &q, int lpp, hipStream_t stream);
-hipError_t launch_admm_kq_e2(const BatchArgs &a, const BandArgs &q, int lpp, hipStream_t stream);
-int admm_kq_scratch_bytes_e4();      // largest private-segment bytes per lane over them, -1 on error
-int admm_kq_scratch_bytes_e2();
-hipError_t launch_biconvex_admm_band(const BatchArgs &a, const BandArgs &q, int n_eff, hipStream_t stream);
+// The dispatch switches of the process (the set_* calls below) and what they decide: a pure function of the batch's sizes, the
+// chip's SIMD count and the switches -- no HIP call, no pointer of `a` dereferenced.
+struct DispatchKnobs {
+    int three_per_wave = 2;            // 21-lane segments for 17..21 knots: 0 never, 1 always, 2 when it pays
+    int two_per_simd = 2;              // the two-waves-per-SIMD build of the fp64 kernels: 0 never, 1 always, 2 when it pays
+    int work_stealing = 1;             // the segment-level work-stealing kernel for num_iters >= 25
+    int steal_grid = 0;                // waves of its persistent grid (experiments): 0 = one or two per SIMD
+    int latency_max_batch = 1024;      // the one-problem-per-wave kernel up to this many problems
+    int exact_step_decisions = 0;      // every step decision from the fp64 sums, in every centroidal kernel (tests)
+    int certified_steps = 1;           // the fp64 batch kernels' per-phase step certificate
+};
+struct LaunchPlan {
+    hipError_t status;       // hipErrorInvalidValue: a shape no kernel is built for
+    const char *kernel;      // the kernel template's name; null (with hipSuccess): B == 0, nothing to launch
+    AdmmLaunch l;
+    bool latency;            // the one-problem-per-wave kernel (biconvex_latency.hip)
+    int certified_steps;     // BatchArgs::certified_steps of the launch
+};
+LaunchPlan plan_launch(const BatchArgs &a, CostShape shape, int n_eff, long simds, const DispatchKnobs &knobs);
+LaunchPlan plan_launch(const BatchArgs &a, CostShape shape, int n_eff, long simds);      // ... with the process's switches
 
-// The one-problem-per-wave mapping (biconvex_latency.hip): fp64, n_eff = 2 or 4, H + 1 <= 21.  launch_biconvex_admm takes it for
+// Launch the batched ADMM kernel on `stream`: plan_launch with the current device's SIMD count, the device's momentum table (and a
+// counter of its work-stealing ring if the plan steals), the "last launch" record, then the unit of (shape, precision, n_eff).
+// Returns hipSuccess or the launch error; hipErrorInvalidValue for unsupported shapes (n_eff not 2 or 4, H + 1 > 256; with block or
+// band costs: not raw, not fp64, H + 1 > 64 -- the C-ABI refuses those with a message first).
+hipError_t launch_biconvex_admm(const BatchArgs &a, const CostArgs &cost, int n_eff, hipStream_t stream);
+
+// The one-problem-per-wave mapping (biconvex_latency.hip): fp64, n_eff = 2 or 4, H + 1 <= 21.  plan_launch takes it for
 // batches of at most latency_mapping_max_batch() problems that fit.
 bool latency_mapping_fits(const BatchArgs &a, int n_eff);
 hipError_t launch_biconvex_latency(const BatchArgs &a, int n_eff, hipStream_t stream);
@@ -126,14 +156,6 @@ int set_work_stealing(int on);                       // the segment-level work-s
 int biconvex_last_lanes_per_problem();               // of the calling host thread's latest launch: 16 / 21 / 32 / 64, 0 = one problem per wave
 int set_exact_step_decisions(int on);                // every step decision from the fp64 sums, in every centroidal kernel; returns the old value
 int set_certified_steps(int on);                     // the fp64 batch kernels' per-phase step certificate (default on); returns the old value
-
-// fp32 instantiations (biconvex_admm_f32.hip: E = 4, biconvex_admm_f32_e2.hip: E = 2); called by launch_biconvex_admm with the
-// lanes per problem (16 / 32 / 64), the grid and the LDS bytes it has worked out
-hipError_t launch_biconvex_admm_f32(const BatchArgs &a, int lpp, unsigned grid, size_t lds, hipStream_t stream);
-hipError_t launch_biconvex_admm_f32_e2(const BatchArgs &a, int lpp, unsigned grid, size_t lds, hipStream_t stream);
-
-int biconvex_admm_f32_scratch_bytes();    // private-segment bytes per lane of the fp32 kernels (hipFuncGetAttributes), -1 on error
-int biconvex_admm_f32_e2_scratch_bytes();
 
 // Lane-exchange self test (DPP shifts and segment sums used by the kernel).
 // out must hold 12*64 doubles.

@@ -65,8 +65,8 @@ bunmpc::BatchArgs to_args(const bmpc_batch_t &d) {
     return a;
 }
 
-// x_blk / f_blk: that side's cost comes as blocks (bmpc_block_cost_t), its diagonal is not needed
-int check_batch(const bmpc_batch_t *d, bool x_blk = false, bool f_blk = false) {
+// x_blk / f_blk: that side's cost comes as blocks (bmpc_block_cost_t), its diagonal is not needed; arrays false: the scalar fields only
+int check_batch(const bmpc_batch_t *d, bool x_blk = false, bool f_blk = false, bool arrays = true) {
     if (!d) return fail(BMPC_BAD_ARG, "null batch descriptor");
     if (d->B < 0 || d->n_col < 1) return fail(BMPC_BAD_ARG, "B < 0 or n_col < 1");
     if (d->n_eff != 2 && d->n_eff != 4) return fail(BMPC_BAD_ARG, "n_eff must be 2 or 4: the centroidal kernels are built for n_eff in {2, 4}");
@@ -78,13 +78,13 @@ int check_batch(const bmpc_batch_t *d, bool x_blk = false, bool f_blk = false) {
     if (d->cold_start < 0 || d->cold_start > 2) return fail(BMPC_BAD_ARG, "cold_start must be 0, 1 or 2");
     if (d->precision != 0 && d->precision != 1) return fail(BMPC_BAD_ARG, "precision must be 0 (fp64) or 1 (fp32)");
     if (d->precision == 1 && d->raw) return fail(BMPC_BAD_ARG, "fp32 arithmetic is built for the harness form only");
-    if (!d->cnt_plan || !d->dt || !d->x_init || !d->X || !d->F || !d->P || !d->L_x || !d->L_f)
+    if (arrays && (!d->cnt_plan || !d->dt || !d->x_init || !d->X || !d->F || !d->P || !d->L_x || !d->L_f))
         return fail(BMPC_BAD_ARG, "missing required array");
     if (d->raw) {
-        if ((!d->Qx && !x_blk) || !d->qx || !d->lbx || !d->ubx || (!d->Qf && !f_blk))
+        if (arrays && ((!d->Qx && !x_blk) || !d->qx || !d->lbx || !d->ubx || (!d->Qf && !f_blk)))
             return fail(BMPC_BAD_ARG, "raw form needs Qx, qx, lbx, ubx, Qf");
     } else {
-        if (!d->W_X || !d->W_X_ter || !d->W_F || !d->bounds || !d->X_nom || !d->X_ter)
+        if (arrays && (!d->W_X || !d->W_X_ter || !d->W_F || !d->bounds || !d->X_nom || !d->X_ter))
             return fail(BMPC_BAD_ARG, "harness form needs W_X, W_X_ter, W_F, bounds, X_nom, X_ter");
         // batch strides: 0 (one block shared by all problems) or the distance between two problems' blocks, in doubles.  The
         // kernels reach the (at most four) problems of a wave by 32-bit byte offsets from the wave's first problem.
@@ -94,19 +94,32 @@ int check_batch(const bmpc_batch_t *d, bool x_blk = false, bool f_blk = false) {
     return BMPC_OK;
 }
 
-bool has_blocks(const bmpc_block_cost_t *c) { return c && (c->Qx_blk || c->Qf_blk); }
+// The cost arrays of a call as the launcher takes them.  bmpc_block_cost_t and bmpc_band_cost_t without an array are diagonal costs; a
+// side without an array has no stride.
+bunmpc::CostArgs cost_args(bunmpc::CostShape shape, const double *x, long sx, const double *f, long sf) {
+    bunmpc::CostArgs c;
+    if (!x && !f) return c;
+    c.shape = shape; c.x = x; c.f = f; c.sx = x ? sx : 0; c.sf = f ? sf : 0;
+    return c;
+}
+bunmpc::CostArgs cost_of(const bmpc_block_cost_t *c) { return c ? cost_args(bunmpc::kBlocks, c->Qx_blk, c->sQx_blk, c->Qf_blk, c->sQf_blk) : bunmpc::CostArgs(); }
+bunmpc::CostArgs cost_of(const bmpc_band_cost_t *c) { return c ? cost_args(bunmpc::kBand, c->Qx_off, c->sQx_off, c->Qf_off, c->sQf_off) : bunmpc::CostArgs(); }
 
-// a batch with block costs: what the block kernels are built for, then the batch itself
-int check_blocks(const bmpc_batch_t *d, const bmpc_block_cost_t *c) {
+// a batch with its costs: what the kernels of block costs / costs between neighbouring knots are built for, then the batch itself
+int check_cost(const bmpc_batch_t *d, const bunmpc::CostArgs &c, bool arrays = true) {
+    if (c.shape == bunmpc::kDiag) return check_batch(d, false, false, arrays);
+    const bool blocks = c.shape == bunmpc::kBlocks;
+    const std::string what = blocks ? "block costs (Qx_blk / Qf_blk)" : "costs between neighbouring knots (Qx_off / Qf_off)";
     if (!d) return fail(BMPC_BAD_ARG, "null batch descriptor");
-    if (d->precision != 0) return fail(BMPC_BAD_ARG, "block costs (Qx_blk / Qf_blk) are built for fp64 only: precision must be 0");
-    if (!d->raw) return fail(BMPC_BAD_ARG, "block costs (Qx_blk / Qf_blk) are built for the raw form only: raw must be 1");
-    if (d->n_col + 1 > 64) return fail(BMPC_BAD_ARG, "block costs (Qx_blk / Qf_blk) are built for n_col + 1 <= 64 knots only (one problem per wave segment)");
-    if (int rc = check_batch(d, c->Qx_blk != nullptr, c->Qf_blk != nullptr)) return rc;
-    const long need_x = 81L * (d->n_col + 1), need_f = 9L * d->n_eff * d->n_eff * d->n_col;
-    if ((c->Qx_blk && (c->sQx_blk < 0 || c->sQx_blk > (1L << 26) || (c->sQx_blk != 0 && c->sQx_blk < need_x))) ||
-        (c->Qf_blk && (c->sQf_blk < 0 || c->sQf_blk > (1L << 26) || (c->sQf_blk != 0 && c->sQf_blk < need_f))))
-        return fail(BMPC_BAD_ARG, "batch stride of a block array must be 0 (shared) or between one problem's blocks and 2^26 doubles");
+    if (d->precision != 0) return fail(BMPC_BAD_ARG, what + " are built for fp64 only: precision must be 0");
+    if (!d->raw) return fail(BMPC_BAD_ARG, what + " are built for the raw form only: raw must be 1");
+    if (d->n_col + 1 > 64) return fail(BMPC_BAD_ARG, what + " are built for n_col + 1 <= 64 knots only (one problem per wave segment)");
+    if (int rc = check_batch(d, blocks && c.x, blocks && c.f, arrays)) return rc;
+    const long need_x = blocks ? 81L * (d->n_col + 1) : 9L * d->n_col;
+    const long need_f = blocks ? 9L * d->n_eff * d->n_eff * d->n_col : 3L * d->n_eff * (d->n_col - 1);
+    if ((c.x && (c.sx < 0 || c.sx > (1L << 26) || (c.sx != 0 && c.sx < need_x))) || (c.f && (c.sf < 0 || c.sf > (1L << 26) || (c.sf != 0 && c.sf < need_f))))
+        return fail(BMPC_BAD_ARG, blocks ? "batch stride of a block array must be 0 (shared) or between one problem's blocks and 2^26 doubles"
+                                         : "batch stride of a coupling array (Qx_off / Qf_off) must be 0 (shared) or between one problem's weights and 2^26 doubles");
     return BMPC_OK;
 }
 
@@ -118,36 +131,6 @@ int check_symmetric(const double *blk, size_t n, int k, const char *what) {
                 if (blk[(i * k + r) * k + c] != blk[(i * k + c) * k + r])
                     return fail(BMPC_BAD_ARG, std::string(what) + ": block " + std::to_string(i) + " is not symmetric at (" + std::to_string(r) + ", " + std::to_string(c) + ")");
     return BMPC_OK;
-}
-
-bunmpc::BlockArgs to_block_args(const bmpc_block_cost_t &c) {
-    bunmpc::BlockArgs q;
-    q.Qx_blk = c.Qx_blk; q.Qf_blk = c.Qf_blk;
-    q.sQx_blk = c.Qx_blk ? c.sQx_blk : 0; q.sQf_blk = c.Qf_blk ? c.sQf_blk : 0;
-    return q;
-}
-
-bool has_band(const bmpc_band_cost_t *c) { return c && (c->Qx_off || c->Qf_off); }
-
-// a batch with costs between neighbouring knots: what the band kernels are built for, then the batch itself
-int check_band(const bmpc_batch_t *d, const bmpc_band_cost_t *c) {
-    if (!d) return fail(BMPC_BAD_ARG, "null batch descriptor");
-    if (d->precision != 0) return fail(BMPC_BAD_ARG, "costs between neighbouring knots (Qx_off / Qf_off) are built for fp64 only: precision must be 0");
-    if (!d->raw) return fail(BMPC_BAD_ARG, "costs between neighbouring knots (Qx_off / Qf_off) are built for the raw form only: raw must be 1");
-    if (d->n_col + 1 > 64) return fail(BMPC_BAD_ARG, "costs between neighbouring knots (Qx_off / Qf_off) are built for n_col + 1 <= 64 knots only (one problem per wave segment)");
-    if (int rc = check_batch(d)) return rc;
-    const long need_x = 9L * d->n_col, need_f = 3L * d->n_eff * (d->n_col - 1);
-    if ((c->Qx_off && (c->sQx_off < 0 || c->sQx_off > (1L << 26) || (c->sQx_off != 0 && c->sQx_off < need_x))) ||
-        (c->Qf_off && (c->sQf_off < 0 || c->sQf_off > (1L << 26) || (c->sQf_off != 0 && c->sQf_off < need_f))))
-        return fail(BMPC_BAD_ARG, "batch stride of a coupling array (Qx_off / Qf_off) must be 0 (shared) or between one problem's weights and 2^26 doubles");
-    return BMPC_OK;
-}
-
-bunmpc::BandArgs to_band_args(const bmpc_band_cost_t &c) {
-    bunmpc::BandArgs q;
-    q.Qx_off = c.Qx_off; q.Qf_off = c.Qf_off;
-    q.sQx_off = c.Qx_off ? c.sQx_off : 0; q.sQf_off = c.Qf_off ? c.sQf_off : 0;
-    return q;
 }
 
 }  // namespace
@@ -212,21 +195,41 @@ int bmpc_biconvex_last_lanes_per_problem(void) { return bunmpc::biconvex_last_la
 int bmpc_set_latency_mapping_max_batch(int max_batch) { return bunmpc::set_latency_mapping_max_batch(max_batch); }
 int bmpc_set_exact_step_decisions(int on) { return bunmpc::set_exact_step_decisions(on); }
 int bmpc_set_certified_steps(int on) { return bunmpc::set_certified_steps(on); }
-int bmpc_biconvex_fp32_scratch_bytes(void) { return bunmpc::biconvex_admm_f32_scratch_bytes(); }
+int bmpc_biconvex_fp32_scratch_bytes(void) { return bunmpc::admm_unit(bunmpc::kDiag, 1, 4).scratch_bytes(); }
 int bmpc_block_cost_struct_size(void) { return (int)sizeof(bmpc_block_cost_t); }
 int bmpc_band_cost_struct_size(void) { return (int)sizeof(bmpc_band_cost_t); }
-int bmpc_biconvex_band_kernel_scratch_bytes(int n_eff) {
-    if (n_eff != 2 && n_eff != 4) { fail(BMPC_BAD_ARG, "n_eff must be 2 or 4"); return -1; }
-    return n_eff == 4 ? bunmpc::admm_kq_scratch_bytes_e4() : bunmpc::admm_kq_scratch_bytes_e2();
+static int unit_scratch_bytes(bunmpc::CostShape shape, int precision, int n_eff, const char *msg) {
+    if ((n_eff != 2 && n_eff != 4) || (precision != 0 && precision != 1)) { fail(BMPC_BAD_ARG, msg); return -1; }
+    return bunmpc::admm_unit(shape, precision, n_eff).scratch_bytes();
 }
-int bmpc_biconvex_block_kernel_scratch_bytes(int n_eff) {
-    if (n_eff != 2 && n_eff != 4) { fail(BMPC_BAD_ARG, "n_eff must be 2 or 4"); return -1; }
-    return n_eff == 4 ? bunmpc::admm_bq_scratch_bytes_e4() : bunmpc::admm_bq_scratch_bytes_e2();
-}
-int bmpc_biconvex_kernel_scratch_bytes(int n_eff, int precision) {
-    if ((n_eff != 2 && n_eff != 4) || (precision != 0 && precision != 1)) { fail(BMPC_BAD_ARG, "n_eff must be 2 or 4, precision 0 or 1"); return -1; }
-    if (precision == 1) return n_eff == 4 ? bunmpc::biconvex_admm_f32_scratch_bytes() : bunmpc::biconvex_admm_f32_e2_scratch_bytes();
-    return n_eff == 4 ? bunmpc::admm_scratch_bytes_e4() : bunmpc::admm_scratch_bytes_e2();
+int bmpc_biconvex_band_kernel_scratch_bytes(int n_eff) { return unit_scratch_bytes(bunmpc::kBand, 0, n_eff, "n_eff must be 2 or 4"); }
+int bmpc_biconvex_block_kernel_scratch_bytes(int n_eff) { return unit_scratch_bytes(bunmpc::kBlocks, 0, n_eff, "n_eff must be 2 or 4"); }
+int bmpc_biconvex_kernel_scratch_bytes(int n_eff, int precision) { return unit_scratch_bytes(bunmpc::kDiag, precision, n_eff, "n_eff must be 2 or 4, precision 0 or 1"); }
+int bmpc_biconvex_plan_launch(const bmpc_batch_t *d, int cost_shape, long simds, bmpc_launch_plan_t *out) {
+    if (!out) return fail(BMPC_BAD_ARG, "null plan");
+    std::memset(out, 0, sizeof(*out));
+    out->kernel = "";
+    out->status = BMPC_BAD_ARG;
+    if (cost_shape < 0 || cost_shape > 2) return fail(BMPC_BAD_ARG, "cost_shape must be 0 (diagonal), 1 (blocks) or 2 (band)");
+    if (simds < 1) return fail(BMPC_BAD_ARG, "simds < 1");
+    bunmpc::CostArgs c;
+    c.shape = static_cast<bunmpc::CostShape>(cost_shape);
+    if (int rc = check_cost(d, c, false)) return rc;
+    bunmpc::BatchArgs a;      // (to_args copies pointers without reading through them; plan_launch reads none)
+    std::memset(&a, 0, sizeof(a));
+    a.B = d->B; a.H = d->n_col; a.raw = d->raw; a.precision = d->precision;
+    a.c.maxit = d->maxit; a.c.num_iters = d->num_iters;
+    a.sW_X = d->sW_X; a.sW_X_ter = d->sW_X_ter; a.sW_F = d->sW_F; a.sbounds = d->sbounds;
+    const bunmpc::LaunchPlan p = bunmpc::plan_launch(a, c.shape, d->n_eff, simds);
+    if (p.status != hipSuccess) return fail(BMPC_BAD_ARG, "no centroidal kernel is built for this batch shape");
+    out->status = BMPC_OK;
+    if (!p.kernel) return BMPC_OK;      // (B == 0: nothing to launch)
+    out->kernel = p.kernel;
+    out->lanes_per_problem = p.l.lpp;
+    out->waves_per_simd = p.latency ? 0 : (p.l.w2 ? 2 : 1);
+    out->steal = p.l.steal;
+    out->steal_waves = p.l.steal_waves;
+    return BMPC_OK;
 }
 const char *bmpc_last_error(void) { return g_err.c_str(); }
 
@@ -732,24 +735,10 @@ int bmpc_biconvex_optimize(bmpc_biconvex_t *h, const double *x_init, int num_ite
     b.qf = h->qf_nonzero ? d + o_qf : nullptr;
     b.X = d + o_X; b.F = d + o_F; b.P = d + o_P; b.L_x = d + o_L; b.L_f = d + o_L + 1;
     b.dyn_viol = d + o_viol; b.hist = d + o_hist; b.stats = static_cast<int *>(h->dstats.p);
-    bmpc_block_cost_t blk;
-    std::memset(&blk, 0, sizeof(blk));
-    if (!h->Qx_blk.empty()) blk.Qx_blk = d + o_Qxb;
-    if (!h->Qf_blk.empty()) blk.Qf_blk = d + o_Qfb;
-    bmpc_band_cost_t band;
-    std::memset(&band, 0, sizeof(band));
-    if (h->has_x_off) band.Qx_off = d + o_Qxo;
-    if (h->has_f_off) band.Qf_off = d + o_Qfo;
-    if (has_band(&band)) {
-        if (int rc = check_band(&b, &band)) return rc;
-        HIP_TRY(bunmpc::launch_biconvex_admm_band(to_args(b), to_band_args(band), E, nullptr));
-    } else if (has_blocks(&blk)) {
-        if (int rc = check_blocks(&b, &blk)) return rc;
-        HIP_TRY(bunmpc::launch_biconvex_admm_blocks(to_args(b), to_block_args(blk), E, nullptr));
-    } else {
-        if (int rc = check_batch(&b)) return rc;
-        HIP_TRY(bunmpc::launch_biconvex_admm(to_args(b), E, nullptr));
-    }
+    bunmpc::CostArgs cost = cost_args(bunmpc::kBand, h->has_x_off ? d + o_Qxo : nullptr, 0, h->has_f_off ? d + o_Qfo : nullptr, 0);
+    if (cost.shape == bunmpc::kDiag) cost = cost_args(bunmpc::kBlocks, h->Qx_blk.empty() ? nullptr : d + o_Qxb, 0, h->Qf_blk.empty() ? nullptr : d + o_Qfb, 0);
+    if (int rc = check_cost(&b, cost)) return rc;
+    HIP_TRY(bunmpc::launch_biconvex_admm(to_args(b), cost, E, nullptr));
     HIP_TRY(hipMemcpy(stage.data() + o_X, d + o_X, sizeof(double) * (o_end - o_X), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(h->last_stats, h->dstats.p, sizeof(int) * bunmpc::kStats, hipMemcpyDeviceToHost));
     std::memcpy(h->X.data(), stage.data() + o_X, sizeof(double) * nx);
@@ -775,75 +764,56 @@ void bmpc_batch_defaults(bmpc_batch_t *d) {
     d->rho = 1e5; d->mu = 1.0; d->beta = 1.5; d->tol = 1e-5; d->exit_tol = 1e-3;
 }
 
-int bmpc_biconvex_solve_batch_device(const bmpc_batch_t *d, void *hip_stream) {
-    if (int rc = check_batch(d)) return rc;
-    HIP_TRY(bunmpc::launch_biconvex_admm(to_args(*d), d->n_eff, static_cast<hipStream_t>(hip_stream)));
+static int solve_batch_device(const bmpc_batch_t *d, const bunmpc::CostArgs &c, void *hip_stream) {
+    if (int rc = check_cost(d, c)) return rc;
+    HIP_TRY(bunmpc::launch_biconvex_admm(to_args(*d), c, d->n_eff, static_cast<hipStream_t>(hip_stream)));
     return BMPC_OK;
 }
-
-int bmpc_biconvex_solve_batch_blocks_device(const bmpc_batch_t *d, const bmpc_block_cost_t *c, void *hip_stream) {
-    if (!has_blocks(c)) return bmpc_biconvex_solve_batch_device(d, hip_stream);
-    if (int rc = check_blocks(d, c)) return rc;
-    HIP_TRY(bunmpc::launch_biconvex_admm_blocks(to_args(*d), to_block_args(*c), d->n_eff, static_cast<hipStream_t>(hip_stream)));
-    return BMPC_OK;
-}
-
-int bmpc_biconvex_solve_batch_band_device(const bmpc_batch_t *d, const bmpc_band_cost_t *c, void *hip_stream) {
-    if (!has_band(c)) return bmpc_biconvex_solve_batch_device(d, hip_stream);
-    if (int rc = check_band(d, c)) return rc;
-    HIP_TRY(bunmpc::launch_biconvex_admm_band(to_args(*d), to_band_args(*c), d->n_eff, static_cast<hipStream_t>(hip_stream)));
-    return BMPC_OK;
-}
+int bmpc_biconvex_solve_batch_device(const bmpc_batch_t *d, void *hip_stream) { return solve_batch_device(d, bunmpc::CostArgs(), hip_stream); }
+int bmpc_biconvex_solve_batch_blocks_device(const bmpc_batch_t *d, const bmpc_block_cost_t *c, void *hip_stream) { return solve_batch_device(d, cost_of(c), hip_stream); }
+int bmpc_biconvex_solve_batch_band_device(const bmpc_batch_t *d, const bmpc_band_cost_t *c, void *hip_stream) { return solve_batch_device(d, cost_of(c), hip_stream); }
 
 namespace {
-int solve_batch_host(const bmpc_batch_t *d, const bmpc_block_cost_t *c, const bmpc_band_cost_t *kc);
+int solve_batch_host(const bmpc_batch_t *d, bunmpc::CostArgs c);
 }
-int bmpc_biconvex_solve_batch_host(const bmpc_batch_t *d) { return solve_batch_host(d, nullptr, nullptr); }
-int bmpc_biconvex_solve_batch_blocks_host(const bmpc_batch_t *d, const bmpc_block_cost_t *c) { return solve_batch_host(d, c, nullptr); }
-int bmpc_biconvex_solve_batch_band_host(const bmpc_batch_t *d, const bmpc_band_cost_t *c) { return solve_batch_host(d, nullptr, c); }
+int bmpc_biconvex_solve_batch_host(const bmpc_batch_t *d) { return solve_batch_host(d, bunmpc::CostArgs()); }
+int bmpc_biconvex_solve_batch_blocks_host(const bmpc_batch_t *d, const bmpc_block_cost_t *c) { return solve_batch_host(d, cost_of(c)); }
+int bmpc_biconvex_solve_batch_band_host(const bmpc_batch_t *d, const bmpc_band_cost_t *c) { return solve_batch_host(d, cost_of(c)); }
 
 }  // extern "C"
 
 namespace {
-// the host entry points: arrays to the device, one launch, results back (c: per-knot blocks, kc: costs between neighbouring knots; at most one of them)
-int solve_batch_host(const bmpc_batch_t *d, const bmpc_block_cost_t *c, const bmpc_band_cost_t *kc) {
-    const bool blocks = has_blocks(c), band = has_band(kc);
-    if (int rc = blocks ? check_blocks(d, c) : (band ? check_band(d, kc) : check_batch(d))) return rc;
+// the host entry points: arrays to the device, one launch, results back (c: the host arrays of per-knot blocks or of costs between neighbouring knots, if any)
+int solve_batch_host(const bmpc_batch_t *d, bunmpc::CostArgs c) {
+    const bool blocks = c.shape == bunmpc::kBlocks, band = c.shape == bunmpc::kBand;
+    if (int rc = check_cost(d, c)) return rc;
     const size_t B = (size_t)d->B, H = (size_t)d->n_col, E = (size_t)d->n_eff;
     const size_t nx = 9 * (H + 1), nf = 3 * E * H;
     if (B == 0) return BMPC_OK;
     bmpc_batch_t b = *d;
-    bmpc_block_cost_t cb;
-    std::memset(&cb, 0, sizeof(cb));
-    if (blocks) cb = *c;
-    bmpc_band_cost_t kb;
-    std::memset(&kb, 0, sizeof(kb));
-    if (band) kb = *kc;
-    if (H < 2) kb.Qf_off = nullptr;      // (one force knot: no pair)
+    if (band && H < 2) c = cost_args(bunmpc::kBand, c.x, c.sx, nullptr, 0);      // (one force knot: no pair; with Qf_off alone: diagonal costs)
     struct In { const double **slot; size_t n; };
     struct Out { double **slot; double *host; size_t n; };
     auto rows = [&](long stride) { return stride == 0 ? (size_t)1 : B; };
     std::vector<In> ins = {{&b.cnt_plan, B * H * E * 4}, {&b.dt, B * H}, {&b.x_init, B * 9}};
     if (d->raw) {
-        if (cb.Qx_blk) {
-            const size_t n = (rows(cb.sQx_blk) - 1) * (size_t)cb.sQx_blk + 81 * (H + 1);
-            for (size_t i = 0; i < rows(cb.sQx_blk); ++i)
-                if (int rc = check_symmetric(cb.Qx_blk + i * (size_t)cb.sQx_blk, H + 1, 9, "Qx_blk")) return rc;
-            ins.push_back({&cb.Qx_blk, n});
+        if (blocks && c.x) {
+            for (size_t i = 0; i < rows(c.sx); ++i)
+                if (int rc = check_symmetric(c.x + i * (size_t)c.sx, H + 1, 9, "Qx_blk")) return rc;
+            ins.push_back({&c.x, (rows(c.sx) - 1) * (size_t)c.sx + 81 * (H + 1)});
             b.Qx = nullptr;
         } else ins.push_back({&b.Qx, B * nx});
         ins.push_back({&b.qx, B * nx});
         ins.push_back({&b.lbx, B * nx}); ins.push_back({&b.ubx, B * nx});
-        if (cb.Qf_blk) {
-            const size_t kk = 9 * E * E, n = (rows(cb.sQf_blk) - 1) * (size_t)cb.sQf_blk + kk * H;
-            for (size_t i = 0; i < rows(cb.sQf_blk); ++i)
-                if (int rc = check_symmetric(cb.Qf_blk + i * (size_t)cb.sQf_blk, H, 3 * (int)E, "Qf_blk")) return rc;
-            ins.push_back({&cb.Qf_blk, n});
+        if (blocks && c.f) {
+            for (size_t i = 0; i < rows(c.sf); ++i)
+                if (int rc = check_symmetric(c.f + i * (size_t)c.sf, H, 3 * (int)E, "Qf_blk")) return rc;
+            ins.push_back({&c.f, (rows(c.sf) - 1) * (size_t)c.sf + 9 * E * E * H});
             b.Qf = nullptr;
         } else ins.push_back({&b.Qf, B * nf});
         if (d->qf) ins.push_back({&b.qf, B * nf});
-        if (kb.Qx_off) ins.push_back({&kb.Qx_off, (rows(kb.sQx_off) - 1) * (size_t)kb.sQx_off + 9 * H});
-        if (kb.Qf_off) ins.push_back({&kb.Qf_off, (rows(kb.sQf_off) - 1) * (size_t)kb.sQf_off + 3 * E * (H - 1)});
+        if (band && c.x) ins.push_back({&c.x, (rows(c.sx) - 1) * (size_t)c.sx + 9 * H});
+        if (band && c.f) ins.push_back({&c.f, (rows(c.sf) - 1) * (size_t)c.sf + 3 * E * (H - 1)});
     } else {
         ins.push_back({&b.W_X, (rows(d->sW_X) - 1) * (size_t)d->sW_X + 9 * H});
         ins.push_back({&b.W_X_ter, (rows(d->sW_X_ter) - 1) * (size_t)d->sW_X_ter + 9});
@@ -880,9 +850,7 @@ int solve_batch_host(const bmpc_batch_t *d, const bmpc_block_cost_t *c, const bm
         HIP_TRY(hipMemcpy(tbuf.p, d->trace, sizeof(int) * ntrace, hipMemcpyHostToDevice));
         b.trace = static_cast<int *>(tbuf.p);
     }
-    if (blocks) HIP_TRY(bunmpc::launch_biconvex_admm_blocks(to_args(b), to_block_args(cb), d->n_eff, nullptr));
-    else if (has_band(&kb)) HIP_TRY(bunmpc::launch_biconvex_admm_band(to_args(b), to_band_args(kb), d->n_eff, nullptr));
-    else HIP_TRY(bunmpc::launch_biconvex_admm(to_args(b), d->n_eff, nullptr));
+    HIP_TRY(bunmpc::launch_biconvex_admm(to_args(b), c, d->n_eff, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     for (auto &o : outs) HIP_TRY(hipMemcpy(o.host, *o.slot, sizeof(double) * o.n, hipMemcpyDeviceToHost));
     if (d->stats) HIP_TRY(hipMemcpy(d->stats, sbuf.p, sizeof(int) * bunmpc::kStats * B, hipMemcpyDeviceToHost));

@@ -206,6 +206,23 @@ const char *bmpc_biconvex_kernel_name(int n_col, int raw);
  * "biconvex_admm_kernel" or "biconvex_admm_kernel_f32" (one knot per lane), "biconvex_admm_bq_kernel" (block costs),
  * "biconvex_admm_kq_kernel" (costs between neighbouring knots); "" before the first solve */
 const char *bmpc_biconvex_last_kernel_name(void);
+/* Which kernel a batch solve of descriptor d would be dispatched to on a chip of `simds` SIMDs (an MI355X: 256 CUs x 4 = 1024), with
+ * the process's current dispatch switches (the bmpc_set_* calls above).  cost_shape 0: diagonal costs (bmpc_biconvex_solve_batch_*),
+ * 1: block costs, 2: costs between neighbouring knots.  A pure function: it reads only the scalar fields of d (B, n_col, n_eff, raw,
+ * precision, num_iters, maxit, cold_start, the strides) -- no pointer in d is looked at, let alone dereferenced -- and makes no GPU
+ * call, so it runs on a machine without one.  status: BMPC_OK, or BMPC_BAD_ARG (also returned; bmpc_last_error explains) for a shape
+ * the solve calls refuse.  lanes_per_problem / waves_per_simd / kernel: what bmpc_biconvex_last_* report after the solve, except
+ * waves_per_simd = 0 for the one-problem-per-wave kernel (which leaves that record alone); kernel is "" when B == 0 (no launch).
+ * steal / steal_waves: the work-stealing kernel and its persistent grid. */
+typedef struct {
+    int status;
+    int lanes_per_problem;
+    int waves_per_simd;
+    int steal;
+    long steal_waves;
+    const char *kernel;
+} bmpc_launch_plan_t;
+int bmpc_biconvex_plan_launch(const bmpc_batch_t *d, int cost_shape, long simds, bmpc_launch_plan_t *out);
 
 /* Per-knot block-diagonal costs (additive) --------------------------------------------------------------------------------
  * The reference's set_cost_x / set_cost_f take a sparse matrix (biconvex.hpp:54-60) and ProblemData uses all of it
