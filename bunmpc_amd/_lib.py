@@ -214,6 +214,10 @@ _SIGS = {
     "bmpc_ik_layout": (None, [_I, _P]),
     "bmpc_ik_layout_trace": (None, [_I, _P, _P, _P]),
     "bmpc_ik_selftest_state_ops": (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
+    "bmpc_ik_selftest_passes": (_I, [_P, _P, _P, _I, _D, _I, _I, _P]),
+    "bmpc_ik_layout_all": (_I, [_I, _P, _I]),
+    "bmpc_ik_set_calcdiff_one_wave_above": (_I, [_I]),
+    "bmpc_ik_last_calcdiff_kernel": (_I, []),
     "bmpc_ik_set_profile": (_I, [_I]),
     "bmpc_ik_set_all_steps": (_I, [_I]),
     "bmpc_ik_set_gains_wave_below": (_I, [_I]),

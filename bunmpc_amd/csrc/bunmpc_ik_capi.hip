@@ -779,6 +779,47 @@ int bmpc_ik_centroidal_state_device(const bmpc_model_t *model, const double *x, 
     HIP_TRY(bunmpc::ik_launch_centroidal_state(m->dptr(), x, out9, B, static_cast<hipStream_t>(hip_stream)));
     return BMPC_OK;
 }
+// Self test of the derivative and Riccati passes (tests/test_ik_passes_gpu.py): ONE ik_state + ik_calcdiff + ik_backward launch
+// at the caller's trajectory -- the launchers of the DDP loop, no forward pass, no host loop; the caller reads the workspace back
+int bmpc_ik_selftest_passes(const bmpc_ik_batch_t *d, const double *xs, const double *us, int feasible, double xreg, int calcdiff_kernel,
+                            int bwd_waves, void *hip_stream) {
+    using namespace bunmpc;
+    if (!d || !d->model) return ik_fail(BMPC_BAD_ARG, "null batch descriptor / model");
+    if (d->B < 0 || d->n_col < 1) return ik_fail(BMPC_BAD_ARG, "bad sizes");
+    if (d->n_col > kMaxIkCol) return ik_fail(BMPC_BAD_ARG, "n_col > 255 is not supported");
+    if (!d->x0 || !d->dt || !d->tasks || !d->state_w || !d->x_reg || !d->ctrl_w || !d->ws || !d->active || !xs || !us)
+        return ik_fail(BMPC_BAD_ARG, "missing array");
+    if ((feasible != 0 && feasible != 1) || (calcdiff_kernel != 0 && calcdiff_kernel != 1) || (bwd_waves != 1 && bwd_waves != 2))
+        return ik_fail(BMPC_BAD_ARG, "feasible and calcdiff_kernel must be 0 or 1, bwd_waves 1 or 2");
+    if (!(xreg >= 1e-9 && xreg < 1e9)) return ik_fail(BMPC_BAD_ARG, "xreg outside [1e-9, 1e9)");
+    if (d->B == 0) return BMPC_OK;
+    auto *model = const_cast<bmpc_model *>(d->model);
+    if (int rc = model->upload()) return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    IkBatchArgs a = make_args(d->B, d->n_col, 1, model, d->x0, d->dt, d->tasks, d->state_w, d->s_state_w, d->x_reg,
+                              d->ctrl_w, d->s_ctrl_w, d->ws, d->active);
+    a.s_x_reg = d->s_x_reg ? d->s_x_reg : kNX;
+    a.sn_state_w = d->sn_state_w; a.sn_x_reg = d->sn_x_reg; a.sn_ctrl_w = d->sn_ctrl_w;
+    if (d->active_list) set_list(a, d->active_list);
+    a.bwd_waves = bwd_waves;
+    HIP_TRY(ik_launch_init(a, st));
+    HIP_TRY(ik_launch_selftest_set(a, xs, us, feasible, xreg, st));
+    HIP_TRY(ik_launch_state(a, st));
+    HIP_TRY(ik_launch_calcdiff(a, st, calcdiff_kernel));
+    HIP_TRY(ik_launch_selftest_keep_costs(a, st));      // (the Riccati pass overwrites the parked node costs with the gaps)
+    HIP_TRY(ik_launch_backward(a, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return BMPC_OK;
+}
+int bmpc_ik_set_calcdiff_one_wave_above(int n_pairs) { return bunmpc::ik_set_calcdiff_one_wave_above(n_pairs); }
+int bmpc_ik_last_calcdiff_kernel(void) { return bunmpc::ik_last_calcdiff_kernel(); }
+int bmpc_ik_layout_all(int n_col, long *offsets, int n) {
+    const bunmpc::IkLayout L = bunmpc::IkLayout::make(n_col);
+    const long all[] = {L.xs, L.us, L.scal, L.K, L.kff, L.fs, L.Lx, L.Lqq, L.xnext, L.Hn, L.Lu, L.Luu, L.A6, L.B6, L.nrs, L.njl, L.ncs, L.total, L.Quuk};
+    const int have = (int)(sizeof(all) / sizeof(all[0]));
+    for (int i = 0; offsets && i < n && i < have; ++i) offsets[i] = all[i];
+    return have;
+}
 void bmpc_ik_layout(int n_col, long *offsets8) {   // xs, us, scal, K, kff, fs, Lx, Lqq offsets for callers that read the workspace
     const bunmpc::IkLayout L = bunmpc::IkLayout::make(n_col);
     offsets8[0] = L.xs; offsets8[1] = L.us; offsets8[2] = L.scal; offsets8[3] = L.K; offsets8[4] = L.kff;

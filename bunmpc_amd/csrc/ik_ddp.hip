@@ -40,6 +40,8 @@
 #include "rbd_quad.h"
 #include "lds_batch.h"
 
+#include <atomic>
+
 namespace bunmpc {
 namespace {
 
@@ -456,7 +458,8 @@ __device__ __forceinline__ void calc_assemble(const IkBatchArgs &a, long b, int 
     // on their own), and every weight a lane needs requested here, in one batch, before anything waits.
     typedef const double __attribute__((address_space(1))) *gcd_t;
     typedef double __attribute__((address_space(1))) *gd_t;
-    const gcd_t state_w = (gcd_t)(state_w0 + a.sn_state_w * t), ctrl_w = (gcd_t)(ctrl_w0 + a.sn_ctrl_w * t);
+    // (ctrl_w has no terminal row -- [n_col][18] per problem: the terminal node, whose control terms are not stored, reads row 0)
+    const gcd_t state_w = (gcd_t)(state_w0 + a.sn_state_w * t), ctrl_w = (gcd_t)(ctrl_w0 + a.sn_ctrl_w * (terminal ? 0 : t));
     const gd_t wsg = (gd_t)ws;
     const int li_ = lane & 15;
     double sw_k[6];
@@ -2201,6 +2204,29 @@ __global__ void ik_state_ops_selftest_kernel(const double *x0, const double *x1,
     for (int k = 0; k < kNX; ++k) ir[(long)i * kNX + k] = o[k];
 }
 
+// per-pass self test (bmpc_ik_selftest_passes): one thread per element of the caller's trajectory, xs [B][T+1][37] | us [B][T][18]
+// into the workspace rows; the first thread of a problem sets the scalars the two passes read
+__global__ void ik_selftest_set_kernel(const IkBatchArgs a, const double *xs, const double *us, int feasible, double xreg) {
+    const long per = (long)(a.T + 1) * kNX + (long)a.T * kNV, nx = (long)(a.T + 1) * kNX;
+    const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= (long)a.B * per) return;
+    const long b = id / per, e = id % per;
+    const IkLayout L = IkLayout::make(a.T);
+    double *ws = a.ws + b * L.total;
+    if (e < nx) ws[L.xs + e] = xs[b * nx + e];
+    else ws[L.us + (e - nx)] = us[b * (long)a.T * kNV + (e - nx)];
+    if (e == 0) { ws[L.scal + S_FEAS] = feasible ? 1.0 : 0.0; ws[L.scal + S_WASFEAS] = 0.0; ws[L.scal + S_XREG] = xreg; }
+}
+// ... and, between the derivative and the Riccati launch: the node costs, which the derivative pass parks in the gap slots and the
+// Riccati pass overwrites with the gaps once it has summed them, kept for the caller in Quuk[0 .. T] (unused by the solver)
+__global__ void ik_selftest_keep_costs_kernel(const IkBatchArgs a) {
+    const long id = (long)blockIdx.x * blockDim.x + threadIdx.x, nn = a.T + 1;
+    if (id >= (long)a.B * nn) return;
+    const IkLayout L = IkLayout::make(a.T);
+    double *ws = a.ws + (id / nn) * L.total;
+    ws[L.Quuk + id % nn] = ws[L.fs + (id % nn) * kNDX];
+}
+
 // the active-problem counter, copied to a host-mapped word: the host reads it after its stream synchronisation
 // without a device-to-host copy operation (a 4-byte hipMemcpy into pageable memory costs ~50 us per DDP iteration)
 __global__ void ik_publish_active_kernel(const int *active, const int *err, const int *count_next, const int *xmeta, volatile int *host_word,
@@ -2261,11 +2287,27 @@ hipError_t ik_launch_state(const IkBatchArgs &a, hipStream_t st) {
     hipLaunchKernelGGL(ik_state_kernel, dim3(2u * (unsigned)((n + 63) / 64)), dim3(64), 0, st, a);      // two workgroups per 64 nodes
     return hipGetLastError();
 }
-int g_calcdiff_one_wave_above = 1024;     // node pairs per launch above which one wave takes a pair (the two-wave kernel has 1024 pairs resident on an MI355X)
-hipError_t ik_launch_calcdiff(const IkBatchArgs &a, hipStream_t st) {
+std::atomic<int> g_calcdiff_one_wave_above{1024};     // node pairs per launch above which one wave takes a pair (the two-wave kernel has 1024 pairs resident on an MI355X)
+std::atomic<int> g_calcdiff_last_kernel{-1};          // 0 = ik_calcdiff_kernel, 1 = ik_calcdiff1_kernel (tests assert which one ran)
+int ik_set_calcdiff_one_wave_above(int n_pairs) { return g_calcdiff_one_wave_above.exchange(n_pairs); }
+int ik_last_calcdiff_kernel() { return g_calcdiff_last_kernel.load(); }
+hipError_t ik_launch_calcdiff(const IkBatchArgs &a, hipStream_t st, int kernel) {
     const long n = launch_problems(a) * ((a.T + 1 + 1) / 2);   // two nodes per workgroup
-    if (n > g_calcdiff_one_wave_above) hipLaunchKernelGGL(ik_calcdiff1_kernel, dim3((unsigned)((n + 1) / 2)), dim3(128), 0, st, a);
+    const bool one_wave = kernel < 0 ? n > g_calcdiff_one_wave_above.load() : kernel == 1;
+    if (one_wave) hipLaunchKernelGGL(ik_calcdiff1_kernel, dim3((unsigned)((n + 1) / 2)), dim3(128), 0, st, a);
     else hipLaunchKernelGGL(ik_calcdiff_kernel, dim3((unsigned)n), dim3(128), 0, st, a);
+    g_calcdiff_last_kernel.store(one_wave ? 1 : 0);
+    return hipGetLastError();
+}
+hipError_t ik_launch_selftest_set(const IkBatchArgs &a, const double *xs, const double *us, int feasible, double xreg, hipStream_t st) {
+    const long n = (long)a.B * ((long)(a.T + 1) * kNX + (long)a.T * kNV);
+    hipLaunchKernelGGL(ik_selftest_set_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, xs, us, feasible, xreg);
+    return hipGetLastError();
+}
+hipError_t ik_launch_selftest_keep_costs(const IkBatchArgs &a, hipStream_t st) {
+    static_assert(kNV >= 2, "Quuk (T x kNV doubles) holds T + 1 node costs");
+    const long n = (long)a.B * (a.T + 1);
+    hipLaunchKernelGGL(ik_selftest_keep_costs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 // workgroups of each IK kernel one CU holds at once, as the runtime's occupancy query sees them (registers, LDS, wave slots):

@@ -135,7 +135,16 @@ struct IkBatchArgs {
 
 hipError_t ik_launch_init(const IkBatchArgs &a, hipStream_t s);
 hipError_t ik_launch_state(const IkBatchArgs &a, hipStream_t s);      // before every calcdiff
-hipError_t ik_launch_calcdiff(const IkBatchArgs &a, hipStream_t s);
+// kernel: -1 = by the launch's size (more node pairs than ik_set_calcdiff_one_wave_above's bound: one wave per pair), 0 = two waves
+// per pair, 1 = one wave per pair (the per-pass self test forces either)
+hipError_t ik_launch_calcdiff(const IkBatchArgs &a, hipStream_t s, int kernel = -1);
+int ik_set_calcdiff_one_wave_above(int n_pairs);     // returns the old bound
+int ik_last_calcdiff_kernel();                       // which of the two the last ik_launch_calcdiff of this process launched (-1: none yet)
+// per-pass self test: the caller's trajectory xs [B][T+1][37], us [B][T][18] and the scalars S_FEAS / S_WASFEAS (0) / S_XREG over
+// what ik_launch_init left in the workspace
+hipError_t ik_launch_selftest_set(const IkBatchArgs &a, const double *xs, const double *us, int feasible, double xreg, hipStream_t s);
+// ... and the node costs (parked in the gap slots until the Riccati pass has summed them) copied to Quuk[0 .. T], between the two passes
+hipError_t ik_launch_selftest_keep_costs(const IkBatchArgs &a, hipStream_t s);
 hipError_t ik_launch_backward(const IkBatchArgs &a, hipStream_t s);
 hipError_t ik_launch_forward(const IkBatchArgs &a, hipStream_t s);
 // host_word_dev[0..3] = *active, index-check code, length of the list iteration next_iter runs over, express lane taken

@@ -426,6 +426,26 @@ int bmpc_ik_solve_batch_device(const bmpc_ik_batch_t *d, void *hip_stream);
 /* self test (host arrays): the state operators diff(x0, x1) and x0 (+) dx of n samples, x [n][37], dx [n][36], by the
  * quaternion versions the forward pass uses (dq [n][36], iq [n][37]) and by the rotation-matrix versions (dr, ir) */
 int bmpc_ik_selftest_state_ops(const double *x0, const double *x1, const double *dx, int n, double *dq, double *dr, double *iq, double *ir);
+/* TEST ONLY.  Self test of the derivative pass and the Riccati pass, each launched ONCE at a trajectory of the caller's (device
+ * arrays xs [B][n_col+1][37], us [B][n_col][18]; d as for bmpc_ik_solve_batch_device, maxiter / iters_run / sched ignored): the
+ * workspace is initialised as a solve does, its rows xs / us and the scalars feasible (is_feasible_; was_feasible_ = 0) and xreg
+ * (= ureg, in [1e-9, 1e9)) are overwritten, then the DDP loop's own launchers run the state kernel, the derivative kernel
+ * (calcdiff_kernel: 0 = two waves per node pair, 1 = one wave per pair, whatever the launch's size) and the backward kernel
+ * (bwd_waves: 1, or 2 = with the gains wave).  No forward pass, no host loop; returns after the stream has drained, the results
+ * are in d->ws (bmpc_ik_layout_all); the node costs, which the Riccati pass sums and then overwrites, are kept in the solver's
+ * unused Quuk rows, node t at Quuk[t].  Bad arguments: BMPC_BAD_ARG. */
+int bmpc_ik_selftest_passes(const bmpc_ik_batch_t *d, const double *xs, const double *us, int feasible, double xreg, int calcdiff_kernel,
+                            int bwd_waves, void *hip_stream);
+/* TEST ONLY.  Offsets (doubles) into a problem's workspace, the first min(n, count) of: xs, us, scalars, K, k, fs, Lx, Lqq (as
+ * bmpc_ik_layout), xnext, Hn (momentum Jacobian, its weight and the velocity diagonal of L_xx), Lu, Luu (diagonal), A6, B6 (the
+ * 6 x 6 Jintegrate blocks), nrs, njl, ncs (state residual, its Jlog6 block transposed, state + control cost of a node), total,
+ * Quuk (unused by the solver; bmpc_ik_selftest_passes keeps the node costs there).  Returns count (19). */
+int bmpc_ik_layout_all(int n_col, long *offsets, int n);
+/* Derivative-pass scheduling (no effect on results): a launch with MORE than n_pairs node pairs (active problems x ceil((n_col + 1)
+ * / 2)) runs one wave per pair instead of two.  Default 1024 (what an MI355X holds of the two-wave kernel); returns the old value.
+ * bmpc_ik_last_calcdiff_kernel: which kernel the last derivative launch of this process was (0 two waves, 1 one wave, -1 none yet). */
+int bmpc_ik_set_calcdiff_one_wave_above(int n_pairs);
+int bmpc_ik_last_calcdiff_kernel(void);
 int bmpc_ik_set_profile(int on);            /* returns the old setting */
 void bmpc_ik_last_profile(double *ms5);
 /* [com, vcom, hg.angular] of x = [q, v]: what KinoDynMP::optimize feeds the centroidal solve (kino_dyn.cpp:42,86-97) */

@@ -151,7 +151,7 @@ def node_calc(prob, t, x, u, diff=False):
 def solve_ddp(prob, x0, maxiter=100, reg_min=1e-9, reg_max=1e9, verbose=False):
     """crocoddyl 1.9.0 SolverDDP::solve(init_xs={}, init_us={}, maxiter=100, is_feasible=false,
     reginit=NaN) as called by InverseKinematics::optimize (inverse_kinematics.cpp:56-58).
-    Returns dict(xs, us, iters, cost, stop, converged, reg)."""
+    Returns dict(xs, us, iters, cost, stop, converged, reg, K, k)."""
     model, T = prob.model, prob.T
     nv = model.nv
     ndx = 2 * nv
@@ -280,4 +280,5 @@ def solve_ddp(prob, x0, maxiter=100, reg_min=1e-9, reg_max=1e9, verbose=False):
         if was_feasible and stop < th_stop:
             converged = True
             break
-    return dict(xs=xs, us=us, iters=it_done, cost=cost, stop=stop, converged=converged, reg=xreg)
+    # K, k: the gains of the last backward pass (tests/test_ik_passes_cpu.py holds the stand-alone Riccati reference to them)
+    return dict(xs=xs, us=us, iters=it_done, cost=cost, stop=stop, converged=converged, reg=xreg, K=K, k=k)
