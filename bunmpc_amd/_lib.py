@@ -218,6 +218,7 @@ _SIGS = {
     "bmpc_ik_layout_all": (_I, [_I, _P, _I]),
     "bmpc_ik_set_calcdiff_one_wave_above": (_I, [_I]),
     "bmpc_ik_last_calcdiff_kernel": (_I, []),
+    "bmpc_ik_plan_iteration": (_I, [_I, _I, _I, _I, _I, _I, _P, _P]),
     "bmpc_ik_set_profile": (_I, [_I]),
     "bmpc_ik_set_all_steps": (_I, [_I]),
     "bmpc_ik_set_gains_wave_below": (_I, [_I]),
@@ -249,6 +250,19 @@ IK_NODE_TASK_DOUBLES = 33
 class IkSched(C.Structure):
     """bmpc_ik_sched_t: per-batch scheduling thresholds (0 = process default, < 0 = never)"""
     _fields_ = [("spec_below", C.c_int), ("all_steps_below", C.c_int), ("gains_wave_below", C.c_int), ("express_cap", C.c_int), ("debug_inject", C.c_int)]
+
+
+class IkPlannedLaunch(C.Structure):
+    """bmpc_ik_planned_launch_t"""
+    _fields_ = [("kernel", C.c_char * 24), ("grid", C.c_uint), ("block", C.c_uint)]
+
+
+class IkIterPlan(C.Structure):
+    """bmpc_ik_iter_plan_t"""
+    _fields_ = ([(n, C.c_int) for n in ("status", "fused_direct", "express_cap")] + [("fused_grid", C.c_uint), ("express_grid", C.c_uint)] +
+                [(n, C.c_int) for n in ("chunk", "fwd_map", "bwd_waves", "n_launch")] +
+                [(n, IkPlannedLaunch) for n in ("state", "calcdiff", "backward", "forward")] +
+                [(n, C.c_int) for n in ("max_fused_col", "express_first_iter", "express_last_iter", "tail_chunk")])
 
 
 class IkBatch(C.Structure):

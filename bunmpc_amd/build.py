@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 SOURCES = ["biconvex_admm.hip", "biconvex_admm_e2.hip", "biconvex_admm_bq.hip", "biconvex_admm_bq_e2.hip", "biconvex_admm_kq.hip", "biconvex_admm_kq_e2.hip", "biconvex_admm_f32.hip", "biconvex_admm_f32_e2.hip", "biconvex_latency.hip", "bunmpc_capi.hip", "ik_ddp.hip", "bunmpc_ik_capi.hip", "plan_gen.hip", "id_ctrl.hip", "perturb.hip"]
-HEADERS = [os.path.join(CSRC, h) for h in ("biconvex_kernels.h", "biconvex_lanes.h", "biconvex_admm_body.h", "biconvex_admm_inst.h", "ik_types.h", "rbd_device.h", "rbd_quad.h", "lds_batch.h", "id_types.h", "perturb_types.h")] + \
+HEADERS = [os.path.join(CSRC, h) for h in ("biconvex_kernels.h", "biconvex_lanes.h", "biconvex_admm_body.h", "biconvex_admm_inst.h", "ik_types.h", "ik_plan.h", "rbd_device.h", "rbd_quad.h", "lds_batch.h", "id_types.h", "perturb_types.h")] + \
           [os.path.join(os.path.dirname(_HERE), "include", "bunmpc.h")]
 LIB = os.path.join(_HERE, "libbunmpc_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

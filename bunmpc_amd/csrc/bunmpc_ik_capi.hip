@@ -10,8 +10,8 @@ namespace bunmpc {
 int launch_wb_plan(const RobotModelDev *model, const bmpc_wb_plan_batch_t &d, hipStream_t st);   // plan_gen.hip
 }
 
-#include <atomic>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <iostream>
@@ -141,50 +141,50 @@ int pack_tasks(const bmpc_ik *h, std::vector<double> &tasks) {
     return BMPC_OK;
 }
 
-// the pieces of the scratch behind bmpc_ik_batch_t.active_list (ik_types.h::active_list_ints)
-void set_list(bunmpc::IkBatchArgs &a, int *p) {
+constexpr int kMaxIkCol = 255;
+// The checks on a batch descriptor and the kernel arguments made from it (more_arrays / more_error: the caller's further arrays are there /
+// what is wrong with its further arguments, or null -- reported in their place among the checks).  Uploads the model.  B == 0 passes the
+// checks and fills nothing: the caller returns before any launch.
+int args_from_batch(const bmpc_ik_batch_t *d, int maxiter, bool more_arrays, const char *more_error, bunmpc::IkBatchArgs *a) {
     using namespace bunmpc;
-    a.list = p; a.count = a.list + 2 * (long)a.B; a.wcount = a.count + 2; a.wide = a.wcount + 2; a.err = a.wide + 2 * kWideMax;
-    a.near = a.err + 2; a.xmeta = a.near + 2; a.xlist = a.xmeta + 4;
+    if (!d || !d->model) return ik_fail(BMPC_BAD_ARG, "null batch descriptor / model");
+    if (d->B < 0 || d->n_col < 1 || maxiter < 1) return ik_fail(BMPC_BAD_ARG, "bad sizes");
+    if (d->n_col > kMaxIkCol) return ik_fail(BMPC_BAD_ARG, "n_col > 255 is not supported");
+    if (!d->x0 || !d->dt || !d->tasks || !d->state_w || !d->x_reg || !d->ctrl_w || !d->ws || !d->active || !more_arrays)
+        return ik_fail(BMPC_BAD_ARG, "missing array");
+    if (more_error) return ik_fail(BMPC_BAD_ARG, more_error);
+    if (d->B == 0) return BMPC_OK;
+    auto *model = const_cast<bmpc_model *>(d->model);
+    if (int rc = model->upload()) return rc;
+    *a = IkBatchArgs{};      // (every field below unset: zero, the list pointers null)
+    a->B = d->B; a->T = d->n_col; a->maxiter = maxiter; a->model = model->dptr(); a->bwd_waves = 1; a->n_launch = d->B;
+    a->x0 = d->x0; a->dt = d->dt; a->tasks = d->tasks; a->state_w = d->state_w; a->x_reg = d->x_reg; a->ctrl_w = d->ctrl_w; a->ws = d->ws; a->active = d->active;
+    a->s_state_w = d->s_state_w; a->s_ctrl_w = d->s_ctrl_w; a->s_x_reg = d->s_x_reg ? d->s_x_reg : kNX; a->sn_state_w = d->sn_state_w; a->sn_x_reg = d->sn_x_reg; a->sn_ctrl_w = d->sn_ctrl_w;
+    if (d->active_list) {      // the pieces of that scratch (ik_types.h::active_list_ints)
+        a->list = d->active_list; a->count = a->list + 2 * (long)a->B; a->wcount = a->count + 2; a->wide = a->wcount + 2;
+        a->err = a->wide + 2 * kWideMax; a->near = a->err + 2; a->xmeta = a->near + 2; a->xlist = a->xmeta + 4;
+    }
+    return BMPC_OK;
 }
-std::atomic<double> g_express_near{1.0};   // the express lane's trigger: |Q_u|^2 below this = "within reach of the stopping threshold"
 
-bunmpc::IkBatchArgs make_args(int B, int T, int maxiter, const bmpc_model *model, const double *x0, const double *dt,
-                              const double *tasks, const double *state_w, long s_sw, const double *x_reg,
-                              const double *ctrl_w, long s_cw, double *ws, int *active) {
-    bunmpc::IkBatchArgs a;
-    a.B = B; a.T = T; a.maxiter = maxiter; a.model = model->dptr();
-    a.x0 = x0; a.dt = dt; a.tasks = tasks; a.state_w = state_w; a.x_reg = x_reg; a.ctrl_w = ctrl_w;
-    a.s_state_w = s_sw; a.s_ctrl_w = s_cw; a.ws = ws; a.active = active;
-    a.s_x_reg = bunmpc::kNX; a.sn_state_w = a.sn_x_reg = a.sn_ctrl_w = 0; a.fwd_spec = 0; a.bwd_waves = 1;
-    a.list = nullptr; a.count = nullptr; a.wide = nullptr; a.wcount = nullptr; a.err = nullptr; a.near = nullptr; a.xmeta = nullptr; a.xlist = nullptr;
-    a.iter = 0; a.n_launch = B; a.near_stop = g_express_near.load();
-    return a;
+// The scheduling knobs (ik_plan.h): ONE store of the process-wide defaults, which the bmpc_ik_set_* entry points update; a batch may
+// carry its own thresholds in bmpc_ik_batch_t.sched.  A DDP loop takes one copy when it starts (resolve_knobs) and reads no global
+// afterwards: a setter called meanwhile (another host thread) changes the next loop, never one that is running.
+std::mutex g_knobs_lock; bunmpc::IkKnobs g_knobs;
+template <class T> T set_knob(T bunmpc::IkKnobs::*field, T value) {      // returns the old setting
+    std::lock_guard<std::mutex> hold(g_knobs_lock);
+    return std::exchange(g_knobs.*field, value);
 }
-
-// the DDP iteration loop (SolverDDP::solve): three launches per iteration, stop when every problem is done
-// below this many active problems the forward pass runs four step lengths of a problem side by side (one wave per
-// problem: 1024 SIMDs on an MI355X)
-// Process-wide DEFAULTS of the scheduling thresholds (the bmpc_ik_set_* entry points); a batch may carry its own in
-// bmpc_ik_batch_t.sched.  A DDP loop reads them once, when it starts: a setter called meanwhile (another host thread) changes
-// the next loop, never one that is running.
-std::atomic<int> g_spec_line_search_below{1024};
-std::atomic<int> g_spec_one_wave_above{0};      // (experiment) above this many active problems the speculative line search runs on ONE wave per problem; 0 = never
-std::atomic<int> g_all_steps{0};  // at most this many active problems: all ten step lengths at once, three workgroups per problem
-                                  // (0 = never, the default: measured on the MI355X it gains < 1 % on the Go2 H = 60 batch at <= 85 -- one workgroup of
-                                  // three waves per CU is the forward kernel's residency -- and loses 2 % on Solo12, EXPERIMENTS.md 9)
-std::atomic<int> g_gains_wave_below{512};   // at most this many active problems: the backward pass gives each a second wave for the gains
-                                  // (two waves per problem on the MI355X's 1024 SIMDs; no effect on results)
-std::atomic<int> g_blocking_waits{1};       // the DDP loop's host waits sleep on an interrupt (hipEventBlockingSync) instead of spinning
-constexpr int kMaxIkCol = 255;    // (T + 1 <= 64 nodes: also the fused kernel and the express lane, whose per-node flags sit in LDS; longer horizons run the four lock-step kernels only)
-constexpr int kMaxFusedCol = 63;
-
-// thresholds of ONE DDP loop: field of bmpc_ik_batch_t.sched (0 = the process default, < 0 = never, n > 0 = n)
-struct Sched { int spec_below, all_steps, gains_wave_below; int debug_inject = 0; int express_cap = 0; int fused_direct = 0; };
-int sched_pick(int field, const std::atomic<int> &dflt) { return field == 0 ? dflt.load() : field < 0 ? 0 : field; }
-std::atomic<int> g_express_cap{96};         // the express lane takes at most this many problems of a batch (0 = no express lane)
-std::atomic<int> g_fused_direct{16};        // batches of at most this many problems run entirely inside the fused kernel (0 = never)
-Sched default_sched() { return Sched{g_spec_line_search_below.load(), g_all_steps.load(), g_gains_wave_below.load(), 0, g_express_cap.load(), g_fused_direct.load()}; }
+// the knobs of one loop: a field of bmpc_ik_batch_t.sched (null: none) of 0 = the process default, < 0 = never, n > 0 = n
+bunmpc::IkKnobs resolve_knobs(const bmpc_ik_sched_t *sched) {
+    bunmpc::IkKnobs k;
+    { std::lock_guard<std::mutex> hold(g_knobs_lock); k = g_knobs; }
+    if (!sched) return k;
+    auto pick = [](int field, int &knob) { if (field != 0) knob = field < 0 ? 0 : field; };
+    pick(sched->spec_below, k.spec_below); pick(sched->all_steps_below, k.all_steps); pick(sched->gains_wave_below, k.gains_wave_below);
+    pick(sched->express_cap, k.express_cap); k.debug_inject = sched->debug_inject;
+    return k;
+}
 
 // Two host-mapped words and events per (device, stream), through which the kernels' active counter reaches the DDP loop.
 // Keyed by the stream, not by the host thread: a stream's publishes are ordered among themselves, so a late publish of one
@@ -248,9 +248,11 @@ int index_check_failed(int code) {
                    " (code " + std::to_string(code) + "); results of this batch are invalid");
 }
 
-int run_ddp(const bunmpc::IkBatchArgs &a0, hipStream_t st, int *iters_run, const Sched sched) {
-    bunmpc::IkBatchArgs a = a0;
-    a.fwd_spec = 0;
+// the DDP iteration loop (SolverDDP::solve): four launches per iteration, stop when every problem is done
+int run_ddp(bunmpc::IkBatchArgs a, hipStream_t st, int *iters_run, const bunmpc::IkKnobs knobs) {
+    using namespace bunmpc;
+    a.near_stop = knobs.express_near;
+    const IkBatchPlan batch = plan_batch(a.B, a.T, a.maxiter, a.list != nullptr, knobs);
     const bool prof = g_profile;
     std::vector<hipEvent_t> pev;
     auto stamp = [&]() -> int {
@@ -272,15 +274,14 @@ int run_ddp(const bunmpc::IkBatchArgs &a0, hipStream_t st, int *iters_run, const
         hipStream_t side; bool armed = false;
         ~SideDrain() { if (armed) (void)hipStreamSynchronize(side); }
     } side_drain{w.side};
-    hipEvent_t *ev = w.evs[g_blocking_waits.load() ? 1 : 0];
-    HIP_TRY(bunmpc::ik_launch_init(a, st));
-    if (sched.debug_inject == 1 && a.list) HIP_TRY(hipMemsetAsync(a.list, 0x7f, sizeof(int), st));      // tests: an entry far out of range
+    hipEvent_t *ev = w.evs[knobs.blocking_waits ? 1 : 0];
+    HIP_TRY(ik_launch_init(a, st));
+    if (knobs.debug_inject == 1 && a.list) HIP_TRY(hipMemsetAsync(a.list, 0x7f, sizeof(int), st));      // tests: an entry far out of range
     // A handful of problems (the single-problem handles of the drop-in classes above all): every one of them gets a CU of its own
     // from the first iteration on -- the whole DDP in ONE launch of the fused kernel, no host look in between.
-    if (a.list && a.B <= sched.fused_direct && a.maxiter > 0 && a.T <= kMaxFusedCol) {
-        a.iter = 0; a.n_launch = a.B;
-        HIP_TRY(bunmpc::ik_launch_fused_tail(a, st));
-        HIP_TRY(bunmpc::ik_launch_publish_active(a, 0, w.dev[0], st, a.B));
+    if (batch.fused_direct) {
+        HIP_TRY(ik_launch_fused(a, batch.fused_grid, false, st));
+        HIP_TRY(ik_launch_publish_active(a, 0, w.dev[0], st, a.B));
         HIP_TRY(hipEventRecord(ev[0], st));
         HIP_TRY(hipEventSynchronize(ev[0]));
         const volatile int *hw = static_cast<volatile int *>(w.host[0]);
@@ -298,45 +299,34 @@ int run_ddp(const bunmpc::IkBatchArgs &a0, hipStream_t st, int *iters_run, const
     // kernels of a finished problem return at once, so an iteration too many costs a few microseconds.  And it looks
     // one chunk late: the next chunk is enqueued BEFORE the host waits for the counter of the one before, so the queue
     // never drains while the host turns around (at the end one chunk of no-op kernels runs out on its own).
-    constexpr int kTailChunk = 3;
     // The express lane (ik_select_kernel / ik_fused_kernel): in front of the early iterations a one-workgroup kernel looks at the
     // batch and -- once, when it finds it converging fast with a thin tail of laggards -- moves the laggards-to-be off the active
     // list; the fused kernel enqueued behind it on the side stream runs them to the end at their own pace, on CUs of their own,
     // while the batch goes on without them.  The decision is the device's (the host would learn of it an iteration late); the
     // host enqueues the pair until a look tells it that the lane has taken its problems, or the window has passed.
-    constexpr int kExpressFirstIter = 2, kExpressLastIter = 12;
-    const int express_cap = a.list && a.B >= 64 && a.T <= kMaxFusedCol ? sched.express_cap : 0;
     bool express_taken = false;
-    int express_enqueued = 0;
-    int active = a.B, it = 0, it_end[2] = {0, 0};
+    int express_enqueued = 0, active = a.B, it = 0, it_end[2] = {0, 0};
     auto enqueue_chunk = [&](int slot) -> int {
-        const int chunk = active <= sched.spec_below ? kTailChunk : 1;
-        a.fwd_spec = active <= sched.all_steps ? 4 : active <= sched.spec_below / 3 ? 3 : active <= sched.spec_below ? 2 : 0;
-        if (a.fwd_spec == 2 && g_spec_one_wave_above.load() > 0 && active > g_spec_one_wave_above.load()) a.fwd_spec = 1;
-        a.bwd_waves = active <= sched.gains_wave_below ? 2 : 1;
-        a.n_launch = active;        // the host's latest look at the counter: an upper bound of the active list's length
-        for (int k = 0; k < chunk && it < a.maxiter; ++k, ++it) {
+        const IkIterPlan plan = plan_iteration(active, a.B, a.T, a.list != nullptr, a.wide != nullptr, knobs);
+        a.fwd_spec = plan.fwd; a.bwd_waves = plan.bwd_waves; a.n_launch = plan.n_launch;      // (n_launch: the host's latest look at the counter)
+        for (int k = 0; k < plan.chunk && it < a.maxiter; ++k, ++it) {
             a.iter = it;
-            if (express_cap > 0 && !express_taken && it >= kExpressFirstIter && it <= kExpressLastIter) {
-                HIP_TRY(bunmpc::ik_launch_select(a, express_cap, sched.debug_inject == 2, st));
+            if (batch.express_cap > 0 && !express_taken && it >= kExpressFirstIter && it <= kExpressLastIter) {
+                HIP_TRY(ik_launch_select(a, batch.express_cap, knobs.debug_inject == 2, st));
                 HIP_TRY(hipEventRecord(w.x_go, st));
                 HIP_TRY(hipStreamWaitEvent(w.side, w.x_go, 0));
                 side_drain.armed = true;
-                HIP_TRY(bunmpc::ik_launch_fused_express(a, express_cap, w.side));
+                HIP_TRY(ik_launch_fused(a, batch.express_grid, true, w.side));
                 HIP_TRY(hipEventRecord(w.x_done, w.side));
                 ++express_enqueued;
             }
-            if (int rc = stamp()) return rc;
-            HIP_TRY(bunmpc::ik_launch_state(a, st));
-            if (int rc = stamp()) return rc;
-            HIP_TRY(bunmpc::ik_launch_calcdiff(a, st));
-            if (int rc = stamp()) return rc;
-            HIP_TRY(bunmpc::ik_launch_backward(a, st));
-            if (int rc = stamp()) return rc;
-            HIP_TRY(bunmpc::ik_launch_forward(a, st));
+            for (const IkLaunch *l : {&plan.state, &plan.calcdiff, &plan.backward, &plan.forward}) {
+                if (int rc = stamp()) return rc;
+                HIP_TRY(ik_launch(*l, a, st));
+            }
             if (int rc = stamp()) return rc;
         }
-        HIP_TRY(bunmpc::ik_launch_publish_active(a, it, w.dev[slot], st));
+        HIP_TRY(ik_launch_publish_active(a, it, w.dev[slot], st));
         HIP_TRY(hipEventRecord(ev[slot], st));
         it_end[slot] = it;
         return BMPC_OK;
@@ -369,7 +359,7 @@ int run_ddp(const bunmpc::IkBatchArgs &a0, hipStream_t st, int *iters_run, const
         // the lane's kernel ends when its last problem has: the caller's stream is ordered behind it, and one more look tells
         // whether it left an error code (or a problem) behind
         HIP_TRY(hipStreamWaitEvent(st, w.x_done, 0));
-        HIP_TRY(bunmpc::ik_launch_publish_active(a, it, w.dev[0], st));
+        HIP_TRY(ik_launch_publish_active(a, it, w.dev[0], st));
         HIP_TRY(hipEventRecord(ev[0], st));
         HIP_TRY(hipEventSynchronize(ev[0]));
         const volatile int *hw = static_cast<volatile int *>(w.host[0]);
@@ -543,15 +533,18 @@ int bmpc_ik_selftest_state_ops(const double *x0, const double *x1, const double 
     HIP_TRY(hipMemcpy(ir, out.d() + 2 * nd + nx, sizeof(double) * nx, hipMemcpyDeviceToHost));
     return BMPC_OK;
 }
-int bmpc_ik_set_all_steps(int n_active) { return g_all_steps.exchange(n_active); }
-int bmpc_ik_set_blocking_waits(int on) { return g_blocking_waits.exchange(on != 0); }
-int bmpc_ik_set_express_capacity(int n) { return g_express_cap.exchange(n); }
-int bmpc_ik_set_fused_direct_max(int n) { return g_fused_direct.exchange(n); }
-double bmpc_ik_set_express_near(double stop) { return g_express_near.exchange(stop); }
+// the process-wide defaults of the scheduling knobs (ik_plan.h); each returns the old setting
+int bmpc_ik_set_speculative_below(int n_active) { return set_knob(&bunmpc::IkKnobs::spec_below, n_active); }
+int bmpc_ik_set_spec_one_wave_above(int n_active) { return set_knob(&bunmpc::IkKnobs::spec_one_wave_above, n_active); }
+int bmpc_ik_set_all_steps(int n_active) { return set_knob(&bunmpc::IkKnobs::all_steps, n_active); }
+int bmpc_ik_set_gains_wave_below(int n_active) { return set_knob(&bunmpc::IkKnobs::gains_wave_below, n_active); }
+int bmpc_ik_set_calcdiff_one_wave_above(int n_pairs) { return set_knob(&bunmpc::IkKnobs::calcdiff_one_wave_above, n_pairs); }
+int bmpc_ik_set_express_capacity(int n) { return set_knob(&bunmpc::IkKnobs::express_cap, n); }
+int bmpc_ik_set_fused_direct_max(int n) { return set_knob(&bunmpc::IkKnobs::fused_direct, n); }
+int bmpc_ik_set_blocking_waits(int on) { return set_knob(&bunmpc::IkKnobs::blocking_waits, int(on != 0)); }
+double bmpc_ik_set_express_near(double stop) { return set_knob(&bunmpc::IkKnobs::express_near, stop); }
 void bmpc_ik_kernel_occupancy(int *out8) { bunmpc::ik_kernel_occupancy(out8); }
 int bmpc_ik_batch_struct_size(void) { return (int)sizeof(bmpc_ik_batch_t); }
-int bmpc_ik_set_speculative_below(int n_active) { return g_spec_line_search_below.exchange(n_active); }
-int bmpc_ik_set_spec_one_wave_above(int n_active) { return g_spec_one_wave_above.exchange(n_active); }
 double bmpc_model_total_mass(const bmpc_model_t *m) { return m ? m->host.total_mass : 0.0; }
 
 // ----------------------------------------------------------- InverseKinematics ----
@@ -698,11 +691,10 @@ int bmpc_ik_optimize(bmpc_ik_t *h, const double *x0) {
     HIP_TRY(h->dactive.ensure(sizeof(int) * (1 + active_list_ints(1))));     // the counter + a one-problem active list (index checks, fused kernel)
     HIP_TRY(hipMemcpy(h->din.p, stage.data(), sizeof(double) * stage.size(), hipMemcpyHostToDevice));
     const double *d = h->din.d();
-    IkBatchArgs a = make_args(1, T, 100, model, d + o_x0, d + o_dt, d + o_tk, d + o_sw, 0, d + o_xr, d + o_cw, 0, h->dws.d(),
-                              static_cast<int *>(h->dactive.p));
-    a.sn_state_w = kNDX; a.sn_x_reg = kNX; a.sn_ctrl_w = kNV;
-    set_list(a, static_cast<int *>(h->dactive.p) + 1);
-    if (int rc = run_ddp(a, nullptr, nullptr, default_sched())) return rc;
+    bmpc_ik_batch_t b{};      // (a zero sched: the process's knobs)
+    b.B = 1; b.n_col = T; b.maxiter = 100; b.model = model; b.x0 = d + o_x0; b.dt = d + o_dt; b.tasks = d + o_tk; b.state_w = d + o_sw; b.x_reg = d + o_xr; b.ctrl_w = d + o_cw;
+    b.sn_state_w = kNDX; b.sn_x_reg = kNX; b.sn_ctrl_w = kNV; b.ws = h->dws.d(); b.active = static_cast<int *>(h->dactive.p); b.active_list = b.active + 1;
+    if (int rc = bmpc_ik_solve_batch_device(&b, nullptr)) return rc;
     h->xs.resize((size_t)nn * kNX); h->us.resize((size_t)T * kNV);
     double scal[16];
     HIP_TRY(hipMemcpy(h->xs.data(), h->dws.d() + L.xs, sizeof(double) * h->xs.size(), hipMemcpyDeviceToHost));
@@ -750,25 +742,10 @@ int bmpc_ik_last_stats(const bmpc_ik_t *h, int *iters, int *status, double *cost
 
 // batch: many independent IK problems, everything on the device
 int bmpc_ik_solve_batch_device(const bmpc_ik_batch_t *d, void *hip_stream) {
-    using namespace bunmpc;
-    if (!d || !d->model) return ik_fail(BMPC_BAD_ARG, "null batch descriptor / model");
-    if (d->B < 0 || d->n_col < 1 || d->maxiter < 1) return ik_fail(BMPC_BAD_ARG, "bad sizes");
-    if (d->n_col > kMaxIkCol) return ik_fail(BMPC_BAD_ARG, "n_col > 255 is not supported");
-    if (!d->x0 || !d->dt || !d->tasks || !d->state_w || !d->x_reg || !d->ctrl_w || !d->ws || !d->active)
-        return ik_fail(BMPC_BAD_ARG, "missing array");
+    bunmpc::IkBatchArgs a;
+    if (int rc = args_from_batch(d, d ? d->maxiter : 0, true, nullptr, &a)) return rc;
     if (d->B == 0) return BMPC_OK;
-    auto *model = const_cast<bmpc_model *>(d->model);
-    if (int rc = model->upload()) return rc;
-    IkBatchArgs a = make_args(d->B, d->n_col, d->maxiter, model, d->x0, d->dt, d->tasks, d->state_w, d->s_state_w, d->x_reg,
-                              d->ctrl_w, d->s_ctrl_w, d->ws, d->active);
-    a.s_x_reg = d->s_x_reg ? d->s_x_reg : kNX;
-    a.sn_state_w = d->sn_state_w; a.sn_x_reg = d->sn_x_reg; a.sn_ctrl_w = d->sn_ctrl_w;
-    if (d->active_list) set_list(a, d->active_list);
-    int iters = 0;
-    const Sched sched{sched_pick(d->sched.spec_below, g_spec_line_search_below), sched_pick(d->sched.all_steps_below, g_all_steps),
-                      sched_pick(d->sched.gains_wave_below, g_gains_wave_below), d->sched.debug_inject, sched_pick(d->sched.express_cap, g_express_cap),
-                      g_fused_direct.load()};
-    int rc = run_ddp(a, static_cast<hipStream_t>(hip_stream), &iters, sched);
+    int iters = 0, rc = run_ddp(a, static_cast<hipStream_t>(hip_stream), &iters, resolve_knobs(&d->sched));
     if (d->iters_run) *d->iters_run = iters;
     return rc;
 }
@@ -784,35 +761,46 @@ int bmpc_ik_centroidal_state_device(const bmpc_model_t *model, const double *x, 
 int bmpc_ik_selftest_passes(const bmpc_ik_batch_t *d, const double *xs, const double *us, int feasible, double xreg, int calcdiff_kernel,
                             int bwd_waves, void *hip_stream) {
     using namespace bunmpc;
-    if (!d || !d->model) return ik_fail(BMPC_BAD_ARG, "null batch descriptor / model");
-    if (d->B < 0 || d->n_col < 1) return ik_fail(BMPC_BAD_ARG, "bad sizes");
-    if (d->n_col > kMaxIkCol) return ik_fail(BMPC_BAD_ARG, "n_col > 255 is not supported");
-    if (!d->x0 || !d->dt || !d->tasks || !d->state_w || !d->x_reg || !d->ctrl_w || !d->ws || !d->active || !xs || !us)
-        return ik_fail(BMPC_BAD_ARG, "missing array");
-    if ((feasible != 0 && feasible != 1) || (calcdiff_kernel != 0 && calcdiff_kernel != 1) || (bwd_waves != 1 && bwd_waves != 2))
-        return ik_fail(BMPC_BAD_ARG, "feasible and calcdiff_kernel must be 0 or 1, bwd_waves 1 or 2");
-    if (!(xreg >= 1e-9 && xreg < 1e9)) return ik_fail(BMPC_BAD_ARG, "xreg outside [1e-9, 1e9)");
+    IkBatchArgs a;
+    const char *bad = (feasible != 0 && feasible != 1) || (calcdiff_kernel != 0 && calcdiff_kernel != 1) || (bwd_waves != 1 && bwd_waves != 2)
+                          ? "feasible and calcdiff_kernel must be 0 or 1, bwd_waves 1 or 2" : !(xreg >= 1e-9 && xreg < 1e9) ? "xreg outside [1e-9, 1e9)" : nullptr;
+    if (int rc = args_from_batch(d, 1, xs && us, bad, &a)) return rc;
     if (d->B == 0) return BMPC_OK;
-    auto *model = const_cast<bmpc_model *>(d->model);
-    if (int rc = model->upload()) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    IkBatchArgs a = make_args(d->B, d->n_col, 1, model, d->x0, d->dt, d->tasks, d->state_w, d->s_state_w, d->x_reg,
-                              d->ctrl_w, d->s_ctrl_w, d->ws, d->active);
-    a.s_x_reg = d->s_x_reg ? d->s_x_reg : kNX;
-    a.sn_state_w = d->sn_state_w; a.sn_x_reg = d->sn_x_reg; a.sn_ctrl_w = d->sn_ctrl_w;
-    if (d->active_list) set_list(a, d->active_list);
-    a.bwd_waves = bwd_waves;
+    IkKnobs knobs = resolve_knobs(nullptr);      // the plan of a first look at the whole batch, with the two kernels under test forced through their knobs
+    knobs.calcdiff_one_wave_above = calcdiff_kernel == 1 ? 0 : INT_MAX;
+    knobs.gains_wave_below = bwd_waves == 2 ? INT_MAX : 0;
+    const IkIterPlan plan = plan_iteration(a.B, a.B, a.T, a.list != nullptr, a.wide != nullptr, knobs);
+    a.bwd_waves = plan.bwd_waves;
     HIP_TRY(ik_launch_init(a, st));
     HIP_TRY(ik_launch_selftest_set(a, xs, us, feasible, xreg, st));
-    HIP_TRY(ik_launch_state(a, st));
-    HIP_TRY(ik_launch_calcdiff(a, st, calcdiff_kernel));
+    HIP_TRY(ik_launch(plan.state, a, st));
+    HIP_TRY(ik_launch(plan.calcdiff, a, st));
     HIP_TRY(ik_launch_selftest_keep_costs(a, st));      // (the Riccati pass overwrites the parked node costs with the gaps)
-    HIP_TRY(ik_launch_backward(a, st));
+    HIP_TRY(ik_launch(plan.backward, a, st));
     HIP_TRY(hipStreamSynchronize(st));
     return BMPC_OK;
 }
-int bmpc_ik_set_calcdiff_one_wave_above(int n_pairs) { return bunmpc::ik_set_calcdiff_one_wave_above(n_pairs); }
 int bmpc_ik_last_calcdiff_kernel(void) { return bunmpc::ik_last_calcdiff_kernel(); }
+// TEST ONLY: plan_batch + plan_iteration (ik_plan.h) of a batch shape under the process's knobs and `sched`; no GPU call
+int bmpc_ik_plan_iteration(int B, int n_col, int maxiter, int has_list, int has_wide, int active, const bmpc_ik_sched_t *sched, bmpc_ik_iter_plan_t *out) {
+    using namespace bunmpc;
+    if (!out) return ik_fail(BMPC_BAD_ARG, "null plan");
+    *out = bmpc_ik_iter_plan_t{};
+    if (B < 1 || n_col < 1 || n_col > kMaxIkCol || maxiter < 1 || active < 1 || active > B) return out->status = ik_fail(BMPC_BAD_ARG, "bad sizes");
+    const IkKnobs knobs = resolve_knobs(sched);
+    const IkBatchPlan b = plan_batch(B, n_col, maxiter, has_list != 0, knobs);
+    const IkIterPlan p = plan_iteration(active, B, n_col, has_list != 0, has_wide != 0, knobs);
+    *out = bmpc_ik_iter_plan_t{BMPC_OK, b.fused_direct, b.express_cap, b.fused_grid, b.express_grid, p.chunk, p.fwd, p.bwd_waves, p.n_launch, {}, {}, {}, {},
+                               kMaxFusedCol, kExpressFirstIter, kExpressLastIter, kTailChunk};
+    const IkLaunch *from[4] = {&p.state, &p.calcdiff, &p.backward, &p.forward};
+    bmpc_ik_planned_launch_t *to[4] = {&out->state, &out->calcdiff, &out->backward, &out->forward};
+    for (int i = 0; i < 4; ++i) {
+        std::strncpy(to[i]->kernel, kIkKernelNames[from[i]->kernel], sizeof(to[i]->kernel) - 1);
+        to[i]->grid = from[i]->grid; to[i]->block = from[i]->block;
+    }
+    return BMPC_OK;
+}
 int bmpc_ik_layout_all(int n_col, long *offsets, int n) {
     const bunmpc::IkLayout L = bunmpc::IkLayout::make(n_col);
     const long all[] = {L.xs, L.us, L.scal, L.K, L.kff, L.fs, L.Lx, L.Lqq, L.xnext, L.Hn, L.Lu, L.Luu, L.A6, L.B6, L.nrs, L.njl, L.ncs, L.total, L.Quuk};
@@ -820,13 +808,8 @@ int bmpc_ik_layout_all(int n_col, long *offsets, int n) {
     for (int i = 0; offsets && i < n && i < have; ++i) offsets[i] = all[i];
     return have;
 }
-void bmpc_ik_layout(int n_col, long *offsets8) {   // xs, us, scal, K, kff, fs, Lx, Lqq offsets for callers that read the workspace
-    const bunmpc::IkLayout L = bunmpc::IkLayout::make(n_col);
-    offsets8[0] = L.xs; offsets8[1] = L.us; offsets8[2] = L.scal; offsets8[3] = L.K; offsets8[4] = L.kff;
-    offsets8[5] = L.fs; offsets8[6] = L.Lx; offsets8[7] = L.Lqq;
-}
+void bmpc_ik_layout(int n_col, long *offsets8) { (void)bmpc_ik_layout_all(n_col, offsets8, 8); }   // xs, us, scal, K, kff, fs, Lx, Lqq: for callers that read the workspace
 
-int bmpc_ik_set_gains_wave_below(int n_active) { return g_gains_wave_below.exchange(n_active); }
 long bmpc_ik_active_list_ints(long B) { return bunmpc::active_list_ints(B); }
 
 void bmpc_ik_layout_trace(int n_col, long *offset, int *iters, int *width) {   // the per-iteration telemetry rows of a problem's workspace

@@ -2260,55 +2260,40 @@ __global__ void kd_fill_refs_kernel(double *tasks, const double *X, double m, in
 
 }  // namespace
 
-hipError_t ik_launch_fill_refs(double *tasks, const double *X, double m, int B, int H, int T, hipStream_t st) {
-    const long n = 9L * B * (T + 1);
-    hipLaunchKernelGGL(kd_fill_refs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tasks, X, m, B, H, T);
+// every launcher below: the kernel on `grid` workgroups of `block` threads, and the launch's own error
+template <class K, class... A> static hipError_t launch(K kernel, long grid, unsigned block, hipStream_t st, A... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(block), 0, st, args...);
     return hipGetLastError();
+}
+hipError_t ik_launch_fill_refs(double *tasks, const double *X, double m, int B, int H, int T, hipStream_t st) {
+    return launch(kd_fill_refs_kernel, (9L * B * (T + 1) + 255) / 256, 256, st, tasks, X, m, B, H, T);
 }
 hipError_t ik_launch_state_ops_selftest(const double *x0, const double *x1, const double *dx, int n, double *dq, double *dr, double *iq, double *ir,
                                         hipStream_t st) {
-    hipLaunchKernelGGL(ik_state_ops_selftest_kernel, dim3((n + 63) / 64), dim3(64), 0, st, x0, x1, dx, n, dq, dr, iq, ir);
-    return hipGetLastError();
+    return launch(ik_state_ops_selftest_kernel, (n + 63) / 64, 64, st, x0, x1, dx, n, dq, dr, iq, ir);
 }
 hipError_t ik_launch_publish_active(const IkBatchArgs &a, int next_iter, int *host_word_dev, hipStream_t st, int n_iters_of) {
     const IkLayout L = IkLayout::make(a.T);
-    hipLaunchKernelGGL(ik_publish_active_kernel, dim3(1), dim3(1), 0, st, a.active, a.err, a.count ? a.count + (next_iter & 1) : nullptr, a.xmeta, host_word_dev,
-                       a.ws, L.total, L.scal, n_iters_of);
-    return hipGetLastError();
+    return launch(ik_publish_active_kernel, 1, 1, st, a.active, a.err, a.count ? a.count + (next_iter & 1) : nullptr, a.xmeta, host_word_dev, a.ws, L.total,
+                  L.scal, n_iters_of);
 }
-hipError_t ik_launch_init(const IkBatchArgs &a, hipStream_t st) {
-    hipLaunchKernelGGL(ik_init_kernel, dim3((a.B + 63) / 64), dim3(64), 0, st, a);
-    return hipGetLastError();
-}
-// launches cover the problems of the active list (a.n_launch, the host's last look at the counter, bounds its length)
-static long launch_problems(const IkBatchArgs &a) { return a.list ? (a.n_launch < a.B ? a.n_launch : a.B) : a.B; }
-hipError_t ik_launch_state(const IkBatchArgs &a, hipStream_t st) {
-    const long n = launch_problems(a) * (a.T + 1);
-    hipLaunchKernelGGL(ik_state_kernel, dim3(2u * (unsigned)((n + 63) / 64)), dim3(64), 0, st, a);      // two workgroups per 64 nodes
-    return hipGetLastError();
-}
-std::atomic<int> g_calcdiff_one_wave_above{1024};     // node pairs per launch above which one wave takes a pair (the two-wave kernel has 1024 pairs resident on an MI355X)
+hipError_t ik_launch_init(const IkBatchArgs &a, hipStream_t st) { return launch(ik_init_kernel, (a.B + 63) / 64, 64, st, a); }
+// one launch of an iteration plan: the plan (ik_plan.h) names the kernel, its grid and its workgroup size
 std::atomic<int> g_calcdiff_last_kernel{-1};          // 0 = ik_calcdiff_kernel, 1 = ik_calcdiff1_kernel (tests assert which one ran)
-int ik_set_calcdiff_one_wave_above(int n_pairs) { return g_calcdiff_one_wave_above.exchange(n_pairs); }
 int ik_last_calcdiff_kernel() { return g_calcdiff_last_kernel.load(); }
-hipError_t ik_launch_calcdiff(const IkBatchArgs &a, hipStream_t st, int kernel) {
-    const long n = launch_problems(a) * ((a.T + 1 + 1) / 2);   // two nodes per workgroup
-    const bool one_wave = kernel < 0 ? n > g_calcdiff_one_wave_above.load() : kernel == 1;
-    if (one_wave) hipLaunchKernelGGL(ik_calcdiff1_kernel, dim3((unsigned)((n + 1) / 2)), dim3(128), 0, st, a);
-    else hipLaunchKernelGGL(ik_calcdiff_kernel, dim3((unsigned)n), dim3(128), 0, st, a);
-    g_calcdiff_last_kernel.store(one_wave ? 1 : 0);
-    return hipGetLastError();
+hipError_t ik_launch(const IkLaunch &l, const IkBatchArgs &a, hipStream_t st) {
+    static void (*const kernels[IK_KERNELS])(const IkBatchArgs) = {ik_state_kernel, ik_calcdiff_kernel, ik_calcdiff1_kernel, ik_backward_kernel<1>,
+                                                                   ik_backward_kernel<2>, ik_forward_kernel<1>, ik_forward_kernel<2>, ik_forward_kernel<3>};
+    if (l.kernel == IK_CALCDIFF || l.kernel == IK_CALCDIFF1) g_calcdiff_last_kernel.store(l.kernel == IK_CALCDIFF1);
+    return launch(kernels[l.kernel], l.grid, l.block, st, a);
 }
 hipError_t ik_launch_selftest_set(const IkBatchArgs &a, const double *xs, const double *us, int feasible, double xreg, hipStream_t st) {
     const long n = (long)a.B * ((long)(a.T + 1) * kNX + (long)a.T * kNV);
-    hipLaunchKernelGGL(ik_selftest_set_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, xs, us, feasible, xreg);
-    return hipGetLastError();
+    return launch(ik_selftest_set_kernel, (n + 255) / 256, 256, st, a, xs, us, feasible, xreg);
 }
 hipError_t ik_launch_selftest_keep_costs(const IkBatchArgs &a, hipStream_t st) {
     static_assert(kNV >= 2, "Quuk (T x kNV doubles) holds T + 1 node costs");
-    const long n = (long)a.B * (a.T + 1);
-    hipLaunchKernelGGL(ik_selftest_keep_costs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
-    return hipGetLastError();
+    return launch(ik_selftest_keep_costs_kernel, ((long)a.B * (a.T + 1) + 255) / 256, 256, st, a);
 }
 // workgroups of each IK kernel one CU holds at once, as the runtime's occupancy query sees them (registers, LDS, wave slots):
 // {calcdiff (two waves per pair), calcdiff1 (one wave per pair), backward<1>, backward<2>, forward<1>, forward<2>, forward<3>, state}
@@ -2323,42 +2308,18 @@ void ik_kernel_occupancy(int *out8) {
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&out8[6], ik_forward_kernel<3>, 192, 0);
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&out8[7], ik_state_kernel, 64, 0);
 }
-hipError_t ik_launch_backward(const IkBatchArgs &a, hipStream_t st) {
-    if (a.bwd_waves == 2) hipLaunchKernelGGL(ik_backward_kernel<2>, dim3((unsigned)launch_problems(a)), dim3(128), 0, st, a);
-    else hipLaunchKernelGGL(ik_backward_kernel<1>, dim3((unsigned)launch_problems(a)), dim3(64), 0, st, a);
-    return hipGetLastError();
-}
-hipError_t ik_launch_forward(const IkBatchArgs &a, hipStream_t st) {
-    const unsigned n = (unsigned)launch_problems(a);
-    if (a.fwd_spec == 4) hipLaunchKernelGGL(ik_forward_kernel<3>, dim3(3 * n), dim3(192), 0, st, a);
-    else if (a.fwd_spec == 3) hipLaunchKernelGGL(ik_forward_kernel<3>, dim3(n + (a.wide ? 2 * kWideMax : 0)), dim3(192), 0, st, a);
-    else if (a.fwd_spec == 2) hipLaunchKernelGGL(ik_forward_kernel<2>, dim3(n + (a.wide ? 2 * kWideMax : 0)), dim3(128), 0, st, a);
-    else if (a.fwd_spec == 1) hipLaunchKernelGGL(ik_forward_kernel<1>, dim3(n), dim3(64), 0, st, a);      // four step lengths of one problem per wave, every role on that wave
-    else hipLaunchKernelGGL(ik_forward_kernel<1>, dim3((n + 3) / 4), dim3(64), 0, st, a);
-    return hipGetLastError();
-}
-// the express lane (a.iter = the iteration about to start): selection on `st`, the fused kernel for what it took on `side`
-hipError_t ik_launch_select(const IkBatchArgs &a, int cap, int force, hipStream_t st) {
-    hipLaunchKernelGGL(ik_select_kernel, dim3(1), dim3(1024), 0, st, a, cap, force);
-    return hipGetLastError();
-}
-hipError_t ik_launch_fused_express(const IkBatchArgs &a, int cap, hipStream_t side) {
-    hipLaunchKernelGGL(ik_fused_kernel, dim3((unsigned)(cap < kExpressMax ? cap : kExpressMax)), dim3(256), 0, side, a, a.xlist, a.xmeta + 1, a.xmeta, a.iter);
-    return hipGetLastError();
-}
-// the tail: every problem still on the active list of iteration a.iter (at most a.n_launch of them) to the end
-hipError_t ik_launch_fused_tail(const IkBatchArgs &a, hipStream_t st) {
-    hipLaunchKernelGGL(ik_fused_kernel, dim3((unsigned)launch_problems(a)), dim3(256), 0, st, a, a.list + (long)(a.iter & 1) * a.B, a.count + (a.iter & 1),
-                       static_cast<const int *>(nullptr), 0);
-    return hipGetLastError();
+// the express lane (a.iter = the iteration about to start): selection on the batch's stream, then the fused kernel for what it took
+// (express, on the side stream); not express: every problem still on the active list of iteration a.iter (at most `grid`), to the end
+hipError_t ik_launch_select(const IkBatchArgs &a, int cap, int force, hipStream_t st) { return launch(ik_select_kernel, 1, 1024, st, a, cap, force); }
+hipError_t ik_launch_fused(const IkBatchArgs &a, unsigned grid, bool express, hipStream_t st) {
+    return express ? launch(ik_fused_kernel, grid, 256, st, a, a.xlist, a.xmeta + 1, a.xmeta, a.iter)
+                   : launch(ik_fused_kernel, grid, 256, st, a, a.list + (long)(a.iter & 1) * a.B, a.count + (a.iter & 1), static_cast<const int *>(nullptr), 0);
 }
 hipError_t ik_launch_centroidal_state(const RobotModelDev *model, const double *x, double *out9, int B, hipStream_t st) {
-    hipLaunchKernelGGL(ik_centroidal_state_kernel, dim3((B + 63) / 64), dim3(64), 0, st, model, x, out9, B);
-    return hipGetLastError();
+    return launch(ik_centroidal_state_kernel, (B + 63) / 64, 64, st, model, x, out9, B);
 }
 hipError_t ik_launch_com_mom(const RobotModelDev *model, const double *xs, double *com, double *mom, int n, hipStream_t st) {
-    hipLaunchKernelGGL(ik_com_mom_kernel, dim3((n + 63) / 64), dim3(64), 0, st, model, xs, com, mom, n);
-    return hipGetLastError();
+    return launch(ik_com_mom_kernel, (n + 63) / 64, 64, st, model, xs, com, mom, n);
 }
 
 }  // namespace bunmpc

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
+#include "ik_plan.h"
 
 namespace bunmpc {
 
@@ -88,14 +89,8 @@ struct IkLayout {
 enum IkScal { S_COST = 0, S_XREG, S_D1, S_D2, S_STOP, S_FEAS, S_WASFEAS, S_DONE, S_ITERS, S_RECALC, S_STATUS, S_NODECOST,
               S_WIDE,       // sticky: a line search of this problem once needed more than the four step lengths of one workgroup
               S_WIDENOW };  // its next forward pass runs as three workgroups (it holds one of the kWideMax places of the wide list)
-// Problems whose line search goes past four step lengths are few and always the same ones (Go2 H = 60, 1024 problems: three
-// problems cause a second round in 76 of the 100 iterations), and a second round costs the whole batch a rollout's latency.
-// Such a problem is flagged (S_WIDE) and from then on gets all ten step lengths at once, on three workgroups.
-constexpr int kWideMax = 32;
-// The express lane (ik_select_kernel / ik_fused_kernel in ik_ddp.hip): at most this many problems leave the batch early
-constexpr int kExpressMax = 256;
 // ints of device scratch behind bmpc_ik_batch_t.active_list: list[2][B], count[2], wide_count[2], wide[2][kWideMax], err[2],
-// near[2], xmeta[4], xlist[kExpressMax]
+// near[2], xmeta[4], xlist[kExpressMax]  (kWideMax, kExpressMax: ik_plan.h)
 inline long active_list_ints(long B) { return 2 * B + 4 + 2 * kWideMax + 2 + 2 + 4 + kExpressMax; }
 // Index checks of the list code (always on: a few scalar compares per workgroup).  A list entry, a list length or an append
 // position outside its range is never used as an index: the kernel records the code in err[0] (first one wins), drops the
@@ -105,9 +100,7 @@ enum IkIndexError { IK_ERR_NONE = 0, IK_ERR_LIST_ENTRY = 1, IK_ERR_LIST_COUNT = 
 
 struct IkBatchArgs {
     int B, T, maxiter;
-    int fwd_spec;              // forward pass: 0 = four problems per wave; 2 / 3 = one problem per workgroup of 2 / 3 waves,
-                               // four step lengths at once (few active problems); 4 = three such workgroups per problem, all
-                               // ten step lengths at once (very few active problems)
+    int fwd_spec;              // forward pass: an IkFwdMap (ik_plan.h), 0 .. 4
     // Active-problem list (or null: every launch covers all B problems, finished ones return at once).  Two ping-pong
     // lists of B problem indices + two counts: DDP iteration k works on list[k & 1][0 .. count[k & 1]) and its forward pass
     // appends the problems that go on to list[(k + 1) & 1].  n_launch (host side, one look behind) bounds count.
@@ -134,26 +127,20 @@ struct IkBatchArgs {
 };
 
 hipError_t ik_launch_init(const IkBatchArgs &a, hipStream_t s);
-hipError_t ik_launch_state(const IkBatchArgs &a, hipStream_t s);      // before every calcdiff
-// kernel: -1 = by the launch's size (more node pairs than ik_set_calcdiff_one_wave_above's bound: one wave per pair), 0 = two waves
-// per pair, 1 = one wave per pair (the per-pass self test forces either)
-hipError_t ik_launch_calcdiff(const IkBatchArgs &a, hipStream_t s, int kernel = -1);
-int ik_set_calcdiff_one_wave_above(int n_pairs);     // returns the old bound
-int ik_last_calcdiff_kernel();                       // which of the two the last ik_launch_calcdiff of this process launched (-1: none yet)
+// one launch of an iteration plan (ik_plan.h: plan_iteration gives the four of a DDP iteration -- state, derivative, Riccati, line search)
+hipError_t ik_launch(const IkLaunch &l, const IkBatchArgs &a, hipStream_t s);
+int ik_last_calcdiff_kernel();      // which derivative kernel the last ik_launch of one in this process was: 0 two waves per pair, 1 one wave (-1: none yet)
 // per-pass self test: the caller's trajectory xs [B][T+1][37], us [B][T][18] and the scalars S_FEAS / S_WASFEAS (0) / S_XREG over
 // what ik_launch_init left in the workspace
 hipError_t ik_launch_selftest_set(const IkBatchArgs &a, const double *xs, const double *us, int feasible, double xreg, hipStream_t s);
 // ... and the node costs (parked in the gap slots until the Riccati pass has summed them) copied to Quuk[0 .. T], between the two passes
 hipError_t ik_launch_selftest_keep_costs(const IkBatchArgs &a, hipStream_t s);
-hipError_t ik_launch_backward(const IkBatchArgs &a, hipStream_t s);
-hipError_t ik_launch_forward(const IkBatchArgs &a, hipStream_t s);
 // host_word_dev[0..3] = *active, index-check code, length of the list iteration next_iter runs over, express lane taken
 // (device alias of four host-mapped ints)
 // n_iters_of > 0: also host word [4] = the most DDP iterations any of the first n_iters_of problems ran (fused-direct path)
 hipError_t ik_launch_publish_active(const IkBatchArgs &a, int next_iter, int *host_word_dev, hipStream_t s, int n_iters_of = 0);
 hipError_t ik_launch_select(const IkBatchArgs &a, int cap, int force, hipStream_t s);   // force: tests (take the lane whatever the batch looks like)
-hipError_t ik_launch_fused_express(const IkBatchArgs &a, int cap, hipStream_t side);
-hipError_t ik_launch_fused_tail(const IkBatchArgs &a, hipStream_t s);
+hipError_t ik_launch_fused(const IkBatchArgs &a, unsigned grid, bool express, hipStream_t s);     // what the express lane took, or the whole active list
 // centroidal state [com, vcom, L] (9) of (q, v): KinoDynMP::optimize's x0 (kino_dyn.cpp:42,86-97)
 hipError_t ik_launch_centroidal_state(const RobotModelDev *model, const double *x, double *out9, int B, hipStream_t s);
 // com (3) and h_g (6) along a state trajectory [B][n][37]  (InverseKinematics::return_opt_com/mom)

@@ -446,6 +446,27 @@ int bmpc_ik_layout_all(int n_col, long *offsets, int n);
  * bmpc_ik_last_calcdiff_kernel: which kernel the last derivative launch of this process was (0 two waves, 1 one wave, -1 none yet). */
 int bmpc_ik_set_calcdiff_one_wave_above(int n_pairs);
 int bmpc_ik_last_calcdiff_kernel(void);
+/* TEST ONLY.  What the DDP loop of a batch of B problems and n_col running nodes would launch at a host look that finds `active`
+ * problems (1 .. B) still iterating, under the process's current bmpc_ik_set_* defaults and `sched` (NULL: none; fields as in
+ * bmpc_ik_batch_t.sched): the loop's own plan functions (bunmpc_amd/csrc/ik_plan.h), which make no GPU call -- this runs on a machine
+ * without one.  has_list / has_wide: the batch has an active_list (both 1) or none (both 0).  Batch level: fused_direct (the whole
+ * solve is one launch of ik_fused_kernel, of fused_grid workgroups; the rest of the plan then does not run), express_cap (what the
+ * express lane may take, 0 = no lane; its ik_fused_kernel has express_grid workgroups).  Look level: chunk (DDP iterations enqueued
+ * before the next look), fwd_map (0 four problems per wave, 1 / 2 / 3 four step lengths at once on one / two / three waves, 4 all ten
+ * on three workgroups), bwd_waves, n_launch, and kernel name, workgroups and workgroup size of the four launches of an iteration.
+ * The constants: the longest horizon of the fused kernel, the iterations in front of which the express lane looks, the chunk length
+ * once the line search is no longer sequential.  status: BMPC_OK, or BMPC_BAD_ARG (also returned) for sizes out of range. */
+typedef struct { char kernel[24]; unsigned grid, block; } bmpc_ik_planned_launch_t;
+typedef struct {
+    int status;
+    int fused_direct, express_cap;
+    unsigned fused_grid, express_grid;
+    int chunk, fwd_map, bwd_waves, n_launch;
+    bmpc_ik_planned_launch_t state, calcdiff, backward, forward;
+    int max_fused_col, express_first_iter, express_last_iter, tail_chunk;
+} bmpc_ik_iter_plan_t;
+int bmpc_ik_plan_iteration(int B, int n_col, int maxiter, int has_list, int has_wide, int active, const bmpc_ik_sched_t *sched,
+                           bmpc_ik_iter_plan_t *out);
 int bmpc_ik_set_profile(int on);            /* returns the old setting */
 void bmpc_ik_last_profile(double *ms5);
 /* [com, vcom, hg.angular] of x = [q, v]: what KinoDynMP::optimize feeds the centroidal solve (kino_dyn.cpp:42,86-97) */

@@ -1,8 +1,8 @@
-"""Is the device code of the centroidal ADMM units the same in two source trees?  Kernel by kernel.
+"""Is the device code of the kernel units (the eight centroidal ADMM units and ik_ddp.hip) the same in two source trees?  Kernel by kernel.
 
-    python tools/device_asm_diff.py PARENT_TREE THIS_TREE [--keep DIR] [--units biconvex_admm_kq.hip ...]
+    python tools/device_asm_diff.py PARENT_TREE THIS_TREE [--keep DIR] [--units biconvex_admm_kq.hip ik_ddp.hip ...]
 
-Each of the eight units is compiled in both trees to gfx950 assembly with the tree's own flags (bunmpc_amd/build.py: FLAGS and
+Each unit (any source of bunmpc_amd/csrc may be named) is compiled in both trees to gfx950 assembly with the tree's own flags (bunmpc_amd/build.py: FLAGS and
 FILE_FLAGS, plus --cuda-device-only -S).  The files are not compared with diff: host templates that move reorder the kernels within a
 file, which renumbers the function index of local labels (.LBB<n>_<m>), and the __hip_cuid_* symbol differs on every compilation.
 Instead every kernel's text -- from its symbol label to its .end_amdhsa_kernel -- and its entry in the metadata note are cut out by
@@ -17,7 +17,7 @@ import sys
 import tempfile
 
 UNITS = ["biconvex_admm.hip", "biconvex_admm_e2.hip", "biconvex_admm_bq.hip", "biconvex_admm_bq_e2.hip", "biconvex_admm_kq.hip", "biconvex_admm_kq_e2.hip",
-         "biconvex_admm_f32.hip", "biconvex_admm_f32_e2.hip"]
+         "biconvex_admm_f32.hip", "biconvex_admm_f32_e2.hip", "ik_ddp.hip"]
 
 
 def build_settings(tree):
