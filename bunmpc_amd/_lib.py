@@ -27,7 +27,7 @@ class Batch(C.Structure):
                                            "bounds", "X_nom", "X_ter")] +
                 [(n, C.c_long) for n in ("sW_X", "sW_X_ter", "sW_F", "sbounds")] +
                 [(n, C.c_void_p) for n in ("Qx", "qx", "lbx", "ubx", "Qf", "qf", "X", "F", "P",
-                                           "L_x", "L_f", "dyn_viol", "hist", "stats", "trace")])
+                                           "L_x", "L_f", "dyn_viol", "hist", "stats", "trace", "cert_phases")])
 
 
 class BandCost(C.Structure):
@@ -101,6 +101,7 @@ _P = C.c_void_p
 
 _SIGS = {
     "bmpc_abi_version": (_I, []),
+    "bmpc_abi_minor_version": (_I, []),
     "bmpc_set_three_per_wave": (_I, [_I]),
     "bmpc_set_work_stealing": (_I, [_I]),
     "bmpc_set_two_waves_per_simd": (_I, [_I]),

@@ -183,14 +183,16 @@ class DeviceBatch:
 
 
 def solve_host(batch, num_iters=10, maxit=150, tol=1e-5, exit_tol=1e-3, beta=1.5, mu=None,
-               warm=None, L_x=None, L_f=None, raw=None, keep_hist=False, precision="f64"):
+               warm=None, L_x=None, L_f=None, raw=None, keep_hist=False, precision="f64", cert_phases=False):
     """numpy in / numpy out through bmpc_biconvex_solve_batch_host (copies in, one launch,
     copies out).  warm = (X, F, P) or None for a cold start.  raw = dict(Qx,qx,lbx,ubx,Qf[,qf])
     switches to the raw cost/bound form; with Qx_blk (1 or B, H + 1, 9, 9) and / or Qf_blk (1 or B, H, 3E, 3E) in it that side's
     cost is block-diagonal per knot (symmetric blocks; a leading dimension of 1: shared by the batch) and its Qx / Qf may be left
     out (bmpc_biconvex_solve_batch_blocks_host).  With Qx_off (1 or B, H, 9) and / or Qf_off (1 or B, H - 1, 3E) in it, Q has the
     weight off[t][i] between component i of knots t and t + 1 beside its diagonal Qx / Qf -- force-rate and momentum-rate costs
-    (bmpc_biconvex_solve_batch_band_host); not together with blocks."""
+    (bmpc_biconvex_solve_batch_band_host); not together with blocks.  cert_phases: also return "cert_phases" (B, 2), the force and
+    motion phases per problem that ran the certified FISTA loop from their first iteration (bmpc_batch_t.cert_phases; -1 where the
+    kernel records none)."""
     B, H, E = batch.B, batch.H, batch.E
     nx, nf = 9 * (H + 1), 3 * E * H
     keep = []
@@ -243,8 +245,12 @@ def solve_host(batch, num_iters=10, maxit=150, tol=1e-5, exit_tol=1e-3, beta=1.5
     trace = np.full((B, max(num_iters, 1), 4), -1, dtype=np.int32) if keep_hist else None
     d.hist = hist.ctypes.data if keep_hist else None
     d.trace = trace.ctypes.data if keep_hist else None
+    certn = np.full((B, 2), -1, dtype=np.int32) if cert_phases else None
+    d.cert_phases = certn.ctypes.data if cert_phases else None
     _launch(d, blocks, band)
     out = dict(X=X, F=F, P=P, L_x=Lx, L_f=Lf, dyn_viol=viol, stats=stats.astype(np.int64))
+    if cert_phases:
+        out["cert_phases"] = certn.astype(np.int64)
     if keep_hist:
         out["hist"] = hist
         out["trace"] = trace.astype(np.int64)

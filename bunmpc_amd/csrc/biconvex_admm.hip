@@ -201,7 +201,7 @@ LaunchPlan plan_launch(const BatchArgs &a, CostShape shape, int n_eff, long simd
         p.latency = true;
         return p;
     }
-    p.certified_steps = diag && kn.certified_steps != 0;
+    p.certified_steps = !diag ? 0 : (kn.certified_steps == 2 ? 2 : (kn.certified_steps != 0 ? 1 : 0));      // (2: force phases only)
     p.kernel = shape == kBlocks ? "biconvex_admm_bq_kernel" : (shape == kBand ? "biconvex_admm_kq_kernel" : (a.precision == 1 ? "biconvex_admm_kernel_f32" : "biconvex_admm_kernel"));
     // the same decisions for two feet as for four, with the LDS record of the foot count (knot_lds)
     auto segments = [&](int lpp) { p.l.lpp = lpp; p.l.w2 = diag && two_per_simd_pays(a, 64 / lpp, simds, kn); return p; };

@@ -347,6 +347,12 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
         }
     }
 
+    // BAND: how many force and motion phases of the problem ran the certified loop from their first iteration (BatchArgs::cert_phases),
+    // counted by lane 0 in two ints of LDS nothing else uses -- the F block of knot H's record (the last knot has no forces) -- once per
+    // phase, in front of its FISTA loop; written out once, behind the last ADMM iteration.
+    [[maybe_unused]] int *const certn = reinterpret_cast<int *>(Sg + kSegLds + (long)H * KL + 18);      // (lane 0's: its record is the segment's first)
+    if constexpr (BAND) { if (l0) { certn[0] = 0; certn[1] = 0; } }
+
     for (int it = 0; STEAL || it < a.c.num_iters; ++it) {
         if (alive == 0) break;
         // contact data of this knot: flags c_n, positions r_n  (centroidal.cpp:39-49); re-read in
@@ -454,6 +460,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                 cert = certify(ok, alive);
                 if (cert) floor2 = cert_floor(b2 + (T / (double)rho) * x2, Lh0, alive);
             }
+            if constexpr (BAND) { if (cert && l0 && lanes(alive)) ++certn[0]; }
             // u = A v + bPk on rows 9t+3..8
             auto applyA = [&](const R (&v)[NF], R (&u)[6]) {
                 R s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0;
@@ -975,11 +982,126 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                 it_x += lanes(act) ? 1 : 0;
                 act &= ~done;
             };
+            if constexpr (BAND) {
+                // The step certificate of a motion phase (tools/certify_rate.py: motion_bound_terms).  M = Q + rho A_f'A_f
+                // couples knot t with t + 1: with dg = diag(M) (lane 0's Q carries the rho of the folded x_init rows), u = |A_f| dg -- row
+                // block t takes dg of knots t and t + 1 -- and v = |A_f|' u -- knot t takes u of row blocks t and t - 1 -- the lane's
+                // rows pass if Q_i dg_i + rho v_i <= T dg_i.  Two wave shifts of nine values per phase; what a shift brings across the
+                // end of a segment is removed by keep_if (a diverged wave-mate's NaNs stay its own), NaN inputs fail the comparison.
+                bool cert = false;
+                double floor2 = 0.0;
+                if (a.certified_steps == 1) {
+                    const double Lh0 = (double)L_x * 0.5, T = Lh0 * (1.0 - kCertEta);
+                    const double ax = fabs((double)SX), ay = fabs((double)SY), az = fabs((double)SZ);
+                    const double cn = (rvalid ? 1.0 : 0.0) + (kvalid && t >= 1 ? 1.0 : 0.0);      // the 1 / -1 of row blocks t and t - 1
+                    double dg[9], dgn[9], u[9], up[9], x2 = 0.0, b2 = 0.0;
+                    const double col[9] = {cn + (ay * ay + az * az), cn + (ax * ax + az * az), cn + (ax * ax + ay * ay),
+                                           cn + (double)dtp * (double)dtp, cn + (double)dtp * (double)dtp, cn + (double)dtp * (double)dtp, cn, cn, cn};
+                    UNROLL for (int l = 0; l < 9; ++l) dg[l] = (double)qd[l] + (double)rho * col[l];
+                    shift_next(dg, dgn);
+                    UNROLL for (int l = 0; l < 9; ++l) { dgn[l] = keep_if(dgn[l], rmask); u[l] = dg[l] + dgn[l]; }
+                    UNROLL for (int k = 0; k < 3; ++k) u[k] += (double)dt * dgn[3 + k];
+                    u[6] += az * dg[1] + ay * dg[2];
+                    u[7] += az * dg[0] + ax * dg[2];
+                    u[8] += ay * dg[0] + ax * dg[1];
+                    UNROLL for (int l = 0; l < 9; ++l) u[l] = keep_if(u[l], rmask);
+                    shift_prev(u, up);
+                    UNROLL for (int l = 0; l < 9; ++l) up[l] = keep_if(up[l], xpm);
+                    double v[9];
+                    UNROLL for (int l = 0; l < 9; ++l) v[l] = u[l] + up[l];
+                    UNROLL for (int k = 0; k < 3; ++k) v[3 + k] += (double)dtp * up[k];
+                    v[0] += az * u[7] + ay * u[8];
+                    v[1] += az * u[6] + ax * u[8];
+                    v[2] += ay * u[6] + ax * u[7];
+                    bool ok = true;
+                    UNROLL for (int l = 0; l < 9; ++l) ok = ok && (double)qd[l] * dg[l] + (double)rho * v[l] <= T * dg[l];
+                    if (kvalid) { UNROLL for (int l = 0; l < 9; ++l) x2 += (double)Xg[l] * (double)Xg[l]; }      // (x_0: the X block)
+                    UNROLL for (int l = 0; l < 9; ++l) b2 += (double)bpk[l] * (double)bpk[l];
+                    cert = certify(ok, alive);
+                    if (cert) floor2 = cert_floor(b2 + (T / (double)rho) * x2, Lh0, alive);
+                }
+                if (cert && l0 && lanes(alive)) ++certn[1];
+                float flo = 0.0f, fhi = 0.0f;
+                if (banded != 0) band_u(floor2, flo, fhi);
+                // one iteration of the certified loop: the tested loop's step, momentum and write-back, operation for operation, without
+                // the image difference, cv and the retry loop around them (bt = 0 whatever the step); a live problem's step below the
+                // floor commits nothing and hands the phase to the tested loop from this iteration (x_k and its image are in LDS: nothing
+                // to move)
+                auto iterate_c = [&](int i) -> bool {
+                    const R cm = (R)cmtab[i];
+                    R xn[9], rn[9], xo[9], ro[9];
+                    mask_t done;
+                    {
+                        R z[9], wp[9];
+                        shift_prev(ry, wp);  // row-block t-1 (0 for t == 0)
+                        UNROLL for (int l = 0; l < 9; ++l) z[l] = ry[l] - wp[l];
+                        UNROLL for (int k = 0; k < 3; ++k) z[3 + k] = fmaR(dtp, wp[k], z[3 + k]);
+                        z[0] += SZ * ry[7] - SY * ry[8];
+                        z[1] += SX * ry[8] - SZ * ry[6];
+                        z[2] += SY * ry[6] - SX * ry[7];
+                        UNROLL for (int l = 0; l < 9; ++l) {
+                            R g = fmaR(rho, z[l], q[l]);
+                            g = fmaR(qd[l], y[l], g);
+                            R v = fmaR(-g, invL, y[l]);
+                            if (l < NB) v = clamp_box(v, lb[l], ub[l]);
+                            xn[l] = v;
+                        }
+                    }
+                    applyA(xn, rn);
+                    R g2 = 0;
+                    UNROLL for (int l = 0; l < 9; ++l) { const R d = xn[l] - y[l]; g2 = fmaR(d, d, g2); }
+                    UNROLL for (int l = 0; l < 9; ++l) { xo[l] = Xz[l]; ro[l] = RXz[l]; }      // (see the force step)
+                    mask_t unclear = ~mask_t(0);
+                    if (banded != 0) {      // the fp32 decisions -- floor and exit -- if every live problem's are clear (see the force step)
+                        float gf = (float)g2;
+                        seg_sum1_f32<LPP>(gf);
+                        const mask_t yes = __ballot(gf < flo), no = __ballot(gf > fhi);
+                        const mask_t dyes = __ballot(gf < t2lo), dno = __ballot(gf > t2hi);
+                        const mask_t clear = (yes | no) & (dyes | dno) & __ballot(gf >= 1e-24f) & __ballot(gf <= 1e30f);
+                        unclear = ~clear & act;
+                        if (unclear == 0) {
+                            if ((yes & act) != 0) return false;
+                            done = dyes;
+                        }
+                    }
+                    if (unclear != 0) {
+                        double g2s = (double)g2;
+                        sum1(g2s);
+                        if ((__ballot(g2s < floor2) & act) != 0) return false;
+                        done = __ballot(g2s < tol2);      // the tested loop's exit rule (see the force loop for the sqrt-free form)
+                        if (__ballot(fabs(g2s - tol2) <= 1e-14 * tol2) != 0) done = __ballot(sqrt(g2s) < tol);
+                    }
+                    UNROLL for (int l = 0; l < 9; ++l) { keep_here(xo[l]); keep_here(ro[l]); }
+                    UNROLL for (int l = 0; l < 9; ++l) {
+                        y[l] = fmaR(cm, xn[l] - xo[l], xn[l]);
+                        ry[l] = fmaR(cm, rn[l] - ro[l], rn[l]);
+                    }
+                    if (lanes(act & kvalid_m)) { UNROLL for (int l = 0; l < 9; ++l) { Xg[l] = xn[l]; Rg[l] = rn[l]; } }
+                    it_x += lanes(act) ? 1 : 0;
+                    act &= ~done;
+                    return true;
+                };
+                int i0 = 0;
+                if (cert) {
+                    for (; i0 < maxit; ++i0) {
+                        if (act == 0) break;
+                        if (!iterate_c(i0)) break;
+                    }
+                }
+                // the tested loop, from the iteration the certified one left undone
+                for (int i = i0; i < maxit; i += 2) {
+                    if (act == 0) break;
+                    iterate(xa, ra, xb, rb, i);
+                    if (i + 1 >= maxit || act == 0) break;
+                    iterate(xb, rb, xa, ra, i + 1);
+                }
+            } else {
             for (int i = 0; i < maxit; i += 2) {
                 if (act == 0) break;
                 iterate(xa, ra, xb, rb, i);
                 if (i + 1 >= maxit || act == 0) break;
                 iterate(xb, rb, xa, ra, i + 1);
+            }
             }
             R fin[9];
             UNROLL for (int l = 0; l < 9; ++l) fin[l] = kvalid ? Xg[l] : R(0);
@@ -1070,6 +1192,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                 int *s = a.stats + (wave0 + sl) * kStats;
                 s[0] = n_admm; s[1] = it_f; s[2] = it_x; s[3] = bt_f; s[4] = bt_x; s[5] = status;
             }
+            if constexpr (BAND) { if (a.cert_phases) { int *o = a.cert_phases + (wave0 + sl) * 2; o[0] = certn[0]; o[1] = certn[1]; } }
         }
     }
 }

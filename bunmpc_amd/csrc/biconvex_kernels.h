@@ -39,7 +39,8 @@ struct BatchArgs {
     int B, H, raw, cold_start;
     int precision;   // 0: fp64 arithmetic; 1: fp32 iterates with fp64 decisions (harness form only)
     int exact_step_decisions;   // (set by the launcher) 1: the kernels with the fp32 shortcut of their step decisions skip it (tests)
-    int certified_steps;        // (set by the launcher) 1: fp64 batch kernels skip the backtracking test in phases whose step is certified
+    int certified_steps;        // (set by the launcher) fp64 batch kernels skip the backtracking test in phases whose step is certified: 1 force and
+                                // motion phases, 2 force phases only, 0 none
     double L0_x, L0_f;
     SolverConsts c;
     const double *cnt_plan, *dt, *x_init;
@@ -51,7 +52,13 @@ struct BatchArgs {
     int *stats;
     int *trace;      // [B][num_iters][4] running totals {it_f, it_x, bt_f, bt_x} after every ADMM iteration, or null
     const double *cmtab;   // (set by the launcher) FISTA's momentum coefficients (t_k - 1) / t_{k+1}, k = 0 .. kMaxFistaIters - 1: a function of k alone
-    int *queue;      // (set by the launcher) the work-stealing kernel's device counter: problems handed out beyond the first per segment
+    // One slot for two pointers that never meet (the kernels' argument block keeps its size): the work-stealing kernel has its counter
+    // here and records no certificate telemetry; every other launch has the caller's telemetry array or null.
+    union {
+        int *queue;          // (set by the launcher) the work-stealing kernel's device counter: problems handed out beyond the first per segment
+        int *cert_phases;    // [B][2] {force phases, motion phases} that ran the certified loop from their first iteration, or null; written
+                             // by the benchmark's instantiation alone (biconvex_admm_body.h: BAND), left as it is by every other kernel
+    };
 };
 
 // Per-knot block-diagonal costs (bmpc_block_cost_t): the knot's symmetric block in place of its diagonal weights, raw form, fp64, one
@@ -125,7 +132,7 @@ struct DispatchKnobs {
     int steal_grid = 0;                // waves of its persistent grid (experiments): 0 = one or two per SIMD
     int latency_max_batch = 1024;      // the one-problem-per-wave kernel up to this many problems
     int exact_step_decisions = 0;      // every step decision from the fp64 sums, in every centroidal kernel (tests)
-    int certified_steps = 1;           // the fp64 batch kernels' per-phase step certificate
+    int certified_steps = 1;           // the fp64 batch kernels' per-phase step certificate: 0 off, 1 on, 2 force phases only
 };
 struct LaunchPlan {
     hipError_t status;       // hipErrorInvalidValue: a shape no kernel is built for
@@ -155,7 +162,7 @@ int set_steal_grid(int waves);                       // waves of the work-steali
 int set_work_stealing(int on);                       // the segment-level work-stealing kernel for num_iters >= 25 (default on); returns the old value
 int biconvex_last_lanes_per_problem();               // of the calling host thread's latest launch: 16 / 21 / 32 / 64, 0 = one problem per wave
 int set_exact_step_decisions(int on);                // every step decision from the fp64 sums, in every centroidal kernel; returns the old value
-int set_certified_steps(int on);                     // the fp64 batch kernels' per-phase step certificate (default on); returns the old value
+int set_certified_steps(int on);                     // the fp64 batch kernels' per-phase step certificate: 0 off, 1 on (default), 2 force phases only; returns the old value
 
 // Lane-exchange self test (DPP shifts and segment sums used by the kernel).
 // out must hold 12*64 doubles.

@@ -62,6 +62,7 @@ bunmpc::BatchArgs to_args(const bmpc_batch_t &d) {
     a.Qx = d.Qx; a.qx = d.qx; a.lbx = d.lbx; a.ubx = d.ubx; a.Qf = d.Qf; a.qf = d.qf;
     a.X = d.X; a.F = d.F; a.P = d.P; a.L_x = d.L_x; a.L_f = d.L_f;
     a.dyn_viol = d.dyn_viol; a.hist = d.hist; a.stats = d.stats; a.trace = d.trace;
+    a.cert_phases = d.cert_phases;
     return a;
 }
 
@@ -185,6 +186,7 @@ struct bmpc_biconvex {
 extern "C" {
 
 int bmpc_abi_version(void) { return 2; }
+int bmpc_abi_minor_version(void) { return 1; }
 int bmpc_batch_struct_size(void) { return (int)sizeof(bmpc_batch_t); }
 int bmpc_set_three_per_wave(int mode) { return bunmpc::set_three_per_wave(mode); }
 int bmpc_set_work_stealing(int on) { return bunmpc::set_work_stealing(on); }
@@ -828,7 +830,7 @@ int solve_batch_host(const bmpc_batch_t *d, bunmpc::CostArgs c) {
     size_t total = 0;
     for (auto &i : ins) total += i.n;
     for (auto &o : outs) total += o.n;
-    DevBuf buf, sbuf, tbuf;
+    DevBuf buf, sbuf, tbuf, cbuf;
     const size_t ntrace = B * (size_t)(d->num_iters > 0 ? d->num_iters : 1) * 4;
     HIP_TRY(buf.ensure(sizeof(double) * total));
     double *p = buf.d();
@@ -850,11 +852,17 @@ int solve_batch_host(const bmpc_batch_t *d, bunmpc::CostArgs c) {
         HIP_TRY(hipMemcpy(tbuf.p, d->trace, sizeof(int) * ntrace, hipMemcpyHostToDevice));
         b.trace = static_cast<int *>(tbuf.p);
     }
+    if (d->cert_phases) {      // kernels that record no certificate telemetry leave the caller's values
+        HIP_TRY(cbuf.ensure(sizeof(int) * 2 * B));
+        HIP_TRY(hipMemcpy(cbuf.p, d->cert_phases, sizeof(int) * 2 * B, hipMemcpyHostToDevice));
+        b.cert_phases = static_cast<int *>(cbuf.p);
+    }
     HIP_TRY(bunmpc::launch_biconvex_admm(to_args(b), c, d->n_eff, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     for (auto &o : outs) HIP_TRY(hipMemcpy(o.host, *o.slot, sizeof(double) * o.n, hipMemcpyDeviceToHost));
     if (d->stats) HIP_TRY(hipMemcpy(d->stats, sbuf.p, sizeof(int) * bunmpc::kStats * B, hipMemcpyDeviceToHost));
     if (d->trace) HIP_TRY(hipMemcpy(d->trace, tbuf.p, sizeof(int) * ntrace, hipMemcpyDeviceToHost));
+    if (d->cert_phases) HIP_TRY(hipMemcpy(d->cert_phases, cbuf.p, sizeof(int) * 2 * B, hipMemcpyDeviceToHost));
     return BMPC_OK;
 }
 }  // namespace

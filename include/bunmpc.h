@@ -28,6 +28,7 @@ extern "C" {
 
 /* library / device ----------------------------------------------------------- */
 int bmpc_abi_version(void);
+int bmpc_abi_minor_version(void);            /* additions within an ABI version: 1 = bmpc_batch_t ends in cert_phases */
 int bmpc_batch_struct_size(void);            /* sizeof(bmpc_batch_t), to catch binding drift  */
 const char *bmpc_last_error(void);           /* thread-local text of the last failure   */
 int bmpc_device_count(int *count);           /* hipGetDeviceCount                        */
@@ -114,6 +115,9 @@ int bmpc_biconvex_set_robot_mass(bmpc_biconvex_t *h, double m);
  *   trace [B][num_iters][4] ints or NULL: running totals {F-step FISTA iterations, X-step FISTA iterations, F-step retries,
  *       X-step retries} after every ADMM iteration that ran (rows of iterations that did not run are not written) -- with hist
  *       the solve's discrete path per ADMM iteration, what the prefix-parity tests compare with the CPU oracle's
+ *   cert_phases [B][2] ints or NULL: per problem, how many force phases and how many motion phases ran the certified FISTA loop
+ *       from their first iteration (bmpc_set_certified_steps).  Written by the two-waves-per-SIMD build of the batch kernel at 32
+ *       lanes per problem, four feet, harness form (the benchmark's kernel); every other kernel leaves the array as it is.
  *   A caller built against an older header must zero-initialise the whole struct (bmpc_batch_defaults does) and check
  *   bmpc_batch_struct_size() == sizeof(bmpc_batch_t).
  *   Shapes: n_eff in {2, 4}; n_col + 1 <= 256 knots (up to 64: 4 / 3 / 2 / 1 problems per wave, fp64 or fp32 iterates; 65 .. 256: one
@@ -140,6 +144,7 @@ typedef struct {
     double *dyn_viol, *hist;
     int *stats;
     int *trace;       /* ABI version 2 */
+    int *cert_phases; /* ABI version 2, minor version 1 */
 } bmpc_batch_t;
 
 /* reference defaults: rho 1e5 (biconvex.hpp:148), mu 1, beta 1.5, tol 1e-5, exit_tol 1e-3,
@@ -189,8 +194,10 @@ int bmpc_biconvex_last_waves_per_simd(void);
 int bmpc_set_exact_step_decisions(int on);
 /* The fp64 batch kernels skip FISTA's backtracking test for a whole force step (one ADMM iteration's force-QP loop) of a wave whose
  * live problems all carry a certificate that the test cannot fire: a diagonally scaled Gershgorin bound of the step's Hessian
- * below (L/2)(1 - 2^-6).  on = 0: every step is tested (a test switch: results must be
- * bit-identical either way).  Default 1.  Returns the old value. */
+ * below (L/2)(1 - 2^-6).  The benchmark's kernel (two waves per SIMD, 32 lanes per problem, four feet, harness
+ * form) does the same for the motion step, whose bound couples neighbouring knots.  on = 0: every step is tested; 1 (default): both
+ * steps where a kernel has them; 2: the force step only (test switches: results must be bit-identical whatever the value).
+ * Returns the old value. */
 int bmpc_set_certified_steps(int on);
 /* Scratch (private-segment) bytes per lane of the fp32 kernels as the loaded code object reports them, -1 on error.  0 is what
  * the build is set up for (bunmpc_amd/build.py: their translation unit is compiled without the SLP vectoriser); a compiler that

@@ -1,6 +1,7 @@
 """How often the centroidal kernel's per-phase step certificate holds (biconvex_admm_body.h: `cert`).
-The kernel applies it to the force step; the motion step's bound is restated here as a measurement (DESIGN.md says why the kernel
-does not use it yet).
+Every fp64 batch kernel applies it to the force step; the benchmark's kernel (two waves per SIMD, 32 lanes per problem, four feet,
+harness form) applies the motion step's bound too (biconvex_admm_body.h: BAND).  `phase_predictions` says, phase by phase, what the
+kernel's certificate decides -- tests/test_certified_motion_gpu.py holds the kernel's telemetry to it.
 
 FISTA's backtracking test retries a step iff d'(Q + rho A'A) d > (L/2)|d|^2.  Where a diagonally scaled Gershgorin bound of
 M = Q + rho A'A is below (L/2)(1 - eta), no d can make it retry, so the kernel runs that phase's FISTA loop without the test.  This
@@ -97,6 +98,53 @@ def certified(lhs, dg, L, eta=ETA):
     """per problem: every lane's test lhs_i <= (L/2)(1 - eta) dg_i"""
     T = (np.asarray(L, np.float64) * 0.5 * (1.0 - eta)).reshape(-1, *([1] * (lhs.ndim - 1)))
     return np.all(lhs <= T * dg, axis=tuple(range(1, lhs.ndim)))
+
+
+def threshold_gap(lhs, dg, L, eta=ETA):
+    """per problem: how close the nearest lane test lhs_i <= (L/2)(1 - eta) dg_i is to flipping, |lhs_i / (T dg_i) - 1| (lanes with dg_i = 0
+    test 0 <= 0 and cannot flip)"""
+    T = (np.asarray(L, np.float64) * 0.5 * (1.0 - eta)).reshape(-1, *([1] * (lhs.ndim - 1)))
+    rhs = T * dg
+    with np.errstate(divide="ignore", invalid="ignore"):
+        gap = np.where(rhs != 0.0, np.abs(lhs / rhs - 1.0), np.inf)
+    return gap.reshape(lhs.shape[0], -1).min(1)
+
+
+def phase_predictions(batch, oracle_c, num_iters, warm=None, L_x=2.25e6, L_f=506.25):
+    """What the certificates decide in every phase of a solve, from the strict CPU oracle's states at the ADMM boundaries: the force
+    phase of ADMM iteration k sees X and L_f after k iterations, its motion phase F after k + 1 and L_x after k.  Returns
+    force, motion [B][num_iters] bool (the problem's own lanes pass), force_gap, motion_gap [B][num_iters] (threshold_gap) and
+    ran [B][num_iters] bool (the problem was still iterating)."""
+    Qx, W_F = _costs(batch)
+    B = batch.B
+    X0, F0, P0 = batch.warm_start() if warm is None else warm
+    st = [dict(X=np.asarray(X0, np.float64).reshape(B, -1), F=np.asarray(F0, np.float64).reshape(B, -1),
+               L_x=np.broadcast_to(np.asarray(L_x, np.float64), (B,)), L_f=np.broadcast_to(np.asarray(L_f, np.float64), (B,)), n=np.zeros(B, int))]
+    for k in range(1, num_iters + 1):
+        o = oracle_c.solve_batch(batch, num_iters=k, warm=(X0, F0, P0), L_x=L_x, L_f=L_f)
+        st.append(dict(X=o["X"], F=o["F"], L_x=o["L_x"], L_f=o["L_f"], n=o["stats"][:, 0]))
+    out = {k: np.zeros((B, num_iters), bool) for k in ("force", "motion", "ran")}
+    out.update({k: np.zeros((B, num_iters)) for k in ("force_gap", "motion_gap")})
+    for k in range(num_iters):
+        lf, df = force_bound_terms(batch.cnt_plan, batch.dt, batch.m, st[k]["X"], W_F, batch.rho)
+        lm, dm = motion_bound_terms(batch.cnt_plan, batch.dt, st[k + 1]["F"], Qx, batch.rho)
+        out["force"][:, k], out["force_gap"][:, k] = certified(lf, df, st[k]["L_f"]), threshold_gap(lf, df, st[k]["L_f"])
+        out["motion"][:, k], out["motion_gap"][:, k] = certified(lm, dm, st[k]["L_x"]), threshold_gap(lm, dm, st[k]["L_x"])
+        out["ran"][:, k] = st[k + 1]["n"] > k
+    return out
+
+
+def wave_phases(pred, which, per_wave=2, near=1e-9):
+    """The kernel's decision per problem and phase: a wave runs the certified loop if every problem of it that still iterates passes, so
+    a failing problem takes its wave-mates' phase with it.  Returns (certified, usable) [B][num_iters]: usable is False where the
+    problem did not run the phase or a running problem of the wave lies within `near` (relative) of its threshold."""
+    ok, gap, ran = pred[which], pred[which + "_gap"], pred["ran"]
+    cert, usable = np.zeros_like(ok), np.zeros_like(ok)
+    for w in range(0, ok.shape[0], per_wave):
+        s = slice(w, w + per_wave)
+        cert[s] = np.all(ok[s] | ~ran[s], axis=0) & ran[s]
+        usable[s] = np.all((gap[s] > near) | ~ran[s], axis=0) & ran[s]
+    return cert, usable
 
 
 def _costs(batch):
