@@ -40,6 +40,11 @@ class BlockCost(C.Structure):
     _fields_ = [("Qx_blk", C.c_void_p), ("sQx_blk", C.c_long), ("Qf_blk", C.c_void_p), ("sQf_blk", C.c_long)]
 
 
+class Cone(C.Structure):
+    """bmpc_cone_t"""
+    _fields_ = [("projection", C.c_int), ("mu", C.c_void_p), ("smu", C.c_long)]
+
+
 class LaunchPlan(C.Structure):
     """bmpc_launch_plan_t"""
     _fields_ = [("status", C.c_int), ("lanes_per_problem", C.c_int), ("waves_per_simd", C.c_int), ("steal", C.c_int), ("steal_waves", C.c_long),
@@ -178,6 +183,12 @@ _SIGS = {
     "bmpc_biconvex_set_cost_x_band": (_I, [_P, _P, _P, _P]),
     "bmpc_biconvex_set_cost_f_band": (_I, [_P, _P, _P, _P]),
     "bmpc_biconvex_band_kernel_scratch_bytes": (_I, [_I]),
+    "bmpc_cone_struct_size": (_I, []),
+    "bmpc_biconvex_solve_batch_cone_device": (_I, [_P, _P, _P]),
+    "bmpc_biconvex_solve_batch_cone_host": (_I, [_P, _P]),
+    "bmpc_biconvex_set_cone_projection": (_I, [_P, _I]),
+    "bmpc_biconvex_set_friction_coefficients": (_I, [_P, _P]),
+    "bmpc_biconvex_cone_kernel_scratch_bytes": (_I, [_I]),
     "bmpc_biconvex_kernel_name": (C.c_char_p, [_I, _I]),
     "bmpc_biconvex_last_kernel_name": (C.c_char_p, []),
     "bmpc_biconvex_plan_launch": (_I, [_P, _I, C.c_long, _P]),
@@ -318,6 +329,8 @@ def lib():
             raise ImportError("bmpc_block_cost_t layout differs between include/bunmpc.h and bunmpc_amd/_lib.py")
         if handle.bmpc_band_cost_struct_size() != C.sizeof(BandCost):
             raise ImportError("bmpc_band_cost_t layout differs between include/bunmpc.h and bunmpc_amd/_lib.py")
+        if handle.bmpc_cone_struct_size() != C.sizeof(Cone):
+            raise ImportError("bmpc_cone_t layout differs between include/bunmpc.h and bunmpc_amd/_lib.py")
         if handle.bmpc_ik_batch_struct_size() != C.sizeof(IkBatch):
             raise ImportError("bmpc_ik_batch_t layout differs between include/bunmpc.h and bunmpc_amd/_lib.py")
         _lib = handle

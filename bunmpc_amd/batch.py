@@ -45,10 +45,35 @@ def _cost_ext(kind, B, H, E, x, f, put):
     return c if getattr(c, "Qx_" + kind) or getattr(c, "Qf_" + kind) else None
 
 
-def _launch(desc, blocks, band, stream=None):
+PROJECTIONS = {"reference": 0, "euclidean": 1}
+
+
+def _cone_ext(cone, B, H, E, put):
+    """bmpc_cone_t of cone = dict(projection="reference" | "euclidean", mu=None | array (1 or B, H, E)); put(array) -> its address after
+    whatever copy the caller needs (its result is kept by the caller).  None without a dict."""
+    if cone is None:
+        return None
+    unknown = set(cone) - {"projection", "mu"}
+    if unknown or cone.get("projection", "reference") not in PROJECTIONS:
+        raise ValueError("cone: expected dict(projection=\"reference\" | \"euclidean\", mu=None | array), got %r" % (cone,))
+    c = _lib.Cone(projection=PROJECTIONS[cone.get("projection", "reference")])
+    mu = cone.get("mu")
+    if mu is not None:
+        if np.shape(mu)[1:] != (H, E) or np.shape(mu)[0] not in (1, B):
+            raise ValueError("cone mu: expected shape (1 or %d, %d, %d), got %s" % (B, H, E, np.shape(mu)))
+        c.mu = put(mu)
+        c.smu = 0 if np.shape(mu)[0] == 1 else H * E
+    return c
+
+
+def _launch(desc, blocks, band, stream=None, cone=None):
     """the solve call of the batch's cost shape: on `stream` with device arrays, or (None) the host call"""
     lib, where = _lib.lib(), "host" if stream is None else "device"
     tail = () if stream is None else (C.c_void_p(stream),)
+    if cone is not None:
+        if blocks is not None or band is not None:
+            raise ValueError("cone= cannot be combined with Qx_blk / Qf_blk or Qx_off / Qf_off: the cone kernels hold diagonal costs only")
+        return _lib.check(getattr(lib, "bmpc_biconvex_solve_batch_cone_" + where)(C.byref(desc), C.byref(cone), *tail))
     for kind, cost in (("blocks_", blocks), ("band_", band)):
         if cost is not None:
             return _lib.check(getattr(lib, "bmpc_biconvex_solve_batch_" + kind + where)(C.byref(desc), C.byref(cost), *tail))
@@ -69,12 +94,14 @@ class DeviceBatch:
     create_cost_F / create_bound_constraints itself) or, with raw=, the raw form."""
 
     def __init__(self, batch, device="cuda", num_iters=10, maxit=150, tol=1e-5, exit_tol=1e-3,
-                 beta=1.5, mu=None, keep_hist=False, precision="f64", plan=None, raw=None):
+                 beta=1.5, mu=None, keep_hist=False, precision="f64", plan=None, raw=None, cone=None):
         """plan: a plan_batch.DevicePlan whose tensors (cnt_plan, dt, X_nom, X_ter, x_init) are used in place of the
         batch's host arrays -- inputs built on the GPU never leave HBM.
         raw: dict(Qx, qx, lbx, ubx, Qf[, qf][, Qx_blk][, Qf_blk]) -- the raw cost / bound form (solve_host explains it); with
         Qx_blk / Qf_blk the per-knot block costs, through bmpc_biconvex_solve_batch_blocks_device; with Qx_off / Qf_off the costs
-        between neighbouring knots, through bmpc_biconvex_solve_batch_band_device"""
+        between neighbouring knots, through bmpc_biconvex_solve_batch_band_device
+        cone: dict(projection="reference" | "euclidean", mu=None | array (1 or B, H, E)) -- the force step's projection and per-foot
+        friction coefficients, through bmpc_biconvex_solve_batch_cone_device (solve_host explains it)"""
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("DeviceBatch needs a GPU: no CPU fallback exists for the solve")
@@ -111,6 +138,11 @@ class DeviceBatch:
             if self.tb and self.tk:
                 raise ValueError(_COMBINED)
             self.band = _cost_ext("off", B, H, E, self.tk.get("Qx_off"), self.tk.get("Qf_off"), lambda t: t.data_ptr())
+
+        def up_mu(a):
+            self.t_mu = up(a)
+            return self.t_mu.data_ptr()
+        self.cone = _cone_ext(cone, B, H, E, up_mu)
         self.X = torch.empty((B, 9 * (H + 1)), dtype=f64, device=self.device)
         self.F = torch.empty((B, 3 * E * H), dtype=f64, device=self.device)
         self.P = torch.empty((B, 9 * (H + 1)), dtype=f64, device=self.device)
@@ -169,7 +201,7 @@ class DeviceBatch:
         if self.hist is not None:      # rows of ADMM iterations that do not run keep their NaN / -1
             self.hist.fill_(float("nan"))
             self.trace.fill_(-1)
-        _launch(self.desc, self.blocks, self.band, stream)
+        _launch(self.desc, self.blocks, self.band, stream, cone=self.cone)
 
     def results(self):
         self.torch.cuda.synchronize(self.device)
@@ -183,7 +215,7 @@ class DeviceBatch:
 
 
 def solve_host(batch, num_iters=10, maxit=150, tol=1e-5, exit_tol=1e-3, beta=1.5, mu=None,
-               warm=None, L_x=None, L_f=None, raw=None, keep_hist=False, precision="f64", cert_phases=False):
+               warm=None, L_x=None, L_f=None, raw=None, keep_hist=False, precision="f64", cert_phases=False, cone=None):
     """numpy in / numpy out through bmpc_biconvex_solve_batch_host (copies in, one launch,
     copies out).  warm = (X, F, P) or None for a cold start.  raw = dict(Qx,qx,lbx,ubx,Qf[,qf])
     switches to the raw cost/bound form; with Qx_blk (1 or B, H + 1, 9, 9) and / or Qf_blk (1 or B, H, 3E, 3E) in it that side's
@@ -192,7 +224,10 @@ def solve_host(batch, num_iters=10, maxit=150, tol=1e-5, exit_tol=1e-3, beta=1.5
     weight off[t][i] between component i of knots t and t + 1 beside its diagonal Qx / Qf -- force-rate and momentum-rate costs
     (bmpc_biconvex_solve_batch_band_host); not together with blocks.  cert_phases: also return "cert_phases" (B, 2), the force and
     motion phases per problem that ran the certified FISTA loop from their first iteration (bmpc_batch_t.cert_phases; -1 where the
-    kernel records none)."""
+    kernel records none).  cone = dict(projection="euclidean", mu=None | array (1 or B, H, E)): the force step projects onto the
+    friction cone |f_xy| <= mu f_z (the nearest point; the default, "reference", is the reference's "SoC" step) with a coefficient per
+    problem, knot and foot (a leading dimension of 1: shared by the batch; None: the scalar mu) -- either form, fp64, H + 1 <= 64, not
+    together with blocks or band costs (bmpc_biconvex_solve_batch_cone_host)."""
     B, H, E = batch.B, batch.H, batch.E
     nx, nf = 9 * (H + 1), 3 * E * H
     keep = []
@@ -247,7 +282,7 @@ def solve_host(batch, num_iters=10, maxit=150, tol=1e-5, exit_tol=1e-3, beta=1.5
     d.trace = trace.ctypes.data if keep_hist else None
     certn = np.full((B, 2), -1, dtype=np.int32) if cert_phases else None
     d.cert_phases = certn.ctypes.data if cert_phases else None
-    _launch(d, blocks, band)
+    _launch(d, blocks, band, cone=_cone_ext(cone, B, H, E, lambda a: f64(a).ctypes.data))
     out = dict(X=X, F=F, P=P, L_x=Lx, L_f=Lf, dyn_viol=viol, stats=stats.astype(np.int64))
     if cert_phases:
         out["cert_phases"] = certn.astype(np.int64)

@@ -230,6 +230,27 @@ class BiconvexMP:
     def set_friction_coefficient(self, mu):
         _lib.check(self._lib.bmpc_biconvex_set_friction_coefficient(self._h, float(mu)))
 
+    def set_cone_projection(self, projection):
+        """"reference" (default: the reference's "SoC" step) or "euclidean" (the nearest point of the friction cone |f_xy| <= mu f_z);
+        persists across optimize calls.  Euclidean: diagonal costs, n_col + 1 <= 64 -- optimize refuses otherwise."""
+        from .batch import PROJECTIONS
+        if projection not in PROJECTIONS:
+            raise ValueError("projection must be \"reference\" or \"euclidean\", got %r" % (projection,))
+        _lib.check(self._lib.bmpc_biconvex_set_cone_projection(self._h, PROJECTIONS[projection]))
+
+    def set_friction_coefficients(self, mu):
+        """A scalar (set_friction_coefficient, and no per-foot array), one coefficient per foot (n_eff,) or per knot and foot
+        (n_col, n_eff); arrays need set_cone_projection("euclidean") and persist across optimize calls."""
+        mu = np.asarray(mu, dtype=np.float64)
+        if mu.ndim == 0:
+            _lib.check(self._lib.bmpc_biconvex_set_friction_coefficients(self._h, None))
+            self.set_friction_coefficient(float(mu))
+            return
+        if mu.shape not in ((self.n_eff,), (self.n_col, self.n_eff)):
+            raise ValueError("mu: expected a scalar, (%d,) or (%d, %d), got %s" % (self.n_eff, self.n_col, self.n_eff, mu.shape))
+        mu = np.ascontiguousarray(np.broadcast_to(mu, (self.n_col, self.n_eff)))
+        _lib.check(self._lib.bmpc_biconvex_set_friction_coefficients(self._h, mu.ctypes.data))
+
     def set_robot_mass(self, m):
         _lib.check(self._lib.bmpc_biconvex_set_robot_mass(self._h, float(m)))
 

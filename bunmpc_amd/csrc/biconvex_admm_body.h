@@ -66,8 +66,20 @@ constexpr int sym_index(int n, int r, int c) { return r <= c ? r * n - r * (r - 
 // code's own term, so zero weights follow the diagonal kernel's path.  No step certificate (W + rho A_x'A_x is no longer block-diagonal
 // per knot) and no fp32 step decisions.  Every KQ operation is under `if constexpr` (its few declarations beside them are dead in the
 // other instantiations): those compile to the instructions they compiled to without it.
-template <typename R, int LPP, int E, bool RAW, bool HASQF, bool STEAL = false, bool XLDS = false, int WAVES = 1, bool BQ = false, bool KQ = false>
-__device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &bq = BlockArgs{}, const BandArgs &kq = BandArgs{}) {
+//
+// CONE (the Euclidean projection onto the friction cone |f_xy| <= mu f_z, per-foot coefficients: both forms, fp64, one wave per SIMD,
+// diagonal costs): the force step's projection is the nearest point of the cone instead of the reference's "SoC" step -- with
+// s2 = fx^2 + fy^2: the origin for a step in the polar cone (fz <= 0, mu^2 s2 <= fz^2), the step itself inside the cone (fz >= 0,
+// s2 <= mu^2 fz^2), otherwise t = (mu s + fz) / (mu^2 + 1) along the axis and mu t along f_xy.  The two tests are on squared
+// quantities; the square root and the divisions are behind the wave-uniform ballot the reference's cone branch sits behind.  A lane
+// loads its knot's coefficients mu[t][0 .. E) once per solve (ConeArgs; without an array every foot has SolverConsts::mu) and keeps
+// them in registers.  No step certificate and no fp32 step decisions: every step is tested on the fp64 sums, as with BQ and KQ.  Every
+// CONE operation is under `if constexpr`: the other instantiations compile what they compiled without it.
+// (A CONE instantiation has no band costs, and its coefficients come in the band costs' place: a fourth argument, even an empty
+// struct, is one more temporary in every kernel and reordered the block kernels' prologues.)
+template <typename R, int LPP, int E, bool RAW, bool HASQF, bool STEAL = false, bool XLDS = false, int WAVES = 1, bool BQ = false, bool KQ = false, bool CONE = false>
+__device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &bq = BlockArgs{}, const std::conditional_t<CONE, ConeArgs, BandArgs> &kq = std::conditional_t<CONE, ConeArgs, BandArgs>{}) {
+    static_assert(!CONE || (!BQ && !KQ && !STEAL && !XLDS && WAVES == 1 && LPP <= 64 && sizeof(R) == sizeof(double)), "Euclidean cone projection: diagonal costs, fp64, one problem per <= 64 lanes, one wave per SIMD");
     static_assert(!BQ || (RAW && !STEAL && !XLDS && WAVES == 1 && sizeof(R) == sizeof(double)), "block costs: raw form, fp64, one wave per problem, one wave per SIMD");
     static_assert(!KQ || (RAW && !BQ && !STEAL && !XLDS && WAVES == 1 && sizeof(R) == sizeof(double)), "neighbour-knot costs: raw form, diagonal per-knot weights, fp64, one wave per problem, one wave per SIMD");
     constexpr bool MW = WAVES > 1;
@@ -163,7 +175,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
     // The step certificate of a force phase: every lane of every live problem found its scaled Gershgorin row test
     // (`ok`) true -- then no step of the phase's FISTA loop can fail the backtracking test, and the loop runs without it.  Wave-
     // (MW: workgroup-) uniform.
-    constexpr bool CAN_CERT = sizeof(R) == sizeof(double) && !BQ && !KQ;      // (BQ, KQ: the rows below assume a diagonal W; fp32: the image noise does make the test fire, see the force step)
+    constexpr bool CAN_CERT = sizeof(R) == sizeof(double) && !BQ && !KQ && !CONE;      // (BQ, KQ: the rows below assume a diagonal W; CONE: every step tested; fp32: the image noise does make the test fire, see the force step)
     auto certify = [&](bool ok, mask_t live) -> bool {
         if (!CAN_CERT || !a.certified_steps) return false;
         if (!MW) return (__ballot(!ok) & live) == 0;
@@ -344,6 +356,19 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                 UNROLL for (int l = 0; l < 9; ++l) Pg[l] = (R)at(Pu, oX)[l];
             }
             if (l0) { UNROLL for (int l = 0; l < 9; ++l) PIg[l] = (R)at(Pu, oPI)[l]; }
+        }
+    }
+
+    // CONE: the friction coefficients of this lane's knot, one per foot, for the whole solve (lanes without a force knot: 1, their
+    // forces are zero and stay zero)
+    [[maybe_unused]] R muf[CONE ? E : 1];
+    if constexpr (CONE) {
+        const auto &cn = kq;      // (ConeArgs: see the signature)
+        if (cn.mu) {
+            const unsigned oM = 8u * (sl * (unsigned)cn.smu + (unsigned)E * tr);
+            UNROLL for (int n = 0; n < E; ++n) { const double v = at(cn.mu + wave0 * cn.smu, oM)[n]; muf[n] = rvalid ? (R)v : R(1); }
+        } else {
+            UNROLL for (int n = 0; n < E; ++n) muf[n] = mu;
         }
     }
 
@@ -546,13 +571,40 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                         fr[3 * n + 2] = fmaR(-gz, invL, y[3 * n + 2]);
                         const R s = fmaR(fr[3 * n], fr[3 * n], fr[3 * n + 1] * fr[3 * n + 1]);
                         const R fz = fr[3 * n + 2];
+                        if constexpr (CONE) {      // the Euclidean projection: origin, unchanged, or (below) the cone's surface
+                            const R m2 = muf[n] * muf[n], z2 = fz * fz;
+                            const bool zero = fz <= R(0) && m2 * s <= z2;      // (the polar cone; wins at the origin)
+                            const bool inside = fz >= R(0) && s <= m2 * z2;
+                            anycone |= __ballot(!zero && !inside);
+                            const R keep = zero ? R(0) : R(1);
+                            xn[3 * n] = keep * fr[3 * n];
+                            xn[3 * n + 1] = keep * fr[3 * n + 1];
+                            xn[3 * n + 2] = keep * fz;
+                        } else {
                         const bool zero = (s * mu < -fz) || (fz < 0);
                         anycone |= __ballot(!zero && (s > mu * fz));
                         const R keep = zero ? R(0) : R(1);
                         xn[3 * n] = keep * fr[3 * n];
                         xn[3 * n + 1] = keep * fr[3 * n + 1];
                         xn[3 * n + 2] = keep * fz;
+                        }
                     }
+                    if constexpr (CONE) {
+                        if (anycone != 0) {   // a force outside both cones: onto the surface; skipped while no lane needs it
+                            UNROLL for (int n = 0; n < E; ++n) {
+                                const R s2 = fmaR(fr[3 * n], fr[3 * n], fr[3 * n + 1] * fr[3 * n + 1]);
+                                const R fz = fr[3 * n + 2], mf = muf[n];
+                                const R m2 = mf * mf, z2 = fz * fz;
+                                const bool surf = !(fz <= R(0) && m2 * s2 <= z2) && !(fz >= R(0) && s2 <= m2 * z2);
+                                const R s = sqrt(s2);
+                                const R tz = fast_div(fmaR(mf, s, fz), m2 + R(1));
+                                const R k = fast_div(mf * tz, s);      // (s > 0 on this branch: s2 = 0 is the origin or inside)
+                                xn[3 * n] = surf ? fr[3 * n] * k : xn[3 * n];
+                                xn[3 * n + 1] = surf ? fr[3 * n + 1] * k : xn[3 * n + 1];
+                                xn[3 * n + 2] = surf ? tz : xn[3 * n + 2];
+                            }
+                        }
+                    } else
                     if (anycone != 0) {   // cone branch (fista.cpp:64-68); skipped while no lane needs it
                         UNROLL for (int n = 0; n < E; ++n) {
                             const R s = fmaR(fr[3 * n], fr[3 * n], fr[3 * n + 1] * fr[3 * n + 1]);

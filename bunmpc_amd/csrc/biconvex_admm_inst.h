@@ -5,6 +5,8 @@
 //   biconvex_admm_e2.hip     fp64, E = 2                      biconvex_admm_f32_e2.hip   fp32, E = 2
 //   biconvex_admm_bq.hip     blocks, E = 4   launch_bq        biconvex_admm_kq.hip       band, E = 4   launch_kq
 //   biconvex_admm_bq_e2.hip  blocks, E = 2                    biconvex_admm_kq_e2.hip    band, E = 2
+//   biconvex_admm_cone.hip   Euclidean cone projection, E = 4   launch_cone
+//   biconvex_admm_cone_e2.hip                           E = 2
 // so that every unit is built with its own flags (bunmpc_amd/build.py), the units build in parallel and one feature's kernels cannot
 // disturb another's code object.  Which kernel a batch gets is decided once, for every unit, by plan_launch (biconvex_admm.hip).
 #pragma once
@@ -48,6 +50,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 template <int LPP, int E, bool HASQF>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void biconvex_admm_kq_kernel(const BatchArgs a, const BandArgs q) {
     admm_body<double, LPP, E, true, HASQF, false, false, 1, false, true>(a, BlockArgs{}, q);
+}
+// The Euclidean cone projection with per-foot friction coefficients (biconvex_admm_body.h: CONE).  Both forms, fp64, one wave per SIMD:
+// beside what the diagonal kernel holds a lane keeps its knot's E coefficients over the whole solve.
+template <int LPP, int E, bool RAW, bool HASQF>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void biconvex_admm_cone_kernel(const BatchArgs a, const ConeArgs c) {
+    admm_body<double, LPP, E, RAW, HASQF, false, false, 1, false, false, true>(a, BlockArgs{}, c);
 }
 
 // The one switch over the lanes per problem: f(std::integral_constant<int, LPP>) of the plan's lpp.  A launch names the values its unit
@@ -154,6 +162,19 @@ hipError_t launch_kq(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream
                          : launch_segments<LPP, E>(biconvex_admm_kq_kernel<LPP, E, false>, sizeof(double), a, stream, q);
     });
 }
+// ... the Euclidean cone projection: either form, fp64, at most 64 lanes per problem
+template <int E>
+hipError_t launch_cone(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream) {
+    if (a.precision != 0 || a.H + 1 > l.lpp) return hipErrorInvalidValue;
+    const ConeArgs c = {l.cost.f, l.cost.sf};
+    return with_lpp(l.lpp, [&](auto lanes) {
+        constexpr int LPP = decltype(lanes)::value;
+        if constexpr (LPP > 64) return hipErrorInvalidValue;
+        else if (!a.raw) return launch_segments<LPP, E>(biconvex_admm_cone_kernel<LPP, E, false, false>, sizeof(double), a, stream, c);
+        else return a.qf ? launch_segments<LPP, E>(biconvex_admm_cone_kernel<LPP, E, true, true>, sizeof(double), a, stream, c)
+                         : launch_segments<LPP, E>(biconvex_admm_cone_kernel<LPP, E, true, false>, sizeof(double), a, stream, c);
+    });
+}
 
 // private-segment (scratch) bytes per lane, the largest over the kernels listed
 template <typename... K>
@@ -200,4 +221,17 @@ template <int E>
 int kq_scratch_bytes() {
     return max_scratch_bytes(&biconvex_admm_kq_kernel<16, E, false>, &biconvex_admm_kq_kernel<16, E, true>, &biconvex_admm_kq_kernel<21, E, false>, &biconvex_admm_kq_kernel<21, E, true>,
                              &biconvex_admm_kq_kernel<32, E, false>, &biconvex_admm_kq_kernel<32, E, true>, &biconvex_admm_kq_kernel<64, E, false>, &biconvex_admm_kq_kernel<64, E, true>);
+}
+template <int E, int LPP>
+int cone_lpp_scratch_bytes() {
+    return max_scratch_bytes(&biconvex_admm_cone_kernel<LPP, E, false, false>, &biconvex_admm_cone_kernel<LPP, E, true, false>, &biconvex_admm_cone_kernel<LPP, E, true, true>);
+}
+template <int E>
+int cone_scratch_bytes() {
+    int worst = 0;
+    for (int s : {cone_lpp_scratch_bytes<E, 16>(), cone_lpp_scratch_bytes<E, 21>(), cone_lpp_scratch_bytes<E, 32>(), cone_lpp_scratch_bytes<E, 64>()}) {
+        if (s < 0) return -1;
+        worst = s > worst ? s : worst;
+    }
+    return worst;
 }

@@ -79,6 +79,14 @@ struct BandArgs {
     long sQx_off, sQf_off;
 };
 
+// The Euclidean projection onto the friction cone (bmpc_cone_t, projection 1): per-foot friction coefficients, diagonal costs in either
+// form, fp64, one knot per lane (biconvex_admm_body.h: CONE).  A null pointer: every foot has SolverConsts::mu.  Stride in doubles,
+// 0 = one set of coefficients shared by the batch.
+struct ConeArgs {
+    const double *mu;       // [.][H][E]
+    long smu;
+};
+
 constexpr int kStats = 6;
 // LDS elements per knot of a problem (biconvex_admm_body.h: X 9, P 9, F 3E, R 9): 39 for four feet, 33 for two -- odd strides, so no
 // two lanes of a segment share a bank (an odd E would make it even: only E = 2 and 4 are built)
@@ -89,8 +97,9 @@ constexpr int kMaxFistaIters = 4096;  // length of the momentum table (one per d
 constexpr int kMaxKnots = 256; // H + 1 <= 256: one knot per lane, one problem per <= 64 lanes of a wave, or (65 .. 256 knots) per workgroup of 2 / 4 waves
 
 // Which Q a batch has beside BatchArgs' diagonal (Qx / Qf), and that Q's arrays: BlockArgs' for kBlocks, BandArgs' for kBand, x = the
-// motion side (Qx_blk / Qx_off), f = the force side
-enum CostShape { kDiag = 0, kBlocks = 1, kBand = 2 };
+// motion side (Qx_blk / Qx_off), f = the force side.  kCone: diagonal costs under the Euclidean cone projection -- a kernel family of
+// its own like the two others, chosen the same way; f = ConeArgs' coefficients (null: the scalar), sf their stride, x unused
+enum CostShape { kDiag = 0, kBlocks = 1, kBand = 2, kCone = 3 };
 struct CostArgs {
     CostShape shape = kDiag;
     const double *x = nullptr, *f = nullptr;
@@ -119,8 +128,9 @@ struct AdmmUnit {
     hipError_t (*launch)(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream);
     int (*scratch_bytes)();
 };
-const AdmmUnit &admm_unit_e4(), &admm_unit_e2(), &admm_unit_f32_e4(), &admm_unit_f32_e2(), &admm_unit_bq_e4(), &admm_unit_bq_e2(), &admm_unit_kq_e4(), &admm_unit_kq_e2();
-// ... of a combination the caller has validated: n_eff 2 or 4, precision 0 or 1 (blocks / band: 0)
+const AdmmUnit &admm_unit_e4(), &admm_unit_e2(), &admm_unit_f32_e4(), &admm_unit_f32_e2(), &admm_unit_bq_e4(), &admm_unit_bq_e2(), &admm_unit_kq_e4(), &admm_unit_kq_e2(),
+               &admm_unit_cone_e4(), &admm_unit_cone_e2();
+// ... of a combination the caller has validated: n_eff 2 or 4, precision 0 or 1 (blocks / band / cone: 0)
 const AdmmUnit &admm_unit(CostShape shape, int precision, int n_eff);
 
 // The dispatch switches of the process (the set_* calls below) and what they decide: a pure function of the batch's sizes, the
@@ -147,7 +157,8 @@ LaunchPlan plan_launch(const BatchArgs &a, CostShape shape, int n_eff, long simd
 // Launch the batched ADMM kernel on `stream`: plan_launch with the current device's SIMD count, the device's momentum table (and a
 // counter of its work-stealing ring if the plan steals), the "last launch" record, then the unit of (shape, precision, n_eff).
 // Returns hipSuccess or the launch error; hipErrorInvalidValue for unsupported shapes (n_eff not 2 or 4, H + 1 > 256; with block or
-// band costs: not raw, not fp64, H + 1 > 64 -- the C-ABI refuses those with a message first).
+// band costs: not raw, not fp64, H + 1 > 64; with the cone projection: not fp64, H + 1 > 64 -- the C-ABI refuses those with a message
+// first).
 hipError_t launch_biconvex_admm(const BatchArgs &a, const CostArgs &cost, int n_eff, hipStream_t stream);
 
 // The one-problem-per-wave mapping (biconvex_latency.hip): fp64, n_eff = 2 or 4, H + 1 <= 21.  plan_launch takes it for

@@ -106,9 +106,36 @@ bunmpc::CostArgs cost_args(bunmpc::CostShape shape, const double *x, long sx, co
 bunmpc::CostArgs cost_of(const bmpc_block_cost_t *c) { return c ? cost_args(bunmpc::kBlocks, c->Qx_blk, c->sQx_blk, c->Qf_blk, c->sQf_blk) : bunmpc::CostArgs(); }
 bunmpc::CostArgs cost_of(const bmpc_band_cost_t *c) { return c ? cost_args(bunmpc::kBand, c->Qx_off, c->sQx_off, c->Qf_off, c->sQf_off) : bunmpc::CostArgs(); }
 
+// bmpc_cone_t as the launcher takes it (kCone: f = the coefficients, null for the scalar); without a struct, or with the reference's
+// projection and no array: the plain call.  false (g_err set): a projection that does not exist, or an array under the reference's.
+bool cone_of(const bmpc_cone_t *c, bunmpc::CostArgs &out) {
+    out = bunmpc::CostArgs();
+    if (!c || (c->projection == 0 && !c->mu)) return true;
+    if (c->projection != 0 && c->projection != 1) { fail(BMPC_BAD_ARG, "projection must be 0 (the reference's \"SoC\" step) or 1 (Euclidean)"); return false; }
+    if (c->projection == 0) { fail(BMPC_BAD_ARG, "per-foot friction coefficients (mu array) need projection = 1: the kernels of the reference's projection take the scalar mu of bmpc_batch_t"); return false; }
+    out.shape = bunmpc::kCone; out.f = c->mu; out.sf = c->mu ? c->smu : 0;
+    return true;
+}
+const char kBadMu[] = "friction coefficients must be finite and > 0";
+int check_mu(const double *mu, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (!(mu[i] > 0.0) || !std::isfinite(mu[i])) return fail(BMPC_BAD_ARG, std::string(kBadMu) + ": entry " + std::to_string(i) + " is " + std::to_string(mu[i]));
+    return BMPC_OK;
+}
+
 // a batch with its costs: what the kernels of block costs / costs between neighbouring knots are built for, then the batch itself
 int check_cost(const bmpc_batch_t *d, const bunmpc::CostArgs &c, bool arrays = true) {
     if (c.shape == bunmpc::kDiag) return check_batch(d, false, false, arrays);
+    if (c.shape == bunmpc::kCone) {
+        const std::string what = "the Euclidean cone projection (bmpc_cone_t, projection = 1)";
+        if (!d) return fail(BMPC_BAD_ARG, "null batch descriptor");
+        if (d->precision != 0) return fail(BMPC_BAD_ARG, what + " is built for fp64 only: precision must be 0");
+        if (d->n_col + 1 > 64) return fail(BMPC_BAD_ARG, what + " is built for n_col + 1 <= 64 knots only (one problem per wave segment)");
+        if (d->n_eff != 2 && d->n_eff != 4) return fail(BMPC_BAD_ARG, what + " is built for n_eff in {2, 4} only");
+        if (c.f && (c.sf < 0 || c.sf > (1L << 26) || (c.sf != 0 && c.sf < (long)d->n_col * d->n_eff)))
+            return fail(BMPC_BAD_ARG, "batch stride of the friction coefficients (smu) must be 0 (shared) or between one problem's n_col * n_eff and 2^26 doubles");
+        return check_batch(d, false, false, arrays);
+    }
     const bool blocks = c.shape == bunmpc::kBlocks;
     const std::string what = blocks ? "block costs (Qx_blk / Qf_blk)" : "costs between neighbouring knots (Qx_off / Qf_off)";
     if (!d) return fail(BMPC_BAD_ARG, "null batch descriptor");
@@ -171,6 +198,10 @@ struct bmpc_biconvex {
     // weights between neighbouring knots (set_cost_x_band / set_cost_f_band); has_*_off false: that side has none
     std::vector<double> Qx_off, Qf_off;
     bool has_x_off = false, has_f_off = false;
+    // the force step's projection (0 the reference's, 1 Euclidean) and per-foot friction coefficients [n_col][n_eff] (empty: the scalar
+    // mu); both persist across optimize
+    int cone_projection = 0;
+    std::vector<double> mu_arr;
     // iterates
     std::vector<double> X, F, P;
     std::vector<double> rot;  // set_rotation_matrix_f: stored, unused (as in the reference)
@@ -186,7 +217,7 @@ struct bmpc_biconvex {
 extern "C" {
 
 int bmpc_abi_version(void) { return 2; }
-int bmpc_abi_minor_version(void) { return 1; }
+int bmpc_abi_minor_version(void) { return 2; }
 int bmpc_batch_struct_size(void) { return (int)sizeof(bmpc_batch_t); }
 int bmpc_set_three_per_wave(int mode) { return bunmpc::set_three_per_wave(mode); }
 int bmpc_set_work_stealing(int on) { return bunmpc::set_work_stealing(on); }
@@ -200,11 +231,13 @@ int bmpc_set_certified_steps(int on) { return bunmpc::set_certified_steps(on); }
 int bmpc_biconvex_fp32_scratch_bytes(void) { return bunmpc::admm_unit(bunmpc::kDiag, 1, 4).scratch_bytes(); }
 int bmpc_block_cost_struct_size(void) { return (int)sizeof(bmpc_block_cost_t); }
 int bmpc_band_cost_struct_size(void) { return (int)sizeof(bmpc_band_cost_t); }
+int bmpc_cone_struct_size(void) { return (int)sizeof(bmpc_cone_t); }
 static int unit_scratch_bytes(bunmpc::CostShape shape, int precision, int n_eff, const char *msg) {
     if ((n_eff != 2 && n_eff != 4) || (precision != 0 && precision != 1)) { fail(BMPC_BAD_ARG, msg); return -1; }
     return bunmpc::admm_unit(shape, precision, n_eff).scratch_bytes();
 }
 int bmpc_biconvex_band_kernel_scratch_bytes(int n_eff) { return unit_scratch_bytes(bunmpc::kBand, 0, n_eff, "n_eff must be 2 or 4"); }
+int bmpc_biconvex_cone_kernel_scratch_bytes(int n_eff) { return unit_scratch_bytes(bunmpc::kCone, 0, n_eff, "n_eff must be 2 or 4"); }
 int bmpc_biconvex_block_kernel_scratch_bytes(int n_eff) { return unit_scratch_bytes(bunmpc::kBlocks, 0, n_eff, "n_eff must be 2 or 4"); }
 int bmpc_biconvex_kernel_scratch_bytes(int n_eff, int precision) { return unit_scratch_bytes(bunmpc::kDiag, precision, n_eff, "n_eff must be 2 or 4, precision 0 or 1"); }
 int bmpc_biconvex_plan_launch(const bmpc_batch_t *d, int cost_shape, long simds, bmpc_launch_plan_t *out) {
@@ -639,6 +672,19 @@ int bmpc_biconvex_create_bound_constraints(bmpc_biconvex_t *h, const double *b, 
 }
 int bmpc_biconvex_set_rho(bmpc_biconvex_t *h, double rho) { H_CHECK(h); h->rho = rho; return BMPC_OK; }
 int bmpc_biconvex_set_friction_coefficient(bmpc_biconvex_t *h, double mu) { H_CHECK(h); h->mu = mu; return BMPC_OK; }
+int bmpc_biconvex_set_cone_projection(bmpc_biconvex_t *h, int projection) {
+    H_CHECK(h);
+    if (projection != 0 && projection != 1) return fail(BMPC_BAD_ARG, "projection must be 0 (the reference's \"SoC\" step) or 1 (Euclidean)");
+    h->cone_projection = projection;
+    return BMPC_OK;
+}
+int bmpc_biconvex_set_friction_coefficients(bmpc_biconvex_t *h, const double *mu) {
+    H_CHECK(h);
+    if (!mu) { h->mu_arr.clear(); return BMPC_OK; }
+    if (int rc = check_mu(mu, (size_t)h->n_col * h->n_eff)) return rc;
+    h->mu_arr.assign(mu, mu + (size_t)h->n_col * h->n_eff);
+    return BMPC_OK;
+}
 int bmpc_biconvex_set_robot_mass(bmpc_biconvex_t *h, double m) { H_CHECK(h); h->m = m; return BMPC_OK; }
 
 int bmpc_biconvex_return_opt_x(bmpc_biconvex_t *h, double *X) { H_CHECK(X); std::memcpy(X, h->X.data(), sizeof(double) * h->nx()); return BMPC_OK; }
@@ -693,6 +739,15 @@ int bmpc_biconvex_optimize(bmpc_biconvex_t *h, const double *x_init, int num_ite
                                   "(set_cost_x_blocks / set_cost_f_blocks): coupling between knots needs diagonal per-knot weights on both sides");
     if ((h->has_x_off || h->has_f_off) && h->n_col + 1 > 64)
         return fail(BMPC_BAD_ARG, "costs between neighbouring knots (Qx_off / Qf_off) are built for n_col + 1 <= 64 knots only (one problem per wave segment)");
+    const bool blk_or_band = h->has_x_off || h->has_f_off || !h->Qx_blk.empty() || !h->Qf_blk.empty();
+    if (h->cone_projection == 1 && blk_or_band)
+        return fail(BMPC_BAD_ARG, "the handle carries block or band costs (set_cost_x/f_blocks, set_cost_x/f_band) and the Euclidean cone projection "
+                                  "(set_cone_projection): the cone kernels hold diagonal costs only");
+    if (h->cone_projection == 1 && h->n_col + 1 > 64)
+        return fail(BMPC_BAD_ARG, "the Euclidean cone projection (set_cone_projection) is built for n_col + 1 <= 64 knots only (one problem per wave segment)");
+    if (h->cone_projection == 0 && !h->mu_arr.empty())
+        return fail(BMPC_BAD_ARG, "the handle carries per-foot friction coefficients (set_friction_coefficients) under the reference's projection: they need "
+                                  "set_cone_projection(1); the kernels of the reference's projection take the scalar of set_friction_coefficient");
     if (int rc = need_plan(h)) return rc;
     if (num_iters < 0) return fail(BMPC_BAD_ARG, "num_iters < 0");
     const int H = h->n_col, E = h->n_eff, nx = h->nx(), nf = h->nf();
@@ -710,7 +765,7 @@ int bmpc_biconvex_optimize(bmpc_biconvex_t *h, const double *x_init, int num_ite
                  o_lb = take(nx), o_ub = take(nx), o_Qf = take(nf), o_qf = take(nf), o_X = take(nx),
                  o_F = take(nf), o_P = take(nx), o_L = take(2), o_viol = take(1), o_hist = take(nh);
     const size_t o_end = off, o_Qxb = take(h->Qx_blk.size()), o_Qfb = take(h->Qf_blk.size());      // (blocks: behind what comes back)
-    const size_t o_Qxo = take(h->has_x_off ? h->Qx_off.size() : 0), o_Qfo = take(h->has_f_off ? h->Qf_off.size() : 0);
+    const size_t o_Qxo = take(h->has_x_off ? h->Qx_off.size() : 0), o_Qfo = take(h->has_f_off ? h->Qf_off.size() : 0), o_mu = take(h->mu_arr.size());
     std::vector<double> stage(off, 0.0);
     auto put = [&](size_t o, const double *src, size_t n) { std::memcpy(stage.data() + o, src, sizeof(double) * n); };
     put(o_cnt, cnt.data(), cnt.size()); put(o_dt, h->dt.data(), H); put(o_xi, x_init, 9);
@@ -721,6 +776,7 @@ int bmpc_biconvex_optimize(bmpc_biconvex_t *h, const double *x_init, int num_ite
     if (!h->Qf_blk.empty()) put(o_Qfb, h->Qf_blk.data(), h->Qf_blk.size());
     if (h->has_x_off) put(o_Qxo, h->Qx_off.data(), h->Qx_off.size());
     if (h->has_f_off) put(o_Qfo, h->Qf_off.data(), h->Qf_off.size());
+    if (!h->mu_arr.empty()) put(o_mu, h->mu_arr.data(), h->mu_arr.size());
     stage[o_L] = h->L_x; stage[o_L + 1] = h->L_f;
     HIP_TRY(h->dbuf.ensure(sizeof(double) * off));
     HIP_TRY(h->dstats.ensure(sizeof(int) * bunmpc::kStats));
@@ -739,6 +795,11 @@ int bmpc_biconvex_optimize(bmpc_biconvex_t *h, const double *x_init, int num_ite
     b.dyn_viol = d + o_viol; b.hist = d + o_hist; b.stats = static_cast<int *>(h->dstats.p);
     bunmpc::CostArgs cost = cost_args(bunmpc::kBand, h->has_x_off ? d + o_Qxo : nullptr, 0, h->has_f_off ? d + o_Qfo : nullptr, 0);
     if (cost.shape == bunmpc::kDiag) cost = cost_args(bunmpc::kBlocks, h->Qx_blk.empty() ? nullptr : d + o_Qxb, 0, h->Qf_blk.empty() ? nullptr : d + o_Qfb, 0);
+    if (h->cone_projection == 1) {
+        cost = bunmpc::CostArgs();
+        cost.shape = bunmpc::kCone;
+        cost.f = h->mu_arr.empty() ? nullptr : d + o_mu;
+    }
     if (int rc = check_cost(&b, cost)) return rc;
     HIP_TRY(bunmpc::launch_biconvex_admm(to_args(b), cost, E, nullptr));
     HIP_TRY(hipMemcpy(stage.data() + o_X, d + o_X, sizeof(double) * (o_end - o_X), hipMemcpyDeviceToHost));
@@ -774,6 +835,11 @@ static int solve_batch_device(const bmpc_batch_t *d, const bunmpc::CostArgs &c, 
 int bmpc_biconvex_solve_batch_device(const bmpc_batch_t *d, void *hip_stream) { return solve_batch_device(d, bunmpc::CostArgs(), hip_stream); }
 int bmpc_biconvex_solve_batch_blocks_device(const bmpc_batch_t *d, const bmpc_block_cost_t *c, void *hip_stream) { return solve_batch_device(d, cost_of(c), hip_stream); }
 int bmpc_biconvex_solve_batch_band_device(const bmpc_batch_t *d, const bmpc_band_cost_t *c, void *hip_stream) { return solve_batch_device(d, cost_of(c), hip_stream); }
+int bmpc_biconvex_solve_batch_cone_device(const bmpc_batch_t *d, const bmpc_cone_t *c, void *hip_stream) {
+    bunmpc::CostArgs a;
+    if (!cone_of(c, a)) return BMPC_BAD_ARG;
+    return solve_batch_device(d, a, hip_stream);
+}
 
 namespace {
 int solve_batch_host(const bmpc_batch_t *d, bunmpc::CostArgs c);
@@ -781,13 +847,18 @@ int solve_batch_host(const bmpc_batch_t *d, bunmpc::CostArgs c);
 int bmpc_biconvex_solve_batch_host(const bmpc_batch_t *d) { return solve_batch_host(d, bunmpc::CostArgs()); }
 int bmpc_biconvex_solve_batch_blocks_host(const bmpc_batch_t *d, const bmpc_block_cost_t *c) { return solve_batch_host(d, cost_of(c)); }
 int bmpc_biconvex_solve_batch_band_host(const bmpc_batch_t *d, const bmpc_band_cost_t *c) { return solve_batch_host(d, cost_of(c)); }
+int bmpc_biconvex_solve_batch_cone_host(const bmpc_batch_t *d, const bmpc_cone_t *c) {
+    bunmpc::CostArgs a;
+    if (!cone_of(c, a)) return BMPC_BAD_ARG;
+    return solve_batch_host(d, a);
+}
 
 }  // extern "C"
 
 namespace {
 // the host entry points: arrays to the device, one launch, results back (c: the host arrays of per-knot blocks or of costs between neighbouring knots, if any)
 int solve_batch_host(const bmpc_batch_t *d, bunmpc::CostArgs c) {
-    const bool blocks = c.shape == bunmpc::kBlocks, band = c.shape == bunmpc::kBand;
+    const bool blocks = c.shape == bunmpc::kBlocks, band = c.shape == bunmpc::kBand, cone = c.shape == bunmpc::kCone;
     if (int rc = check_cost(d, c)) return rc;
     const size_t B = (size_t)d->B, H = (size_t)d->n_col, E = (size_t)d->n_eff;
     const size_t nx = 9 * (H + 1), nf = 3 * E * H;
@@ -798,6 +869,13 @@ int solve_batch_host(const bmpc_batch_t *d, bunmpc::CostArgs c) {
     struct Out { double **slot; double *host; size_t n; };
     auto rows = [&](long stride) { return stride == 0 ? (size_t)1 : B; };
     std::vector<In> ins = {{&b.cnt_plan, B * H * E * 4}, {&b.dt, B * H}, {&b.x_init, B * 9}};
+    if (cone && c.f) {
+        for (size_t i = 0; i < rows(c.sf); ++i)
+            if (int rc = check_mu(c.f + i * (size_t)c.sf, H * E)) return rc;
+        ins.push_back({&c.f, (rows(c.sf) - 1) * (size_t)c.sf + H * E});
+    } else if (cone) {
+        if (int rc = check_mu(&d->mu, 1)) return rc;
+    }
     if (d->raw) {
         if (blocks && c.x) {
             for (size_t i = 0; i < rows(c.sx); ++i)

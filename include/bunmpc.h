@@ -28,7 +28,8 @@ extern "C" {
 
 /* library / device ----------------------------------------------------------- */
 int bmpc_abi_version(void);
-int bmpc_abi_minor_version(void);            /* additions within an ABI version: 1 = bmpc_batch_t ends in cert_phases */
+int bmpc_abi_minor_version(void);            /* additions within an ABI version: 1 = bmpc_batch_t ends in cert_phases; 2 = the
+                                              * Euclidean cone projection (bmpc_cone_t and the calls beside it) */
 int bmpc_batch_struct_size(void);            /* sizeof(bmpc_batch_t), to catch binding drift  */
 const char *bmpc_last_error(void);           /* thread-local text of the last failure   */
 int bmpc_device_count(int *count);           /* hipGetDeviceCount                        */
@@ -291,6 +292,45 @@ int bmpc_biconvex_set_cost_f_band(bmpc_biconvex_t *h, const double *Q_diag, cons
 /* The largest scratch (private-segment) bytes per lane over the band-cost kernels of one foot count (n_eff 2 or 4), as the loaded
  * code object reports them; -1 for another n_eff, or on error. */
 int bmpc_biconvex_band_kernel_scratch_bytes(int n_eff);
+
+/* Euclidean projection onto the friction cone, per-foot friction coefficients (additive, opt-in) ------------------------------
+ * The force QP's projection is by default the reference's "SoC" step (fista.cpp:52-70), which compares the SQUARED tangential norm
+ * with mu fz, zeroes every force with fz < 0 and is expansive on its cone branch.  projection = 1 replaces it by the nearest point of
+ * the cone |f_xy| <= mu fz, per foot and knot, with s2 = fx^2 + fy^2 of the gradient step (fx, fy, fz):
+ *     fz <= 0 and mu^2 s2 <= fz^2   -> (0, 0, 0)          (the polar cone; wins at the origin)
+ *     fz >= 0 and s2 <= mu^2 fz^2   -> unchanged
+ *     otherwise                     -> s = sqrt(s2), t = (mu s + fz) / (mu^2 + 1): (fx mu t / s, fy mu t / s, t)
+ * Everything else of the solve is unchanged: gradient, backtracking test, momentum, exits, ADMM.  As under the reference's
+ * projection, the force bounds of create_bound_constraints / set_bounds_f are not applied, and the contact frame is world-z
+ * (set_rotation_matrix_f stays stored and unused).
+ * mu: friction coefficients [.][n_col][n_eff], each finite and > 0 (the host entry point and the handle's setter check that, the
+ * device entry point cannot), or NULL: every foot has bmpc_batch_t's scalar mu.  smu: batch stride in doubles, 0 = one set shared by
+ * the batch, otherwise at least n_col * n_eff and at most 2^26.
+ * c == NULL, or projection == 0 with mu == NULL, is the plain call: same kernel, same bits.  BMPC_BAD_ARG with a message naming the
+ * limit: projection == 0 with a mu array (the kernels of the reference's projection take the scalar), projection other than 0 / 1,
+ * fp32 (precision = 1), n_col + 1 > 64 knots, n_eff other than 2 or 4, a stride outside the rule above.  Both forms (raw = 0 / 1, with
+ * and without qf) are built.  Such a batch runs "biconvex_admm_cone_kernel" (one knot per lane, 16 / 21 / 32 / 64 lanes per problem, one
+ * wave per SIMD) at every batch size and num_iters; every FISTA step is tested on fp64 sums (no step certificate, no fp32 step
+ * decisions), so bmpc_set_certified_steps, bmpc_set_exact_step_decisions, bmpc_set_work_stealing, bmpc_set_two_waves_per_simd and
+ * bmpc_set_latency_mapping_max_batch do not touch it.  Not combinable with block or band costs (their entry points take no
+ * bmpc_cone_t).  bmpc_kinodyn_solve_batch_device keeps the reference's projection. */
+typedef struct {
+    int projection;                        /* 0: the reference's "SoC" step, 1: Euclidean */
+    const double *mu; long smu;            /* [.][n_col][n_eff], NULL: bmpc_batch_t's scalar mu */
+} bmpc_cone_t;
+int bmpc_cone_struct_size(void);             /* sizeof(bmpc_cone_t), to catch binding drift */
+int bmpc_biconvex_solve_batch_cone_device(const bmpc_batch_t *d, const bmpc_cone_t *c, void *hip_stream);
+int bmpc_biconvex_solve_batch_cone_host(const bmpc_batch_t *d, const bmpc_cone_t *c);
+/* The handle's projection (0 / 1) and per-foot coefficients mu [n_col][n_eff] (NULL: back to the scalar of
+ * bmpc_biconvex_set_friction_coefficient); both persist across optimize calls.  optimize refuses (BMPC_BAD_ARG) projection 1 on a
+ * handle that carries block or band costs or has n_col + 1 > 64, and a coefficient array under projection 0.  A KinoDynMP's
+ * centroidal handle (bmpc_kinodyn_return_dyn) is solved through bmpc_biconvex_optimize: bmpc_kinodyn_optimize honours both settings
+ * or returns that refusal. */
+int bmpc_biconvex_set_cone_projection(bmpc_biconvex_t *h, int projection);
+int bmpc_biconvex_set_friction_coefficients(bmpc_biconvex_t *h, const double *mu);
+/* The largest scratch (private-segment) bytes per lane over the cone-projection kernels of one foot count (n_eff 2 or 4), as the
+ * loaded code object reports them; -1 for another n_eff, or on error. */
+int bmpc_biconvex_cone_kernel_scratch_bytes(int n_eff);
 
 /* rigid-body model -------------------------------------------------------------------
  * What pinocchio::urdf::buildModel(urdf, JointModelFreeFlyer()) yields (inverse_kinematics.cpp:10,

@@ -1,4 +1,4 @@
-"""Is the device code of the kernel units (the eight centroidal ADMM units and ik_ddp.hip) the same in two source trees?  Kernel by kernel.
+"""Is the device code of the kernel units (the ten centroidal ADMM units and ik_ddp.hip) the same in two source trees?  Kernel by kernel.
 
     python tools/device_asm_diff.py PARENT_TREE THIS_TREE [--keep DIR] [--units biconvex_admm_kq.hip ik_ddp.hip ...]
 
@@ -7,7 +7,8 @@ FILE_FLAGS, plus --cuda-device-only -S).  The files are not compared with diff: 
 file, which renumbers the function index of local labels (.LBB<n>_<m>), and the __hip_cuid_* symbol differs on every compilation.
 Instead every kernel's text -- from its symbol label to its .end_amdhsa_kernel -- and its entry in the metadata note are cut out by
 name, comments are dropped, the function index in local labels is replaced by a placeholder, and the two sides are compared.  One line per kernel, `same` or
-`DIFFERS`; a kernel that exists on one side only is a difference.  Exit status 0 only if every kernel of every unit is the same."""
+`DIFFERS`; a kernel that exists on one side only is a difference (so is every kernel of a unit whose source one tree does not have).
+Exit status 0 only if every kernel of every unit is the same."""
 import argparse
 import importlib.util
 import os
@@ -17,7 +18,7 @@ import sys
 import tempfile
 
 UNITS = ["biconvex_admm.hip", "biconvex_admm_e2.hip", "biconvex_admm_bq.hip", "biconvex_admm_bq_e2.hip", "biconvex_admm_kq.hip", "biconvex_admm_kq_e2.hip",
-         "biconvex_admm_f32.hip", "biconvex_admm_f32_e2.hip", "ik_ddp.hip"]
+         "biconvex_admm_cone.hip", "biconvex_admm_cone_e2.hip", "biconvex_admm_f32.hip", "biconvex_admm_f32_e2.hip", "ik_ddp.hip"]
 
 
 def build_settings(tree):
@@ -28,19 +29,22 @@ def build_settings(tree):
 
 
 def compile_units(tree, units, out_dir):
-    """start hipcc -S for every unit of the tree; returns [(unit, path, process)]"""
+    """start hipcc -S for every unit of the tree; returns [(unit, path, process)], process None for a unit the tree does not have"""
     b = build_settings(tree)
     os.makedirs(out_dir, exist_ok=True)
     jobs = []
     for u in units:
         path = os.path.join(out_dir, u.replace(".hip", ".s"))
-        cmd = [b.HIPCC] + b.FLAGS + b.FILE_FLAGS.get(u, []) + ["--cuda-device-only", "-S", os.path.join(tree, "bunmpc_amd", "csrc", u), "-o", path]
-        jobs.append((u, path, subprocess.Popen(cmd)))
+        src = os.path.join(tree, "bunmpc_amd", "csrc", u)
+        cmd = [b.HIPCC] + b.FLAGS + b.FILE_FLAGS.get(u, []) + ["--cuda-device-only", "-S", src, "-o", path]
+        jobs.append((u, path, subprocess.Popen(cmd) if os.path.exists(src) else None))
     return jobs
 
 
 def kernels_of(path):
     """{kernel symbol: normalised text + metadata entry}"""
+    if not os.path.exists(path):      # (the tree has no such unit)
+        return {}
     text = open(path).read()
     out = {}
     for m in re.finditer(r"^\t\.amdhsa_kernel (\S+)\n", text, re.M):
@@ -68,7 +72,7 @@ def main():
             for side, tree in (("parent", args.parent_tree), ("this", args.this_tree))}
     for side in jobs:
         for u, path, p in jobs[side]:
-            if p.wait() != 0:
+            if p is not None and p.wait() != 0:
                 sys.exit("hipcc failed on %s of the %s tree" % (u, side))
     differing = 0
     for (u, pa, _), (_, th, _) in zip(jobs["parent"], jobs["this"]):
