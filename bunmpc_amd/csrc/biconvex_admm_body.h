@@ -512,13 +512,18 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
             R invL = R(2) * (R(1) / L_f);      // 2 / L, see above
             mask_t banded = 0;      // the fp32 step decisions (see BAND): all ones or 0 (a mask: a bool here would live in a vector register)
             float Llo = 0.0f, Lhi = 0.0f, flo = 0.0f, fhi = 0.0f;
-            if constexpr (BAND) if (!a.exact_step_decisions) {
+            if constexpr (BAND) if (a.exact_step_decisions != 1) {
                 bool wneg = false;
                 UNROLL for (int j = 0; j < NF; ++j) wneg = wneg || wf[j] < R(0);
                 banded = rho >= R(0) && __ballot(wneg) == 0 ? ~mask_t(0) : mask_t(0);
                 band_L((double)L_f * 0.5, Llo, Lhi);
                 band_u(floor2, flo, fhi);
             }
+            // the lane-local screen of the certified loop (biconvex_lanes.h: screen_theta): a lane's own |d|^2 above theta settles the
+            // iteration's floor and exit decisions for its problem without any sum; +inf (no lane is above it) unless the switch is 0.
+            // Whatever `banded` says: squares are non-negative under any weights.
+            [[maybe_unused]] double theta = __builtin_inf();
+            if constexpr (BAND) if (a.exact_step_decisions == 0) theta = screen_theta(tol2, floor2);
             mask_t act = alive;
             // one FISTA iteration: reads x from xo/ro, leaves x_{k+1} in xn/rn, advances y/ry (XLDS: x_k from LDS, x_{k+1} to LDS;
             // the four arrays are then no more than the iteration's temporaries)
@@ -667,40 +672,45 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                     mask_t bt;
                     if constexpr (BAND) {      // (the other instantiations compile the code below the `else` alone, as before the shortcut)
                         bt = 0;      // (certified: cvs <= rhs whatever the step)
-                        mask_t unclear = ~mask_t(0);      // designated lanes of live problems whose fp32 decisions are not clear
-                        if (banded != 0) {      // the fp32 decisions, if every live problem's are clear (see BAND)
-                            float gf = (float)g2, cf = (float)cv;
-                            if (CERT) seg_sum1_f32<LPP>(gf);
-                            else seg_sum2_f32<LPP>(gf, cf);
-                            const mask_t yes = CERT ? __ballot(gf < flo) : __ballot(cf > gf * Lhi);
-                            const mask_t no = CERT ? __ballot(gf > fhi) : __ballot(cf < gf * Llo);
-                            const mask_t dyes = __ballot(gf < t2lo), dno = __ballot(gf > t2hi);
-                            const mask_t clear = (yes | no) & (dyes | dno) & __ballot(gf >= 1e-24f) & __ballot(gf <= 1e30f);
-                            unclear = ~clear & seg_desig<LPP>() & act;
-                            if (unclear == 0) {
-                                if (CERT && (seg_uniform<LPP>(yes & seg_desig<LPP>()) & act) != 0) return false;      // (see below)
-                                if (!CERT) bt = yes;
-                                done = dyes;
+                        bool settled = false;      // the screen: every live problem has a lane above theta -- no hand-over, no exit, no sum
+                        if constexpr (CERT) settled = seg_covered<LPP>(__ballot(g2 > theta), act);
+                        if (settled) done = 0;
+                        else {
+                            mask_t unclear = ~mask_t(0);      // designated lanes of live problems whose fp32 decisions are not clear
+                            if (banded != 0) {      // the fp32 decisions, if every live problem's are clear (see BAND)
+                                float gf = (float)g2, cf = (float)cv;
+                                if (CERT) seg_sum1_f32<LPP>(gf);
+                                else seg_sum2_f32<LPP>(gf, cf);
+                                const mask_t yes = CERT ? __ballot(gf < flo) : __ballot(cf > gf * Lhi);
+                                const mask_t no = CERT ? __ballot(gf > fhi) : __ballot(cf < gf * Llo);
+                                const mask_t dyes = __ballot(gf < t2lo), dno = __ballot(gf > t2hi);
+                                const mask_t clear = (yes | no) & (dyes | dno) & __ballot(gf >= 1e-24f) & __ballot(gf <= 1e30f);
+                                unclear = ~clear & seg_desig<LPP>() & act;
+                                if (unclear == 0) {
+                                    if (CERT && (seg_uniform<LPP>(yes & seg_desig<LPP>()) & act) != 0) return false;      // (see below)
+                                    if (!CERT) bt = yes;
+                                    done = dyes;
+                                }
                             }
-                        }
-                        if (unclear != 0) {
-                            double g2s = (double)g2, cvs = (double)cv;
-                            if (CERT) {
-                                sum1(g2s);
-                                // a live problem's step below the floor: nothing of this iteration is kept, the tested loop runs it again
-                                if ((seg_uniform<LPP>(__ballot(g2s < floor2) & seg_desig<LPP>()) & act) != 0) return false;
-                            } else sum2(g2s, cvs);
-                            // fista.cpp:14-17: G = sqrt(g2); retry if cv > (L/2) G*G; done if G < tol.  G*G and g2
-                            // differ by a few ulp, so outside a 1e-14 relative band the sqrt cannot change either
-                            // decision; inside it the reference expression is evaluated as written.
-                            const double Lh = (double)L_f * 0.5, rhs = Lh * g2s;
-                            if (!CERT) bt = __ballot(cvs > rhs);
-                            done = __ballot(g2s < tol2);
-                            const mask_t edge = __ballot((!CERT && fabs(cvs - rhs) <= 1e-14 * rhs) || (fabs(g2s - tol2) <= 1e-14 * tol2)) & seg_desig<LPP>();
-                            if (edge != 0) {
-                                const double Gn = sqrt(g2s);
-                                if (!CERT) bt = __ballot(cvs > Lh * (Gn * Gn));
-                                done = __ballot(Gn < tol);
+                            if (unclear != 0) {
+                                double g2s = (double)g2, cvs = (double)cv;
+                                if (CERT) {
+                                    sum1(g2s);
+                                    // a live problem's step below the floor: nothing of this iteration is kept, the tested loop runs it again
+                                    if ((seg_uniform<LPP>(__ballot(g2s < floor2) & seg_desig<LPP>()) & act) != 0) return false;
+                                } else sum2(g2s, cvs);
+                                // fista.cpp:14-17: G = sqrt(g2); retry if cv > (L/2) G*G; done if G < tol.  G*G and g2
+                                // differ by a few ulp, so outside a 1e-14 relative band the sqrt cannot change either
+                                // decision; inside it the reference expression is evaluated as written.
+                                const double Lh = (double)L_f * 0.5, rhs = Lh * g2s;
+                                if (!CERT) bt = __ballot(cvs > rhs);
+                                done = __ballot(g2s < tol2);
+                                const mask_t edge = __ballot((!CERT && fabs(cvs - rhs) <= 1e-14 * rhs) || (fabs(g2s - tol2) <= 1e-14 * tol2)) & seg_desig<LPP>();
+                                if (edge != 0) {
+                                    const double Gn = sqrt(g2s);
+                                    if (!CERT) bt = __ballot(cvs > Lh * (Gn * Gn));
+                                    done = __ballot(Gn < tol);
+                                }
                             }
                         }
                     } else {
@@ -741,7 +751,15 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                     if (lanes(last)) { UNROLL for (int j = 0; j < NF; ++j) Fg[j] = xn[j]; }   // x_k of a finishing problem is latched
                 }
                 // momentum (fista.cpp:33-47); A-images follow by linearity
-                UNROLL for (int j = 0; j < NF; ++j) y[j] = fmaR(cm, xn[j] - xo[j], xn[j]);
+                // (the headline kernel's certified loop: fma3, no copies at the loop's end.  Nested conditions on purpose: `BAND && CERT`
+                // depends on the lambda's own parameter, which makes the closure capture BAND -- and that moved the register allocation
+                // of the block- and band-cost kernels)
+                UNROLL for (int j = 0; j < NF; ++j) {
+                    if constexpr (BAND) {
+                        if constexpr (CERT) y[j] = fma3(cm, xn[j] - xo[j], xn[j]);
+                        else y[j] = fmaR(cm, xn[j] - xo[j], xn[j]);
+                    } else y[j] = fmaR(cm, xn[j] - xo[j], xn[j]);
+                }
                 UNROLL for (int k = 0; k < 6; ++k) ry[k] = fmaR(cm, rn[k] - ro[k], rn[k]);
                 if (XLDS && lanes(act & rvalid_m)) {      // problems still iterating (a finished one keeps the x_k it finished with)
                     UNROLL for (int j = 0; j < NF; ++j) Fg[j] = xn[j];
@@ -910,7 +928,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
             R invL = R(2) * (R(1) / L_x);
             mask_t banded = 0;      // (see the force step)
             float Llo = 0.0f, Lhi = 0.0f;
-            if constexpr (BAND) if (!a.exact_step_decisions) {
+            if constexpr (BAND) if (a.exact_step_decisions != 1) {
                 bool wneg = false;
                 UNROLL for (int l = 0; l < 9; ++l) wneg = wneg || qd[l] < R(0);
                 banded = rho >= R(0) && __ballot(wneg) == 0 ? ~mask_t(0) : mask_t(0);
@@ -1075,6 +1093,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                 if (cert && l0 && lanes(alive)) ++certn[1];
                 float flo = 0.0f, fhi = 0.0f;
                 if (banded != 0) band_u(floor2, flo, fhi);
+                const double theta = cert && a.exact_step_decisions == 0 ? screen_theta(tol2, floor2) : __builtin_inf();      // (see the force step)
                 // one iteration of the certified loop: the tested loop's step, momentum and write-back, operation for operation, without
                 // the image difference, cv and the retry loop around them (bt = 0 whatever the step); a live problem's step below the
                 // floor commits nothing and hands the phase to the tested loop from this iteration (x_k and its image are in LDS: nothing
@@ -1103,29 +1122,32 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                     R g2 = 0;
                     UNROLL for (int l = 0; l < 9; ++l) { const R d = xn[l] - y[l]; g2 = fmaR(d, d, g2); }
                     UNROLL for (int l = 0; l < 9; ++l) { xo[l] = Xz[l]; ro[l] = RXz[l]; }      // (see the force step)
-                    mask_t unclear = ~mask_t(0);
-                    if (banded != 0) {      // the fp32 decisions -- floor and exit -- if every live problem's are clear (see the force step)
-                        float gf = (float)g2;
-                        seg_sum1_f32<LPP>(gf);
-                        const mask_t yes = __ballot(gf < flo), no = __ballot(gf > fhi);
-                        const mask_t dyes = __ballot(gf < t2lo), dno = __ballot(gf > t2hi);
-                        const mask_t clear = (yes | no) & (dyes | dno) & __ballot(gf >= 1e-24f) & __ballot(gf <= 1e30f);
-                        unclear = ~clear & act;
-                        if (unclear == 0) {
-                            if ((yes & act) != 0) return false;
-                            done = dyes;
+                    if (seg_covered<LPP>(__ballot(g2 > theta), act)) done = 0;      // the screen (see the force step)
+                    else {
+                        mask_t unclear = ~mask_t(0);
+                        if (banded != 0) {      // the fp32 decisions -- floor and exit -- if every live problem's are clear (see the force step)
+                            float gf = (float)g2;
+                            seg_sum1_f32<LPP>(gf);
+                            const mask_t yes = __ballot(gf < flo), no = __ballot(gf > fhi);
+                            const mask_t dyes = __ballot(gf < t2lo), dno = __ballot(gf > t2hi);
+                            const mask_t clear = (yes | no) & (dyes | dno) & __ballot(gf >= 1e-24f) & __ballot(gf <= 1e30f);
+                            unclear = ~clear & act;
+                            if (unclear == 0) {
+                                if ((yes & act) != 0) return false;
+                                done = dyes;
+                            }
                         }
-                    }
-                    if (unclear != 0) {
-                        double g2s = (double)g2;
-                        sum1(g2s);
-                        if ((__ballot(g2s < floor2) & act) != 0) return false;
-                        done = __ballot(g2s < tol2);      // the tested loop's exit rule (see the force loop for the sqrt-free form)
-                        if (__ballot(fabs(g2s - tol2) <= 1e-14 * tol2) != 0) done = __ballot(sqrt(g2s) < tol);
+                        if (unclear != 0) {
+                            double g2s = (double)g2;
+                            sum1(g2s);
+                            if ((__ballot(g2s < floor2) & act) != 0) return false;
+                            done = __ballot(g2s < tol2);      // the tested loop's exit rule (see the force loop for the sqrt-free form)
+                            if (__ballot(fabs(g2s - tol2) <= 1e-14 * tol2) != 0) done = __ballot(sqrt(g2s) < tol);
+                        }
                     }
                     UNROLL for (int l = 0; l < 9; ++l) { keep_here(xo[l]); keep_here(ro[l]); }
                     UNROLL for (int l = 0; l < 9; ++l) {
-                        y[l] = fmaR(cm, xn[l] - xo[l], xn[l]);
+                        y[l] = fma3(cm, xn[l] - xo[l], xn[l]);      // (no copies at the loop's end: see fma3)
                         ry[l] = fmaR(cm, rn[l] - ro[l], rn[l]);
                     }
                     if (lanes(act & kvalid_m)) { UNROLL for (int l = 0; l < 9; ++l) { Xg[l] = xn[l]; Rg[l] = rn[l]; } }

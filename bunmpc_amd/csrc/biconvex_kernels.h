@@ -38,7 +38,8 @@ struct SolverConsts {
 struct BatchArgs {
     int B, H, raw, cold_start;
     int precision;   // 0: fp64 arithmetic; 1: fp32 iterates with fp64 decisions (harness form only)
-    int exact_step_decisions;   // (set by the launcher) 1: the kernels with the fp32 shortcut of their step decisions skip it (tests)
+    int exact_step_decisions;   // (set by the launcher; tests) 0: the headline kernel screens its certified loops lane by lane, then fp32 decisions; 1: every decision
+                                // from the fp64 sums, no screen; 2: fp32 decisions without the screen (kernels without the screen read non-zero as 1)
     int certified_steps;        // (set by the launcher) fp64 batch kernels skip the backtracking test in phases whose step is certified: 1 force and
                                 // motion phases, 2 force phases only, 0 none
     double L0_x, L0_f;
@@ -141,7 +142,7 @@ struct DispatchKnobs {
     int work_stealing = 1;             // the segment-level work-stealing kernel for num_iters >= 25
     int steal_grid = 0;                // waves of its persistent grid (experiments): 0 = one or two per SIMD
     int latency_max_batch = 1024;      // the one-problem-per-wave kernel up to this many problems
-    int exact_step_decisions = 0;      // every step decision from the fp64 sums, in every centroidal kernel (tests)
+    int exact_step_decisions = 0;      // 1: every step decision from the fp64 sums, in every centroidal kernel; 2: the headline kernel without its lane-local screen (tests)
     int certified_steps = 1;           // the fp64 batch kernels' per-phase step certificate: 0 off, 1 on, 2 force phases only
 };
 struct LaunchPlan {
@@ -172,7 +173,7 @@ int biconvex_last_waves_per_simd();                  // of the calling host thre
 int set_steal_grid(int waves);                       // waves of the work-stealing kernel's persistent grid (experiments; 0 = what the chip holds); returns the old value
 int set_work_stealing(int on);                       // the segment-level work-stealing kernel for num_iters >= 25 (default on); returns the old value
 int biconvex_last_lanes_per_problem();               // of the calling host thread's latest launch: 16 / 21 / 32 / 64, 0 = one problem per wave
-int set_exact_step_decisions(int on);                // every step decision from the fp64 sums, in every centroidal kernel; returns the old value
+int set_exact_step_decisions(int on);                // 1: every step decision from the fp64 sums, in every centroidal kernel; 2: fp32 decisions without the headline kernel's lane-local screen; returns the old value
 int set_certified_steps(int on);                     // the fp64 batch kernels' per-phase step certificate: 0 off, 1 on (default), 2 force phases only; returns the old value
 
 // Lane-exchange self test (DPP shifts and segment sums used by the kernel).

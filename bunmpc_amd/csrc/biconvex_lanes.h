@@ -198,6 +198,33 @@ __device__ __forceinline__ void seg_sum1_f32(float &a) {
     if (LPP >= 64) { auto x = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(a), false, false); a = __uint_as_float(x[0]) + __uint_as_float(x[1]); }
 }
 
+// ---- the lane-local screen of the certified FISTA loops (biconvex_admm_body.h: `theta`).  The squared step is a
+// sum S of non-negative lane partials, and fl(a + b) >= max(a, b) for a, b >= 0 under round-to-nearest, so S >= every partial in
+// any order of additions.  One partial above theta = max(tol^2, floor2) (1 + 2^-40) therefore settles, without the sum, that S is
+// neither below the floor nor below tol^2 nor within the 1e-14 band around tol^2 in which the reference's sqrt form is evaluated (a
+// NaN partial elsewhere in the segment makes S NaN: the three comparisons are false then too).  The lower limit 2^-1000 keeps the
+// statement true where tol^2 is subnormal and the relative margins round away.  Wave-uniform (scalar registers).
+__device__ __forceinline__ double screen_theta(double tol2, double floor2) {
+    const double th = __builtin_fmax(__builtin_fmax(tol2, floor2) * (1.0 + 0x1p-40), 0x1p-1000);
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(th)), __builtin_amdgcn_readfirstlane(__double2loint(th)));
+}
+// does every LPP-lane segment with a bit in `need` have a bit in `have`?  (power-of-two segments; scalar bit operations)
+template <int LPP>
+__device__ __forceinline__ bool seg_covered(mask_t have, mask_t need) {
+    static_assert(LPP == 16 || LPP == 32 || LPP == 64, "power-of-two segments");
+    if (LPP == 64) return need == 0 || have != 0;
+    // (32-bit words: scalar compares; a 64-bit "greater than" of two masks becomes vector instructions)
+    const unsigned nw[2] = {(unsigned)need, (unsigned)(need >> 32)}, hw[2] = {(unsigned)have, (unsigned)(have >> 32)};
+    bool ok = true;
+    UNROLL for (int w = 0; w < 2; ++w) {
+        UNROLL for (int k = 0; k < 32 / LPP; ++k) {
+            const unsigned m = LPP == 32 ? ~0u : 0xffffu << (16 * k);
+            ok = ok && ((nw[w] & m) == 0 || (hw[w] & m) != 0);
+        }
+    }
+    return ok;
+}
+
 // The two decisions of a FISTA step -- retry (cv > (L/2) g2) and exit (g2 < tol^2) -- from WAVE sums of g2 and cv taken in fp32:
 // 4 DPP-fused v_add_f32 per value, one v_permlane16_swap that leaves the sums of g2 in rows 0 / 2 and of cv in rows 1 / 3, one
 // v_permlane32_swap, two v_readlane: 19 instructions against the 36 of the fp64 butterfly (seg_sum2<64>).  The fp32 sums of
@@ -272,6 +299,15 @@ __device__ __forceinline__ double fmaxR(double a, double b) { return __builtin_f
 __device__ __forceinline__ float fmaxR(float a, float b) { return __builtin_fmaxf(a, b); }
 __device__ __forceinline__ double fminR(double a, double b) { return __builtin_fmin(a, b); }
 __device__ __forceinline__ float fminR(float a, float b) { return __builtin_fminf(a, b); }
+
+// fma(a, b, c) as the three-address instruction, result in registers of its own.  hipcc selects v_fmac_f64, which leaves the result in
+// c's registers; where the result is loop-carried and c is not (the momentum step y+ = x+ + cm (x+ - x): c is x+, the result the next
+// iteration's y), every value then takes a v_mov_b64 to its place at the loop's end.  The same operation, hence the same bits.
+__device__ __forceinline__ double fma3(double a, double b, double c) {
+    double r;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
 
 // The box projection max(min(v, hi), lo) as the two bare instructions.  Through fmin / fmax hipcc re-quiets the bounds inside
 // the FISTA loop (`v_max_f64 x, x, x` in front of every min / max: six extra instructions per motion iteration), although

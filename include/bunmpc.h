@@ -190,8 +190,14 @@ int bmpc_biconvex_last_waves_per_simd(void);
 /* Two centroidal kernels take the decisions of a FISTA step (retry, fista.cpp:16; exit, fista.cpp:29) from fp32 sums whenever every
  * comparison of the wave's live problems is clear of its threshold by 1e-5 relative, from the fp64 sums and the reference expression
  * otherwise: the one-problem-per-wave kernel, and the two-waves-per-SIMD build of the batch kernel at 32 lanes per problem, four feet,
- * harness form (the benchmark's kernel).  Every other kernel always uses the fp64 sums.  on = 1: those two as well
- * (a test switch: results must be bit-identical either way).  Returns the old value. */
+ * harness form (the benchmark's kernel).  Every other kernel always uses the fp64 sums.  The benchmark's kernel
+ * also screens the iterations of its certified loops lane by lane: a lane whose own share of the squared step is above
+ * max(tol^2, floor) (1 + 2^-40) settles its problem's exit and floor decisions without any sum.
+ *   on = 0 (default): the screen, then the fp32 decisions, then the fp64 sums;
+ *   on = 1: every decision from the fp64 sums, no screen, in both kernels (what the A/B tests compare against);
+ *   on = 2: the benchmark's kernel takes the fp32 decisions without the screen; the one-problem-per-wave kernel has no screen and
+ *           reads any non-zero value as 1.
+ * A test switch: results must be bit-identical under every value.  Returns the old value. */
 int bmpc_set_exact_step_decisions(int on);
 /* The fp64 batch kernels skip FISTA's backtracking test for a whole force step (one ADMM iteration's force-QP loop) of a wave whose
  * live problems all carry a certificate that the test cannot fire: a diagonally scaled Gershgorin bound of the step's Hessian

@@ -6,10 +6,15 @@ iteration that takes none of the branches it can skip -- the cone step, the retr
 decisions), with that path's fp64 arithmetic (v_fma_f64, v_fmac_f64, v_mul_f64, v_add_f64), DPP moves, DPP-fused operations and
 permlanes.  Also the kernel's registers, scratch and static LDS as the compiler reports them.
 
-    python tools/loop_valu.py LISTING.s KERNEL_SUBSTRING [--through RE] [--blocks]
-    python tools/loop_valu.py --compile bunmpc_amd/csrc/biconvex_admm.hip KERNEL_SUBSTRING [--through RE] [--blocks]
+    python tools/loop_valu.py LISTING.s KERNEL_SUBSTRING [--through RE]... [--committing] [--blocks]
+    python tools/loop_valu.py --compile bunmpc_amd/csrc/biconvex_admm.hip KERNEL_SUBSTRING [--through RE]... [--committing] [--blocks]
         (--compile: device code of the unit with bunmpc_amd/build.py's flags for it; --through RE: the cheapest path that runs an
-        instruction matching RE, e.g. 'permlane' for an iteration that reduces its sums -- in fp32 where it can)
+        instruction matching RE, e.g. 'permlane' for an iteration that reduces its sums -- in fp32 where it can; given more than
+        once: a path that runs an instruction of every RE, each in a block of its own; --committing: --through ds_write2, the
+        iteration that writes x_{k+1} and its image back to LDS.  The plain cheapest path of a certified loop is NOT an iteration
+        that commits: it leaves the loop before applyA(xn), the momentum step and the write-back.  The headline kernel's certified
+        loops: --committing is the screened iteration, --committing --through permlane16 the one that takes the fp32 sum; in the
+        force loop, whose two unrolled copies are one loop here, the path runs one copy and leaves by the other's exit test.)
 
 The headline kernel: 'biconvex_admm_kernelIdLi32ELi4ELb0ELb0ELi2E' (biconvex_admm_kernel<double, 32, 4, false, false, 2>)."""
 import collections
@@ -75,9 +80,11 @@ def resources(lines, end):
 
 def main():
     argv = sys.argv[1:]
-    through = argv[argv.index("--through") + 1] if "--through" in argv else None
-    if through:
+    through = ["ds_write2"] if "--committing" in argv else []
+    while "--through" in argv:
+        through.append(argv[argv.index("--through") + 1])
         del argv[argv.index("--through"):argv.index("--through") + 2]
+    want = (1 << len(through)) - 1
     args = [a for a in argv if not a.startswith("--")]
     listing = compile_listing(args[0]) if "--compile" in sys.argv else args[0]
     lines = open(listing).read().split("\n")
@@ -106,19 +113,20 @@ def main():
         for src, dst, _ in edges:
             if a <= src < dst <= b:
                 succ[src].add(dst)
-        # (--through RE: the cheapest path that executes an instruction matching RE -- the segment sums: 'permlane')
-        has = [bool(through) and any(re.search(through, t) for _, t in blk[2]) for blk in blocks]
-        cost, prev = {(a, has[a] or not through): (nvalu[a], None)}, {}
+        # (--through RE: the cheapest path that executes an instruction matching RE -- the segment sums: 'permlane'; the state of the
+        # search is the block and the set of REs met so far, as a bit mask)
+        has = [sum(1 << j for j, rx in enumerate(through) if any(re.search(rx, t) for _, t in blk[2])) for blk in blocks]
+        cost = {(a, has[a]): (nvalu[a], None)}
         for k in range(a, b + 1):
-            for seen in (False, True):
+            for seen in range(want + 1):
                 if (k, seen) in cost:
                     for n in succ[k]:
-                        st = (n, seen or has[n])
+                        st = (n, seen | has[n])
                         c = cost[(k, seen)][0] + nvalu[n]
                         if st not in cost or c < cost[st][0]:
                             cost[st] = (c, (k, seen))
-        path, st = [], (b, True)
-        while st is not None and (b, True) in cost:
+        path, st = [], (b, want)
+        while st is not None and (b, want) in cost:
             path.append(st[0])
             st = cost[st][1]
         hot = [(mn, t) for k in path for mn, t in blocks[k][2]]
