@@ -45,6 +45,11 @@ class Cone(C.Structure):
     _fields_ = [("projection", C.c_int), ("mu", C.c_void_p), ("smu", C.c_long)]
 
 
+class ContactFrame(C.Structure):
+    """bmpc_contact_frame_t"""
+    _fields_ = [("normals", C.c_void_p), ("snormals", C.c_long)]
+
+
 class LaunchPlan(C.Structure):
     """bmpc_launch_plan_t"""
     _fields_ = [("status", C.c_int), ("lanes_per_problem", C.c_int), ("waves_per_simd", C.c_int), ("steal", C.c_int), ("steal_waves", C.c_long),
@@ -189,6 +194,12 @@ _SIGS = {
     "bmpc_biconvex_set_cone_projection": (_I, [_P, _I]),
     "bmpc_biconvex_set_friction_coefficients": (_I, [_P, _P]),
     "bmpc_biconvex_cone_kernel_scratch_bytes": (_I, [_I]),
+    "bmpc_contact_frame_struct_size": (_I, []),
+    "bmpc_biconvex_solve_batch_cone_frames_device": (_I, [_P, _P, _P, _P]),
+    "bmpc_biconvex_solve_batch_cone_frames_host": (_I, [_P, _P, _P]),
+    "bmpc_biconvex_set_contact_normals": (_I, [_P, _P]),
+    "bmpc_biconvex_set_contact_normals_from_rotations": (_I, [_P]),
+    "bmpc_biconvex_cone_frame_kernel_scratch_bytes": (_I, [_I]),
     "bmpc_biconvex_kernel_name": (C.c_char_p, [_I, _I]),
     "bmpc_biconvex_last_kernel_name": (C.c_char_p, []),
     "bmpc_biconvex_plan_launch": (_I, [_P, _I, C.c_long, _P]),
@@ -331,6 +342,8 @@ def lib():
             raise ImportError("bmpc_band_cost_t layout differs between include/bunmpc.h and bunmpc_amd/_lib.py")
         if handle.bmpc_cone_struct_size() != C.sizeof(Cone):
             raise ImportError("bmpc_cone_t layout differs between include/bunmpc.h and bunmpc_amd/_lib.py")
+        if handle.bmpc_contact_frame_struct_size() != C.sizeof(ContactFrame):
+            raise ImportError("bmpc_contact_frame_t layout differs between include/bunmpc.h and bunmpc_amd/_lib.py")
         if handle.bmpc_ik_batch_struct_size() != C.sizeof(IkBatch):
             raise ImportError("bmpc_ik_batch_t layout differs between include/bunmpc.h and bunmpc_amd/_lib.py")
         _lib = handle

@@ -49,13 +49,14 @@ PROJECTIONS = {"reference": 0, "euclidean": 1}
 
 
 def _cone_ext(cone, B, H, E, put):
-    """bmpc_cone_t of cone = dict(projection="reference" | "euclidean", mu=None | array (1 or B, H, E)); put(array) -> its address after
-    whatever copy the caller needs (its result is kept by the caller).  None without a dict."""
+    """bmpc_cone_t of cone = dict(projection="reference" | "euclidean", mu=None | array (1 or B, H, E), normals=None | array (1 or B, H, E,
+    3)); put(array) -> its address after whatever copy the caller needs (its result is kept by the caller).  None without a dict.
+    With normals: (bmpc_cone_t, bmpc_contact_frame_t)."""
     if cone is None:
         return None
-    unknown = set(cone) - {"projection", "mu"}
+    unknown = set(cone) - {"projection", "mu", "normals"}
     if unknown or cone.get("projection", "reference") not in PROJECTIONS:
-        raise ValueError("cone: expected dict(projection=\"reference\" | \"euclidean\", mu=None | array), got %r" % (cone,))
+        raise ValueError("cone: expected dict(projection=\"reference\" | \"euclidean\", mu=None | array, normals=None | array), got %r" % (cone,))
     c = _lib.Cone(projection=PROJECTIONS[cone.get("projection", "reference")])
     mu = cone.get("mu")
     if mu is not None:
@@ -63,6 +64,14 @@ def _cone_ext(cone, B, H, E, put):
             raise ValueError("cone mu: expected shape (1 or %d, %d, %d), got %s" % (B, H, E, np.shape(mu)))
         c.mu = put(mu)
         c.smu = 0 if np.shape(mu)[0] == 1 else H * E
+    normals = cone.get("normals")
+    if normals is not None:
+        if cone.get("projection", "reference") != "euclidean":
+            raise ValueError("cone normals need projection=\"euclidean\": the reference's \"SoC\" step is about world z")
+        if np.ndim(normals) != 4 or np.shape(normals)[1:] != (H, E, 3) or np.shape(normals)[0] not in (1, B):
+            raise ValueError("cone normals: expected shape (1 or %d, %d, %d, 3), got %s" % (B, H, E, np.shape(normals)))
+        fr = _lib.ContactFrame(normals=put(normals), snormals=0 if np.shape(normals)[0] == 1 else 3 * H * E)
+        return c, fr
     return c
 
 
@@ -73,6 +82,8 @@ def _launch(desc, blocks, band, stream=None, cone=None):
     if cone is not None:
         if blocks is not None or band is not None:
             raise ValueError("cone= cannot be combined with Qx_blk / Qf_blk or Qx_off / Qf_off: the cone kernels hold diagonal costs only")
+        if isinstance(cone, tuple):      # (with contact normals)
+            return _lib.check(getattr(lib, "bmpc_biconvex_solve_batch_cone_frames_" + where)(C.byref(desc), C.byref(cone[0]), C.byref(cone[1]), *tail))
         return _lib.check(getattr(lib, "bmpc_biconvex_solve_batch_cone_" + where)(C.byref(desc), C.byref(cone), *tail))
     for kind, cost in (("blocks_", blocks), ("band_", band)):
         if cost is not None:
@@ -100,8 +111,9 @@ class DeviceBatch:
         raw: dict(Qx, qx, lbx, ubx, Qf[, qf][, Qx_blk][, Qf_blk]) -- the raw cost / bound form (solve_host explains it); with
         Qx_blk / Qf_blk the per-knot block costs, through bmpc_biconvex_solve_batch_blocks_device; with Qx_off / Qf_off the costs
         between neighbouring knots, through bmpc_biconvex_solve_batch_band_device
-        cone: dict(projection="reference" | "euclidean", mu=None | array (1 or B, H, E)) -- the force step's projection and per-foot
-        friction coefficients, through bmpc_biconvex_solve_batch_cone_device (solve_host explains it)"""
+        cone: dict(projection="reference" | "euclidean", mu=None | array (1 or B, H, E)[, normals=array (1 or B, H, E, 3)]) -- the force
+        step's projection, per-foot friction coefficients and contact normals, through bmpc_biconvex_solve_batch_cone_device or, with
+        normals, bmpc_biconvex_solve_batch_cone_frames_device (solve_host explains it)"""
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("DeviceBatch needs a GPU: no CPU fallback exists for the solve")
@@ -139,10 +151,14 @@ class DeviceBatch:
                 raise ValueError(_COMBINED)
             self.band = _cost_ext("off", B, H, E, self.tk.get("Qx_off"), self.tk.get("Qf_off"), lambda t: t.data_ptr())
 
-        def up_mu(a):
-            self.t_mu = up(a)
-            return self.t_mu.data_ptr()
-        self.cone = _cone_ext(cone, B, H, E, up_mu)
+        self.t_cone = []      # (the coefficients and the normals on the device)
+
+        def up_cone(a):
+            self.t_cone.append(up(a))
+            return self.t_cone[-1].data_ptr()
+        self.cone = _cone_ext(cone, B, H, E, up_cone)
+        if cone is not None and cone.get("mu") is not None:
+            self.t_mu = self.t_cone[0]
         self.X = torch.empty((B, 9 * (H + 1)), dtype=f64, device=self.device)
         self.F = torch.empty((B, 3 * E * H), dtype=f64, device=self.device)
         self.P = torch.empty((B, 9 * (H + 1)), dtype=f64, device=self.device)
@@ -227,7 +243,9 @@ def solve_host(batch, num_iters=10, maxit=150, tol=1e-5, exit_tol=1e-3, beta=1.5
     kernel records none).  cone = dict(projection="euclidean", mu=None | array (1 or B, H, E)): the force step projects onto the
     friction cone |f_xy| <= mu f_z (the nearest point; the default, "reference", is the reference's "SoC" step) with a coefficient per
     problem, knot and foot (a leading dimension of 1: shared by the batch; None: the scalar mu) -- either form, fp64, H + 1 <= 64, not
-    together with blocks or band costs (bmpc_biconvex_solve_batch_cone_host)."""
+    together with blocks or band costs (bmpc_biconvex_solve_batch_cone_host).  With normals=array (1 or B, H, E, 3) in it, unit vectors in
+    the world frame, the cone of a contact is about its surface normal instead of world z: |f - (n.f) n| <= mu n.f
+    (bmpc_biconvex_solve_batch_cone_frames_host; "euclidean" only)."""
     B, H, E = batch.B, batch.H, batch.E
     nx, nf = 9 * (H + 1), 3 * E * H
     keep = []

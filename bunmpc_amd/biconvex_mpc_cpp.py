@@ -251,6 +251,24 @@ class BiconvexMP:
         mu = np.ascontiguousarray(np.broadcast_to(mu, (self.n_col, self.n_eff)))
         _lib.check(self._lib.bmpc_biconvex_set_friction_coefficients(self._h, mu.ctypes.data))
 
+    def set_contact_normals(self, normals):
+        """Unit normals of the contacts in the world frame, (n_col, n_eff, 3), or one per foot (n_eff, 3) for every knot: the friction
+        cone of a contact is about its normal instead of world z.  None: back to world z.  Needs set_cone_projection("euclidean");
+        persists across optimize calls."""
+        if normals is None:
+            _lib.check(self._lib.bmpc_biconvex_set_contact_normals(self._h, None))
+            return
+        n = np.asarray(normals, dtype=np.float64)
+        if n.shape not in ((self.n_eff, 3), (self.n_col, self.n_eff, 3)):
+            raise ValueError("normals: expected (%d, 3) or (%d, %d, 3), got %s" % (self.n_eff, self.n_col, self.n_eff, n.shape))
+        n = np.ascontiguousarray(np.broadcast_to(n, (self.n_col, self.n_eff, 3)))
+        _lib.check(self._lib.bmpc_biconvex_set_contact_normals(self._h, n.ctypes.data))
+
+    def use_rotation_matrices_as_contact_frames(self):
+        """The contact normals from the matrices of set_rotation_matrix_f -- the third row of each, local z in the world frame; exactly
+        n_col * n_eff matrices, knot-major."""
+        _lib.check(self._lib.bmpc_biconvex_set_contact_normals_from_rotations(self._h))
+
     def set_robot_mass(self, m):
         _lib.check(self._lib.bmpc_biconvex_set_robot_mass(self._h, float(m)))
 

@@ -17,7 +17,7 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
-SOURCES = ["biconvex_admm.hip", "biconvex_admm_e2.hip", "biconvex_admm_bq.hip", "biconvex_admm_bq_e2.hip", "biconvex_admm_kq.hip", "biconvex_admm_kq_e2.hip", "biconvex_admm_cone.hip", "biconvex_admm_cone_e2.hip", "biconvex_admm_f32.hip", "biconvex_admm_f32_e2.hip", "biconvex_latency.hip", "bunmpc_capi.hip", "ik_ddp.hip", "bunmpc_ik_capi.hip", "plan_gen.hip", "id_ctrl.hip", "perturb.hip"]
+SOURCES = ["biconvex_admm.hip", "biconvex_admm_e2.hip", "biconvex_admm_bq.hip", "biconvex_admm_bq_e2.hip", "biconvex_admm_kq.hip", "biconvex_admm_kq_e2.hip", "biconvex_admm_cone.hip", "biconvex_admm_cone_e2.hip", "biconvex_admm_conef.hip", "biconvex_admm_conef_e2.hip", "biconvex_admm_f32.hip", "biconvex_admm_f32_e2.hip", "biconvex_latency.hip", "bunmpc_capi.hip", "ik_ddp.hip", "bunmpc_ik_capi.hip", "plan_gen.hip", "id_ctrl.hip", "perturb.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("biconvex_kernels.h", "biconvex_lanes.h", "biconvex_admm_body.h", "biconvex_admm_inst.h", "ik_types.h", "ik_plan.h", "rbd_device.h", "rbd_quad.h", "lds_batch.h", "id_types.h", "perturb_types.h")] + \
           [os.path.join(os.path.dirname(_HERE), "include", "bunmpc.h")]
 LIB = os.path.join(_HERE, "libbunmpc_hip.so")
@@ -43,14 +43,14 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # pass against register pressure -- the kernel has 512 registers to itself): headline 4.014 -> 3.98 ms (64-lane shape 8.95 -> 9.0).
 # No effect or worse on top: -amdgpu-schedule-metric-bias=0, -amdgpu-schedule-relaxed-occupancy, -amdgpu-early-ifcvt, max-ilp,
 # -amdgpu-disable-clustered-low-occupancy-reschedule.
-# The ten centroidal units share two flag lists (one header, biconvex_admm_inst.h, holds all their kernels and launches; each unit
+# The twelve centroidal units share two flag lists (one header, biconvex_admm_inst.h, holds all their kernels and launches; each unit
 # instantiates its own): _FP64_ADMM_FLAGS for biconvex_admm.hip and its two-feet (_e2), block-cost (_bq, _bq_e2), neighbour-knot-cost
-# (_kq, _kq_e2) and cone-projection (_cone, _cone_e2) siblings, _FP32_ADMM_FLAGS for biconvex_admm_f32.hip and biconvex_admm_f32_e2.hip.
+# (_kq, _kq_e2) cone-projection (_cone, _cone_e2) and cone-about-normals (_conef, _conef_e2) siblings, _FP32_ADMM_FLAGS for biconvex_admm_f32.hip and biconvex_admm_f32_e2.hip.
 _FP64_ADMM_FLAGS = ["-mllvm", "-amdgpu-use-amdgpu-trackers", "-mllvm", "-amdgpu-disable-unclustered-high-rp-reschedule"]
 _FP32_ADMM_FLAGS = ["-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 FILE_FLAGS = {"ik_ddp.hip": ["-ffp-contract=on"],
               "biconvex_latency.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
-FILE_FLAGS.update({"biconvex_admm%s.hip" % unit: _FP64_ADMM_FLAGS for unit in ("", "_e2", "_bq", "_bq_e2", "_kq", "_kq_e2", "_cone", "_cone_e2")})
+FILE_FLAGS.update({"biconvex_admm%s.hip" % unit: _FP64_ADMM_FLAGS for unit in ("", "_e2", "_bq", "_bq_e2", "_kq", "_kq_e2", "_cone", "_cone_e2", "_conef", "_conef_e2")})
 FILE_FLAGS.update({"biconvex_admm%s.hip" % unit: _FP32_ADMM_FLAGS for unit in ("_f32", "_f32_e2")})
 
 

@@ -164,6 +164,7 @@ const AdmmUnit &admm_unit(CostShape shape, int precision, int n_eff) {
     if (shape == kBlocks) return four ? admm_unit_bq_e4() : admm_unit_bq_e2();
     if (shape == kBand) return four ? admm_unit_kq_e4() : admm_unit_kq_e2();
     if (shape == kCone) return four ? admm_unit_cone_e4() : admm_unit_cone_e2();
+    if (shape == kConeFrame) return four ? admm_unit_conef_e4() : admm_unit_conef_e2();
     if (precision == 1) return four ? admm_unit_f32_e4() : admm_unit_f32_e2();
     return four ? admm_unit_e4() : admm_unit_e2();
 }
@@ -182,19 +183,19 @@ const char *biconvex_last_kernel_name() { return t_last_kernel; }
 // Which kernel a batch gets.  Block and band costs: their own kernels at every batch size and num_iters -- never the
 // one-problem-per-wave, work-stealing, workgroup or two-waves kernels, which hold diagonal weights only -- with every step tested on
 // the fp64 sums; the lanes per problem are chosen as for diagonal costs.  The Euclidean cone projection (kCone): likewise, in either form
-// (those other kernels restate the reference's projection only).
+// (those other kernels restate the reference's projection only); about per-contact normals (kConeFrame): exactly as kCone.
 LaunchPlan plan_launch(const BatchArgs &a, CostShape shape, int n_eff, long simds, const DispatchKnobs &kn) {
     LaunchPlan p = {hipErrorInvalidValue, nullptr, {0, false, false, 0, {}}, false, a.certified_steps};
-    const bool diag = shape == kDiag;
+    const bool diag = shape == kDiag, cone = shape == kCone || shape == kConeFrame;
     const int k = a.H + 1;
     const bool built = diag ? k <= kMaxKnots && (a.precision == 0 || a.precision == 1)
-                            : (shape == kCone ? k <= 64 && a.precision == 0      // (cone: fp64, one problem per wave segment)
+                            : (cone ? k <= 64 && a.precision == 0      // (cone: fp64, one problem per wave segment)
                                               : (shape == kBlocks || shape == kBand) && k <= 64 && a.precision == 0 && a.raw);      // (blocks / band: raw form, fp64, one problem per wave segment)
     if ((n_eff != 2 && n_eff != 4) || a.H < 1 || a.B < 0 || !built) return p;
     if (a.B == 0) { p.status = hipSuccess; return p; }
     if (a.c.maxit > kMaxFistaIters) return p;
     // the kernels address a wave's problems by 32-bit byte offsets from the wave's first problem (at most four problems)
-    if (diag || (shape == kCone && !a.raw))
+    if (diag || (cone && !a.raw))
         for (long stride : {a.sW_X, a.sW_X_ter, a.sW_F, a.sbounds})
             if (stride < 0 || stride > (1L << 26)) return p;
     p.status = hipSuccess;
@@ -205,7 +206,7 @@ LaunchPlan plan_launch(const BatchArgs &a, CostShape shape, int n_eff, long simd
         return p;
     }
     p.certified_steps = !diag ? 0 : (kn.certified_steps == 2 ? 2 : (kn.certified_steps != 0 ? 1 : 0));      // (2: force phases only)
-    p.kernel = shape == kCone ? "biconvex_admm_cone_kernel" : shape == kBlocks ? "biconvex_admm_bq_kernel" : (shape == kBand ? "biconvex_admm_kq_kernel" : (a.precision == 1 ? "biconvex_admm_kernel_f32" : "biconvex_admm_kernel"));
+    p.kernel = shape == kConeFrame ? "biconvex_admm_conef_kernel" : shape == kCone ? "biconvex_admm_cone_kernel" : shape == kBlocks ? "biconvex_admm_bq_kernel" : (shape == kBand ? "biconvex_admm_kq_kernel" : (a.precision == 1 ? "biconvex_admm_kernel_f32" : "biconvex_admm_kernel"));
     // the same decisions for two feet as for four, with the LDS record of the foot count (knot_lds)
     auto segments = [&](int lpp) { p.l.lpp = lpp; p.l.w2 = diag && two_per_simd_pays(a, 64 / lpp, simds, kn); return p; };
     if (k <= 16) return segments(16);

@@ -77,8 +77,18 @@ constexpr int sym_index(int n, int r, int c) { return r <= c ? r * n - r * (r - 
 // CONE operation is under `if constexpr`: the other instantiations compile what they compiled without it.
 // (A CONE instantiation has no band costs, and its coefficients come in the band costs' place: a fourth argument, even an empty
 // struct, is one more temporary in every kernel and reordered the block kernels' prologues.)
-template <typename R, int LPP, int E, bool RAW, bool HASQF, bool STEAL = false, bool XLDS = false, int WAVES = 1, bool BQ = false, bool KQ = false, bool CONE = false>
-__device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &bq = BlockArgs{}, const std::conditional_t<CONE, ConeArgs, BandArgs> &kq = std::conditional_t<CONE, ConeArgs, BandArgs>{}) {
+//
+// FRAME (CONE about per-contact surface normals, ConeFrameArgs): the cone's axis is the unit normal n of the foot's contact at the lane's
+// knot, world frame, instead of world z.  With fn = n.f, ft = f - fn n, s2 = |ft|^2 the three branches are CONE's with fn for fz --
+// origin, the step's own bits, or k ft + t n with t = (mu s + fn) / (mu^2 + 1), k = mu t / s -- behind the same ballot.  The
+// accumulation orders (fn = fma(nx, fx, fma(ny, fy, nz fz)), ft = fma(-fn, n, f), s2 = fma(ftx, ftx, fma(ftz, ftz, fty fty)), each
+// output fma(t, n_i, k ft_i)) make every extra term an exact zero for n = (0, 0, 1): the cone kernel's values, up to the sign of a zero.
+// A lane loads its knot's 3E normal components once per solve, beside the coefficients, and keeps them (the compiler rests them in
+// accumulation registers; lanes without a force knot: world z).  The kernel does not normalise.  Every FRAME operation is under
+// `if constexpr`, and its arguments come in the same third slot.
+template <typename R, int LPP, int E, bool RAW, bool HASQF, bool STEAL = false, bool XLDS = false, int WAVES = 1, bool BQ = false, bool KQ = false, bool CONE = false, bool FRAME = false>
+__device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &bq = BlockArgs{}, const std::conditional_t<FRAME, ConeFrameArgs, std::conditional_t<CONE, ConeArgs, BandArgs>> &kq = std::conditional_t<FRAME, ConeFrameArgs, std::conditional_t<CONE, ConeArgs, BandArgs>>{}) {
+    static_assert(!FRAME || CONE, "per-contact normals: the Euclidean cone projection only");
     static_assert(!CONE || (!BQ && !KQ && !STEAL && !XLDS && WAVES == 1 && LPP <= 64 && sizeof(R) == sizeof(double)), "Euclidean cone projection: diagonal costs, fp64, one problem per <= 64 lanes, one wave per SIMD");
     static_assert(!BQ || (RAW && !STEAL && !XLDS && WAVES == 1 && sizeof(R) == sizeof(double)), "block costs: raw form, fp64, one wave per problem, one wave per SIMD");
     static_assert(!KQ || (RAW && !BQ && !STEAL && !XLDS && WAVES == 1 && sizeof(R) == sizeof(double)), "neighbour-knot costs: raw form, diagonal per-knot weights, fp64, one wave per problem, one wave per SIMD");
@@ -371,6 +381,13 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
             UNROLL for (int n = 0; n < E; ++n) muf[n] = mu;
         }
     }
+    // FRAME: ... and the unit normals of its contacts, three components per foot (lanes without a force knot read an existing element,
+    // as above, and take world z)
+    [[maybe_unused]] R nrm[FRAME ? NF : 1];
+    if constexpr (FRAME) {
+        const unsigned oN = 8u * (sl * (unsigned)kq.snormals + (unsigned)NF * tr);
+        UNROLL for (int j = 0; j < NF; ++j) { const double v = at(kq.normals + wave0 * kq.snormals, oN)[j]; nrm[j] = rvalid ? (R)v : R(j % 3 == 2 ? 1 : 0); }
+    }
 
     // BAND: how many force and motion phases of the problem ran the certified loop from their first iteration (BatchArgs::cert_phases),
     // counted by lane 0 in two ints of LDS nothing else uses -- the F block of knot H's record (the last knot has no forces) -- once per
@@ -574,6 +591,21 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                         fr[3 * n] = fmaR(-gx, invL, y[3 * n]);
                         fr[3 * n + 1] = fmaR(-gy, invL, y[3 * n + 1]);
                         fr[3 * n + 2] = fmaR(-gz, invL, y[3 * n + 2]);
+                        if constexpr (FRAME) {     // the Euclidean projection about the contact's normal: fn along it, s2 = |f - fn n|^2
+                            const R nx = nrm[3 * n], ny = nrm[3 * n + 1], nz = nrm[3 * n + 2];
+                            const R fn = fmaR(nx, fr[3 * n], fmaR(ny, fr[3 * n + 1], nz * fr[3 * n + 2]));
+                            const R tx = fmaR(-fn, nx, fr[3 * n]), ty = fmaR(-fn, ny, fr[3 * n + 1]), tz = fmaR(-fn, nz, fr[3 * n + 2]);
+                            const R s2 = fmaR(tx, tx, fmaR(tz, tz, ty * ty));
+                            const R m2 = muf[n] * muf[n], z2 = fn * fn;
+                            const bool zero = fn <= R(0) && m2 * s2 <= z2;      // (the polar cone; wins at the origin)
+                            const bool inside = fn >= R(0) && s2 <= m2 * z2;
+                            anycone |= __ballot(!zero && !inside);
+                            const R keep = zero ? R(0) : R(1);
+                            xn[3 * n] = keep * fr[3 * n];
+                            xn[3 * n + 1] = keep * fr[3 * n + 1];
+                            xn[3 * n + 2] = keep * fr[3 * n + 2];
+                            continue;
+                        }
                         const R s = fmaR(fr[3 * n], fr[3 * n], fr[3 * n + 1] * fr[3 * n + 1]);
                         const R fz = fr[3 * n + 2];
                         if constexpr (CONE) {      // the Euclidean projection: origin, unchanged, or (below) the cone's surface
@@ -594,6 +626,24 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                         xn[3 * n + 2] = keep * fz;
                         }
                     }
+                    if constexpr (FRAME) {
+                        if (anycone != 0) {   // a force outside both cones: onto the surface k ft + t n; skipped while no lane needs it
+                            UNROLL for (int n = 0; n < E; ++n) {
+                                const R nx = nrm[3 * n], ny = nrm[3 * n + 1], nz = nrm[3 * n + 2], mf = muf[n];
+                                const R fn = fmaR(nx, fr[3 * n], fmaR(ny, fr[3 * n + 1], nz * fr[3 * n + 2]));
+                                const R tx = fmaR(-fn, nx, fr[3 * n]), ty = fmaR(-fn, ny, fr[3 * n + 1]), tz = fmaR(-fn, nz, fr[3 * n + 2]);
+                                const R s2 = fmaR(tx, tx, fmaR(tz, tz, ty * ty));
+                                const R m2 = mf * mf, z2 = fn * fn;
+                                const bool surf = !(fn <= R(0) && m2 * s2 <= z2) && !(fn >= R(0) && s2 <= m2 * z2);
+                                const R s = sqrt(s2);
+                                const R tn = fast_div(fmaR(mf, s, fn), m2 + R(1));
+                                const R k = fast_div(mf * tn, s);      // (s > 0 on this branch: s2 = 0 is the origin or inside)
+                                xn[3 * n] = surf ? fmaR(tn, nx, k * tx) : xn[3 * n];
+                                xn[3 * n + 1] = surf ? fmaR(tn, ny, k * ty) : xn[3 * n + 1];
+                                xn[3 * n + 2] = surf ? fmaR(tn, nz, k * tz) : xn[3 * n + 2];
+                            }
+                        }
+                    } else
                     if constexpr (CONE) {
                         if (anycone != 0) {   // a force outside both cones: onto the surface; skipped while no lane needs it
                             UNROLL for (int n = 0; n < E; ++n) {

@@ -7,6 +7,8 @@
 //   biconvex_admm_bq_e2.hip  blocks, E = 2                    biconvex_admm_kq_e2.hip    band, E = 2
 //   biconvex_admm_cone.hip   Euclidean cone projection, E = 4   launch_cone
 //   biconvex_admm_cone_e2.hip                           E = 2
+//   biconvex_admm_conef.hip  ... about per-contact normals, E = 4   launch_conef
+//   biconvex_admm_conef_e2.hip                             E = 2
 // so that every unit is built with its own flags (bunmpc_amd/build.py), the units build in parallel and one feature's kernels cannot
 // disturb another's code object.  Which kernel a batch gets is decided once, for every unit, by plan_launch (biconvex_admm.hip).
 #pragma once
@@ -56,6 +58,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 template <int LPP, int E, bool RAW, bool HASQF>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void biconvex_admm_cone_kernel(const BatchArgs a, const ConeArgs c) {
     admm_body<double, LPP, E, RAW, HASQF, false, false, 1, false, false, true>(a, BlockArgs{}, c);
+}
+// ... about per-contact surface normals (biconvex_admm_body.h: FRAME): the cone kernel, and a lane keeps its knot's 3E normal components
+// beside the E coefficients.
+template <int LPP, int E, bool RAW, bool HASQF>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void biconvex_admm_conef_kernel(const BatchArgs a, const ConeFrameArgs c) {
+    admm_body<double, LPP, E, RAW, HASQF, false, false, 1, false, false, true, true>(a, BlockArgs{}, c);
 }
 
 // The one switch over the lanes per problem: f(std::integral_constant<int, LPP>) of the plan's lpp.  A launch names the values its unit
@@ -175,6 +183,19 @@ hipError_t launch_cone(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stre
                          : launch_segments<LPP, E>(biconvex_admm_cone_kernel<LPP, E, true, false>, sizeof(double), a, stream, c);
     });
 }
+// ... the same about per-contact normals (l.cost.x, never null here: without normals the C-ABI takes the cone kernel)
+template <int E>
+hipError_t launch_conef(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream) {
+    if (a.precision != 0 || a.H + 1 > l.lpp || !l.cost.x) return hipErrorInvalidValue;
+    const ConeFrameArgs c = {l.cost.f, l.cost.sf, l.cost.x, l.cost.sx};
+    return with_lpp(l.lpp, [&](auto lanes) {
+        constexpr int LPP = decltype(lanes)::value;
+        if constexpr (LPP > 64) return hipErrorInvalidValue;
+        else if (!a.raw) return launch_segments<LPP, E>(biconvex_admm_conef_kernel<LPP, E, false, false>, sizeof(double), a, stream, c);
+        else return a.qf ? launch_segments<LPP, E>(biconvex_admm_conef_kernel<LPP, E, true, true>, sizeof(double), a, stream, c)
+                         : launch_segments<LPP, E>(biconvex_admm_conef_kernel<LPP, E, true, false>, sizeof(double), a, stream, c);
+    });
+}
 
 // private-segment (scratch) bytes per lane, the largest over the kernels listed
 template <typename... K>
@@ -230,6 +251,19 @@ template <int E>
 int cone_scratch_bytes() {
     int worst = 0;
     for (int s : {cone_lpp_scratch_bytes<E, 16>(), cone_lpp_scratch_bytes<E, 21>(), cone_lpp_scratch_bytes<E, 32>(), cone_lpp_scratch_bytes<E, 64>()}) {
+        if (s < 0) return -1;
+        worst = s > worst ? s : worst;
+    }
+    return worst;
+}
+template <int E, int LPP>
+int conef_lpp_scratch_bytes() {
+    return max_scratch_bytes(&biconvex_admm_conef_kernel<LPP, E, false, false>, &biconvex_admm_conef_kernel<LPP, E, true, false>, &biconvex_admm_conef_kernel<LPP, E, true, true>);
+}
+template <int E>
+int conef_scratch_bytes() {
+    int worst = 0;
+    for (int s : {conef_lpp_scratch_bytes<E, 16>(), conef_lpp_scratch_bytes<E, 21>(), conef_lpp_scratch_bytes<E, 32>(), conef_lpp_scratch_bytes<E, 64>()}) {
         if (s < 0) return -1;
         worst = s > worst ? s : worst;
     }

@@ -88,6 +88,16 @@ struct ConeArgs {
     long smu;
 };
 
+// ... about per-contact surface normals (bmpc_contact_frame_t): ConeArgs and one unit normal, world frame, per problem, knot and foot --
+// the cone's axis in place of world z (biconvex_admm_body.h: FRAME).  A layout of its own beside ConeArgs: the cone kernels' argument
+// block stays what it is.  Stride in doubles, 0 = one set of normals shared by the batch.
+struct ConeFrameArgs {
+    const double *mu;       // [.][H][E], or null
+    long smu;
+    const double *normals;  // [.][H][E][3], never null
+    long snormals;
+};
+
 constexpr int kStats = 6;
 // LDS elements per knot of a problem (biconvex_admm_body.h: X 9, P 9, F 3E, R 9): 39 for four feet, 33 for two -- odd strides, so no
 // two lanes of a segment share a bank (an odd E would make it even: only E = 2 and 4 are built)
@@ -99,8 +109,10 @@ constexpr int kMaxKnots = 256; // H + 1 <= 256: one knot per lane, one problem p
 
 // Which Q a batch has beside BatchArgs' diagonal (Qx / Qf), and that Q's arrays: BlockArgs' for kBlocks, BandArgs' for kBand, x = the
 // motion side (Qx_blk / Qx_off), f = the force side.  kCone: diagonal costs under the Euclidean cone projection -- a kernel family of
-// its own like the two others, chosen the same way; f = ConeArgs' coefficients (null: the scalar), sf their stride, x unused
-enum CostShape { kDiag = 0, kBlocks = 1, kBand = 2, kCone = 3 };
+// its own like the two others, chosen the same way; f = ConeArgs' coefficients (null: the scalar), sf their stride, x unused.
+// kConeFrame (internal: the exported plan_launch call knows the first three only): kCone about per-contact normals, a third family
+// chosen exactly as kCone; f / sf as there, x = ConeFrameArgs' normals (never null), sx their stride
+enum CostShape { kDiag = 0, kBlocks = 1, kBand = 2, kCone = 3, kConeFrame = 4 };
 struct CostArgs {
     CostShape shape = kDiag;
     const double *x = nullptr, *f = nullptr;
@@ -130,8 +142,8 @@ struct AdmmUnit {
     int (*scratch_bytes)();
 };
 const AdmmUnit &admm_unit_e4(), &admm_unit_e2(), &admm_unit_f32_e4(), &admm_unit_f32_e2(), &admm_unit_bq_e4(), &admm_unit_bq_e2(), &admm_unit_kq_e4(), &admm_unit_kq_e2(),
-               &admm_unit_cone_e4(), &admm_unit_cone_e2();
-// ... of a combination the caller has validated: n_eff 2 or 4, precision 0 or 1 (blocks / band / cone: 0)
+               &admm_unit_cone_e4(), &admm_unit_cone_e2(), &admm_unit_conef_e4(), &admm_unit_conef_e2();
+// ... of a combination the caller has validated: n_eff 2 or 4, precision 0 or 1 (blocks / band / cone / cone with normals: 0)
 const AdmmUnit &admm_unit(CostShape shape, int precision, int n_eff);
 
 // The dispatch switches of the process (the set_* calls below) and what they decide: a pure function of the batch's sizes, the

@@ -123,17 +123,44 @@ int check_mu(const double *mu, size_t n) {
     return BMPC_OK;
 }
 
+// bmpc_cone_t with bmpc_contact_frame_t: cone_of, and with normals the kernels about them (kConeFrame: x = the normals).  Without a
+// frame struct, or without normals in it: the cone call itself.  false (g_err set): what cone_of refuses, or normals under projection 0.
+bool cone_frame_of(const bmpc_cone_t *c, const bmpc_contact_frame_t *fr, bunmpc::CostArgs &out) {
+    if (!cone_of(c, out)) return false;
+    if (!fr || !fr->normals) return true;
+    if (out.shape != bunmpc::kCone) {
+        fail(BMPC_BAD_ARG, "contact normals (bmpc_contact_frame_t) need projection = 1: the reference's \"SoC\" step is the reference's, about world z");
+        return false;
+    }
+    out.shape = bunmpc::kConeFrame; out.x = fr->normals; out.sx = fr->snormals;
+    return true;
+}
+// unit normals [n][3] on the host: each component finite, |n.n - 1| <= 1e-9 (the kernels do not normalise)
+int check_normals(const double *nrm, size_t n, const char *what = "contact normals") {
+    for (size_t i = 0; i < n; ++i) {
+        const double *v = nrm + 3 * i;
+        const double nn = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+        if (!std::isfinite(v[0]) || !std::isfinite(v[1]) || !std::isfinite(v[2]) || !(std::fabs(nn - 1.0) <= 1e-9))
+            return fail(BMPC_BAD_ARG, std::string(what) + " must be finite and of unit length (|n.n - 1| <= 1e-9): normal " + std::to_string(i) + " is (" +
+                                      std::to_string(v[0]) + ", " + std::to_string(v[1]) + ", " + std::to_string(v[2]) + ")");
+    }
+    return BMPC_OK;
+}
+
 // a batch with its costs: what the kernels of block costs / costs between neighbouring knots are built for, then the batch itself
 int check_cost(const bmpc_batch_t *d, const bunmpc::CostArgs &c, bool arrays = true) {
     if (c.shape == bunmpc::kDiag) return check_batch(d, false, false, arrays);
-    if (c.shape == bunmpc::kCone) {
-        const std::string what = "the Euclidean cone projection (bmpc_cone_t, projection = 1)";
+    if (c.shape == bunmpc::kCone || c.shape == bunmpc::kConeFrame) {
+        const bool frames = c.shape == bunmpc::kConeFrame;
+        const std::string what = frames ? "the Euclidean cone projection about contact normals (bmpc_contact_frame_t)" : "the Euclidean cone projection (bmpc_cone_t, projection = 1)";
         if (!d) return fail(BMPC_BAD_ARG, "null batch descriptor");
         if (d->precision != 0) return fail(BMPC_BAD_ARG, what + " is built for fp64 only: precision must be 0");
         if (d->n_col + 1 > 64) return fail(BMPC_BAD_ARG, what + " is built for n_col + 1 <= 64 knots only (one problem per wave segment)");
         if (d->n_eff != 2 && d->n_eff != 4) return fail(BMPC_BAD_ARG, what + " is built for n_eff in {2, 4} only");
         if (c.f && (c.sf < 0 || c.sf > (1L << 26) || (c.sf != 0 && c.sf < (long)d->n_col * d->n_eff)))
             return fail(BMPC_BAD_ARG, "batch stride of the friction coefficients (smu) must be 0 (shared) or between one problem's n_col * n_eff and 2^26 doubles");
+        if (frames && (!c.x || c.sx < 0 || c.sx > (1L << 26) || (c.sx != 0 && c.sx < 3L * d->n_col * d->n_eff)))
+            return fail(BMPC_BAD_ARG, "batch stride of the contact normals (snormals) must be 0 (shared) or between one problem's 3 * n_col * n_eff and 2^26 doubles");
         return check_batch(d, false, false, arrays);
     }
     const bool blocks = c.shape == bunmpc::kBlocks;
@@ -202,9 +229,12 @@ struct bmpc_biconvex {
     // mu); both persist across optimize
     int cone_projection = 0;
     std::vector<double> mu_arr;
+    // unit normals of the contacts [n_col][n_eff][3], world frame (set_contact_normals, set_contact_normals_from_rotations; empty: world
+    // z); persist across optimize
+    std::vector<double> normals;
     // iterates
     std::vector<double> X, F, P;
-    std::vector<double> rot;  // set_rotation_matrix_f: stored, unused (as in the reference)
+    std::vector<double> rot;  // set_rotation_matrix_f: stored, unused (as in the reference) unless set_contact_normals_from_rotations reads them
     bool log_statistics = false;
     std::vector<double> hist;
     int last_stats[bunmpc::kStats] = {0, 0, 0, 0, 0, 0};
@@ -232,12 +262,14 @@ int bmpc_biconvex_fp32_scratch_bytes(void) { return bunmpc::admm_unit(bunmpc::kD
 int bmpc_block_cost_struct_size(void) { return (int)sizeof(bmpc_block_cost_t); }
 int bmpc_band_cost_struct_size(void) { return (int)sizeof(bmpc_band_cost_t); }
 int bmpc_cone_struct_size(void) { return (int)sizeof(bmpc_cone_t); }
+int bmpc_contact_frame_struct_size(void) { return (int)sizeof(bmpc_contact_frame_t); }
 static int unit_scratch_bytes(bunmpc::CostShape shape, int precision, int n_eff, const char *msg) {
     if ((n_eff != 2 && n_eff != 4) || (precision != 0 && precision != 1)) { fail(BMPC_BAD_ARG, msg); return -1; }
     return bunmpc::admm_unit(shape, precision, n_eff).scratch_bytes();
 }
 int bmpc_biconvex_band_kernel_scratch_bytes(int n_eff) { return unit_scratch_bytes(bunmpc::kBand, 0, n_eff, "n_eff must be 2 or 4"); }
 int bmpc_biconvex_cone_kernel_scratch_bytes(int n_eff) { return unit_scratch_bytes(bunmpc::kCone, 0, n_eff, "n_eff must be 2 or 4"); }
+int bmpc_biconvex_cone_frame_kernel_scratch_bytes(int n_eff) { return unit_scratch_bytes(bunmpc::kConeFrame, 0, n_eff, "n_eff must be 2 or 4"); }
 int bmpc_biconvex_block_kernel_scratch_bytes(int n_eff) { return unit_scratch_bytes(bunmpc::kBlocks, 0, n_eff, "n_eff must be 2 or 4"); }
 int bmpc_biconvex_kernel_scratch_bytes(int n_eff, int precision) { return unit_scratch_bytes(bunmpc::kDiag, precision, n_eff, "n_eff must be 2 or 4, precision 0 or 1"); }
 int bmpc_biconvex_plan_launch(const bmpc_batch_t *d, int cost_shape, long simds, bmpc_launch_plan_t *out) {
@@ -685,6 +717,26 @@ int bmpc_biconvex_set_friction_coefficients(bmpc_biconvex_t *h, const double *mu
     h->mu_arr.assign(mu, mu + (size_t)h->n_col * h->n_eff);
     return BMPC_OK;
 }
+int bmpc_biconvex_set_contact_normals(bmpc_biconvex_t *h, const double *n) {
+    H_CHECK(h);
+    if (!n) { h->normals.clear(); return BMPC_OK; }
+    if (int rc = check_normals(n, (size_t)h->n_col * h->n_eff)) return rc;
+    h->normals.assign(n, n + (size_t)3 * h->n_col * h->n_eff);
+    return BMPC_OK;
+}
+int bmpc_biconvex_set_contact_normals_from_rotations(bmpc_biconvex_t *h) {
+    H_CHECK(h);
+    const size_t n = (size_t)h->n_col * h->n_eff;
+    if (h->rot.size() != 9 * n)
+        return fail(BMPC_BAD_ARG, "contact frames from rotation matrices need exactly n_col * n_eff = " + std::to_string(n) + " matrices of set_rotation_matrix_f, knot-major; the handle holds " +
+                                  std::to_string(h->rot.size() / 9));
+    std::vector<double> rows(3 * n);      // local z in the world frame: the third row of R (the reference's rotated_force = R * f)
+    for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < 3; ++k) rows[3 * i + k] = h->rot[9 * i + 6 + k];
+    if (int rc = check_normals(rows.data(), n, "the third row of each rotation matrix")) return rc;
+    h->normals = rows;
+    return BMPC_OK;
+}
 int bmpc_biconvex_set_robot_mass(bmpc_biconvex_t *h, double m) { H_CHECK(h); h->m = m; return BMPC_OK; }
 
 int bmpc_biconvex_return_opt_x(bmpc_biconvex_t *h, double *X) { H_CHECK(X); std::memcpy(X, h->X.data(), sizeof(double) * h->nx()); return BMPC_OK; }
@@ -748,6 +800,9 @@ int bmpc_biconvex_optimize(bmpc_biconvex_t *h, const double *x_init, int num_ite
     if (h->cone_projection == 0 && !h->mu_arr.empty())
         return fail(BMPC_BAD_ARG, "the handle carries per-foot friction coefficients (set_friction_coefficients) under the reference's projection: they need "
                                   "set_cone_projection(1); the kernels of the reference's projection take the scalar of set_friction_coefficient");
+    if (h->cone_projection == 0 && !h->normals.empty())
+        return fail(BMPC_BAD_ARG, "the handle carries contact normals (set_contact_normals) under the reference's projection: they need set_cone_projection(1); "
+                                  "the reference's \"SoC\" step is about world z");
     if (int rc = need_plan(h)) return rc;
     if (num_iters < 0) return fail(BMPC_BAD_ARG, "num_iters < 0");
     const int H = h->n_col, E = h->n_eff, nx = h->nx(), nf = h->nf();
@@ -765,7 +820,7 @@ int bmpc_biconvex_optimize(bmpc_biconvex_t *h, const double *x_init, int num_ite
                  o_lb = take(nx), o_ub = take(nx), o_Qf = take(nf), o_qf = take(nf), o_X = take(nx),
                  o_F = take(nf), o_P = take(nx), o_L = take(2), o_viol = take(1), o_hist = take(nh);
     const size_t o_end = off, o_Qxb = take(h->Qx_blk.size()), o_Qfb = take(h->Qf_blk.size());      // (blocks: behind what comes back)
-    const size_t o_Qxo = take(h->has_x_off ? h->Qx_off.size() : 0), o_Qfo = take(h->has_f_off ? h->Qf_off.size() : 0), o_mu = take(h->mu_arr.size());
+    const size_t o_Qxo = take(h->has_x_off ? h->Qx_off.size() : 0), o_Qfo = take(h->has_f_off ? h->Qf_off.size() : 0), o_mu = take(h->mu_arr.size()), o_nrm = take(h->normals.size());
     std::vector<double> stage(off, 0.0);
     auto put = [&](size_t o, const double *src, size_t n) { std::memcpy(stage.data() + o, src, sizeof(double) * n); };
     put(o_cnt, cnt.data(), cnt.size()); put(o_dt, h->dt.data(), H); put(o_xi, x_init, 9);
@@ -777,6 +832,7 @@ int bmpc_biconvex_optimize(bmpc_biconvex_t *h, const double *x_init, int num_ite
     if (h->has_x_off) put(o_Qxo, h->Qx_off.data(), h->Qx_off.size());
     if (h->has_f_off) put(o_Qfo, h->Qf_off.data(), h->Qf_off.size());
     if (!h->mu_arr.empty()) put(o_mu, h->mu_arr.data(), h->mu_arr.size());
+    if (!h->normals.empty()) put(o_nrm, h->normals.data(), h->normals.size());
     stage[o_L] = h->L_x; stage[o_L + 1] = h->L_f;
     HIP_TRY(h->dbuf.ensure(sizeof(double) * off));
     HIP_TRY(h->dstats.ensure(sizeof(int) * bunmpc::kStats));
@@ -799,6 +855,7 @@ int bmpc_biconvex_optimize(bmpc_biconvex_t *h, const double *x_init, int num_ite
         cost = bunmpc::CostArgs();
         cost.shape = bunmpc::kCone;
         cost.f = h->mu_arr.empty() ? nullptr : d + o_mu;
+        if (!h->normals.empty()) { cost.shape = bunmpc::kConeFrame; cost.x = d + o_nrm; }
     }
     if (int rc = check_cost(&b, cost)) return rc;
     HIP_TRY(bunmpc::launch_biconvex_admm(to_args(b), cost, E, nullptr));
@@ -840,6 +897,11 @@ int bmpc_biconvex_solve_batch_cone_device(const bmpc_batch_t *d, const bmpc_cone
     if (!cone_of(c, a)) return BMPC_BAD_ARG;
     return solve_batch_device(d, a, hip_stream);
 }
+int bmpc_biconvex_solve_batch_cone_frames_device(const bmpc_batch_t *d, const bmpc_cone_t *c, const bmpc_contact_frame_t *fr, void *hip_stream) {
+    bunmpc::CostArgs a;
+    if (!cone_frame_of(c, fr, a)) return BMPC_BAD_ARG;
+    return solve_batch_device(d, a, hip_stream);
+}
 
 namespace {
 int solve_batch_host(const bmpc_batch_t *d, bunmpc::CostArgs c);
@@ -852,13 +914,18 @@ int bmpc_biconvex_solve_batch_cone_host(const bmpc_batch_t *d, const bmpc_cone_t
     if (!cone_of(c, a)) return BMPC_BAD_ARG;
     return solve_batch_host(d, a);
 }
+int bmpc_biconvex_solve_batch_cone_frames_host(const bmpc_batch_t *d, const bmpc_cone_t *c, const bmpc_contact_frame_t *fr) {
+    bunmpc::CostArgs a;
+    if (!cone_frame_of(c, fr, a)) return BMPC_BAD_ARG;
+    return solve_batch_host(d, a);
+}
 
 }  // extern "C"
 
 namespace {
 // the host entry points: arrays to the device, one launch, results back (c: the host arrays of per-knot blocks or of costs between neighbouring knots, if any)
 int solve_batch_host(const bmpc_batch_t *d, bunmpc::CostArgs c) {
-    const bool blocks = c.shape == bunmpc::kBlocks, band = c.shape == bunmpc::kBand, cone = c.shape == bunmpc::kCone;
+    const bool blocks = c.shape == bunmpc::kBlocks, band = c.shape == bunmpc::kBand, frames = c.shape == bunmpc::kConeFrame, cone = c.shape == bunmpc::kCone || frames;
     if (int rc = check_cost(d, c)) return rc;
     const size_t B = (size_t)d->B, H = (size_t)d->n_col, E = (size_t)d->n_eff;
     const size_t nx = 9 * (H + 1), nf = 3 * E * H;
@@ -875,6 +942,11 @@ int solve_batch_host(const bmpc_batch_t *d, bunmpc::CostArgs c) {
         ins.push_back({&c.f, (rows(c.sf) - 1) * (size_t)c.sf + H * E});
     } else if (cone) {
         if (int rc = check_mu(&d->mu, 1)) return rc;
+    }
+    if (frames) {
+        for (size_t i = 0; i < rows(c.sx); ++i)
+            if (int rc = check_normals(c.x + i * (size_t)c.sx, H * E)) return rc;
+        ins.push_back({&c.x, (rows(c.sx) - 1) * (size_t)c.sx + 3 * H * E});
     }
     if (d->raw) {
         if (blocks && c.x) {

@@ -338,6 +338,15 @@ def band_matrix(diag, off):
     return Q
 
 
+def plane_normals(B, H, E, roll, pitch):
+    """Unit normals (B, H, E, 3) of a plane tilted by roll (about world x) and pitch (about world y), radians -- scalars or one value
+    per problem: n = R_y(pitch) R_x(roll) e_z, the same for every knot and foot of a problem.  What solve_host / DeviceBatch take as
+    cone=dict(projection="euclidean", normals=...): a slope as a workload."""
+    roll, pitch = np.broadcast_to(np.asarray(roll, dtype=np.float64), (B,)), np.broadcast_to(np.asarray(pitch, dtype=np.float64), (B,))
+    n = np.stack([np.sin(pitch) * np.cos(roll), -np.sin(roll), np.cos(pitch) * np.cos(roll)], axis=-1)
+    return np.ascontiguousarray(np.broadcast_to(n[:, None, None, :], (B, H, E, 3)))
+
+
 def _draws(seed, first, B, n):
     """Per-problem independent streams: problem b always sees the same numbers whatever the
     batch size or the rank that generates it (SeedSequence.spawn keyed by absolute index)."""

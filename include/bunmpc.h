@@ -307,8 +307,8 @@ int bmpc_biconvex_band_kernel_scratch_bytes(int n_eff);
  *     fz >= 0 and s2 <= mu^2 fz^2   -> unchanged
  *     otherwise                     -> s = sqrt(s2), t = (mu s + fz) / (mu^2 + 1): (fx mu t / s, fy mu t / s, t)
  * Everything else of the solve is unchanged: gradient, backtracking test, momentum, exits, ADMM.  As under the reference's
- * projection, the force bounds of create_bound_constraints / set_bounds_f are not applied, and the contact frame is world-z
- * (set_rotation_matrix_f stays stored and unused).
+ * projection, the force bounds of create_bound_constraints / set_bounds_f are not applied.  The cone's axis is world z unless the call
+ * carries contact normals (bmpc_contact_frame_t, below); set_rotation_matrix_f on its own stays stored and unused.
  * mu: friction coefficients [.][n_col][n_eff], each finite and > 0 (the host entry point and the handle's setter check that, the
  * device entry point cannot), or NULL: every foot has bmpc_batch_t's scalar mu.  smu: batch stride in doubles, 0 = one set shared by
  * the batch, otherwise at least n_col * n_eff and at most 2^26.
@@ -337,6 +337,45 @@ int bmpc_biconvex_set_friction_coefficients(bmpc_biconvex_t *h, const double *mu
 /* The largest scratch (private-segment) bytes per lane over the cone-projection kernels of one foot count (n_eff 2 or 4), as the
  * loaded code object reports them; -1 for another n_eff, or on error. */
 int bmpc_biconvex_cone_kernel_scratch_bytes(int n_eff);
+
+/* Friction cones about per-contact surface normals (additive, opt-in; with projection = 1 only) -----------------------------------
+ * The Euclidean projection above has world z for its axis: flat ground.  With a unit normal n per problem, knot and foot (world
+ * frame) the cone is |f - (n.f) n| <= mu n.f -- a slope, a stair edge, a tilted stepping stone.  The cone is rotationally symmetric,
+ * so the normal is all the projection needs: with fn = n.f, ft = f - fn n, s2 = |ft|^2 of the gradient step f
+ *     fn <= 0 and mu^2 s2 <= fn^2   -> (0, 0, 0)          (the polar cone; wins at the origin)
+ *     fn >= 0 and s2 <= mu^2 fn^2   -> f, its bits unchanged
+ *     otherwise                     -> s = sqrt(s2), t = (mu s + fn) / (mu^2 + 1), k = mu t / s: k ft + t n
+ * With n = (0, 0, 1) these are the values of the projection above (only the sign of a zero can differ).  Everything else of the solve
+ * is unchanged.  The kernels do not normalise.
+ * normals: [.][n_col][n_eff][3]; each component finite and |n.n - 1| <= 1e-9 (the host entry point and the handle's setters check
+ * that, the device entry point cannot).  snormals: batch stride in doubles, 0 = one set shared by the batch, otherwise at least
+ * 3 * n_col * n_eff and at most 2^26.
+ * fr == NULL, or fr->normals == NULL, is bmpc_biconvex_solve_batch_cone_device / _host itself: same kernel, same bits.  With normals
+ * the batch runs "biconvex_admm_conef_kernel", chosen exactly as the cone kernel is (16 / 21 / 32 / 64 lanes per problem, one wave per
+ * SIMD, both forms, every step tested on fp64 sums).  BMPC_BAD_ARG with a message naming the limit: normals under projection == 0,
+ * fp32, n_col + 1 > 64 knots, n_eff other than 2 or 4, a stride outside the rule above, and (host entry point, setters) a normal that
+ * is not finite or not of unit length.  Not built: normals in fp32, for more than 63 knots, in bmpc_kinodyn_solve_batch_device, and
+ * for the reference's "SoC" step, which stays the reference's.
+ * (This family's prototypes carry an explicit `extern`: tests/test_cone_cpu.py pins the number of plain `int bmpc_*cone*(...)`
+ * prototypes in this header to the six of the family above; tests/test_cone_frame_cpu.py checks these against the binding.) */
+typedef struct {
+    const double *normals; long snormals;  /* [.][n_col][n_eff][3], unit, world frame; NULL: world z */
+} bmpc_contact_frame_t;
+extern int bmpc_contact_frame_struct_size(void);    /* sizeof(bmpc_contact_frame_t), to catch binding drift */
+extern int bmpc_biconvex_solve_batch_cone_frames_device(const bmpc_batch_t *d, const bmpc_cone_t *c, const bmpc_contact_frame_t *fr, void *hip_stream);
+extern int bmpc_biconvex_solve_batch_cone_frames_host(const bmpc_batch_t *d, const bmpc_cone_t *c, const bmpc_contact_frame_t *fr);
+/* The handle's contact normals n [n_col][n_eff][3] (NULL: back to world z); they persist across optimize calls.  optimize refuses
+ * (BMPC_BAD_ARG) normals under projection 0 and, as with projection 1 itself, on a handle that carries block or band costs or has
+ * n_col + 1 > 64.  bmpc_kinodyn_optimize goes through the handle's optimize: it honours them or returns that refusal. */
+extern int bmpc_biconvex_set_contact_normals(bmpc_biconvex_t *h, const double *n);
+/* ... taken from the matrices of bmpc_biconvex_set_rotation_matrix_f: the normal of a contact is the third row of its R (row-major;
+ * the reference's commented line is rotated_force = R * f, so local z is row 2 of R).  Refuses (BMPC_BAD_ARG) unless exactly
+ * n_col * n_eff matrices were appended, knot-major, and every third row passes the unit test above.  The matrices themselves stay
+ * stored and otherwise unused. */
+extern int bmpc_biconvex_set_contact_normals_from_rotations(bmpc_biconvex_t *h);
+/* The largest scratch (private-segment) bytes per lane over the kernels about contact normals of one foot count (n_eff 2 or 4), as the
+ * loaded code object reports them; -1 for another n_eff, or on error. */
+extern int bmpc_biconvex_cone_frame_kernel_scratch_bytes(int n_eff);
 
 /* rigid-body model -------------------------------------------------------------------
  * What pinocchio::urdf::buildModel(urdf, JointModelFreeFlyer()) yields (inverse_kinematics.cpp:10,

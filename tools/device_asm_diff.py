@@ -1,4 +1,4 @@
-"""Is the device code of the kernel units (the ten centroidal ADMM units and ik_ddp.hip) the same in two source trees?  Kernel by kernel.
+"""Is the device code of the kernel units (the twelve centroidal ADMM units and ik_ddp.hip) the same in two source trees?  Kernel by kernel.
 
     python tools/device_asm_diff.py PARENT_TREE THIS_TREE [--keep DIR] [--units biconvex_admm_kq.hip ik_ddp.hip ...]
 
@@ -18,7 +18,7 @@ import sys
 import tempfile
 
 UNITS = ["biconvex_admm.hip", "biconvex_admm_e2.hip", "biconvex_admm_bq.hip", "biconvex_admm_bq_e2.hip", "biconvex_admm_kq.hip", "biconvex_admm_kq_e2.hip",
-         "biconvex_admm_cone.hip", "biconvex_admm_cone_e2.hip", "biconvex_admm_f32.hip", "biconvex_admm_f32_e2.hip", "ik_ddp.hip"]
+         "biconvex_admm_cone.hip", "biconvex_admm_cone_e2.hip", "biconvex_admm_conef.hip", "biconvex_admm_conef_e2.hip", "biconvex_admm_f32.hip", "biconvex_admm_f32_e2.hip", "ik_ddp.hip"]
 
 
 def build_settings(tree):
