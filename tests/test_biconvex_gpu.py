@@ -568,10 +568,12 @@ def test_full_size_invariants_and_sampled_parity(oracle):
 @pytest.mark.parametrize("config,B,H", [("go2_bound", 256, 40), ("solo12_trot", 256, None)])
 def test_fp32_variant_with_fp64_residual_check(oracle, config, B, H):
     """BASELINE config 3: fp32 iterates / operators / projections (precision = 1), every accept and
-    exit decision and the dynamics violation reduced in fp64.  No fp32 reference exists: the fp32
-    result is held to the fp64 kernel's (itself oracle-checked above) -- median 1e-4 rel-L2, and
-    for problems in the chaotic regime (test_chaotic_envelope) the same envelope -- and the
-    violation it reports is re-derived in fp64 numpy from the returned X, F."""
+    exit decision and the dynamics violation reduced in fp64.  Full-length solves at the reference's
+    tol = 1e-5 leave the fp64 discrete path on almost every problem, so here the fp32 result is held
+    to the fp64 kernel's (itself oracle-checked above) as a population -- median 1e-4 rel-L2, at most
+    10 % above 5e-3 -- and the violation it reports is re-derived in fp64 numpy from the returned
+    X, F.  The fp32 reference (tests/f32_np.py) pins short solves decision by decision in
+    tests/test_f32_gpu.py."""
     b = problems.make_batch(config, B, H=H) if H else problems.make_batch(config, B)
     d64 = bb.solve_host(b, num_iters=10)
     d32 = bb.solve_host(b, num_iters=10, precision="f32")
