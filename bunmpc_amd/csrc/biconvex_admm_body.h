@@ -44,6 +44,13 @@
 // split.
 constexpr double kCertEta = 1.0 / 64.0;
 constexpr double kCertFloor = 2.0 * 25.0 / (kCertEta * kCertEta) * 0x1p-80;
+// Stage 1 of the lane-local screen in the headline kernel's certified loops ("Two-stage screen"): the components of
+// the lane's step whose squares are summed first -- the motion step's velocity z, the force step's fz of the third foot (one foot's fz
+// settles 77-78 % of the trot batch's wave-iterations whichever foot it is).  Any subset is sound (see the force step); which one is a
+// matter of speed alone, tuned on the trot batch with tools/screen_rate.py --terms.
+// (Namespace scope: a constexpr array of admm_body indexed inside a lambda would be captured by its closure.)
+[[maybe_unused]] constexpr int kScreenTermsX[] = {5};
+[[maybe_unused]] constexpr int kScreenTermsF[] = {8};
 
 // BQ (per-knot block-diagonal costs: raw form, fp64, one wave per SIMD): a lane holds its knot's SYMMETRIC block -- the upper triangle,
 // 45 values for X, 3E (3E + 1) / 2 for F -- where the other instantiations hold the knot's diagonal weights, loaded once per phase like
@@ -675,7 +682,8 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                     applyA(xn, rn);
                     R g2 = 0, cv = 0, e2 = 0, dv[NF];
                     if (CERT) {
-                        UNROLL for (int j = 0; j < NF; ++j) { const R d = xn[j] - y[j]; g2 = fmaR(d, d, g2); }
+                        if constexpr (BAND) {}      // (the headline kernel's certified loop: in the screen below, and only where stage 1 misses)
+                        else { UNROLL for (int j = 0; j < NF; ++j) { const R d = xn[j] - y[j]; g2 = fmaR(d, d, g2); } }
                     } else {
                     UNROLL for (int j = 0; j < NF; ++j) {
                         const R d = xn[j] - y[j];
@@ -723,7 +731,25 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                     if constexpr (BAND) {      // (the other instantiations compile the code below the `else` alone, as before the shortcut)
                         bt = 0;      // (certified: cvs <= rhs whatever the step)
                         bool settled = false;      // the screen: every live problem has a lane above theta -- no hand-over, no exit, no sum
-                        if constexpr (CERT) settled = seg_covered<LPP>(__ballot(g2 > theta), act);
+                        if constexpr (CERT) {
+                            // Two stages.  Stage 1 asks it of s, an fma chain over a few of the lane's squares (kScreenTermsF): s > theta
+                            // settles what the whole partial g2 > theta settles.  The exact sums are ordered (squares are non-negative, a
+                            // subset's sum is at most the whole) and each chain rounds at most NF = 12 times, by at most 2^-53 relative
+                            // where the result is normal and by at most 2^-1075 absolute where it is not -- 24 x 2^-1075 is 2^-70 of
+                            // s > theta >= 2^-1000 -- hence g2 >= s (1 - 24 x 2^-53 - 2^-70) > s (1 - 2^-48); the segment sum S in any order
+                            // is at least g2 (fl(a + b) >= max(a, b) for a, b >= 0); and theta carries (1 + 2^-40) over max(tol^2, floor2):
+                            // S > max(tol^2, floor2) (1 + 2^-41), above the floor, above tol^2 and outside the 1e-14 edge band.  NaN
+                            // elsewhere in the segment makes S NaN and the three comparisons false, as with one stage.  Only on a miss is
+                            // g2 made, in the one-stage order (its bits), and asked the one-stage question; then the code as it stood.
+                            // theta = +inf (switch 1 or 2) fails both stages.
+                            R s = 0;
+                            UNROLL for (int k = 0; k < (int)(sizeof(kScreenTermsF) / sizeof(int)); ++k) { const R d = xn[kScreenTermsF[k]] - y[kScreenTermsF[k]]; s = fmaR(d, d, s); }
+                            settled = seg_covered<LPP>(__ballot(s > theta), act);
+                            if (!settled) {
+                                UNROLL for (int j = 0; j < NF; ++j) { const R d = xn[j] - y[j]; g2 = fmaR(d, d, g2); }
+                                settled = seg_covered<LPP>(__ballot(g2 > theta), act);
+                            }
+                        }
                         if (settled) done = 0;
                         else {
                             mask_t unclear = ~mask_t(0);      // designated lanes of live problems whose fp32 decisions are not clear
@@ -1148,6 +1174,22 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                 // the image difference, cv and the retry loop around them (bt = 0 whatever the step); a live problem's step below the
                 // floor commits nothing and hands the phase to the tested loop from this iteration (x_k and its image are in LDS: nothing
                 // to move)
+                // ... and A_f of the certified loop: applyA without the row mask.  The image of a lane without a dynamics row (t >= H) is
+                // not zeroed but never used: its ry is not advanced (it stays the exact zero the phase's first, masked applyA(y, ry) left)
+                // and its R block is not written (knot H's keeps those zeros, which the tested loop reads after a hand-over and, through
+                // ry, lane 0 of the next segment when H = 31).  What a wave shift brings across a segment's end -- a diverged wave-mate's
+                // NaN -- therefore ends in those unused values; the lane a shift reads across the end is always one with t >= H.
+                auto applyA_c = [&](const R (&v)[9], R (&u)[9]) {
+                    R vn[9];
+                    shift_next(v, vn);
+                    R w[9];
+                    UNROLL for (int l = 0; l < 9; ++l) w[l] = v[l] - vn[l];
+                    UNROLL for (int k = 0; k < 3; ++k) w[k] += dt * vn[3 + k];
+                    w[6] += SY * v[2] - SZ * v[1];
+                    w[7] += SZ * v[0] - SX * v[2];
+                    w[8] += SX * v[1] - SY * v[0];
+                    UNROLL for (int l = 0; l < 9; ++l) u[l] = w[l] + bpk[l];
+                };
                 auto iterate_c = [&](int i) -> bool {
                     const R cm = (R)cmtab[i];
                     R xn[9], rn[9], xo[9], ro[9];
@@ -1168,11 +1210,16 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                             xn[l] = v;
                         }
                     }
-                    applyA(xn, rn);
-                    R g2 = 0;
-                    UNROLL for (int l = 0; l < 9; ++l) { const R d = xn[l] - y[l]; g2 = fmaR(d, d, g2); }
+                    applyA_c(xn, rn);
+                    R g2 = 0, s = 0;
+                    UNROLL for (int k = 0; k < (int)(sizeof(kScreenTermsX) / sizeof(int)); ++k) { const R d = xn[kScreenTermsX[k]] - y[kScreenTermsX[k]]; s = fmaR(d, d, s); }
                     UNROLL for (int l = 0; l < 9; ++l) { xo[l] = Xz[l]; ro[l] = RXz[l]; }      // (see the force step)
-                    if (seg_covered<LPP>(__ballot(g2 > theta), act)) done = 0;      // the screen (see the force step)
+                    bool settled = seg_covered<LPP>(__ballot(s > theta), act);      // the screen, stage 1 (see the force step)
+                    if (!settled) {      // stage 2: the whole partial, with the bits it always had
+                        UNROLL for (int l = 0; l < 9; ++l) { const R d = xn[l] - y[l]; g2 = fmaR(d, d, g2); }
+                        settled = seg_covered<LPP>(__ballot(g2 > theta), act);
+                    }
+                    if (settled) done = 0;
                     else {
                         mask_t unclear = ~mask_t(0);
                         if (banded != 0) {      // the fp32 decisions -- floor and exit -- if every live problem's are clear (see the force step)
@@ -1196,11 +1243,10 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
                         }
                     }
                     UNROLL for (int l = 0; l < 9; ++l) { keep_here(xo[l]); keep_here(ro[l]); }
-                    UNROLL for (int l = 0; l < 9; ++l) {
-                        y[l] = fma3(cm, xn[l] - xo[l], xn[l]);      // (no copies at the loop's end: see fma3)
-                        ry[l] = fmaR(cm, rn[l] - ro[l], rn[l]);
-                    }
-                    if (lanes(act & kvalid_m)) { UNROLL for (int l = 0; l < 9; ++l) { Xg[l] = xn[l]; Rg[l] = rn[l]; } }
+                    UNROLL for (int l = 0; l < 9; ++l) y[l] = fma3(cm, xn[l] - xo[l], xn[l]);      // (no copies at the loop's end: see fma3)
+                    if (rvalid) { UNROLL for (int l = 0; l < 9; ++l) ry[l] = fmaR(cm, rn[l] - ro[l], rn[l]); }      // (see applyA_c)
+                    if (lanes(act & kvalid_m)) { UNROLL for (int l = 0; l < 9; ++l) Xg[l] = xn[l]; }
+                    if (lanes(act & rvalid_m)) { UNROLL for (int l = 0; l < 9; ++l) Rg[l] = rn[l]; }
                     it_x += lanes(act) ? 1 : 0;
                     act &= ~done;
                     return true;

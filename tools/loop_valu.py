@@ -6,15 +6,16 @@ iteration that takes none of the branches it can skip -- the cone step, the retr
 decisions), with that path's fp64 arithmetic (v_fma_f64, v_fmac_f64, v_mul_f64, v_add_f64), DPP moves, DPP-fused operations and
 permlanes.  Also the kernel's registers, scratch and static LDS as the compiler reports them.
 
-    python tools/loop_valu.py LISTING.s KERNEL_SUBSTRING [--through RE]... [--committing] [--blocks]
-    python tools/loop_valu.py --compile bunmpc_amd/csrc/biconvex_admm.hip KERNEL_SUBSTRING [--through RE]... [--committing] [--blocks]
+    python tools/loop_valu.py LISTING.s KERNEL_SUBSTRING [--through RE]... [--committing] [--blocks] [--mnemonics]
+    python tools/loop_valu.py --compile bunmpc_amd/csrc/biconvex_admm.hip KERNEL_SUBSTRING [--through RE]... [--committing] [--blocks] [--mnemonics]
         (--compile: device code of the unit with bunmpc_amd/build.py's flags for it; --through RE: the cheapest path that runs an
         instruction matching RE, e.g. 'permlane' for an iteration that reduces its sums -- in fp32 where it can; given more than
         once: a path that runs an instruction of every RE, each in a block of its own; --committing: --through ds_write2, the
         iteration that writes x_{k+1} and its image back to LDS.  The plain cheapest path of a certified loop is NOT an iteration
         that commits: it leaves the loop before applyA(xn), the momentum step and the write-back.  The headline kernel's certified
         loops: --committing is the screened iteration, --committing --through permlane16 the one that takes the fp32 sum; in the
-        force loop, whose two unrolled copies are one loop here, the path runs one copy and leaves by the other's exit test.)
+        force loop, whose two unrolled copies are one loop here, the path runs one copy and leaves by the other's exit test;
+        --mnemonics: the path's vector instructions counted by mnemonic -- is a select or a mask operation on it?)
 
 The headline kernel: 'biconvex_admm_kernelIdLi32ELi4ELb0ELb0ELi2E' (biconvex_admm_kernel<double, 32, 4, false, false, 2>)."""
 import collections
@@ -100,33 +101,61 @@ def main():
     index = {b[0]: k for k, b in enumerate(blocks)}
     edges = [(k, index[t.split()[-1]], mn) for k, (_, _, ins) in enumerate(blocks) for mn, t in ins
              if mn.startswith(("s_branch", "s_cbranch")) and t.split()[-1] in index]
-    loops = sorted({(dst, src) for src, dst, _ in edges if dst <= src})
-    inner = [(a, b) for a, b in loops if not any((c, d) != (a, b) and a <= c and d <= b for c, d in loops)]
+    # Innermost loops, as [(head, members)].  A backward branch closes a loop only if its target heads one: hipcc also lays a rarely
+    # skipped stretch of a loop's body out of line, behind (or in front of) the rest, and jumps back into the body from there (the
+    # certified loops' screened iteration).  Where the listing carries the compiler's loop comments the heads are the labels followed by
+    # "This Inner Loop Header" and the members the blocks marked "in Loop: Header=<that label>", wherever they lie; without comments:
+    # every innermost range closed by a backward branch, as before.
+    heads = {}
+    for i, l in enumerate(body):
+        m = re.match(r"^(\.LBB\d+_\d+):", l)
+        if m and any("This Inner Loop Header" in x for x in body[i:i + 3] if x is l or x.lstrip().startswith(";")):
+            heads[m.group(1)] = {m.group(1)}
+    for l in body:
+        m = re.match(r"^(\.LBB\d+_\d+):.*in Loop: Header=(BB\d+_\d+) ", l)
+        if m and ".L" + m.group(2) in heads:
+            heads[".L" + m.group(2)].add(m.group(1))
+    if heads:
+        inner = sorted((index[h], sorted(k for k, blk in enumerate(blocks) if blk[0].split("+")[0] in names)) for h, names in heads.items())
+    else:
+        loops = sorted({(dst, src) for src, dst, _ in edges if dst <= src})
+        inner = [(a, list(range(a, b + 1))) for a, b in loops if not any((c, d) != (a, b) and a <= c and d <= b for c, d in loops)]
     nvalu = [sum(1 for mn, _ in blk[2] if is_valu(mn)) for blk in blocks]
-    for a, b in inner:
-        # the cheapest way through the body: from the head to the block of the back edge along forward edges (fall-through or branch)
-        succ = {k: set() for k in range(a, b + 1)}
-        for k in range(a, b):
+    for head, members in inner:
+        a, b = members[0], members[-1]
+        # the cheapest way through the body: from the head to a block that goes back to the head, along the body's edges (fall-through
+        # or branch, forward or backward)
+        inside = set(members)
+        succ = {k: set() for k in members}
+        for k in members:
             ins = blocks[k][2]
-            if not (ins and ins[-1][0] == "s_branch"):
+            if not (ins and ins[-1][0] == "s_branch") and k + 1 in inside:
                 succ[k].add(k + 1)
         for src, dst, _ in edges:
-            if a <= src < dst <= b:
+            if src in inside and dst in inside:
                 succ[src].add(dst)
+        latches = [k for k in members if head in succ[k]]
+        for k in members:
+            succ[k].discard(head)
         # (--through RE: the cheapest path that executes an instruction matching RE -- the segment sums: 'permlane'; the state of the
         # search is the block and the set of REs met so far, as a bit mask)
         has = [sum(1 << j for j, rx in enumerate(through) if any(re.search(rx, t) for _, t in blk[2])) for blk in blocks]
-        cost = {(a, has[a]): (nvalu[a], None)}
-        for k in range(a, b + 1):
-            for seen in range(want + 1):
-                if (k, seen) in cost:
-                    for n in succ[k]:
-                        st = (n, seen | has[n])
-                        c = cost[(k, seen)][0] + nvalu[n]
-                        if st not in cost or c < cost[st][0]:
-                            cost[st] = (c, (k, seen))
-        path, st = [], (b, want)
-        while st is not None and (b, want) in cost:
+        cost = {(head, has[head]): (nvalu[head], None)}
+        changed = True
+        while changed:      # (relaxed until nothing moves: the body's edges need not run forward)
+            changed = False
+            for k in members:
+                for seen in range(want + 1):
+                    if (k, seen) in cost:
+                        for n in succ[k]:
+                            st = (n, seen | has[n])
+                            c = cost[(k, seen)][0] + nvalu[n]
+                            if st not in cost or c < cost[st][0]:
+                                cost[st] = (c, (k, seen))
+                                changed = True
+        ends = [(cost[(k, want)][0], k) for k in latches if (k, want) in cost]
+        path, st = [], (min(ends)[1], want) if ends else None
+        while st is not None:
             path.append(st[0])
             st = cost[st][1]
         hot = [(mn, t) for k in path for mn, t in blocks[k][2]]
@@ -136,10 +165,12 @@ def main():
         perm = sum(1 for mn, _ in hot if mn.startswith("v_permlane"))
         last = blocks[b + 1][1] if b + 1 < len(blocks) else len(body)
         print("  loop %s..%s (listing lines %d..%d): VALU %d in all, %d on the cheapest path | on it: %s, DPP moves %d, DPP-fused ops %d, "
-              "permlanes %d" % (blocks[a][0], blocks[b][0], start + blocks[a][1] + 1, start + last, sum(nvalu[a:b + 1]),
+              "permlanes %d" % (blocks[a][0], blocks[b][0], start + blocks[a][1] + 1, start + last, sum(nvalu[k] for k in members),
                                 sum(1 for mn, _ in hot if is_valu(mn)), " ".join("%s %d" % (f, f64[f]) for f in F64), dpp_mov, dpp_op, perm))
+        if "--mnemonics" in sys.argv:
+            print("    on the path: " + ", ".join("%s %d" % kv for kv in sorted(collections.Counter(base(mn) for mn, _ in hot if is_valu(mn)).items())))
         if "--blocks" in sys.argv:
-            for k in range(a, b + 1):
+            for k in members:
                 br = [t for mn, t in blocks[k][2] if mn.startswith(("s_branch", "s_cbranch"))]
                 print("    %-14s %-4s VALU %4d  %s" % (blocks[k][0], "path" if k in path else "", nvalu[k], "; ".join(br)))
 

@@ -12,13 +12,20 @@ settles both decisions ("no") and keeps the sum clear of the 1e-14 band around t
 A wave-iteration is screened when every problem of the wave that still iterates has such a lane; then the wave takes no sum at all.
 
     python tools/screen_rate.py [--config solo12_trot] [--B 24] [--waves 12] [--num-iters 10] [--per-wave 2]
+                                [--terms force=2 motion=3,5 ...]
 
 solves the problems of `waves` waves spread evenly over the config's batch of B (a wave: per-wave consecutive problems, as the kernel
 takes them) with oracle_np, every FISTA step recorded knot by knot, and prints, per step, the wave-iterations and the share of them
 the screen settles.  Every phase is
 counted as certified (on the benchmark's trot batch every phase is: tools/certify_rate.py).  The floor is restated from the oracle's
 whole b - P (the kernel leaves out the x_init rows of the motion step: a slightly lower floor there); on the benchmark's settings
-tol^2 = 1e-10 is far above it and sets theta alone."""
+tol^2 = 1e-10 is far above it and sets theta alone.
+
+--terms: the two-stage screen (biconvex_admm_body.h: kScreenTermsX, kScreenTermsF).  Stage 1 asks the same question of the sum of a FEW
+of the knot's squares -- the components named, indices into the knot's 9 motion or 3 E force variables; a subset's sum is at most the
+whole, so a hit is as sound -- and only a miss computes the whole partial.  Per step and set of terms given (any number of
+force=... / motion=... items): the share of wave-iterations stage 1 settles and the expected vector instructions per iteration,
+2 k + P(miss) (2 n + 1) for k terms of n (a subtraction and an fma per term, one compare more on a miss) -- against 2 n for one stage."""
 import argparse
 import os
 import sys
@@ -63,7 +70,7 @@ def floor2_of(bPk, x0, L, rho):
 
 def record_solve(b, i, num_iters=10, maxit=150, tol=1e-5):
     """problem i of the batch through oracle_np.biconvex_solve with every FISTA step recorded: returns {"force": [...], "motion": [...]},
-    one (partials [iterations][knots], floor2) per phase -- partials[k][t] is knot t's share of |d|^2 in iteration k"""
+    one (squares [iterations][knots][components], floor2) per phase -- squares[k][t] sums to knot t's share of |d|^2 in iteration k"""
     from oracle import oracle_np as on
     width = {True: 3 * b.E, False: 9}
     phases = {True: [], False: []}
@@ -72,7 +79,7 @@ def record_solve(b, i, num_iters=10, maxit=150, tol=1e-5):
         def step(self, p, y):
             y1, G = super().step(p, y)
             d = (y1 - y).reshape(-1, width[self.soc])
-            self._rows.append((d * d).sum(1))
+            self._rows.append(d * d)
             return y1, G
 
         def optimize(self, p, maxit, tol):
@@ -96,31 +103,50 @@ def record_solve(b, i, num_iters=10, maxit=150, tol=1e-5):
     return {"force": phases[True], "motion": phases[False]}
 
 
-def wave_rate(records, which, tol=1e-5):
+def wave_rate(records, which, tol=1e-5, terms=None):
     """(screened, total) wave-iterations of one wave: records = [record_solve(...)] of its problems.  Per phase the wave runs as many
     iterations as its longest problem; theta takes the largest floor of the problems that run the phase; an iteration is screened
-    when every problem still iterating has a knot above theta."""
+    when every problem still iterating has a knot above theta.  terms: the components whose squares are summed (default: all)."""
     hit = total = 0
+    cols = slice(None) if terms is None else list(terms)
     for k in range(max(len(r[which]) for r in records)):
         ph = [r[which][k] for r in records if k < len(r[which])]
         th = theta(tol * tol, max(fl for _, fl in ph))
         for it in range(max(len(p) for p, _ in ph)):
-            live = [p[it] for p, _ in ph if it < len(p)]
+            live = [p[it][:, cols].sum(1) for p, _ in ph if it < len(p)]
             hit += all(bool(np.any(row > th)) for row in live)
             total += 1
     return hit, total
 
 
+def rates_of(recs, which, per_wave=2, tol=1e-5, terms=None):
+    """(screened, total) wave-iterations of one step over recorded solves taken per_wave at a time"""
+    hit = total = 0
+    for w in range(0, len(recs), per_wave):
+        h, n = wave_rate(recs[w:w + per_wave], which, tol, terms)
+        hit, total = hit + h, total + n
+    return hit, total
+
+
 def rates(b, indices, per_wave=2, num_iters=10, maxit=150, tol=1e-5):
     recs = [record_solve(b, i, num_iters, maxit, tol) for i in indices]
-    out = {}
-    for which in ("force", "motion"):
-        hit = total = 0
-        for w in range(0, len(recs), per_wave):
-            h, n = wave_rate(recs[w:w + per_wave], which, tol)
-            hit, total = hit + h, total + n
-        out[which] = (hit, total)
+    return {which: rates_of(recs, which, per_wave, tol) for which in ("force", "motion")}
+
+
+def parse_terms(items):
+    """["force=2", "motion=3,5", "force=2,5"] -> [("force", (2,)), ("motion", (3, 5)), ("force", (2, 5))]"""
+    out = []
+    for it in items:
+        which, _, idx = it.partition("=")
+        if which not in ("force", "motion") or not idx:
+            raise ValueError("--terms takes force=i,j,... or motion=i,j,...: %r" % it)
+        out.append((which, tuple(int(x) for x in idx.split(","))))
     return out
+
+
+def stage_cost(k, n, p_hit):
+    """expected vector instructions of the two-stage screen per iteration: k of n terms first, the whole chain and a compare on a miss"""
+    return 2 * k + (1.0 - p_hit) * (2 * n + 1)
 
 
 def main():
@@ -131,16 +157,24 @@ def main():
     ap.add_argument("--waves", type=int, default=0, help="waves sampled, spread evenly over the batch (default: all)")
     ap.add_argument("--num-iters", type=int, default=10)
     ap.add_argument("--per-wave", type=int, default=2)
+    ap.add_argument("--terms", nargs="+", default=[], metavar="STEP=I,J", help="stage-1 term sets of the two-stage screen to rate, e.g. force=2 motion=3,5")
     args = ap.parse_args()
+    term_sets = parse_terms(args.terms)
     b = problems.make_batch(args.config, args.B)
     n_waves = -(-args.B // args.per_wave)
     picked = sorted({int(w) for w in np.linspace(0, n_waves - 1, min(args.waves or n_waves, n_waves))})
     idx = [i for w in picked for i in range(w * args.per_wave, min((w + 1) * args.per_wave, args.B))]
-    r = rates(b, idx, args.per_wave, args.num_iters)      # (a last wave with fewer problems comes last: the pairing holds)
+    recs = [record_solve(b, i, args.num_iters) for i in idx]      # (a last wave with fewer problems comes last: the pairing holds)
     for which in ("force", "motion"):
-        hit, total = r[which]
+        hit, total = rates_of(recs, which, args.per_wave)
         print("%-12s %-6s %d problems in waves of %d: %6d wave-iterations, %6d screened (%.1f %%), %.1f per wave"
               % (args.config, which, len(idx), args.per_wave, total, hit, 100.0 * hit / max(total, 1), total / max(1, -(-len(idx) // args.per_wave))))
+    width = {"force": 3 * b.E, "motion": 9}
+    for which, terms in term_sets:
+        hit, total = rates_of(recs, which, args.per_wave, terms=terms)
+        print("%-12s %-6s stage 1 on terms %-12s %6d of %6d wave-iterations settled (%.1f %%), expected cost %.2f instructions (one stage: %d)"
+              % (args.config, which, ",".join(map(str, terms)), hit, total, 100.0 * hit / max(total, 1),
+                 stage_cost(len(terms), width[which], hit / max(total, 1)), 2 * width[which]))
 
 
 if __name__ == "__main__":
