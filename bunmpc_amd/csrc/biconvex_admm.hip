@@ -78,7 +78,7 @@ __global__ void momentum_table_kernel(double *tab, int n) {
     }
 }
 // What a process keeps per device: the momentum table, the work-stealing launches' counters and the chip's size.  (The raised LDS limit
-// of a workgroup kernel is per device too: launch_wg, biconvex_admm_inst.h.)
+// of a workgroup kernel is per device too: launch_inst, biconvex_admm_inst.h.)
 struct DeviceState {
     double *momentum = nullptr;
     int *steal_ring = nullptr;       // 64 counters, one per launch in flight (a launch zeroes its own on its stream in front of the kernel;
@@ -156,7 +156,7 @@ bool two_per_simd_pays(const BatchArgs &a, int per_wave, long simds, const Dispa
 }  // namespace
 
 const AdmmUnit &admm_unit_e4() {
-    static const AdmmUnit unit = {launch_admm<4>, admm_scratch_bytes<4>};
+    static const AdmmUnit unit = {launch_admm<4>, scratch_bytes<AdmmInsts<4>>};
     return unit;
 }
 const AdmmUnit &admm_unit(CostShape shape, int precision, int n_eff) {
@@ -186,16 +186,16 @@ const char *biconvex_last_kernel_name() { return t_last_kernel; }
 // (those other kernels restate the reference's projection only); about per-contact normals (kConeFrame): exactly as kCone.
 LaunchPlan plan_launch(const BatchArgs &a, CostShape shape, int n_eff, long simds, const DispatchKnobs &kn) {
     LaunchPlan p = {hipErrorInvalidValue, nullptr, {0, false, false, 0, {}}, false, a.certified_steps};
-    const bool diag = shape == kDiag, cone = shape == kCone || shape == kConeFrame;
+    if (shape < 0 || shape >= kNumShapes) return p;
+    const ShapeInfo &s = kShapes[shape];
+    const bool diag = shape == kDiag;
     const int k = a.H + 1;
-    const bool built = diag ? k <= kMaxKnots && (a.precision == 0 || a.precision == 1)
-                            : (cone ? k <= 64 && a.precision == 0      // (cone: fp64, one problem per wave segment)
-                                              : (shape == kBlocks || shape == kBand) && k <= 64 && a.precision == 0 && a.raw);      // (blocks / band: raw form, fp64, one problem per wave segment)
+    const bool built = k <= s.max_knots && (a.precision == 0 || (a.precision == 1 && !s.fp64_only)) && (a.raw || !s.raw_only);
     if ((n_eff != 2 && n_eff != 4) || a.H < 1 || a.B < 0 || !built) return p;
     if (a.B == 0) { p.status = hipSuccess; return p; }
     if (a.c.maxit > kMaxFistaIters) return p;
     // the kernels address a wave's problems by 32-bit byte offsets from the wave's first problem (at most four problems)
-    if (diag || (cone && !a.raw))
+    if (diag || !a.raw)
         for (long stride : {a.sW_X, a.sW_X_ter, a.sW_F, a.sbounds})
             if (stride < 0 || stride > (1L << 26)) return p;
     p.status = hipSuccess;
@@ -205,8 +205,8 @@ LaunchPlan plan_launch(const BatchArgs &a, CostShape shape, int n_eff, long simd
         p.latency = true;
         return p;
     }
-    p.certified_steps = !diag ? 0 : (kn.certified_steps == 2 ? 2 : (kn.certified_steps != 0 ? 1 : 0));      // (2: force phases only)
-    p.kernel = shape == kConeFrame ? "biconvex_admm_conef_kernel" : shape == kCone ? "biconvex_admm_cone_kernel" : shape == kBlocks ? "biconvex_admm_bq_kernel" : (shape == kBand ? "biconvex_admm_kq_kernel" : (a.precision == 1 ? "biconvex_admm_kernel_f32" : "biconvex_admm_kernel"));
+    p.certified_steps = !s.certifies ? 0 : (kn.certified_steps == 2 ? 2 : (kn.certified_steps != 0 ? 1 : 0));      // (2: force phases only)
+    p.kernel = diag && a.precision == 1 ? "biconvex_admm_kernel_f32" : s.kernel;
     // the same decisions for two feet as for four, with the LDS record of the foot count (knot_lds)
     auto segments = [&](int lpp) { p.l.lpp = lpp; p.l.w2 = diag && two_per_simd_pays(a, 64 / lpp, simds, kn); return p; };
     if (k <= 16) return segments(16);

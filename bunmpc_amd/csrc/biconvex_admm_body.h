@@ -1,4 +1,4 @@
-// The body of the batched centroidal ADMM kernel (one knot per lane): template admm_body<R, LPP, E, RAW, HASQF>.  Included inside
+// The body of the batched centroidal ADMM kernel (one knot per lane): template admm_body<AdmmCfg<R, LPP, E, RAW, HASQF, ...>>.  Included inside
 // the anonymous namespace of biconvex_admm.hip (fp64 instantiations) and of biconvex_admm_f32.hip (fp32 instantiations, built
 // with other compiler flags: see bunmpc_amd/build.py); the mapping, the reference lines and the algebra are described at the
 // top of biconvex_admm.hip.
@@ -82,8 +82,10 @@ constexpr int sym_index(int n, int r, int c) { return r <= c ? r * n - r * (r - 
 // loads its knot's coefficients mu[t][0 .. E) once per solve (ConeArgs; without an array every foot has SolverConsts::mu) and keeps
 // them in registers.  No step certificate and no fp32 step decisions: every step is tested on the fp64 sums, as with BQ and KQ.  Every
 // CONE operation is under `if constexpr`: the other instantiations compile what they compiled without it.
-// (A CONE instantiation has no band costs, and its coefficients come in the band costs' place: a fourth argument, even an empty
-// struct, is one more temporary in every kernel and reordered the block kernels' prologues.)
+// (The cone KERNELS take their coefficients where the band kernels take their costs, as their one argument beside BatchArgs: a further
+// argument of a kernel, even an empty struct, is one more temporary in it and reordered the block kernels' prologues.  That concerns
+// the kernels' own parameter lists (biconvex_admm_inst.h).  admm_body itself takes the variant's struct as its single argument `ex`,
+// whatever the shape: checked to leave every kernel's instructions what they were, tools/device_asm_diff.py.)
 //
 // FRAME (CONE about per-contact surface normals, ConeFrameArgs): the cone's axis is the unit normal n of the foot's contact at the lane's
 // knot, world frame, instead of world z.  With fn = n.f, ft = f - fn n, s2 = |ft|^2 the three branches are CONE's with fn for fz --
@@ -92,16 +94,35 @@ constexpr int sym_index(int n, int r, int c) { return r <= c ? r * n - r * (r - 
 // output fma(t, n_i, k ft_i)) make every extra term an exact zero for n = (0, 0, 1): the cone kernel's values, up to the sign of a zero.
 // A lane loads its knot's 3E normal components once per solve, beside the coefficients, and keeps them (the compiler rests them in
 // accumulation registers; lanes without a force knot: world z).  The kernel does not normalise.  Every FRAME operation is under
-// `if constexpr`, and its arguments come in the same third slot.
-template <typename R, int LPP, int E, bool RAW, bool HASQF, bool STEAL = false, bool XLDS = false, int WAVES = 1, bool BQ = false, bool KQ = false, bool CONE = false, bool FRAME = false>
-__device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &bq = BlockArgs{}, const std::conditional_t<FRAME, ConeFrameArgs, std::conditional_t<CONE, ConeArgs, BandArgs>> &kq = std::conditional_t<FRAME, ConeFrameArgs, std::conditional_t<CONE, ConeArgs, BandArgs>>{}) {
-    static_assert(!FRAME || CONE, "per-contact normals: the Euclidean cone projection only");
-    static_assert(!CONE || (!BQ && !KQ && !STEAL && !XLDS && WAVES == 1 && LPP <= 64 && sizeof(R) == sizeof(double)), "Euclidean cone projection: diagonal costs, fp64, one problem per <= 64 lanes, one wave per SIMD");
-    static_assert(!BQ || (RAW && !STEAL && !XLDS && WAVES == 1 && sizeof(R) == sizeof(double)), "block costs: raw form, fp64, one wave per problem, one wave per SIMD");
-    static_assert(!KQ || (RAW && !BQ && !STEAL && !XLDS && WAVES == 1 && sizeof(R) == sizeof(double)), "neighbour-knot costs: raw form, diagonal per-knot weights, fp64, one wave per problem, one wave per SIMD");
-    constexpr bool MW = WAVES > 1;
-    static_assert(!MW || (LPP == 64 && !STEAL && sizeof(R) == sizeof(double)), "several waves per problem: fp64, one problem per workgroup");
-    constexpr bool PARK = XLDS && !MW;      // (the LDS header is written by lane 0 and read by the whole problem: across waves that would take barriers)
+// `if constexpr`, and its arguments come as the cone's do, in `ex`.
+//
+// AdmmCfg names one variant of the body: what admm_body is instantiated with.  SHAPE (CostShape, biconvex_kernels.h) says which Q and
+// which projection -- one value, so a variant cannot be two shapes at once -- and with it which argument struct the variant's arrays
+// come in (Extra; kDiag: an empty one).  What a shape's kernels are built for is asserted here from the shape's row of kShapes, the
+// table the launches, plan_launch and the C-ABI read as well.
+template <typename R_, int LPP_, int E_, bool RAW_, bool HASQF_, bool STEAL_ = false, bool XLDS_ = false, int WAVES_ = 1, CostShape SHAPE_ = kDiag>
+struct AdmmCfg {
+    using R = R_;
+    using Extra = ShapeExtra<SHAPE_>;
+    static constexpr int LPP = LPP_, E = E_, WAVES = WAVES_;
+    static constexpr bool RAW = RAW_, HASQF = HASQF_, STEAL = STEAL_, XLDS = XLDS_, FP64 = sizeof(R) == sizeof(double);
+    static constexpr bool BQ = SHAPE_ == kBlocks, KQ = SHAPE_ == kBand, FRAME = SHAPE_ == kConeFrame, CONE = SHAPE_ == kCone || FRAME;
+    static constexpr bool MW = WAVES > 1;
+    static constexpr bool PARK = XLDS && !MW;      // (the LDS header is written by lane 0 and read by the whole problem: across waves that would take barriers)
+    static constexpr bool CAN_CERT = FP64 && kShapes[SHAPE_].certifies;      // (see `certify` in the body)
+    static constexpr bool BAND = !MW && !STEAL && XLDS && !RAW && LPP == 32 && E == 4 && FP64;      // (the headline kernel: see "fp32 step decisions" in the body)
+    static_assert(!kShapes[SHAPE_].fp64_only || FP64, "this cost shape: fp64 only");
+    static_assert(!kShapes[SHAPE_].raw_only || RAW, "this cost shape: raw form only");
+    static_assert(LPP * WAVES <= kShapes[SHAPE_].max_knots, "this cost shape: more lanes per problem than it has kernels for");
+    static_assert(SHAPE_ == kDiag || (!STEAL && !XLDS && WAVES == 1), "cost shapes beside the diagonal: one wave per problem, one wave per SIMD");
+    static_assert(!MW || (LPP == 64 && !STEAL && FP64), "several waves per problem: fp64, one problem per workgroup");
+};
+template <typename C>
+__device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::Extra &ex = {}) {
+    using R = typename C::R;
+    constexpr int LPP = C::LPP, E = C::E, WAVES = C::WAVES;
+    [[maybe_unused]] constexpr bool RAW = C::RAW, HASQF = C::HASQF, STEAL = C::STEAL, XLDS = C::XLDS, BQ = C::BQ, KQ = C::KQ, CONE = C::CONE, FRAME = C::FRAME, MW = C::MW, PARK = C::PARK;
+    [[maybe_unused]] const auto &bq = ex, &kq = ex;      // (the names the BQ and the KQ / CONE / FRAME code reads its arrays by)
     extern __shared__ double lds_raw[];
     constexpr int NF = 3 * E;           // force variables per knot
     constexpr int NB = RAW ? 9 : 3;     // bounded components per knot
@@ -192,7 +213,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
     // The step certificate of a force phase: every lane of every live problem found its scaled Gershgorin row test
     // (`ok`) true -- then no step of the phase's FISTA loop can fail the backtracking test, and the loop runs without it.  Wave-
     // (MW: workgroup-) uniform.
-    constexpr bool CAN_CERT = sizeof(R) == sizeof(double) && !BQ && !KQ && !CONE;      // (BQ, KQ: the rows below assume a diagonal W; CONE: every step tested; fp32: the image noise does make the test fire, see the force step)
+    constexpr bool CAN_CERT = C::CAN_CERT;      // fp64 and a shape whose row of kShapes says so (BQ, KQ: the rows below assume a diagonal W; CONE: every step tested; fp32: the image noise does make the test fire, see the force step)
     auto certify = [&](bool ok, mask_t live) -> bool {
         if (!CAN_CERT || !a.certified_steps) return false;
         if (!MW) return (__ballot(!ok) & live) == 0;
@@ -224,7 +245,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const BlockArgs &b
     // source moved the compiler's register allocation (scratch of the 16- / 21-lane and two-feet kernels 40 -> 116, 32 -> 100, 8 -> 76
     // bytes per lane, reloads inside the FISTA loops), the rounding of the iterates (two feet, 21 lanes) or the time (the work-stealing
     // kernel, 27.6 -> 29.6 ms): they keep the fp64 sums, as do the workgroup kernels (MW) and the fp32 kernel.
-    constexpr bool BAND = !MW && !STEAL && XLDS && !RAW && LPP == 32 && E == 4 && sizeof(R) == sizeof(double);
+    constexpr bool BAND = C::BAND;
     constexpr double kBand = 1e-5;
     // (1 - kBand) x and (1 + kBand) x as floats, wave-uniform (scalar registers): thresholds that need no range check, g2 is confined
     auto band_u = [](double x, float &lo, float &hi) {

@@ -16,7 +16,7 @@ namespace {
 }  // namespace
 
 const AdmmUnit &admm_unit_bq_e4() {
-    static const AdmmUnit unit = {launch_bq<4>, bq_scratch_bytes<4>};
+    static const AdmmUnit unit = {launch_shape<kBlocks, 4>, scratch_bytes<ShapeInsts<kBlocks, 4>>};
     return unit;
 }
 

@@ -13,7 +13,7 @@ namespace {
 }  // namespace
 
 const AdmmUnit &admm_unit_bq_e2() {
-    static const AdmmUnit unit = {launch_bq<2>, bq_scratch_bytes<2>};
+    static const AdmmUnit unit = {launch_shape<kBlocks, 2>, scratch_bytes<ShapeInsts<kBlocks, 2>>};
     return unit;
 }
 

@@ -15,7 +15,7 @@ namespace {
 }  // namespace
 
 const AdmmUnit &admm_unit_cone_e4() {
-    static const AdmmUnit unit = {launch_cone<4>, cone_scratch_bytes<4>};
+    static const AdmmUnit unit = {launch_shape<kCone, 4>, scratch_bytes<ShapeInsts<kCone, 4>>};
     return unit;
 }
 

@@ -13,7 +13,7 @@ namespace {
 }  // namespace
 
 const AdmmUnit &admm_unit_cone_e2() {
-    static const AdmmUnit unit = {launch_cone<2>, cone_scratch_bytes<2>};
+    static const AdmmUnit unit = {launch_shape<kCone, 2>, scratch_bytes<ShapeInsts<kCone, 2>>};
     return unit;
 }
 

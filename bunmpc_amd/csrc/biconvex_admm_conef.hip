@@ -15,7 +15,7 @@ namespace {
 }  // namespace
 
 const AdmmUnit &admm_unit_conef_e4() {
-    static const AdmmUnit unit = {launch_conef<4>, conef_scratch_bytes<4>};
+    static const AdmmUnit unit = {launch_shape<kConeFrame, 4>, scratch_bytes<ShapeInsts<kConeFrame, 4>>};
     return unit;
 }
 

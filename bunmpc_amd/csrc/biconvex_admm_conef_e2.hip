@@ -13,7 +13,7 @@ namespace {
 }  // namespace
 
 const AdmmUnit &admm_unit_conef_e2() {
-    static const AdmmUnit unit = {launch_conef<2>, conef_scratch_bytes<2>};
+    static const AdmmUnit unit = {launch_shape<kConeFrame, 2>, scratch_bytes<ShapeInsts<kConeFrame, 2>>};
     return unit;
 }
 

@@ -15,7 +15,7 @@ namespace {
 }  // namespace
 
 const AdmmUnit &admm_unit_e2() {
-    static const AdmmUnit unit = {launch_admm<2>, admm_scratch_bytes<2>};
+    static const AdmmUnit unit = {launch_admm<2>, scratch_bytes<AdmmInsts<2>>};
     return unit;
 }
 

@@ -21,7 +21,7 @@ namespace {
 }  // namespace
 
 const AdmmUnit &admm_unit_f32_e4() {
-    static const AdmmUnit unit = {launch_f32<4>, f32_scratch_bytes<4>};
+    static const AdmmUnit unit = {launch_f32<4>, scratch_bytes<F32Insts<4>>};
     return unit;
 }
 

@@ -13,7 +13,7 @@ namespace {
 }  // namespace
 
 const AdmmUnit &admm_unit_f32_e2() {
-    static const AdmmUnit unit = {launch_f32<2>, f32_scratch_bytes<2>};
+    static const AdmmUnit unit = {launch_f32<2>, scratch_bytes<F32Insts<2>>};
     return unit;
 }
 

@@ -1,16 +1,17 @@
 // The kernels of the batched centroidal ADMM and their launches, templated on the number of feet E.  Included inside the anonymous
 // namespace of one translation unit per cost shape, precision and foot count (after biconvex_lanes.h and biconvex_admm_body.h), each
-// of which instantiates its own launch and exports it as one AdmmUnit (biconvex_kernels.h):
-//   biconvex_admm.hip        fp64, E = 4   launch_admm        biconvex_admm_f32.hip      fp32, E = 4   launch_f32
-//   biconvex_admm_e2.hip     fp64, E = 2                      biconvex_admm_f32_e2.hip   fp32, E = 2
-//   biconvex_admm_bq.hip     blocks, E = 4   launch_bq        biconvex_admm_kq.hip       band, E = 4   launch_kq
-//   biconvex_admm_bq_e2.hip  blocks, E = 2                    biconvex_admm_kq_e2.hip    band, E = 2
-//   biconvex_admm_cone.hip   Euclidean cone projection, E = 4   launch_cone
-//   biconvex_admm_cone_e2.hip                           E = 2
-//   biconvex_admm_conef.hip  ... about per-contact normals, E = 4   launch_conef
-//   biconvex_admm_conef_e2.hip                             E = 2
+// of which exports its launch and its list of instantiations as one AdmmUnit (biconvex_kernels.h):
+//   biconvex_admm.hip, _e2           fp64, diagonal costs, E = 4, 2      launch_admm, AdmmInsts
+//   biconvex_admm_f32.hip, _f32_e2   fp32                                launch_f32, F32Insts
+//   biconvex_admm_bq.hip, _bq_e2     blocks (kBlocks)                    launch_shape<SHAPE, E>, ShapeInsts<SHAPE, E>
+//   biconvex_admm_kq.hip, _kq_e2     band (kBand)
+//   biconvex_admm_cone.hip, _cone_e2     Euclidean cone projection (kCone)
+//   biconvex_admm_conef.hip, _conef_e2   ... about per-contact normals (kConeFrame)
 // so that every unit is built with its own flags (bunmpc_amd/build.py), the units build in parallel and one feature's kernels cannot
 // disturb another's code object.  Which kernel a batch gets is decided once, for every unit, by plan_launch (biconvex_admm.hip).
+// A new cost shape is: its CostShape value with its row of kShapes and its struct in ShapeExtra (biconvex_kernels.h), its kernel
+// template below with its lines in shape_kernel / shape_extra, two unit files (and admm_unit's line), and its `if constexpr` code in
+// the body.
 #pragma once
 
 // fp64, WPE = 1: ONE wave per SIMD.  The body holds 294 registers; capped at 256 with the FISTA iterates in registers the compiler parks
@@ -22,250 +23,179 @@
 // B = 4096, H = 20: 3.74 against 4.02 ms.
 template <typename R, int LPP, int E, bool RAW, bool HASQF, int WPE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void biconvex_admm_kernel(const BatchArgs a) {
-    admm_body<R, LPP, E, RAW, HASQF, false, WPE == 2>(a);
+    admm_body<AdmmCfg<R, LPP, E, RAW, HASQF, false, WPE == 2>>(a);
 }
 // horizons of 64 .. 255 knots: one problem per workgroup of WAVES waves (biconvex_admm_body.h: WAVES)
 template <int E, int WAVES, bool RAW, bool HASQF, int WPE>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void biconvex_admm_wg_kernel(const BatchArgs a) {
-    admm_body<double, 64, E, RAW, HASQF, false, WPE == 2, WAVES>(a);
+    admm_body<AdmmCfg<double, 64, E, RAW, HASQF, false, WPE == 2, WAVES>>(a);
 }
 // the work-stealing variant (biconvex_admm_body.h: STEAL): three problems per wave, harness form, fp64
 template <int E, int WPE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void biconvex_admm_steal_kernel(const BatchArgs a) {
-    admm_body<double, 21, E, false, false, true, WPE == 2>(a);
+    admm_body<AdmmCfg<double, 21, E, false, false, true, WPE == 2>>(a);
 }
 // fp32: TWO waves per SIMD -- this latency-bound loop gains a second wave to issue from while the first waits (one wave per SIMD:
 // 9.0 ms).  Instantiated only in the fp32 units (biconvex_admm_f32.hip explains their flags).
 template <int LPP, int E>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void biconvex_admm_kernel_f32(const BatchArgs a) {
-    admm_body<float, LPP, E, false, false>(a);
+    admm_body<AdmmCfg<float, LPP, E, false, false>>(a);
 }
 
 // Per-knot block costs (biconvex_admm_body.h: BQ).  Raw form, fp64, one wave per SIMD: the force phase holds the knot's 3E x 3E block
 // (78 values at four feet) beside what the diagonal kernel holds, the motion phase its 9 x 9 block (45).
 template <int LPP, int E, bool HASQF>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void biconvex_admm_bq_kernel(const BatchArgs a, const BlockArgs q) {
-    admm_body<double, LPP, E, true, HASQF, false, false, 1, true>(a, q);
+    admm_body<AdmmCfg<double, LPP, E, true, HASQF, false, false, 1, kBlocks>>(a, q);
 }
 // Costs between neighbouring knots (biconvex_admm_body.h: KQ).  Raw form, fp64, one wave per SIMD: beside what the diagonal kernel holds
 // a phase keeps the coupling weights of its knot's two pairs (2 x 3E or 2 x 9 values) and, over a FISTA iteration, its two neighbours' y.
 template <int LPP, int E, bool HASQF>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void biconvex_admm_kq_kernel(const BatchArgs a, const BandArgs q) {
-    admm_body<double, LPP, E, true, HASQF, false, false, 1, false, true>(a, BlockArgs{}, q);
+    admm_body<AdmmCfg<double, LPP, E, true, HASQF, false, false, 1, kBand>>(a, q);
 }
 // The Euclidean cone projection with per-foot friction coefficients (biconvex_admm_body.h: CONE).  Both forms, fp64, one wave per SIMD:
 // beside what the diagonal kernel holds a lane keeps its knot's E coefficients over the whole solve.
 template <int LPP, int E, bool RAW, bool HASQF>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void biconvex_admm_cone_kernel(const BatchArgs a, const ConeArgs c) {
-    admm_body<double, LPP, E, RAW, HASQF, false, false, 1, false, false, true>(a, BlockArgs{}, c);
+    admm_body<AdmmCfg<double, LPP, E, RAW, HASQF, false, false, 1, kCone>>(a, c);
 }
 // ... about per-contact surface normals (biconvex_admm_body.h: FRAME): the cone kernel, and a lane keeps its knot's 3E normal components
 // beside the E coefficients.
 template <int LPP, int E, bool RAW, bool HASQF>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void biconvex_admm_conef_kernel(const BatchArgs a, const ConeFrameArgs c) {
-    admm_body<double, LPP, E, RAW, HASQF, false, false, 1, false, false, true, true>(a, BlockArgs{}, c);
+    admm_body<AdmmCfg<double, LPP, E, RAW, HASQF, false, false, 1, kConeFrame>>(a, c);
 }
 
-// The one switch over the lanes per problem: f(std::integral_constant<int, LPP>) of the plan's lpp.  A launch names the values its unit
-// instantiates with `if constexpr` and refuses the others.
-template <typename F>
-hipError_t with_lpp(int lpp, F &&f) {
-    switch (lpp) {
-        case 16: return f(std::integral_constant<int, 16>{});
-        case 21: return f(std::integral_constant<int, 21>{});
-        case 32: return f(std::integral_constant<int, 32>{});
-        case 64: return f(std::integral_constant<int, 64>{});
-        case 128: return f(std::integral_constant<int, 128>{});
-        case 192: return f(std::integral_constant<int, 192>{});
-        case 256: return f(std::integral_constant<int, 256>{});
-        default: return hipErrorInvalidValue;
+// One instantiation of a unit: its kernel and the plan that takes it -- lanes per problem (above 64: the workgroup kernel of LPP / 64
+// waves), form (0 harness, 1 raw, 2 raw with qf), AdmmLaunch::w2 and ::steal.
+template <auto K, int LPP_, int FORM, bool W2 = false, bool STEAL_ = false>
+struct Inst {
+    static constexpr auto kernel = K;
+    static constexpr int LPP = LPP_;
+    static constexpr bool STEAL = STEAL_;
+    static bool planned(const BatchArgs &a, const AdmmLaunch &l) {
+        return l.lpp == LPP && l.steal == STEAL && l.w2 == W2 && (a.raw ? (a.qf ? 2 : 1) : 0) == FORM;
     }
-}
-// a kernel of 64 / LPP problems per wave over the batch, with its arguments
-template <int LPP, int E, typename K, typename... A>
-hipError_t launch_segments(K kernel, size_t elem, const BatchArgs &a, hipStream_t stream, const A &...args) {
-    hipLaunchKernelGGL(kernel, dim3(launch_grid(a.B, 64 / LPP)), dim3(64), launch_lds_bytes(elem, 64 / LPP, E, a.H), stream, a, args...);
-    return hipGetLastError();
-}
+};
+// f(std::integral_constant<int, V>) for every V of a list
+template <int... V>
+using Ints = std::integer_sequence<int, V...>;
+template <typename F, int... V>
+void each_int(Ints<V...>, F &&f) { (f(std::integral_constant<int, V>{}), ...); }
 
-template <int LPP, int E, bool RAW, bool HASQF>
-hipError_t launch(const BatchArgs &a, bool two_per_simd, hipStream_t stream) {
-    if (two_per_simd) return launch_segments<LPP, E>(biconvex_admm_kernel<double, LPP, E, RAW, HASQF, 2>, sizeof(double), a, stream);
-    return launch_segments<LPP, E>(biconvex_admm_kernel<double, LPP, E, RAW, HASQF, 1>, sizeof(double), a, stream);
+// The instantiations of each unit, v(Inst<...>{}) for every one: what its launch chooses from and what its scratch query covers.
+// fp64, diagonal costs: batch kernel (every lanes-per-problem, form and build), workgroup kernel likewise, work stealing
+template <int E_>
+struct AdmmInsts {
+    static constexpr int E = E_;
+    template <typename V>
+    static void each(V &&v) {
+        each_int(Ints<0, 1, 2>{}, [&](auto form) { each_int(Ints<1, 2>{}, [&](auto wpe) {
+            constexpr int FORM = decltype(form)::value, WPE = decltype(wpe)::value;
+            each_int(Ints<16, 21, 32, 64>{}, [&](auto lpp) { v(Inst<&biconvex_admm_kernel<double, decltype(lpp)::value, E, (FORM > 0), FORM == 2, WPE>, decltype(lpp)::value, FORM, WPE == 2>{}); });
+            each_int(Ints<2, 3, 4>{}, [&](auto waves) { v(Inst<&biconvex_admm_wg_kernel<E, decltype(waves)::value, (FORM > 0), FORM == 2, WPE>, 64 * decltype(waves)::value, FORM, WPE == 2>{}); });
+        }); });
+        v(Inst<&biconvex_admm_steal_kernel<E, 1>, 21, 0, false, true>{});
+        v(Inst<&biconvex_admm_steal_kernel<E, 2>, 21, 0, true, true>{});
+    }
+};
+// fp32 (the units built without the SLP vectoriser): harness form, 16 / 32 / 64 lanes per problem
+template <int E_>
+struct F32Insts {
+    static constexpr int E = E_;
+    template <typename V>
+    static void each(V &&v) { each_int(Ints<16, 32, 64>{}, [&](auto lpp) { v(Inst<&biconvex_admm_kernel_f32<decltype(lpp)::value, E>, decltype(lpp)::value, 0>{}); }); }
+};
+// the other cost shapes: every lanes-per-problem up to 64, the forms the shape is built for (kShapes)
+template <CostShape SHAPE, int LPP, int E, bool RAW, bool HASQF>
+constexpr auto shape_kernel() {
+    if constexpr (SHAPE == kBlocks) return &biconvex_admm_bq_kernel<LPP, E, HASQF>;
+    else if constexpr (SHAPE == kBand) return &biconvex_admm_kq_kernel<LPP, E, HASQF>;
+    else if constexpr (SHAPE == kCone) return &biconvex_admm_cone_kernel<LPP, E, RAW, HASQF>;
+    else return &biconvex_admm_conef_kernel<LPP, E, RAW, HASQF>;
 }
+template <CostShape SHAPE>
+ShapeExtra<SHAPE> shape_extra(const CostArgs &c) {
+    if constexpr (SHAPE == kCone) return {c.f, c.sf};
+    else if constexpr (SHAPE == kConeFrame) return {c.f, c.sf, c.x, c.sx};
+    else return {c.x, c.f, c.sx, c.sf};
+}
+template <CostShape SHAPE, int E_>
+struct ShapeInsts {
+    static constexpr int E = E_;
+    template <typename V>
+    static void each(V &&v) {
+        each_int(Ints<16, 21, 32, 64>{}, [&](auto lpp) { each_int(Ints<0, 1, 2>{}, [&](auto form) {
+            constexpr int LPP = decltype(lpp)::value, FORM = decltype(form)::value;
+            if constexpr (FORM > 0 || !kShapes[SHAPE].raw_only) v(Inst<shape_kernel<SHAPE, LPP, E, (FORM > 0), FORM == 2>(), LPP, FORM>{});
+        }); });
+    }
+};
 
-template <int E, int WAVES, bool RAW, bool HASQF, int WPE>
-hipError_t launch_wg(const BatchArgs &a, hipStream_t stream) {
-    // more than the 64 KB a kernel may take without asking, from 209 knots on: raised once per device and instantiation
-    static std::mutex lock;
-    static bool raised[16] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return hipErrorInvalidDevice;
-    {
-        std::lock_guard<std::mutex> hold(lock);
-        if (!raised[dev]) {
-            const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&biconvex_admm_wg_kernel<E, WAVES, RAW, HASQF, WPE>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            if (attr != hipSuccess) return attr;
-            raised[dev] = true;
+// Launch one instantiation with the plan's geometry: a kernel of 64 / LPP problems per wave over the batch with the shape's arguments,
+// a workgroup per problem, or the persistent grid of the work-stealing kernel
+template <typename I, int E, typename... X>
+hipError_t launch_inst(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream, const X &...extra) {
+    constexpr auto kernel = I::kernel;
+    const size_t elem = a.precision == 1 ? sizeof(float) : sizeof(double);
+    if constexpr (I::STEAL) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)l.steal_waves), dim3(64), launch_lds_bytes(elem, 3, E, a.H), stream, a);
+    } else if constexpr (I::LPP > 64) {
+        // more than the 64 KB a kernel may take without asking, from 209 knots on: raised once per device and instantiation
+        static std::mutex lock;
+        static bool raised[16] = {};
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return hipErrorInvalidDevice;
+        {
+            std::lock_guard<std::mutex> hold(lock);
+            if (!raised[dev]) {
+                const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+                if (attr != hipSuccess) return attr;
+                raised[dev] = true;
+            }
         }
+        hipLaunchKernelGGL(kernel, dim3(launch_grid(a.B, 1)), dim3(I::LPP), launch_lds_bytes(elem, 1, E, a.H, (size_t)(I::LPP / 64) * 40), stream, a);
+    } else {
+        hipLaunchKernelGGL(kernel, dim3(launch_grid(a.B, 64 / I::LPP)), dim3(64), launch_lds_bytes(elem, 64 / I::LPP, E, a.H), stream, a, extra...);
     }
-    hipLaunchKernelGGL((biconvex_admm_wg_kernel<E, WAVES, RAW, HASQF, WPE>), dim3(launch_grid(a.B, 1)), dim3(64 * WAVES), launch_lds_bytes(sizeof(double), 1, E, a.H, (size_t)WAVES * 40), stream, a);
     return hipGetLastError();
 }
-template <int E, int WAVES, int WPE>
-hipError_t launch_wg_form(const BatchArgs &a, hipStream_t stream) {
-    if (a.precision != 0) return hipErrorInvalidValue;      // (fp64 only)
-    if (!a.raw) return launch_wg<E, WAVES, false, false, WPE>(a, stream);
-    return a.qf ? launch_wg<E, WAVES, true, true, WPE>(a, stream) : launch_wg<E, WAVES, true, false, WPE>(a, stream);
+// the launch plan_launch decided on, from the unit's instantiations (a.queue: the work-stealing kernel's device counter, set by the caller)
+template <typename Insts, typename... X>
+hipError_t launch_planned(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream, const X &...extra) {
+    hipError_t err = hipErrorInvalidValue;      // (a plan the unit has no kernel for)
+    Insts::each([&](auto inst) { if (decltype(inst)::planned(a, l)) err = launch_inst<decltype(inst), Insts::E>(a, l, stream, extra...); });
+    return err;
 }
-
-// the launch plan_launch decided on, fp64 with diagonal costs: batch kernel, workgroup kernel, or the persistent grid of the
-// work-stealing kernel (a.queue: its device counter, set by the caller)
 template <int E>
 hipError_t launch_admm(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream) {
     if (a.precision != 0) return hipErrorInvalidValue;
-    if (l.steal) {
-        const size_t lds = launch_lds_bytes(sizeof(double), 3, E, a.H);
-        if (l.w2) hipLaunchKernelGGL((biconvex_admm_steal_kernel<E, 2>), dim3((unsigned)l.steal_waves), dim3(64), lds, stream, a);
-        else hipLaunchKernelGGL((biconvex_admm_steal_kernel<E, 1>), dim3((unsigned)l.steal_waves), dim3(64), lds, stream, a);
-        return hipGetLastError();
-    }
-    return with_lpp(l.lpp, [&](auto lanes) {
-        constexpr int LPP = decltype(lanes)::value;
-        if constexpr (LPP > 64) return l.w2 ? launch_wg_form<E, LPP / 64, 2>(a, stream) : launch_wg_form<E, LPP / 64, 1>(a, stream);
-        else if (!a.raw) return launch<LPP, E, false, false>(a, l.w2, stream);
-        else return a.qf ? launch<LPP, E, true, true>(a, l.w2, stream) : launch<LPP, E, true, false>(a, l.w2, stream);
-    });
+    return launch_planned<AdmmInsts<E>>(a, l, stream);
 }
-// ... fp32 (the units built without the SLP vectoriser): harness form, 16 / 32 / 64 lanes per problem
 template <int E>
 hipError_t launch_f32(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream) {
     if (a.precision != 1 || a.raw) return hipErrorInvalidValue;
-    return with_lpp(l.lpp, [&](auto lanes) {
-        constexpr int LPP = decltype(lanes)::value;
-        if constexpr (LPP == 16 || LPP == 32 || LPP == 64) return launch_segments<LPP, E>(biconvex_admm_kernel_f32<LPP, E>, sizeof(float), a, stream);
-        else return hipErrorInvalidValue;
-    });
+    return launch_planned<F32Insts<E>>(a, l, stream);
 }
-// ... block costs and costs between neighbouring knots: raw form, fp64, at most 64 lanes per problem
-template <int E>
-hipError_t launch_bq(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream) {
-    if (!a.raw || a.precision != 0 || a.H + 1 > l.lpp) return hipErrorInvalidValue;
-    const BlockArgs q = {l.cost.x, l.cost.f, l.cost.sx, l.cost.sf};
-    return with_lpp(l.lpp, [&](auto lanes) {
-        constexpr int LPP = decltype(lanes)::value;
-        if constexpr (LPP > 64) return hipErrorInvalidValue;
-        else return a.qf ? launch_segments<LPP, E>(biconvex_admm_bq_kernel<LPP, E, true>, sizeof(double), a, stream, q)
-                         : launch_segments<LPP, E>(biconvex_admm_bq_kernel<LPP, E, false>, sizeof(double), a, stream, q);
-    });
-}
-template <int E>
-hipError_t launch_kq(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream) {
-    if (!a.raw || a.precision != 0 || a.H + 1 > l.lpp) return hipErrorInvalidValue;
-    const BandArgs q = {l.cost.x, l.cost.f, l.cost.sx, l.cost.sf};
-    return with_lpp(l.lpp, [&](auto lanes) {
-        constexpr int LPP = decltype(lanes)::value;
-        if constexpr (LPP > 64) return hipErrorInvalidValue;
-        else return a.qf ? launch_segments<LPP, E>(biconvex_admm_kq_kernel<LPP, E, true>, sizeof(double), a, stream, q)
-                         : launch_segments<LPP, E>(biconvex_admm_kq_kernel<LPP, E, false>, sizeof(double), a, stream, q);
-    });
-}
-// ... the Euclidean cone projection: either form, fp64, at most 64 lanes per problem
-template <int E>
-hipError_t launch_cone(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream) {
-    if (a.precision != 0 || a.H + 1 > l.lpp) return hipErrorInvalidValue;
-    const ConeArgs c = {l.cost.f, l.cost.sf};
-    return with_lpp(l.lpp, [&](auto lanes) {
-        constexpr int LPP = decltype(lanes)::value;
-        if constexpr (LPP > 64) return hipErrorInvalidValue;
-        else if (!a.raw) return launch_segments<LPP, E>(biconvex_admm_cone_kernel<LPP, E, false, false>, sizeof(double), a, stream, c);
-        else return a.qf ? launch_segments<LPP, E>(biconvex_admm_cone_kernel<LPP, E, true, true>, sizeof(double), a, stream, c)
-                         : launch_segments<LPP, E>(biconvex_admm_cone_kernel<LPP, E, true, false>, sizeof(double), a, stream, c);
-    });
-}
-// ... the same about per-contact normals (l.cost.x, never null here: without normals the C-ABI takes the cone kernel)
-template <int E>
-hipError_t launch_conef(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream) {
-    if (a.precision != 0 || a.H + 1 > l.lpp || !l.cost.x) return hipErrorInvalidValue;
-    const ConeFrameArgs c = {l.cost.f, l.cost.sf, l.cost.x, l.cost.sx};
-    return with_lpp(l.lpp, [&](auto lanes) {
-        constexpr int LPP = decltype(lanes)::value;
-        if constexpr (LPP > 64) return hipErrorInvalidValue;
-        else if (!a.raw) return launch_segments<LPP, E>(biconvex_admm_conef_kernel<LPP, E, false, false>, sizeof(double), a, stream, c);
-        else return a.qf ? launch_segments<LPP, E>(biconvex_admm_conef_kernel<LPP, E, true, true>, sizeof(double), a, stream, c)
-                         : launch_segments<LPP, E>(biconvex_admm_conef_kernel<LPP, E, true, false>, sizeof(double), a, stream, c);
-    });
+// ... with the shape's arrays, under the guards of its row of kShapes (kConeFrame: l.cost.x, the normals, is never null here -- without
+// normals the C-ABI takes the cone kernel)
+template <CostShape SHAPE, int E>
+hipError_t launch_shape(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream) {
+    constexpr ShapeInfo s = kShapes[SHAPE];
+    if ((s.raw_only && !a.raw) || (s.fp64_only && a.precision != 0) || a.H + 1 > l.lpp || l.lpp > s.max_knots) return hipErrorInvalidValue;
+    if (SHAPE == kConeFrame && !l.cost.x) return hipErrorInvalidValue;
+    return launch_planned<ShapeInsts<SHAPE, E>>(a, l, stream, shape_extra<SHAPE>(l.cost));
 }
 
-// private-segment (scratch) bytes per lane, the largest over the kernels listed
-template <typename... K>
-int max_scratch_bytes(K... kernels) {
-    size_t worst = 0;
-    for (const void *k : {reinterpret_cast<const void *>(kernels)...}) {
+// private-segment (scratch) bytes per lane, the largest over the unit's instantiations; -1 on error
+template <typename Insts>
+int scratch_bytes() {
+    long worst = 0;
+    Insts::each([&](auto inst) {
         hipFuncAttributes at;
-        if (hipFuncGetAttributes(&at, k) != hipSuccess) return -1;
-        worst = at.localSizeBytes > worst ? at.localSizeBytes : worst;
-    }
+        if (worst < 0 || hipFuncGetAttributes(&at, reinterpret_cast<const void *>(decltype(inst)::kernel)) != hipSuccess) worst = -1;
+        else worst = (long)at.localSizeBytes > worst ? (long)at.localSizeBytes : worst;
+    });
     return (int)worst;
-}
-// ... of the fp64 instantiations of one foot count: batch kernel (every lanes-per-problem, form and build), workgroup, work stealing
-template <int E, int LPP>
-int lpp_scratch_bytes() {
-    return max_scratch_bytes(&biconvex_admm_kernel<double, LPP, E, false, false, 1>, &biconvex_admm_kernel<double, LPP, E, true, false, 1>,
-                             &biconvex_admm_kernel<double, LPP, E, true, true, 1>, &biconvex_admm_kernel<double, LPP, E, false, false, 2>,
-                             &biconvex_admm_kernel<double, LPP, E, true, false, 2>, &biconvex_admm_kernel<double, LPP, E, true, true, 2>);
-}
-template <int E, int WAVES>
-int wg_scratch_bytes() {
-    return max_scratch_bytes(&biconvex_admm_wg_kernel<E, WAVES, false, false, 1>, &biconvex_admm_wg_kernel<E, WAVES, true, false, 1>,
-                             &biconvex_admm_wg_kernel<E, WAVES, true, true, 1>, &biconvex_admm_wg_kernel<E, WAVES, false, false, 2>,
-                             &biconvex_admm_wg_kernel<E, WAVES, true, false, 2>, &biconvex_admm_wg_kernel<E, WAVES, true, true, 2>);
-}
-template <int E>
-int admm_scratch_bytes() {
-    int worst = max_scratch_bytes(&biconvex_admm_steal_kernel<E, 1>, &biconvex_admm_steal_kernel<E, 2>);
-    for (int s : {lpp_scratch_bytes<E, 16>(), lpp_scratch_bytes<E, 21>(), lpp_scratch_bytes<E, 32>(), lpp_scratch_bytes<E, 64>(),
-                  wg_scratch_bytes<E, 2>(), wg_scratch_bytes<E, 3>(), wg_scratch_bytes<E, 4>()}) {
-        if (s < 0 || worst < 0) return -1;
-        worst = s > worst ? s : worst;
-    }
-    return worst;
-}
-template <int E>
-int f32_scratch_bytes() { return max_scratch_bytes(&biconvex_admm_kernel_f32<16, E>, &biconvex_admm_kernel_f32<32, E>, &biconvex_admm_kernel_f32<64, E>); }
-template <int E>
-int bq_scratch_bytes() {
-    return max_scratch_bytes(&biconvex_admm_bq_kernel<16, E, false>, &biconvex_admm_bq_kernel<16, E, true>, &biconvex_admm_bq_kernel<21, E, false>, &biconvex_admm_bq_kernel<21, E, true>,
-                             &biconvex_admm_bq_kernel<32, E, false>, &biconvex_admm_bq_kernel<32, E, true>, &biconvex_admm_bq_kernel<64, E, false>, &biconvex_admm_bq_kernel<64, E, true>);
-}
-template <int E>
-int kq_scratch_bytes() {
-    return max_scratch_bytes(&biconvex_admm_kq_kernel<16, E, false>, &biconvex_admm_kq_kernel<16, E, true>, &biconvex_admm_kq_kernel<21, E, false>, &biconvex_admm_kq_kernel<21, E, true>,
-                             &biconvex_admm_kq_kernel<32, E, false>, &biconvex_admm_kq_kernel<32, E, true>, &biconvex_admm_kq_kernel<64, E, false>, &biconvex_admm_kq_kernel<64, E, true>);
-}
-template <int E, int LPP>
-int cone_lpp_scratch_bytes() {
-    return max_scratch_bytes(&biconvex_admm_cone_kernel<LPP, E, false, false>, &biconvex_admm_cone_kernel<LPP, E, true, false>, &biconvex_admm_cone_kernel<LPP, E, true, true>);
-}
-template <int E>
-int cone_scratch_bytes() {
-    int worst = 0;
-    for (int s : {cone_lpp_scratch_bytes<E, 16>(), cone_lpp_scratch_bytes<E, 21>(), cone_lpp_scratch_bytes<E, 32>(), cone_lpp_scratch_bytes<E, 64>()}) {
-        if (s < 0) return -1;
-        worst = s > worst ? s : worst;
-    }
-    return worst;
-}
-template <int E, int LPP>
-int conef_lpp_scratch_bytes() {
-    return max_scratch_bytes(&biconvex_admm_conef_kernel<LPP, E, false, false>, &biconvex_admm_conef_kernel<LPP, E, true, false>, &biconvex_admm_conef_kernel<LPP, E, true, true>);
-}
-template <int E>
-int conef_scratch_bytes() {
-    int worst = 0;
-    for (int s : {conef_lpp_scratch_bytes<E, 16>(), conef_lpp_scratch_bytes<E, 21>(), conef_lpp_scratch_bytes<E, 32>(), conef_lpp_scratch_bytes<E, 64>()}) {
-        if (s < 0) return -1;
-        worst = s > worst ? s : worst;
-    }
-    return worst;
 }

@@ -16,7 +16,7 @@ namespace {
 }  // namespace
 
 const AdmmUnit &admm_unit_kq_e4() {
-    static const AdmmUnit unit = {launch_kq<4>, kq_scratch_bytes<4>};
+    static const AdmmUnit unit = {launch_shape<kBand, 4>, scratch_bytes<ShapeInsts<kBand, 4>>};
     return unit;
 }
 

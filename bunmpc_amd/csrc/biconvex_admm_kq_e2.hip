@@ -13,7 +13,7 @@ namespace {
 }  // namespace
 
 const AdmmUnit &admm_unit_kq_e2() {
-    static const AdmmUnit unit = {launch_kq<2>, kq_scratch_bytes<2>};
+    static const AdmmUnit unit = {launch_shape<kBand, 2>, scratch_bytes<ShapeInsts<kBand, 2>>};
     return unit;
 }
 

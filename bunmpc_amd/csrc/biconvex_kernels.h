@@ -2,6 +2,7 @@
 // (bunmpc_capi.hip) and the batched centroidal ADMM kernel (biconvex_admm.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <tuple>
 #include <type_traits>
 
 namespace bunmpc {
@@ -118,6 +119,29 @@ struct CostArgs {
     const double *x = nullptr, *f = nullptr;
     long sx = 0, sf = 0;
 };
+// What the kernels of each cost shape are built for, one row per CostShape in the enum's order -- stated here and nowhere else: the
+// kernels' static_asserts (biconvex_admm_body.h: AdmmCfg), the launches' guards (biconvex_admm_inst.h: launch_shape), plan_launch and
+// the C-ABI's refusals (bunmpc_capi.hip: check_cost) all read this table.
+struct ShapeInfo {
+    const char *kernel;     // the kernel template's name as plan_launch reports it (kDiag: of the fp64 batch kernel; plan_launch names its siblings)
+    bool raw_only;          // the raw form only
+    bool fp64_only;         // precision 0 only
+    int max_knots;          // H + 1 at most: 64 = one problem per wave segment
+    bool certifies;         // the step certificate may run (BatchArgs::certified_steps)
+    const char *what;       // how the C-ABI's messages call the shape, with their verb
+};
+constexpr ShapeInfo kShapes[] = {
+    {"biconvex_admm_kernel", false, false, kMaxKnots, true, "diagonal costs are"},
+    {"biconvex_admm_bq_kernel", true, true, 64, false, "block costs (Qx_blk / Qf_blk) are"},
+    {"biconvex_admm_kq_kernel", true, true, 64, false, "costs between neighbouring knots (Qx_off / Qf_off) are"},
+    {"biconvex_admm_cone_kernel", false, true, 64, false, "the Euclidean cone projection (bmpc_cone_t, projection = 1) is"},
+    {"biconvex_admm_conef_kernel", false, true, 64, false, "the Euclidean cone projection about contact normals (bmpc_contact_frame_t) is"},
+};
+constexpr int kNumShapes = sizeof(kShapes) / sizeof(kShapes[0]);
+// ... and the struct a shape's arrays reach its kernels in (kDiag: none)
+struct NoArgs {};
+template <CostShape SHAPE>
+using ShapeExtra = std::tuple_element_t<SHAPE, std::tuple<NoArgs, BlockArgs, BandArgs, ConeArgs, ConeFrameArgs>>;
 
 // LDS bytes of a workgroup that holds per_wg problems of H + 1 knots in elements of elem bytes: the zeros, then per problem the
 // x_init rows' multipliers and the header and one record per knot (X, P, F, R), then `extra` elements -- and the workgroups of a batch
@@ -169,9 +193,8 @@ LaunchPlan plan_launch(const BatchArgs &a, CostShape shape, int n_eff, long simd
 
 // Launch the batched ADMM kernel on `stream`: plan_launch with the current device's SIMD count, the device's momentum table (and a
 // counter of its work-stealing ring if the plan steals), the "last launch" record, then the unit of (shape, precision, n_eff).
-// Returns hipSuccess or the launch error; hipErrorInvalidValue for unsupported shapes (n_eff not 2 or 4, H + 1 > 256; with block or
-// band costs: not raw, not fp64, H + 1 > 64; with the cone projection: not fp64, H + 1 > 64 -- the C-ABI refuses those with a message
-// first).
+// Returns hipSuccess or the launch error; hipErrorInvalidValue for unsupported shapes (n_eff not 2 or 4, or what the shape's row of
+// kShapes excludes -- the C-ABI refuses those with a message first).
 hipError_t launch_biconvex_admm(const BatchArgs &a, const CostArgs &cost, int n_eff, hipStream_t stream);
 
 // The one-problem-per-wave mapping (biconvex_latency.hip): fp64, n_eff = 2 or 4, H + 1 <= 21.  plan_launch takes it for

@@ -147,28 +147,24 @@ int check_normals(const double *nrm, size_t n, const char *what = "contact norma
     return BMPC_OK;
 }
 
-// a batch with its costs: what the kernels of block costs / costs between neighbouring knots are built for, then the batch itself
+// a batch with its costs: what the shape's kernels are built for (its row of bunmpc::kShapes), then the batch itself and the cost arrays' strides
 int check_cost(const bmpc_batch_t *d, const bunmpc::CostArgs &c, bool arrays = true) {
     if (c.shape == bunmpc::kDiag) return check_batch(d, false, false, arrays);
+    const bunmpc::ShapeInfo &s = bunmpc::kShapes[c.shape];
+    const std::string what = s.what;
+    if (!d) return fail(BMPC_BAD_ARG, "null batch descriptor");
+    if (s.fp64_only && d->precision != 0) return fail(BMPC_BAD_ARG, what + " built for fp64 only: precision must be 0");
+    if (s.raw_only && !d->raw) return fail(BMPC_BAD_ARG, what + " built for the raw form only: raw must be 1");
+    if (d->n_col + 1 > s.max_knots) return fail(BMPC_BAD_ARG, what + " built for n_col + 1 <= " + std::to_string(s.max_knots) + " knots only (one problem per wave segment)");
     if (c.shape == bunmpc::kCone || c.shape == bunmpc::kConeFrame) {
-        const bool frames = c.shape == bunmpc::kConeFrame;
-        const std::string what = frames ? "the Euclidean cone projection about contact normals (bmpc_contact_frame_t)" : "the Euclidean cone projection (bmpc_cone_t, projection = 1)";
-        if (!d) return fail(BMPC_BAD_ARG, "null batch descriptor");
-        if (d->precision != 0) return fail(BMPC_BAD_ARG, what + " is built for fp64 only: precision must be 0");
-        if (d->n_col + 1 > 64) return fail(BMPC_BAD_ARG, what + " is built for n_col + 1 <= 64 knots only (one problem per wave segment)");
-        if (d->n_eff != 2 && d->n_eff != 4) return fail(BMPC_BAD_ARG, what + " is built for n_eff in {2, 4} only");
+        if (d->n_eff != 2 && d->n_eff != 4) return fail(BMPC_BAD_ARG, what + " built for n_eff in {2, 4} only");
         if (c.f && (c.sf < 0 || c.sf > (1L << 26) || (c.sf != 0 && c.sf < (long)d->n_col * d->n_eff)))
             return fail(BMPC_BAD_ARG, "batch stride of the friction coefficients (smu) must be 0 (shared) or between one problem's n_col * n_eff and 2^26 doubles");
-        if (frames && (!c.x || c.sx < 0 || c.sx > (1L << 26) || (c.sx != 0 && c.sx < 3L * d->n_col * d->n_eff)))
+        if (c.shape == bunmpc::kConeFrame && (!c.x || c.sx < 0 || c.sx > (1L << 26) || (c.sx != 0 && c.sx < 3L * d->n_col * d->n_eff)))
             return fail(BMPC_BAD_ARG, "batch stride of the contact normals (snormals) must be 0 (shared) or between one problem's 3 * n_col * n_eff and 2^26 doubles");
         return check_batch(d, false, false, arrays);
     }
     const bool blocks = c.shape == bunmpc::kBlocks;
-    const std::string what = blocks ? "block costs (Qx_blk / Qf_blk)" : "costs between neighbouring knots (Qx_off / Qf_off)";
-    if (!d) return fail(BMPC_BAD_ARG, "null batch descriptor");
-    if (d->precision != 0) return fail(BMPC_BAD_ARG, what + " are built for fp64 only: precision must be 0");
-    if (!d->raw) return fail(BMPC_BAD_ARG, what + " are built for the raw form only: raw must be 1");
-    if (d->n_col + 1 > 64) return fail(BMPC_BAD_ARG, what + " are built for n_col + 1 <= 64 knots only (one problem per wave segment)");
     if (int rc = check_batch(d, blocks && c.x, blocks && c.f, arrays)) return rc;
     const long need_x = blocks ? 81L * (d->n_col + 1) : 9L * d->n_col;
     const long need_f = blocks ? 9L * d->n_eff * d->n_eff * d->n_col : 3L * d->n_eff * (d->n_col - 1);
