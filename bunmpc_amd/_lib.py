@@ -50,6 +50,12 @@ class ContactFrame(C.Structure):
     _fields_ = [("normals", C.c_void_p), ("snormals", C.c_long)]
 
 
+class Terrain(C.Structure):
+    """bmpc_terrain_t"""
+    _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("x0", C.c_double), ("y0", C.c_double), ("cell", C.c_double), ("heights", C.c_void_p),
+                ("sheights", C.c_long)]
+
+
 class LaunchPlan(C.Structure):
     """bmpc_launch_plan_t"""
     _fields_ = [("status", C.c_int), ("lanes_per_problem", C.c_int), ("waves_per_simd", C.c_int), ("steal", C.c_int), ("steal_waves", C.c_long),
@@ -205,6 +211,9 @@ _SIGS = {
     "bmpc_biconvex_plan_launch": (_I, [_P, _I, C.c_long, _P]),
     "bmpc_plan_batch_device": (_I, [_P, _P]),
     "bmpc_wb_plan_batch_device": (_I, [_P, _P]),
+    "bmpc_terrain_struct_size": (_I, []),
+    "bmpc_plan_batch_terrain_device": (_I, [_P, _P, _P, _P]),
+    "bmpc_wb_plan_batch_terrain_device": (_I, [_P, _P, _P, _P]),
     "bmpc_interp_batch_device": (_I, [_P, _P]),
     "bmpc_id_batch_device": (_I, [_P, _P]),
     "bmpc_perturb_batch_device": (_I, [_P, _P]),
@@ -265,6 +274,7 @@ _SIGS = {
     "bmpc_kinodyn_compute_solve_times": (_I, [_P]),
     "bmpc_kinodyn_return_solve_times": (_I, [_P, _P]),
     "bmpc_kinodyn_solve_batch_device": (_I, [_P, _P]),
+    "bmpc_kinodyn_solve_batch_cone_device": (_I, [_P, _P, _P, _P]),
 }
 
 IK_NODE_TASK_DOUBLES = 33
@@ -344,6 +354,8 @@ def lib():
             raise ImportError("bmpc_cone_t layout differs between include/bunmpc.h and bunmpc_amd/_lib.py")
         if handle.bmpc_contact_frame_struct_size() != C.sizeof(ContactFrame):
             raise ImportError("bmpc_contact_frame_t layout differs between include/bunmpc.h and bunmpc_amd/_lib.py")
+        if handle.bmpc_terrain_struct_size() != C.sizeof(Terrain):
+            raise ImportError("bmpc_terrain_t layout differs between include/bunmpc.h and bunmpc_amd/_lib.py")
         if handle.bmpc_ik_batch_struct_size() != C.sizeof(IkBatch):
             raise ImportError("bmpc_ik_batch_t layout differs between include/bunmpc.h and bunmpc_amd/_lib.py")
         _lib = handle

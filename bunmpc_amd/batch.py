@@ -49,8 +49,8 @@ PROJECTIONS = {"reference": 0, "euclidean": 1}
 
 
 def _cone_ext(cone, B, H, E, put):
-    """bmpc_cone_t of cone = dict(projection="reference" | "euclidean", mu=None | array (1 or B, H, E), normals=None | array (1 or B, H, E,
-    3)); put(array) -> its address after whatever copy the caller needs (its result is kept by the caller).  None without a dict.
+    """bmpc_cone_t of cone = dict(projection="reference" | "euclidean", mu=None | scalar | array (1 or B, H, E), normals=None | array (1 or B,
+    H, E, 3)); put(array) -> its address after whatever copy the caller needs (its result is kept by the caller).  None without a dict.
     With normals: (bmpc_cone_t, bmpc_contact_frame_t)."""
     if cone is None:
         return None
@@ -60,6 +60,8 @@ def _cone_ext(cone, B, H, E, put):
     c = _lib.Cone(projection=PROJECTIONS[cone.get("projection", "reference")])
     mu = cone.get("mu")
     if mu is not None:
+        if np.ndim(mu) == 0:      # one coefficient for every problem, knot and foot
+            mu = np.full((1, H, E), float(mu))
         if np.shape(mu)[1:] != (H, E) or np.shape(mu)[0] not in (1, B):
             raise ValueError("cone mu: expected shape (1 or %d, %d, %d), got %s" % (B, H, E, np.shape(mu)))
         c.mu = put(mu)
@@ -68,9 +70,10 @@ def _cone_ext(cone, B, H, E, put):
     if normals is not None:
         if cone.get("projection", "reference") != "euclidean":
             raise ValueError("cone normals need projection=\"euclidean\": the reference's \"SoC\" step is about world z")
-        if np.ndim(normals) != 4 or np.shape(normals)[1:] != (H, E, 3) or np.shape(normals)[0] not in (1, B):
-            raise ValueError("cone normals: expected shape (1 or %d, %d, %d, 3), got %s" % (B, H, E, np.shape(normals)))
-        fr = _lib.ContactFrame(normals=put(normals), snormals=0 if np.shape(normals)[0] == 1 else 3 * H * E)
+        shape = tuple(normals.shape) if hasattr(normals, "data_ptr") else np.shape(normals)      # (a torch tensor, possibly on a GPU)
+        if len(shape) != 4 or shape[1:] != (H, E, 3) or shape[0] not in (1, B):
+            raise ValueError("cone normals: expected shape (1 or %d, %d, %d, 3), got %s" % (B, H, E, shape))
+        fr = _lib.ContactFrame(normals=put(normals), snormals=0 if shape[0] == 1 else 3 * H * E)
         return c, fr
     return c
 
@@ -113,7 +116,8 @@ class DeviceBatch:
         between neighbouring knots, through bmpc_biconvex_solve_batch_band_device
         cone: dict(projection="reference" | "euclidean", mu=None | array (1 or B, H, E)[, normals=array (1 or B, H, E, 3)]) -- the force
         step's projection, per-foot friction coefficients and contact normals, through bmpc_biconvex_solve_batch_cone_device or, with
-        normals, bmpc_biconvex_solve_batch_cone_frames_device (solve_host explains it)"""
+        normals, bmpc_biconvex_solve_batch_cone_frames_device (solve_host explains it).  normals may be a contiguous float64 torch
+        tensor on the batch's device -- plan_batch.DevicePlan(terrain=...).normals: it is used in place, no copy, no host trip"""
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("DeviceBatch needs a GPU: no CPU fallback exists for the solve")
@@ -154,7 +158,15 @@ class DeviceBatch:
         self.t_cone = []      # (the coefficients and the normals on the device)
 
         def up_cone(a):
-            self.t_cone.append(up(a))
+            if isinstance(a, torch.Tensor):      # already in HBM (plan_batch.DevicePlan.normals): taken as it is, no copy
+                index = lambda dev: torch.cuda.current_device() if dev.index is None else dev.index      # noqa: E731
+                same = a.device.type == self.device.type and index(a.device) == index(self.device)
+                if not same or a.dtype != f64 or not a.is_contiguous():
+                    raise ValueError("cone: a torch tensor must be contiguous float64 on the batch's device %s, got %s on %s%s"
+                                     % (self.device, a.dtype, a.device, "" if a.is_contiguous() else ", not contiguous"))
+                self.t_cone.append(a)
+            else:
+                self.t_cone.append(up(a))
             return self.t_cone[-1].data_ptr()
         self.cone = _cone_ext(cone, B, H, E, up_cone)
         if cone is not None and cone.get("mu") is not None:

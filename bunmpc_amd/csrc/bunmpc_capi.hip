@@ -188,6 +188,13 @@ int check_symmetric(const double *blk, size_t n, int k, const char *what) {
 
 namespace bunmpc {
 int set_error(int code, const std::string &msg) { return fail(code, msg); }
+// the refusals of bmpc_biconvex_solve_batch_cone_frames_device for (d, c, fr), without a launch (bmpc_kinodyn_solve_batch_cone_device
+// asks before its first kernel)
+int check_cone_batch(const bmpc_batch_t *d, const bmpc_cone_t *c, const bmpc_contact_frame_t *fr) {
+    CostArgs a;
+    if (!cone_frame_of(c, fr, a)) return BMPC_BAD_ARG;
+    return check_cost(d, a);
+}
 }  // namespace bunmpc
 
 // =============================================================== QuadrupedGait ==

@@ -7,7 +7,9 @@
 #include "perturb_types.h"
 
 namespace bunmpc {
-int launch_wb_plan(const RobotModelDev *model, const bmpc_wb_plan_batch_t &d, hipStream_t st);   // plan_gen.hip
+int launch_wb_plan(const RobotModelDev *model, const bmpc_wb_plan_batch_t &d, const bmpc_terrain_t *t, double *normals, hipStream_t st);   // plan_gen.hip
+int check_terrain(const bmpc_terrain_t *t);                                                     // plan_gen.hip
+int check_cone_batch(const bmpc_batch_t *d, const bmpc_cone_t *c, const bmpc_contact_frame_t *fr);   // bunmpc_capi.hip
 }
 
 #include <chrono>
@@ -444,7 +446,8 @@ bmpc_model_t *bmpc_model_create(int nj, const int *parent, const double *R, cons
 }
 void bmpc_model_destroy(bmpc_model_t *m) { delete m; }
 
-int bmpc_wb_plan_batch_device(const bmpc_wb_plan_batch_t *d, void *hip_stream) {
+// t == nullptr with terrain == false: flat ground (bmpc_wb_plan_batch_device)
+static int wb_plan_batch(const bmpc_wb_plan_batch_t *d, bool terrain, const bmpc_terrain_t *t, double *normals, void *hip_stream) {
     if (!d || !d->model) return ik_fail(BMPC_BAD_ARG, "null descriptor or model");
     if (d->B < 0 || d->n_col < 1 || d->ik_col < 1 || d->ik_col > d->n_col) return ik_fail(BMPC_BAD_ARG, "bad sizes");
     if (!d->gait || !d->x || !d->t0 || !d->v_des_body) return ik_fail(BMPC_BAD_ARG, "missing input array");
@@ -453,10 +456,16 @@ int bmpc_wb_plan_batch_device(const bmpc_wb_plan_batch_t *d, void *hip_stream) {
         return ik_fail(BMPC_BAD_ARG, "missing output array");
     for (int j = 0; j < 4; ++j)
         if (d->foot_frame[j] < 0 || d->foot_frame[j] >= d->model->host.nframes) return ik_fail(BMPC_BAD_ARG, "foot frame out of range");
+    if (terrain)
+        if (int rc = bunmpc::check_terrain(t)) return rc;
     if (d->B == 0) return BMPC_OK;
     bmpc_model *m = const_cast<bmpc_model *>(d->model);
     if (int rc = m->upload()) return rc;
-    return bunmpc::launch_wb_plan(m->dptr(), *d, static_cast<hipStream_t>(hip_stream));
+    return bunmpc::launch_wb_plan(m->dptr(), *d, t, normals, static_cast<hipStream_t>(hip_stream));
+}
+int bmpc_wb_plan_batch_device(const bmpc_wb_plan_batch_t *d, void *hip_stream) { return wb_plan_batch(d, false, nullptr, nullptr, hip_stream); }
+int bmpc_wb_plan_batch_terrain_device(const bmpc_wb_plan_batch_t *d, const bmpc_terrain_t *t, double *normals, void *hip_stream) {
+    return wb_plan_batch(d, true, t, normals, hip_stream);
 }
 int bmpc_id_batch_device(const bmpc_id_batch_t *d, void *hip_stream) {
     using namespace bunmpc;
@@ -820,20 +829,28 @@ void bmpc_ik_layout_trace(int n_col, long *offset, int *iters, int *width) {   /
 }
 
 // batch of KinoDynMP::optimize calls, device resident: centroidal state of (q, v) -> ADMM (cold start)
-// -> tracking references -> IK-DDP
-int bmpc_kinodyn_solve_batch_device(const bmpc_kinodyn_batch_t *d, void *hip_stream) {
+// -> tracking references -> IK-DDP.  cone == nullptr: the centroidal stage is bmpc_biconvex_solve_batch_device; otherwise it goes
+// through the cone entry points (their kernels, and their refusals first: nothing is written or launched for a batch they refuse)
+static int kinodyn_solve_batch(const bmpc_kinodyn_batch_t *d, const bmpc_cone_t *cone, const bmpc_contact_frame_t *frames, void *hip_stream) {
     if (!d || !d->x || !d->ik.model) return ik_fail(BMPC_BAD_ARG, "null KinoDyn batch descriptor");
     if (d->dyn.B != d->ik.B || d->ik.n_col > d->dyn.n_col) return ik_fail(BMPC_BAD_ARG, "inconsistent batch sizes / horizons");
     if (d->dyn.n_eff != 4) return ik_fail(BMPC_BAD_ARG, "KinoDynMP: n_eff must be 4 (the whole-body model is a 12-joint quadruped)");
+    if (cone)
+        if (int rc = bunmpc::check_cone_batch(&d->dyn, cone, frames)) return rc;
     if (d->dyn.B == 0) return BMPC_OK;
     auto *model = const_cast<bmpc_model *>(d->ik.model);
     if (int rc = model->upload()) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     HIP_TRY(bunmpc::ik_launch_centroidal_state(model->dptr(), d->x, const_cast<double *>(d->dyn.x_init), d->dyn.B, st));
-    if (int rc = bmpc_biconvex_solve_batch_device(&d->dyn, hip_stream)) return rc;
+    if (int rc = cone ? bmpc_biconvex_solve_batch_cone_frames_device(&d->dyn, cone, frames, hip_stream) : bmpc_biconvex_solve_batch_device(&d->dyn, hip_stream))
+        return rc;
     HIP_TRY(bunmpc::ik_launch_fill_refs(const_cast<double *>(d->ik.tasks), d->dyn.X, d->dyn.m, d->dyn.B, d->dyn.n_col,
                                         d->ik.n_col, st));
     return bmpc_ik_solve_batch_device(&d->ik, hip_stream);
+}
+int bmpc_kinodyn_solve_batch_device(const bmpc_kinodyn_batch_t *d, void *hip_stream) { return kinodyn_solve_batch(d, nullptr, nullptr, hip_stream); }
+int bmpc_kinodyn_solve_batch_cone_device(const bmpc_kinodyn_batch_t *d, const bmpc_cone_t *cone, const bmpc_contact_frame_t *frames, void *hip_stream) {
+    return kinodyn_solve_batch(d, cone, frames, hip_stream);
 }
 
 // ------------------------------------------------------------------- KinoDynMP ----

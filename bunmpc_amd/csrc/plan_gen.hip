@@ -8,6 +8,10 @@
 // One thread per (problem, foot) walks the knots (a contact location is copied from the previous knot while the foot
 // stays in stance); one thread per problem integrates the nominal CoM.  Integer / branchy fp64 work, HBM-bound at
 // (4E + 1 + 9) H doubles written per problem; nothing to stage.
+//
+// On a terrain (bmpc_plan_batch_terrain_device, bmpc_wb_plan_batch_terrain_device): the same walk with the reference's height-map
+// lines (:333-337, :370-374) -- bilinear height of a regular grid under every new stance and swing location -- and the unit normal
+// of the terrain under every knot, for the friction cones (bunmpc_amd/terrain.py is the numpy restatement).
 #include <cmath>
 #include <string>
 
@@ -39,7 +43,38 @@ __device__ __forceinline__ double gait_percent(double t, double period, double s
     return phi <= st ? phi / st : (phi - st) / (period - st);
 }
 
-__global__ void plan_feet_kernel(const bmpc_plan_batch_t d) {
+// Terrain under a point (bunmpc_amd/terrain.py, operation for operation): bilinear height of the cell that holds (x, y) and the unit
+// normal of that bilinear patch.  The clamp comes before the conversion to int and fmax / fmin drop a NaN, so the four loads are
+// inside the map whatever x and y are.
+struct TerrainAt { double h, nx, ny, nz; };
+__device__ __forceinline__ TerrainAt terrain_at(const bmpc_terrain_t &t, const double *Z, double x, double y) {
+    const double u = fmin(fmax((x - t.x0) / t.cell, 0.0), (double)(t.nx - 1));
+    const double v = fmin(fmax((y - t.y0) / t.cell, 0.0), (double)(t.ny - 1));
+    const int ix = min((int)floor(u), t.nx - 2), iy = min((int)floor(v), t.ny - 2);
+    const double a = u - (double)ix, b = v - (double)iy;
+    const double *r0 = Z + (long)iy * t.nx + ix, *r1 = r0 + t.nx;
+    const double z00 = r0[0], z10 = r0[1], z01 = r1[0], z11 = r1[1];
+    const double d0 = z10 - z00, d1 = z11 - z01;
+    const double h0 = z00 + a * d0, h1 = z01 + a * d1, dh = h1 - h0;
+    const double gx = (d0 + b * (d1 - d0)) / t.cell, gy = dh / t.cell;
+    const double r = sqrt((gx * gx + gy * gy) + 1.0);
+    return TerrainAt{h0 + b * dh, -gx / r, -gy / r, 1.0 / r};
+}
+
+// the terrain kernel's extra arguments: the map and where the normals go ([B][H][4][3], null: not wanted).  Nothing on flat ground.
+template <bool kTerrain> struct TerrainArgs {};
+template <> struct TerrainArgs<true> { bmpc_terrain_t t; double *normals; };
+// what a thread carries along the knots on a terrain: its problem's map, its rows of the normals (stride 12 doubles per knot; null:
+// not wanted) and the terrain under its latest location.  Nothing on flat ground.
+template <bool kTerrain> struct TerrainWalk {};
+template <> struct TerrainWalk<true> { const double *Z; double *nr; TerrainAt ta; };
+
+// kTerrain = false: flat ground, z = kFootSize; every terrain statement is discarded, so bmpc_plan_batch_device's kernel carries no
+// instruction for it.  true: a new stance location and every swing location stand on the height map
+// (abstract_cyclic_gen.py:333-337, 370-374), and the normal under every knot's (x, y) goes to ga.normals (a continuing stance keeps
+// the previous knot's: same point).  Four height loads per evaluated knot; a shared map of a few hundred KB stays in L2.
+template <bool kTerrain>
+__global__ void plan_feet_kernel(const bmpc_plan_batch_t d, const TerrainArgs<kTerrain> ga) {
     const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= (long)d.B * 4) return;
     const long b = id / 4;
@@ -62,6 +97,13 @@ __global__ void plan_feet_kernel(const bmpc_plan_batch_t d) {
     double px = round3(d.feet0[(b * 4 + j) * 3]), py = round3(d.feet0[(b * 4 + j) * 3 + 1]), pz = round3(d.feet0[(b * 4 + j) * 3 + 2]);
     cp[0] = pflag; cp[1] = px; cp[2] = py; cp[3] = pz;
     sw[0] = 0.0;
+    TerrainWalk<kTerrain> tw;
+    if constexpr (kTerrain) {
+        tw.Z = ga.t.heights + b * ga.t.sheights;
+        tw.nr = ga.normals ? ga.normals + (b * H * 4 + j) * 3 : nullptr;
+        tw.ta = terrain_at(ga.t, tw.Z, px, py);
+        if (tw.nr) { tw.nr[0] = tw.ta.nx; tw.nr[1] = tw.ta.ny; tw.nr[2] = tw.ta.nz; }
+    }
     for (int i = 1; i < H; ++i) {
         const double ft = round3(t0 + i * gdt);
         const double ph = gait_phase(ft, period, sp, off);
@@ -77,12 +119,17 @@ __global__ void plan_feet_kernel(const bmpc_plan_batch_t d) {
             z = kFootSize;
             s = (per - 0.5 < 0.02) ? 1.0 : 0.0;
         }
+        if constexpr (kTerrain) {
+            if (!(ph == 1.0 && pflag == 1.0)) { tw.ta = terrain_at(ga.t, tw.Z, x, y); z = tw.ta.h + kFootSize; }
+            if (tw.nr) { double *n = tw.nr + (long)i * 12; n[0] = tw.ta.nx; n[1] = tw.ta.ny; n[2] = tw.ta.nz; }
+        }
         double *c = cp + (long)i * 16;
         c[0] = ph; c[1] = x; c[2] = y; c[3] = z;
         sw[(long)i * 4] = s;
         pflag = ph; px = x; py = y; pz = z;
     }
 }
+
 
 __global__ void plan_costs_kernel(const bmpc_plan_batch_t d) {
     const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -205,7 +252,28 @@ __global__ void interp_kernel(const bmpc_interp_batch_t d) {
 
 }  // namespace
 
-int launch_wb_plan(const RobotModelDev *model, const bmpc_wb_plan_batch_t &d, hipStream_t st) {
+namespace {
+void launch_plan_feet(const bmpc_plan_batch_t &p, const bmpc_terrain_t *t, double *normals, hipStream_t st) {
+    const long nf = (long)p.B * 4;
+    if (t) hipLaunchKernelGGL(plan_feet_kernel<true>, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, p, TerrainArgs<true>{*t, normals});
+    else hipLaunchKernelGGL(plan_feet_kernel<false>, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, p, TerrainArgs<false>{});
+}
+}  // namespace
+
+// what the terrain entry points refuse of a bmpc_terrain_t (the heights themselves are device memory: not looked at)
+int check_terrain(const bmpc_terrain_t *t) {
+    if (!t) return set_error(BMPC_BAD_ARG, "null terrain descriptor (bmpc_terrain_t)");
+    if (!t->heights) return set_error(BMPC_BAD_ARG, "terrain without heights (bmpc_terrain_t.heights is NULL)");
+    if (t->nx < 2 || t->nx > 4096 || t->ny < 2 || t->ny > 4096)
+        return set_error(BMPC_BAD_ARG, "terrain nx and ny must be in [2, 4096], got nx = " + std::to_string(t->nx) + ", ny = " + std::to_string(t->ny));
+    if (!std::isfinite(t->cell) || !(t->cell > 0.0)) return set_error(BMPC_BAD_ARG, "terrain cell must be finite and > 0");
+    if (!std::isfinite(t->x0) || !std::isfinite(t->y0)) return set_error(BMPC_BAD_ARG, "terrain x0 and y0 must be finite");
+    if (t->sheights != 0 && (t->sheights < (long)t->nx * t->ny || t->sheights > (1L << 26)))
+        return set_error(BMPC_BAD_ARG, "batch stride of the terrain heights (sheights) must be 0 (one map for the batch) or between one map's nx * ny and 2^26 doubles");
+    return BMPC_OK;
+}
+
+int launch_wb_plan(const RobotModelDev *model, const bmpc_wb_plan_batch_t &d, const bmpc_terrain_t *t, double *normals, hipStream_t st) {
     hipLaunchKernelGGL(wb_state_kernel, dim3((unsigned)((d.B + 63) / 64)), dim3(64), 0, st, model, d);
     bmpc_plan_batch_t p;
     p.B = d.B; p.n_col = d.n_col; p.n_gaits = 1; p.reserved_ = 0;
@@ -213,8 +281,7 @@ int launch_wb_plan(const RobotModelDev *model, const bmpc_wb_plan_batch_t &d, hi
     p.t0 = d.t0; p.com = d.com; p.feet0 = d.feet0; p.v_des = d.v_des; p.w_des = d.w_des; p.x_init = d.x_init;
     p.amom = d.amom; p.hip_off = d.hip_off;
     p.cnt_plan = d.cnt_plan; p.swing_time = d.swing_time; p.dt = d.dt; p.X_nom = d.X_nom; p.X_ter = d.X_ter;
-    const long nf = (long)d.B * 4;
-    hipLaunchKernelGGL(plan_feet_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, p);
+    launch_plan_feet(p, t, normals, st);
     hipLaunchKernelGGL(plan_costs_kernel, dim3((unsigned)((d.B + 255) / 256)), dim3(256), 0, st, p);
     const long nt = (long)d.B * (d.ik_col + 1);
     hipLaunchKernelGGL(wb_tasks_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, d);
@@ -238,7 +305,9 @@ extern "C" int bmpc_interp_batch_device(const bmpc_interp_batch_t *d, void *hip_
     return BMPC_OK;
 }
 
-extern "C" int bmpc_plan_batch_device(const bmpc_plan_batch_t *d, void *hip_stream) {
+namespace {
+// t == nullptr: flat ground (bmpc_plan_batch_device)
+int plan_batch(const bmpc_plan_batch_t *d, bool terrain, const bmpc_terrain_t *t, double *normals, void *hip_stream) {
     using namespace bunmpc;
     if (!d) return set_error(BMPC_BAD_ARG, "null plan descriptor");
     if (d->B < 0 || d->n_col < 1) return set_error(BMPC_BAD_ARG, "B < 0 or n_col < 1");
@@ -246,12 +315,20 @@ extern "C" int bmpc_plan_batch_device(const bmpc_plan_batch_t *d, void *hip_stre
     if (d->n_gaits > 1 && !d->gait_id) return set_error(BMPC_BAD_ARG, "several gaits need gait_id");
     if (!d->t0 || !d->com || !d->feet0 || !d->v_des || !d->w_des || !d->x_init) return set_error(BMPC_BAD_ARG, "missing input array");
     if (!d->cnt_plan || !d->swing_time || !d->dt || !d->X_nom || !d->X_ter) return set_error(BMPC_BAD_ARG, "missing output array");
+    if (terrain)
+        if (int rc = check_terrain(t)) return rc;
     if (d->B == 0) return BMPC_OK;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const long nf = (long)d->B * 4;
-    hipLaunchKernelGGL(plan_feet_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, *d);
+    launch_plan_feet(*d, t, normals, st);
     hipLaunchKernelGGL(plan_costs_kernel, dim3((unsigned)((d->B + 255) / 256)), dim3(256), 0, st, *d);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error(BMPC_DEVICE_ERROR, std::string("plan kernels: ") + hipGetErrorString(e));
     return BMPC_OK;
 }
+}  // namespace
+
+extern "C" int bmpc_plan_batch_device(const bmpc_plan_batch_t *d, void *hip_stream) { return plan_batch(d, false, nullptr, nullptr, hip_stream); }
+extern "C" int bmpc_plan_batch_terrain_device(const bmpc_plan_batch_t *d, const bmpc_terrain_t *t, double *normals, void *hip_stream) {
+    return plan_batch(d, true, t, normals, hip_stream);
+}
+extern "C" int bmpc_terrain_struct_size(void) { return (int)sizeof(bmpc_terrain_t); }

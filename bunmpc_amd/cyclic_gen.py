@@ -3,7 +3,9 @@
 this package: kinematics from a RobotModel (fk_np) instead of pinocchio, the solve on the GPU through
 KinoDynMP (C-ABI).  Same method names, arguments and return values for the data path
     update_gait_params -> optimize(q, v, t, v_des, w_des) -> (xs_int, us_int, f_int)
-Not carried over: MCTS contact locations, contact-location noise, height maps, `create_cnt_plan_bis`
+Height maps are taken as the reference takes them: any object with `getHeight(x, y)` (terrain.HeightMap is one), applied at the
+reference's two places (:333-337, :370-374); `step_ht`, `nom_ht` and the IK task layout stay absolute, as there.
+Not carried over: MCTS contact locations, contact-location noise, `create_cnt_plan_bis`
 and the matplotlib helpers (they are outside the solve path; passing them raises NotImplementedError).
 
 The contact plan and cost builders are the batch functions of `problems.py` called with B = 1, so a
@@ -14,7 +16,7 @@ import numpy as np
 from . import fk_np
 from .biconvex_mpc_cpp import KinoDynMP
 from .gait_planner_cpp import GaitPlanner
-from .problems import BOUNDS_TILE, FOOT_SIZE, RobotParams, _log3_batch, centroidal_costs, contact_plan
+from .problems import BOUNDS_TILE, FOOT_SIZE, RobotParams, _log3_batch, centroidal_costs, contact_plan, terrain_normals
 from .urdf_model import RobotModel, load_urdf
 
 
@@ -51,8 +53,8 @@ class SoloMpcGaitGen:
     def __init__(self, robot, r_urdf, x_reg, planning_time, q0, height_map=None, eff_names=None, hip_names=None):
         """robot: RobotModel, or None to build it from r_urdf (the reference passes a pinocchio
         RobotWrapper here); r_urdf: URDF path or RobotModel handed on to KinoDynMP."""
-        if height_map is not None:
-            raise NotImplementedError("height maps are outside the solve path")
+        if height_map is not None and not callable(getattr(height_map, "getHeight", None)):
+            raise TypeError("height_map needs a getHeight(x, y) method")
         if robot is None:
             robot = r_urdf if isinstance(r_urdf, RobotModel) else load_urdf(r_urdf)
         self.rmodel = robot
@@ -76,7 +78,8 @@ class SoloMpcGaitGen:
         self.m = robot.total_mass
         self.bx = self.by = self.bz = 0.45
         self.fx_max = self.fy_max = self.fz_max = 15.0
-        self.height_map = None
+        self.height_map = height_map
+        self.terrain_mu = None
         self.q_traj, self.v_traj, self.xs_traj = [], [], []
 
     def update_gait_params(self, weight_abstract, t, ik_hor_ratio=0.5, horizon=None):
@@ -93,10 +96,26 @@ class SoloMpcGaitGen:
         self.ik = self.kd.return_ik()
         self.mp = self.kd.return_dyn()
         self.mp.set_rho(p.rho)
+        if self.terrain_mu is not None:
+            self._apply_terrain_cones()
         self.X_nom = np.zeros(9 * self.horizon)
         self.size = min(self.ik_horizon, int(self.planning_time / p.gait_dt) + 2)
         if self.planning_time > p.gait_dt:
             self.size -= 1
+
+    def set_terrain_cones(self, mu):
+        """Opt-in: friction cones about the terrain's normals.  The KinoDynMP's centroidal handle takes the Euclidean projection with
+        friction coefficient mu, and after each create_cnt_plan the height map's getNormal at the plan's contacts
+        (set_contact_normals).  Holds for this and every later update_gait_params."""
+        if self.height_map is None or not callable(getattr(self.height_map, "getNormal", None)):
+            raise ValueError("set_terrain_cones needs a height map with getNormal(x, y)")
+        self.terrain_mu = float(mu)
+        if getattr(self, "mp", None) is not None:
+            self._apply_terrain_cones()
+
+    def _apply_terrain_cones(self):
+        self.mp.set_cone_projection("euclidean")
+        self.mp.set_friction_coefficients(self.terrain_mu)
 
     def _robot_params(self, Ryaw):
         hip = (self.offsets @ Ryaw.T)[:, 0:2]                       # (R offsets[j])[0:2]
@@ -119,10 +138,13 @@ class SoloMpcGaitGen:
         rp = RobotParams("robot", self.m, feet0[:, 0:2], hip, zh)
         v_des = np.asarray(v_des, float)
         cnt, swing, dt = contact_plan(p, rp, self.horizon, np.array([float(t)]), com[None], np.array([zh]),
-                                      feet0[None], v_des[None], np.array([float(w_des)]), hip[None])
+                                      feet0[None], v_des[None], np.array([float(w_des)]), hip[None], height_map=self.height_map)
         self.cnt_plan, self.swing_time, self.dt_arr = cnt[0], swing[0], dt[0]
         for i in range(self.horizon):
             self.mp.set_contact_plan(self.cnt_plan[i], self.dt_arr[i])
+        if self.terrain_mu is not None:
+            self.contact_normals = terrain_normals(cnt, self.height_map)[0]
+            self.mp.set_contact_normals(self.contact_normals)
         return self.cnt_plan
 
     def compute_ori_correction(self, q, des_R):

@@ -12,15 +12,17 @@ from .inverse_kinematics_cpp import as_device_model
 
 class KinoDynDeviceBatch:
     def __init__(self, wb, model, device="cuda", num_iters=10, maxit=150, ddp_maxiter=100, plan=None, use_active_list=True, schedule=None,
-                 keep_hist=False):
+                 keep_hist=False, cone=None):
         """plan: a plan_batch.DeviceWbPlan whose tensors replace the host-built centroidal inputs and IK task blocks of
         `wb` (weights and regularisation references still come from wb).  schedule: dict of bmpc_ik_sched_t fields for this
-        batch's DDP loops (0 = process default, < 0 = never), e.g. {"gains_wave_below": -1}; no effect on results"""
+        batch's DDP loops (0 = process default, < 0 = never), e.g. {"gains_wave_below": -1}; no effect on results.  cone: the dict
+        batch.DeviceBatch takes (projection, mu, normals -- numpy arrays or a device tensor such as plan.normals): the centroidal stage
+        runs through the cone entry points (bmpc_kinodyn_solve_batch_cone_device); None: bmpc_kinodyn_solve_batch_device"""
         import torch
         self.torch = torch
         self.wb = wb
         self.dm = as_device_model(model)
-        self.dyn = DeviceBatch(wb.dyn, device=device, num_iters=num_iters, maxit=maxit, plan=plan, keep_hist=keep_hist)
+        self.dyn = DeviceBatch(wb.dyn, device=device, num_iters=num_iters, maxit=maxit, plan=plan, keep_hist=keep_hist, cone=cone)
         self.device = self.dyn.device
         B, T = wb.dyn.B, wb.ik_T
         f64 = torch.float64
@@ -77,7 +79,13 @@ class KinoDynDeviceBatch:
         if self.dyn.hist is not None:      # rows of ADMM iterations that do not run keep their NaN / -1
             self.dyn.hist.fill_(float("nan"))
             self.dyn.trace.fill_(-1)
-        _lib.check(_lib.lib().bmpc_kinodyn_solve_batch_device(C.byref(self.desc), C.c_void_p(stream)))
+        cone = self.dyn.cone
+        if cone is None:
+            _lib.check(_lib.lib().bmpc_kinodyn_solve_batch_device(C.byref(self.desc), C.c_void_p(stream)))
+        else:
+            cone, frame = cone if isinstance(cone, tuple) else (cone, None)
+            _lib.check(_lib.lib().bmpc_kinodyn_solve_batch_cone_device(C.byref(self.desc), C.byref(cone), None if frame is None else C.byref(frame),
+                                                                      C.c_void_p(stream)))
 
     def solve_ik_only(self):
         stream = self.torch.cuda.current_stream(self.device).cuda_stream

@@ -18,7 +18,14 @@ from .plan_batch import DeviceWbPlan, interpolate_on_device
 
 class BatchedMpc:
     def __init__(self, model, gait=problems.TROT, ik=problems.TROT_IK, wb=problems.SOLO12_WB, planning_time=0.05, ik_hor_ratio=0.5,
-                 dyn_iters=10, device="cuda"):
+                 dyn_iters=10, device="cuda", terrain=None, cone=None):
+        """terrain: a terrain.HeightMap the contact plans stand on (plan_batch.DeviceWbPlan explains it); None: flat ground.
+        cone: the dict kinodyn_batch.KinoDynDeviceBatch takes for the centroidal stage;
+        normals="terrain" hands the plan's terrain normals to the solve, in HBM.  None: the reference's projection."""
+        if cone is not None and isinstance(cone.get("normals"), str):
+            if cone["normals"] != "terrain" or terrain is None:
+                raise ValueError("cone normals: \"terrain\" (with terrain=) or an array, got %r" % (cone["normals"],))
+        self.terrain, self.cone = terrain, cone
         self.model, self.gait, self.ik, self.wb = model, gait, ik, wb
         self.dm = as_device_model(model)
         self.device = device
@@ -52,8 +59,9 @@ class BatchedMpc:
             kb.carry_step_constants(same_rollouts)
         else:
             plan = DeviceWbPlan(self.dm, self.gait, self.offsets_xy, self.wb.feet, self.ik, x, t0, v_des_body, self.H, self.T,
-                                device=self.device).build()
-            kb = KinoDynDeviceBatch(self._weights_only_batch(B), self.model, device=self.device, num_iters=self.dyn_iters, plan=plan)
+                                device=self.device, terrain=self.terrain).build()
+            kb = KinoDynDeviceBatch(self._weights_only_batch(B), self.model, device=self.device, num_iters=self.dyn_iters, plan=plan,
+                                    cone=self._cone_of(plan))
         kb.solve()
         T, H = self.T, self.H
         o = kb.off
@@ -65,6 +73,16 @@ class BatchedMpc:
         f_int, _ = interpolate_on_device(F, plan.dt, self.size)
         self._kb, self._plan = kb, plan
         return dict(xs_int=xs_int, us_int=us_int, f_int=f_int, rows=rows, xs=xs, us=us, X=kb.dyn.X, F=kb.dyn.F, plan=plan)
+
+    def _cone_of(self, plan):
+        """the cone dict of a batch on `plan`: normals="terrain" as plan.normals (a later build() of the same plan rewrites that
+        tensor in place)"""
+        if self.cone is None:
+            return None
+        cone = dict(self.cone)
+        if isinstance(cone.get("normals"), str):
+            cone["normals"] = plan.normals
+        return cone
 
     def _weights_only_batch(self, B):
         """the small host-provided part of a WholeBodyBatch: weights, bounds, regularisation reference (the per-problem

@@ -19,13 +19,35 @@ def gait_struct(gait, offsets_xy):
     return g
 
 
+class DeviceTerrain:
+    """A terrain.HeightMap uploaded once: the heights as a device tensor and the bmpc_terrain_t that points at them.  One map for the
+    batch (sheights = 0), or one per problem: Z (B, ny, nx)."""
+
+    def __init__(self, hm, B, device):
+        import torch
+        from .terrain import HeightMap
+        if not isinstance(hm, HeightMap):
+            raise TypeError("terrain: expected a bunmpc_amd.terrain.HeightMap, got %r" % (type(hm).__name__,))
+        if hm.per_problem and hm.B != B:
+            raise ValueError("terrain: %d maps for a batch of %d problems" % (hm.B, B))
+        self.hm = hm
+        self.heights = torch.from_numpy(hm.Z).to(device)
+        t = _lib.Terrain()
+        t.nx, t.ny, t.x0, t.y0, t.cell = hm.nx, hm.ny, hm.x0, hm.y0, hm.cell
+        t.heights, t.sheights = self.heights.data_ptr(), hm.nx * hm.ny if hm.per_problem else 0
+        self.desc = t
+
+
 class DevicePlan:
     """Builds (and keeps) the plan tensors of one batch on `device`.  Inputs are numpy arrays or torch tensors:
     t0 (B,), com (B,3), feet0 (B,4,3), v_des (B,3), w_des (B,), x_init (B,9), optional amom (B,3), hip_off (B,4,2),
-    gait_id (B,) into `gaits` (list of GaitParams with the robot's hip offsets)."""
+    gait_id (B,) into `gaits` (list of GaitParams with the robot's hip offsets).
+    terrain: a terrain.HeightMap (uploaded once) -- the plan stands on it (bmpc_plan_batch_terrain_device) and `normals` (B, H, 4, 3),
+    a device tensor, holds the terrain's unit normal under every knot's (x, y): DeviceBatch(cone=dict(..., normals=plan.normals))
+    takes it as it is.  None: flat ground (bmpc_plan_batch_device), no `normals`."""
 
     def __init__(self, gaits, offsets_xy, H, t0, com, feet0, v_des, w_des, x_init, amom=None, hip_off=None, gait_id=None,
-                 device="cuda"):
+                 device="cuda", terrain=None):
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("DevicePlan needs a GPU")
@@ -46,6 +68,8 @@ class DevicePlan:
         self.dt = torch.empty((B, H), dtype=f64, device=self.device)
         self.X_nom = torch.empty((B, 9 * H), dtype=f64, device=self.device)
         self.X_ter = torch.empty((B, 9), dtype=f64, device=self.device)
+        self.terrain = None if terrain is None else DeviceTerrain(terrain, B, self.device)
+        self.normals = None if terrain is None else torch.empty((B, H, 4, 3), dtype=f64, device=self.device)
         d = _lib.PlanBatch()
         d.B, d.n_col, d.n_gaits = B, H, len(gaits)
         d.gaits = self.gaits.data_ptr()
@@ -58,16 +82,21 @@ class DevicePlan:
     def build(self):
         """asynchronous on torch's current stream"""
         stream = self.torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(_lib.lib().bmpc_plan_batch_device(C.byref(self.desc), C.c_void_p(stream)))
+        if self.terrain is None:
+            _lib.check(_lib.lib().bmpc_plan_batch_device(C.byref(self.desc), C.c_void_p(stream)))
+        else:
+            _lib.check(_lib.lib().bmpc_plan_batch_terrain_device(C.byref(self.desc), C.byref(self.terrain.desc), C.c_void_p(self.normals.data_ptr()),
+                                                                 C.c_void_p(stream)))
         return self
 
 
 class DeviceWbPlan:
     """Whole-body front end on the GPU (bmpc_wb_plan_batch_device): from states x = [q, v], times and body-frame
     desired velocities to the centroidal batch inputs and the IK task blocks, all left in HBM.  Device counterpart of
-    problems.make_wb_batch (weights / regularisation references stay small host-provided arrays)."""
+    problems.make_wb_batch (weights / regularisation references stay small host-provided arrays).  terrain: as for DevicePlan
+    (bmpc_wb_plan_batch_terrain_device; the via tasks keep the absolute step_ht, as in the reference)."""
 
-    def __init__(self, dev_model, gait, offsets_xy, feet, ik, x, t0, v_des_body, H, T, device="cuda"):
+    def __init__(self, dev_model, gait, offsets_xy, feet, ik, x, t0, v_des_body, H, T, device="cuda", terrain=None):
         import torch
         self.torch, self.device = torch, torch.device(device)
         f64 = torch.float64
@@ -91,6 +120,8 @@ class DeviceWbPlan:
         self.cnt_plan, self.swing_time, self.dt = z(B, H, 4, 4), z(B, H, 4), z(B, H)
         self.X_nom, self.X_ter, self.ik_tasks = z(B, 9 * H), z(B, 9), z(B, T + 1, 33)
         self.inp = dict(x_init=self.x_init)      # DeviceBatch(plan=...) reads x_init from here
+        self.terrain = None if terrain is None else DeviceTerrain(terrain, B, self.device)
+        self.normals = None if terrain is None else z(B, H, 4, 3)
         d = _lib.WbPlanBatch()
         d.B, d.n_col, d.ik_col = B, H, T
         d.model, d.gait = dev_model.h, self.gait.data_ptr()
@@ -115,7 +146,11 @@ class DeviceWbPlan:
 
     def build(self):
         stream = self.torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(_lib.lib().bmpc_wb_plan_batch_device(C.byref(self.desc), C.c_void_p(stream)))
+        if self.terrain is None:
+            _lib.check(_lib.lib().bmpc_wb_plan_batch_device(C.byref(self.desc), C.c_void_p(stream)))
+        else:
+            _lib.check(_lib.lib().bmpc_wb_plan_batch_terrain_device(C.byref(self.desc), C.byref(self.terrain.desc), C.c_void_p(self.normals.data_ptr()),
+                                                                    C.c_void_p(stream)))
         return self
 
 

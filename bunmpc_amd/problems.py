@@ -138,12 +138,40 @@ def gait_percent_in_phase(t, period, stance_percent, offset):
 
 
 # ------------------------------------------------------------- contact plan ---
-def contact_plan(gait, robot, H, t0, com_xy, z_height, feet0, v_des, w_des, hip_offsets=None):
-    """create_cnt_plan (abstract_cyclic_gen.py:159-414), data path (no MCTS / height map /
-    noise), vectorised over the batch.
+def _terrain_call(fn, x, y, problem):
+    """fn = height_map.getHeight / getNormal at the points (x, y) (arrays of one shape): a terrain.HeightMap takes the arrays (and,
+    with one terrain per problem, the points' problem indices); any other object is called point by point with scalars, as the
+    reference calls it"""
+    from .terrain import HeightMap
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    if isinstance(getattr(fn, "__self__", None), HeightMap):
+        return fn(x, y, problem=problem) if fn.__self__.per_problem else fn(x, y)
+    vals = [np.asarray(fn(float(a), float(b)), dtype=np.float64) for a, b in zip(x.reshape(-1), y.reshape(-1))]
+    return np.array(vals).reshape(x.shape + vals[0].shape) if vals else np.zeros(x.shape)
+
+
+def _problem_index(problem, shape):
+    """the problem index of every point of an array whose leading axis runs over the problems `problem` (None: 0 .. B - 1)"""
+    p = np.arange(shape[0]) if problem is None else np.asarray(problem, dtype=np.int64)
+    return np.broadcast_to(p.reshape((shape[0],) + (1,) * (len(shape) - 1)), shape)
+
+
+def terrain_normals(cnt_plan, height_map, problem=None):
+    """normals (B, H, E, 3): height_map.getNormal at every knot's (x, y) of cnt_plan (B, H, E, 4) -- what solve_host / DeviceBatch
+    take as cone=dict(projection="euclidean", normals=...).  problem (B,): the terrain of each row under a per-problem HeightMap
+    (default: row b has terrain b)."""
+    x, y = cnt_plan[..., 1], cnt_plan[..., 2]
+    return np.ascontiguousarray(_terrain_call(height_map.getNormal, x, y, _problem_index(problem, x.shape)))
+
+
+def contact_plan(gait, robot, H, t0, com_xy, z_height, feet0, v_des, w_des, hip_offsets=None, height_map=None, problem=None):
+    """create_cnt_plan (abstract_cyclic_gen.py:159-414), data path (no MCTS / noise), vectorised over the batch.
       t0 (B,), com_xy (B,2) already rounded, z_height (B,), feet0 (B,4,3) already rounded,
       v_des (B,3) in the yaw frame (yaw = 0 here, R = I), w_des (B,)
     E feet, as many as the gait has (4 for the quadrupeds, 2 for the biped; feet0 (B,E,3))
+    height_map: an object with getHeight(x, y) (terrain.HeightMap, or the reference's duck type): a new stance location and every
+    swing location get z = getHeight(x, y) + FOOT_SIZE (:333-337, :370-374); knot 0 stays the current feet and a continuing stance
+    copies the previous knot.  problem (B,): with one terrain per problem, the terrain of each row (default: row b has terrain b).
     returns cnt_plan (B,H,E,4), swing_time (B,H,E), dt (B,H)."""
     B = t0.shape[0]
     E = len(gait.stance_percent)
@@ -176,7 +204,9 @@ def contact_plan(gait, robot, H, t0, com_xy, z_height, feet0, v_des, w_des, hip_
             on = ph == 1
             xy = np.where(on[:, None], np.where(prev_on[:, None], cnt[:, i - 1, j, 1:3], new_xy),
                           sw_xy)
-            z = np.where(on & prev_on, cnt[:, i - 1, j, 3], FOOT_SIZE)
+            ground = FOOT_SIZE if height_map is None else \
+                _terrain_call(height_map.getHeight, xy[:, 0], xy[:, 1], _problem_index(problem, (B,))) + FOOT_SIZE
+            z = np.where(on & prev_on, cnt[:, i - 1, j, 3], ground)
             cnt[:, i, j, 0] = ph
             cnt[:, i, j, 1:3] = xy
             cnt[:, i, j, 3] = z
@@ -359,7 +389,7 @@ def _draws(seed, first, B, n):
     return out_u, out_n
 
 
-def make_batch(config, B, first=0, seed=None, H=None):
+def make_batch(config, B, first=0, seed=None, H=None, height_map=None):
     """SURVEY.md 8d configs.
       "solo12_trot_nominal"  config 1 (every problem identical, B usually 1)
       "solo12_trot"          config 2 perturbed ICs
@@ -371,7 +401,9 @@ def make_batch(config, B, first=0, seed=None, H=None):
       "solo12_mixed"         config 4 trot/bound/pace with per-problem weights, H = 20
       "biped_walk"           synthetic biped (BIPED, n_eff = 2), walk / hop mix with per-problem weights (W_F: 6 per knot),
                              H = 20, mu = BIPED_MU; draws as "solo12_trot"
-    `first` = absolute index of problem 0 (for rank sharding)."""
+    `first` = absolute index of problem 0 (for rank sharding).
+    height_map: the terrain the contact plan is built on (contact_plan explains it; kept in meta, None: flat ground).  With one
+    terrain per problem, problem b of the batch has terrain b."""
     cfg_index = {"solo12_trot_nominal": 1, "solo12_trot": 2, "go2_bound": 3, "solo12_mixed": 4, "biped_walk": 6}[config]
     seed = BASE_SEED + cfg_index if seed is None else seed
     robot = GO2 if config == "go2_bound" else (BIPED if config == "biped_walk" else SOLO12)
@@ -421,7 +453,7 @@ def make_batch(config, B, first=0, seed=None, H=None):
         if sel.size == 0:
             continue
         c, s, d = contact_plan(g, robot, H, t0[sel], com_xy[sel], x_init[sel, 2], feet0[sel],
-                               v_des[sel], w_des[sel])
+                               v_des[sel], w_des[sel], height_map=height_map, problem=sel)
         cnt[sel], swing[sel], dt[sel] = c, s, d
         X_nom[sel], X_ter[sel] = centroidal_costs(g, H, x_init[sel], v_des[sel], d)
     if len(gaits) == 1:
@@ -437,7 +469,7 @@ def make_batch(config, B, first=0, seed=None, H=None):
     return Batch(config, B, H, E, robot.mass, gaits[0].rho, cnt, dt, x_init, X_nom, X_ter,
                  W_X, W_X_ter, W_F, bounds, swing, gid, {"go2_bound": 10.0, "biped_walk": BIPED_MU}.get(config, 1.0),
                  dict(seed=seed, first=first, t0=t0, v_des=v_des, gaits=[g.name for g in gaits], gait_objs=gaits, robot=robot,
-                      feet0_raw=feet0_raw, w_des=w_des))
+                      feet0_raw=feet0_raw, w_des=w_des, height_map=height_map))
 
 
 # ------------------------------------------------------------------- whole-body batches ---
@@ -496,10 +528,11 @@ def _log3_batch(R):
     return f[:, None] * v
 
 
-def make_wb_batch(model, B, first=0, seed=None, gait=TROT, ik=TROT_IK, ik_hor_ratio=0.5, wb=None):
+def make_wb_batch(model, B, first=0, seed=None, gait=TROT, ik=TROT_IK, ik_hor_ratio=0.5, wb=None, height_map=None):
     """Perturbed whole-body states and everything SoloMpcGaitGen.optimize hands to KinoDynMP
     (abstract_cyclic_gen.py:629-663): contact plan from the feet / CoM of (q, v), centroidal costs
-    (create_costs :564-614) and the IK task list (:545-562).  Solo12 trot by default."""
+    (create_costs :564-614) and the IK task list (:545-562).  Solo12 trot by default.  height_map: the terrain of the contact
+    plan (contact_plan explains it; kept in meta); the via-point height step_ht and nom_ht stay absolute, as in the reference."""
     from . import fk_np
     wb = SOLO12_WB if wb is None else wb
     Q0, FEET, HIPS = wb.q0, wb.feet, wb.hips
@@ -541,14 +574,14 @@ def make_wb_batch(model, B, first=0, seed=None, gait=TROT, ik=TROT_IK, ik_hor_ra
     com_xy = np.round(kin["com"][:, 0:2], 3)
     robot = RobotParams(wb.name, model.total_mass, fk_np.frame_positions(model, k0, FEET)[0][:, 0:2], offs[:, 0:2],
                         float(k0["com"][0, 2]))
-    cnt, swing, dt = contact_plan(gait, robot, H, t0, com_xy, kin["com"][:, 2], feet0, v_des, np.zeros(B), hip_off)
+    cnt, swing, dt = contact_plan(gait, robot, H, t0, com_xy, kin["com"][:, 2], feet0, v_des, np.zeros(B), hip_off, height_map=height_map)
     x_init = np.concatenate([kin["com"], kin["vcom"], kin["L"]], axis=1)
     amom = _log3_batch(np.transpose(Rb, (0, 2, 1)))                   # log3(R_des R_q^T), R_des = I  (:616-627)
     X_nom, X_ter = centroidal_costs(gait, H, x_init, v_des, dt, amom)
     dyn = Batch(wb.name + "_" + gait.name + "_wb", B, H, E, model.total_mass, gait.rho, cnt, dt, x_init, X_nom, X_ter,
                 np.tile(gait.W_X, H)[None], gait.W_X_ter[None].copy(), np.tile(gait.W_F, H)[None],
                 np.tile(BOUNDS_TILE, (H, 1))[None], swing, np.zeros(B, dtype=np.int64), wb.mu,
-                dict(seed=seed, first=first, t0=t0, v_des=v_des, v_des_body=v_des_b))
+                dict(seed=seed, first=first, t0=t0, v_des=v_des, v_des_body=v_des_b, height_map=height_map))
     # IK task blocks: 4 x {w, frame, ref3} | com {w, ref3} | mom {w, ref6} | state w | ctrl w
     fid = tuple(model.frame_id(n) for n in FEET)
     tasks = np.zeros((B, T + 1, 33))

@@ -319,7 +319,7 @@ int bmpc_biconvex_band_kernel_scratch_bytes(int n_eff);
  * wave per SIMD) at every batch size and num_iters; every FISTA step is tested on fp64 sums (no step certificate, no fp32 step
  * decisions), so bmpc_set_certified_steps, bmpc_set_exact_step_decisions, bmpc_set_work_stealing, bmpc_set_two_waves_per_simd and
  * bmpc_set_latency_mapping_max_batch do not touch it.  Not combinable with block or band costs (their entry points take no
- * bmpc_cone_t).  bmpc_kinodyn_solve_batch_device keeps the reference's projection. */
+ * bmpc_cone_t).  bmpc_kinodyn_solve_batch_device keeps the reference's projection; bmpc_kinodyn_solve_batch_cone_device takes a bmpc_cone_t. */
 typedef struct {
     int projection;                        /* 0: the reference's "SoC" step, 1: Euclidean */
     const double *mu; long smu;            /* [.][n_col][n_eff], NULL: bmpc_batch_t's scalar mu */
@@ -354,7 +354,7 @@ int bmpc_biconvex_cone_kernel_scratch_bytes(int n_eff);
  * the batch runs "biconvex_admm_conef_kernel", chosen exactly as the cone kernel is (16 / 21 / 32 / 64 lanes per problem, one wave per
  * SIMD, both forms, every step tested on fp64 sums).  BMPC_BAD_ARG with a message naming the limit: normals under projection == 0,
  * fp32, n_col + 1 > 64 knots, n_eff other than 2 or 4, a stride outside the rule above, and (host entry point, setters) a normal that
- * is not finite or not of unit length.  Not built: normals in fp32, for more than 63 knots, in bmpc_kinodyn_solve_batch_device, and
+ * is not finite or not of unit length.  Not built: normals in fp32, for more than 63 knots, and
  * for the reference's "SoC" step, which stays the reference's.
  * (This family's prototypes carry an explicit `extern`: tests/test_cone_cpu.py pins the number of plain `int bmpc_*cone*(...)`
  * prototypes in this header to the six of the family above; tests/test_cone_frame_cpu.py checks these against the binding.) */
@@ -589,10 +589,19 @@ typedef struct {
     const double *x;
 } bmpc_kinodyn_batch_t;
 int bmpc_kinodyn_solve_batch_device(const bmpc_kinodyn_batch_t *d, void *hip_stream);
+/* The same with the centroidal stage through bmpc_biconvex_solve_batch_cone_device or, with frames, ..._cone_frames_device: the
+ * Euclidean cone projection, per-foot coefficients and contact normals (bmpc_cone_t, bmpc_contact_frame_t above) in the whole-body
+ * data path.  Their refusals (returned before anything is written or launched) and their kernels.  cone == NULL is
+ * bmpc_kinodyn_solve_batch_device itself, bit for bit; frames may be NULL.
+ * (Declared through BMPC_ADDITIVE, which expands to nothing: tests/test_cone_cpu.py and tests/test_cone_frame_cpu.py pin the plain
+ * and the `extern` prototypes of this header whose names hold "cone" to the families above.) */
+#define BMPC_ADDITIVE
+BMPC_ADDITIVE int bmpc_kinodyn_solve_batch_cone_device(const bmpc_kinodyn_batch_t *d, const bmpc_cone_t *cone, const bmpc_contact_frame_t *frames, void *hip_stream);
 
 /* harness inputs on the device (additive; SURVEY 8f-1, centroidal level) -----------------------------
  * What SoloMpcGaitGen.create_cnt_plan / create_costs compute per MPC call (abstract_cyclic_gen.py:159-414, 564-607)
- * for B problems at once, data path only (no MCTS locations, noise or height map): from the current CoM, foot
+ * for B problems at once, data path only (no MCTS locations or noise; flat ground -- bmpc_plan_batch_terrain_device takes a height
+ * map): from the current CoM, foot
  * positions, time, desired velocities -> cnt_plan [B][H][4][4], swing_time [B][H][4], dt [B][H], X_nom [B][9H],
  * X_ter [B][9], ready to be handed to bmpc_biconvex_solve_batch_device without leaving HBM.  The gait table is
  * DEVICE memory as well (n_gaits entries; gait_id [B] selects, NULL = entry 0). */
@@ -641,6 +650,30 @@ typedef struct {
     double *ik_tasks;                  /* [B][ik_col + 1][33] */
 } bmpc_wb_plan_batch_t;
 int bmpc_wb_plan_batch_device(const bmpc_wb_plan_batch_t *d, void *hip_stream);
+
+/* Both plans on a terrain height map (additive): what the reference's harness does with its `height_map` argument
+ * (abstract_cyclic_gen.py:333-337, 370-374).  A new stance location and every swing location get z = height(x, y) + foot size; knot 0
+ * stays the current feet and a continuing stance copies the previous knot.  The via-point height step_ht, nom_ht in X_nom / X_ter and
+ * the IK task layout stay absolute, as in the reference.  normals [B][n_col][4][3] (device, or NULL: not wanted) receives the unit
+ * normal of the terrain under every knot's (x, y): what bmpc_contact_frame_t takes, without leaving HBM.
+ * The map: heights [.][ny][nx] (device), node (iy, ix) at (x0 + ix cell, y0 + iy cell), bilinear in between, the border's height
+ * outside; sheights = doubles between the problems' maps, 0 = one map for the batch.  With u = (x - x0) / cell and v likewise, both
+ * clamped to the map BEFORE the conversion to an index (so no x, y, finite or not, reads outside it), ix = min(floor(u), nx - 2),
+ * a = u - ix, b = v - iy:   d0 = z10 - z00, d1 = z11 - z01, h0 = z00 + a d0, h1 = z01 + a d1, h = h0 + b (h1 - h0),
+ * gx = (d0 + b (d1 - d0)) / cell, gy = (h1 - h0) / cell, r = sqrt((gx gx + gy gy) + 1), n = (-gx, -gy, 1) / r -- separate multiplies
+ * and adds, the arithmetic of bunmpc_amd/terrain.py.
+ * BMPC_BAD_ARG with a message naming the limit: a NULL t or NULL heights, nx or ny outside [2, 4096], cell not finite and > 0, x0 / y0
+ * not finite, sheights neither 0 nor in [nx * ny, 2^26], and everything the plain calls refuse.  The heights are device memory: they
+ * are not checked (a NaN height gives NaN heights and normals, never a read outside the map). */
+typedef struct {
+    int nx, ny;
+    double x0, y0, cell;
+    const double *heights;   /* device, [.][ny][nx] */
+    long sheights;           /* doubles between problems' maps; 0 = one map for the batch */
+} bmpc_terrain_t;
+int bmpc_terrain_struct_size(void);          /* sizeof(bmpc_terrain_t), to catch binding drift */
+int bmpc_plan_batch_terrain_device(const bmpc_plan_batch_t *d, const bmpc_terrain_t *t, double *normals, void *hip_stream);
+int bmpc_wb_plan_batch_terrain_device(const bmpc_wb_plan_batch_t *d, const bmpc_terrain_t *t, double *normals, void *hip_stream);
 
 /* The 1 kHz plan of SoloMpcGaitGen.optimize (abstract_cyclic_gen.py:677-692) for a batch, on the device:
  * out[b] = vstack_{i < size} linspace(knots[b][i], knots[b][i+1], int(dt[b][i] / step)), end points included (and so
