@@ -34,9 +34,16 @@
 //   * R = float is the mixed-precision variant (BASELINE config 3): iterates, operators and
 //     projections in fp32, while every decision the algorithm takes -- the backtracking test,
 //     both exit tests, the dynamics violation -- is reduced and compared in fp64.  HBM keeps fp64.
+//
+// This file is every centroidal unit: it is compiled once per cost shape, precision and foot count, with three defines that say
+// which (bunmpc_amd/build.py lists the units and gives each its flags), and instantiates that unit's kernels alone.  Which kernel a
+// batch gets, and the launch, are in biconvex_launch.hip.
 #include "biconvex_kernels.h"
-#include <algorithm>
 #include <mutex>
+
+#if !defined(ADMM_UNIT_SHAPE) || !defined(ADMM_UNIT_PRECISION) || !defined(ADMM_UNIT_FEET)
+#error "biconvex_admm.hip is compiled per unit: -DADMM_UNIT_SHAPE=<a CostShape> -DADMM_UNIT_PRECISION=<0 | 1> -DADMM_UNIT_FEET=<2 | 4>"
+#endif
 
 namespace bunmpc {
 namespace {
@@ -47,231 +54,32 @@ namespace {
 
 #include "biconvex_admm_inst.h"
 
-__global__ __launch_bounds__(64) void lane_selftest_kernel(const double *in, double *out) {
-    const int i = threadIdx.x;
-    const double v = in[i];
-    out[i] = from_prev(v);
-    out[64 + i] = from_next(v);
-    out[128 + i] = seg_sum<16>(v);
-    out[192 + i] = seg_sum<32>(v);
-    out[256 + i] = seg_sum<64>(v);
-    out[320 + i] = (double)__popcll(__ballot(v > 0.0));
-    out[384 + i] = seg_sum<21>(i < 63 ? v : 0.0);                                                    // every lane of a 21-lane segment
-    double a = i < 63 ? v : 0.0, b = i < 63 ? 2.0 * v : 0.0;
-    seg_sum2<21>(a, b);                                                                                // the designated lanes only
-    out[448 + i] = a;
-    out[512 + i] = b;
-    out[576 + i] = (double)seg_uniform<21>(__ballot(v > 40.0) & seg_desig<21>());                  // the spread masks, as a number (< 2^63: exact up to 2^53 -- compared by bits on the host through two halves)
-    out[640 + i] = (double)(unsigned)(seg_uniform<21>(__ballot(i == 16 || i == 48)) >> 32);
-    out[704 + i] = (double)(unsigned)(seg_uniform<21>(__ballot(i == 16 || i == 48)) & 0xffffffffu);
-}
+static_assert(unit_is_built(ADMM_UNIT_SHAPE, ADMM_UNIT_PRECISION, ADMM_UNIT_FEET), "no row of kShapes allows this unit");
 
-// FISTA's momentum coefficients: t+ = 1 + sqrt(1 + 4 t^2)/2 (sic, fista.cpp:34), c_k = (t_k - 1)/t_{k+1} -- a function of k alone, so
-// one table per device, filled once by this kernel (until round 4 every wave tabulated them in its LDS: 1.2 KB of the 20 KB a wave
-// may hold when eight of them share a CU)
-__global__ void momentum_table_kernel(double *tab, int n) {
-    double tk = 1.0;
-    for (int i = 0; i < n; ++i) {
-        const double tk1 = 1.0 + sqrt(1.0 + 4.0 * tk * tk) * 0.5;
-        tab[i] = (tk - 1.0) / tk1;
-        tk = tk1;
-    }
-}
-// What a process keeps per device: the momentum table, the work-stealing launches' counters and the chip's size.  (The raised LDS limit
-// of a workgroup kernel is per device too: launch_inst, biconvex_admm_inst.h.)
-struct DeviceState {
-    double *momentum = nullptr;
-    int *steal_ring = nullptr;       // 64 counters, one per launch in flight (a launch zeroes its own on its stream in front of the kernel;
-    unsigned steal_next = 0;         // with 64 a counter comes round again only after 63 later launches on this device)
-    long simds = 0;
+// a unit's instantiations and its launch (biconvex_admm_inst.h)
+template <CostShape SHAPE, int PRECISION, int E>
+struct Unit {
+    using Insts = ShapeInsts<SHAPE, E>;
+    static constexpr auto launch = &launch_shape<SHAPE, E>;
 };
-std::mutex g_device_lock;
-// ... of the current device; call with g_device_lock held.  nullptr on error or beyond 16 devices.
-DeviceState *device_state() {
-    static DeviceState state[16];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-    return &state[dev];
-}
-long device_simds() {
-    std::lock_guard<std::mutex> hold(g_device_lock);
-    DeviceState *d = device_state();
-    if (d && d->simds) return d->simds;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    if (d) d->simds = 4 * cus;
-    return 4 * cus;
-}
-const double *momentum_table(hipStream_t stream) {
-    std::lock_guard<std::mutex> hold(g_device_lock);
-    DeviceState *d = device_state();
-    if (!d) return nullptr;
-    if (!d->momentum) {
-        double *t = nullptr;
-        if (hipMalloc(reinterpret_cast<void **>(&t), kMaxFistaIters * sizeof(double)) != hipSuccess) return nullptr;
-        hipLaunchKernelGGL(momentum_table_kernel, dim3(1), dim3(1), 0, stream, t, kMaxFistaIters);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { (void)hipFree(t); return nullptr; }      // (once per device: later launches on any stream find it filled)
-        d->momentum = t;
-    }
-    return d->momentum;
-}
-int *steal_counter(hipStream_t stream) {
-    std::lock_guard<std::mutex> hold(g_device_lock);
-    DeviceState *d = device_state();
-    if (!d) return nullptr;
-    if (!d->steal_ring && hipMalloc(reinterpret_cast<void **>(&d->steal_ring), 64 * sizeof(int)) != hipSuccess) { d->steal_ring = nullptr; return nullptr; }
-    int *c = d->steal_ring + (d->steal_next++ % 64);
-    if (hipMemsetAsync(c, 0, sizeof(int), stream) != hipSuccess) return nullptr;
-    return c;
-}
-
-DispatchKnobs g_knobs;
-// of the calling host thread's latest launch_biconvex_admm (tests of the default dispatch; profiles)
-thread_local const char *t_last_kernel = "";
-thread_local int t_last_lpp = 0, t_last_wpe = 1;
-
-int set_knob(int &knob, int value) { const int old = knob; knob = value; return old; }
-
-// Horizons of 17..21 knots: 32-lane segments (two problems per wave) or 21-lane segments (three per wave), whichever
-// finishes the batch sooner.  The kernel runs one wave per SIMD; a wave of three problems takes ~8 % longer than a wave of two
-// (the segment sums cost more), so three per wave wins whenever it needs fewer ROUNDS of waves over the chip's SIMDs -- at
-// B = 4096 on an MI355X (1024 SIMDs) both need two rounds, 1366 waves or 2048, and two per wave is the faster one; at B = 3072 or
-// 6144 three per wave saves a whole round (1.41e6 solves/s against 1.03e6) -- or when the waves' run times differ widely anyway
-// (num_iters well above ten: the ADMM's early exit, biconvex.cpp:111-114, makes the iteration counts differ per problem and the
-// scheduler backfills; measured at num_iters = 100, B = 4096: 31 -> 28 ms).  (Tried and dropped: B = 4096 as one round of three per
-// wave for 3072 problems + the one-problem-per-wave kernel for the other 1024 -- 2.29 + 1.7 ms, level with 2 x 2.02 ms.)
-bool three_per_wave_pays(const BatchArgs &a, long simds, const DispatchKnobs &kn) {
-    if (kn.three_per_wave != 2) return kn.three_per_wave != 0;
-    const long w3 = (a.B + 2) / 3, w2 = (a.B + 1) / 2;
-    return (w3 + simds - 1) / simds < (w2 + simds - 1) / simds || a.c.num_iters >= 25;
-}
-// Two waves per SIMD (the XLDS build) where it is the faster one: the batch needs more waves than the chip has SIMDs.  Results do not
-// depend on it.
-bool two_per_simd_pays(const BatchArgs &a, int per_wave, long simds, const DispatchKnobs &kn) {
-    if (a.precision != 0 || kn.two_per_simd == 0) return false;
-    if (kn.two_per_simd == 1) return true;
-    return (a.B + per_wave - 1) / per_wave > simds;
-}
+template <int E>
+struct Unit<kDiag, 0, E> {
+    using Insts = AdmmInsts<E>;
+    static constexpr auto launch = &launch_admm<E>;
+};
+template <int E>
+struct Unit<kDiag, 1, E> {
+    using Insts = F32Insts<E>;
+    static constexpr auto launch = &launch_f32<E>;
+};
+using ThisUnit = Unit<ADMM_UNIT_SHAPE, ADMM_UNIT_PRECISION, ADMM_UNIT_FEET>;
 
 }  // namespace
 
-const AdmmUnit &admm_unit_e4() {
-    static const AdmmUnit unit = {launch_admm<4>, scratch_bytes<AdmmInsts<4>>};
+template <>
+const AdmmUnit &admm_unit_of<ADMM_UNIT_SHAPE, ADMM_UNIT_PRECISION, ADMM_UNIT_FEET>() {
+    static const AdmmUnit unit = {ThisUnit::launch, scratch_bytes<ThisUnit::Insts>};
     return unit;
-}
-const AdmmUnit &admm_unit(CostShape shape, int precision, int n_eff) {
-    const bool four = n_eff == 4;
-    if (shape == kBlocks) return four ? admm_unit_bq_e4() : admm_unit_bq_e2();
-    if (shape == kBand) return four ? admm_unit_kq_e4() : admm_unit_kq_e2();
-    if (shape == kCone) return four ? admm_unit_cone_e4() : admm_unit_cone_e2();
-    if (shape == kConeFrame) return four ? admm_unit_conef_e4() : admm_unit_conef_e2();
-    if (precision == 1) return four ? admm_unit_f32_e4() : admm_unit_f32_e2();
-    return four ? admm_unit_e4() : admm_unit_e2();
-}
-
-int set_steal_grid(int waves) { return set_knob(g_knobs.steal_grid, waves); }
-int set_three_per_wave(int on) { return set_knob(g_knobs.three_per_wave, on); }
-int set_two_waves_per_simd(int mode) { return set_knob(g_knobs.two_per_simd, mode); }
-int set_work_stealing(int on) { return set_knob(g_knobs.work_stealing, on); }
-int set_latency_mapping_max_batch(int max_batch) { return set_knob(g_knobs.latency_max_batch, max_batch); }
-int set_exact_step_decisions(int on) { return set_knob(g_knobs.exact_step_decisions, on); }
-int set_certified_steps(int on) { return set_knob(g_knobs.certified_steps, on); }
-int biconvex_last_waves_per_simd() { return t_last_wpe; }
-int biconvex_last_lanes_per_problem() { return t_last_lpp; }
-const char *biconvex_last_kernel_name() { return t_last_kernel; }
-
-// Which kernel a batch gets.  Block and band costs: their own kernels at every batch size and num_iters -- never the
-// one-problem-per-wave, work-stealing, workgroup or two-waves kernels, which hold diagonal weights only -- with every step tested on
-// the fp64 sums; the lanes per problem are chosen as for diagonal costs.  The Euclidean cone projection (kCone): likewise, in either form
-// (those other kernels restate the reference's projection only); about per-contact normals (kConeFrame): exactly as kCone.
-LaunchPlan plan_launch(const BatchArgs &a, CostShape shape, int n_eff, long simds, const DispatchKnobs &kn) {
-    LaunchPlan p = {hipErrorInvalidValue, nullptr, {0, false, false, 0, {}}, false, a.certified_steps};
-    if (shape < 0 || shape >= kNumShapes) return p;
-    const ShapeInfo &s = kShapes[shape];
-    const bool diag = shape == kDiag;
-    const int k = a.H + 1;
-    const bool built = k <= s.max_knots && (a.precision == 0 || (a.precision == 1 && !s.fp64_only)) && (a.raw || !s.raw_only);
-    if ((n_eff != 2 && n_eff != 4) || a.H < 1 || a.B < 0 || !built) return p;
-    if (a.B == 0) { p.status = hipSuccess; return p; }
-    if (a.c.maxit > kMaxFistaIters) return p;
-    // the kernels address a wave's problems by 32-bit byte offsets from the wave's first problem (at most four problems)
-    if (diag || !a.raw)
-        for (long stride : {a.sW_X, a.sW_X_ter, a.sW_F, a.sbounds})
-            if (stride < 0 || stride > (1L << 26)) return p;
-    p.status = hipSuccess;
-    // few problems, short horizon: one problem per wave (the chain of a solve is ~2.3x shorter; biconvex_latency.hip)
-    if (diag && a.B <= kn.latency_max_batch && latency_mapping_fits(a, n_eff)) {
-        p.kernel = "biconvex_latency_kernel";
-        p.latency = true;
-        return p;
-    }
-    p.certified_steps = !s.certifies ? 0 : (kn.certified_steps == 2 ? 2 : (kn.certified_steps != 0 ? 1 : 0));      // (2: force phases only)
-    p.kernel = diag && a.precision == 1 ? "biconvex_admm_kernel_f32" : s.kernel;
-    // the same decisions for two feet as for four, with the LDS record of the foot count (knot_lds)
-    auto segments = [&](int lpp) { p.l.lpp = lpp; p.l.w2 = diag && two_per_simd_pays(a, 64 / lpp, simds, kn); return p; };
-    if (k <= 16) return segments(16);
-    // 17..21 knots (the headline shape): three problems per wave in 21-lane segments (fp64; the fp32 kernels keep 32-lane segments)
-    if (k <= 21 && a.precision == 0 && three_per_wave_pays(a, simds, kn)) {
-        // many ADMM iterations (the early exit makes the counts differ per problem) and more waves than the chip holds: segments that
-        // finish take the next problem (biconvex_admm_body.h: STEAL); the 32-bit offsets from the problem index must fit (the contact
-        // plan: 32 E H bytes per problem)
-        const long per = std::max<long>({32L * n_eff * a.H, 9L * (a.H + 1) * 8, a.sW_X * 8, a.sW_F * 8, a.sbounds * 8, (long)a.c.num_iters * 16});
-        if (diag && kn.work_stealing && !a.raw && a.c.num_iters >= 25 && (a.B + 2) / 3 > simds && (double)a.B * (double)per < 2.0e9) {
-            p.kernel = "biconvex_admm_steal_kernel";
-            // (one wave per SIMD unless forced: measured at B = 4096, num_iters = 100: 30.7 ms; the two-waves build with grids of
-            // 1024 .. 2048 waves 34.2 .. 37.3 ms -- the stealing itself already fills the gaps the second wave would)
-            const bool w2 = kn.two_per_simd == 1;
-            // the persistent grid: as many waves as the chip holds at once (one or two per SIMD)
-            p.l = {21, w2, true, kn.steal_grid > 0 ? std::min<long>(kn.steal_grid, (a.B + 2) / 3) : (w2 ? 2 * simds : simds), {}};
-            return p;
-        }
-        return segments(21);
-    }
-    if (k > 64) {      // 65 .. 256 knots: a workgroup of two, three or four waves per problem
-        p.kernel = "biconvex_admm_wg_kernel";
-        const int lpp = k <= 128 ? 128 : (k <= 192 ? 192 : 256);
-        // the two-waves-per-SIMD build when there are more waves than SIMDs -- and, for two waves per problem, when four such workgroups'
-        // LDS fits a CU (at 127 knots only three do: 9.2 ms against 6.9 at B = 1024); four waves per problem: always (11.4-12.6 ms
-        // against 15.9-16.8: tools/horizon_sweep.py)
-        const bool fits = k > 128 || 4 * launch_lds_bytes(sizeof(double), 1, n_eff, a.H, (size_t)(lpp / 64) * 40) <= 160 * 1024;
-        p.l = {lpp, kn.two_per_simd == 1 || (kn.two_per_simd == 2 && fits && (long)a.B * (lpp / 64) > simds), false, 0, {}};
-        return p;
-    }
-    return segments(k <= 32 ? 32 : 64);
-}
-LaunchPlan plan_launch(const BatchArgs &a, CostShape shape, int n_eff, long simds) { return plan_launch(a, shape, n_eff, simds, g_knobs); }
-
-hipError_t launch_biconvex_admm(const BatchArgs &args, const CostArgs &cost, int n_eff, hipStream_t stream) {
-    LaunchPlan p = plan_launch(args, cost.shape, n_eff, device_simds(), g_knobs);
-    if (p.status != hipSuccess || !p.kernel) return p.status;
-    for (long stride : {cost.sx, cost.sf})
-        if (stride < 0 || stride > (1L << 26)) return hipErrorInvalidValue;
-    BatchArgs a = args;
-    a.exact_step_decisions = g_knobs.exact_step_decisions;      // (every kernel with the fp32 shortcut of its step decisions; none with block or band costs)
-    a.certified_steps = p.certified_steps;
-    t_last_kernel = p.kernel;
-    t_last_lpp = p.l.lpp;
-    // (the one-problem-per-wave kernel leaves the record of the waves per SIMD what the launch before it set: tests compare whole
-    // (name, lanes, waves) records between consecutive launches, and bmpc_biconvex_plan_launch reports 0 for such a plan)
-    if (p.latency) return launch_biconvex_latency(a, n_eff, stream);
-    t_last_wpe = p.l.w2 ? 2 : 1;
-    a.cmtab = momentum_table(stream);
-    if (!a.cmtab) return hipErrorOutOfMemory;
-    if (p.l.steal && !(a.queue = steal_counter(stream))) return hipErrorOutOfMemory;
-    p.l.cost = cost;
-    if (cost.shape == kBand && a.H < 2) { p.l.cost.f = nullptr; p.l.cost.sf = 0; }      // (one force knot: no pair)
-    return admm_unit(cost.shape, a.precision, n_eff).launch(a, p.l, stream);
-}
-
-hipError_t launch_lane_selftest(const double *in, double *out, hipStream_t stream) {
-    hipLaunchKernelGGL(lane_selftest_kernel, dim3(1), dim3(64), 0, stream, in, out);
-    return hipGetLastError();
-}
-
-const char *biconvex_kernel_name(int H, int raw) {
-    (void)raw;
-    const int k = H + 1;
-    return k <= 16 ? "biconvex_admm_kernel<double, 16" : (k <= 21 && g_knobs.three_per_wave == 1 ? "biconvex_admm_kernel<double, 21" : (k <= 32 ? "biconvex_admm_kernel<double, 32" : "biconvex_admm_kernel<double, 64"));
 }
 
 }  // namespace bunmpc

@@ -1,7 +1,6 @@
 // The body of the batched centroidal ADMM kernel (one knot per lane): template admm_body<AdmmCfg<R, LPP, E, RAW, HASQF, ...>>.  Included inside
-// the anonymous namespace of biconvex_admm.hip (fp64 instantiations) and of biconvex_admm_f32.hip (fp32 instantiations, built
-// with other compiler flags: see bunmpc_amd/build.py); the mapping, the reference lines and the algebra are described at the
-// top of biconvex_admm.hip.
+// the anonymous namespace of biconvex_admm.hip, which is compiled once per unit (the fp32 units with other compiler flags: see
+// bunmpc_amd/build.py); the mapping, the reference lines and the algebra are described at the top of biconvex_admm.hip.
 #pragma once
 
 // ------------------------------------------------------------------------------
@@ -15,7 +14,7 @@
 //     term rho|X_0 - x_init + P_H|^2: a diagonal quadratic in X_0.  Lane 0 adds rho to its Q and
 //     2 rho (P_H - x_init) to its q instead of every lane carrying nine extra residual rows.
 //   * momentum coefficients (t_k - 1)/t_{k+1} (fista.cpp:34-35) depend on the iteration index
-//     only: one table per device (biconvex_admm.hip: momentum_table), read by scalar loads.
+//     only: one table per device (biconvex_launch.hip: momentum_table), read by scalar loads.
 //   * a problem that finishes (|d| < tol or maxit) has its iterate latched into `fin` registers
 //     at that moment; the loop body itself carries no per-lane freeze selects.
 //

@@ -1,17 +1,14 @@
 // The kernels of the batched centroidal ADMM and their launches, templated on the number of feet E.  Included inside the anonymous
-// namespace of one translation unit per cost shape, precision and foot count (after biconvex_lanes.h and biconvex_admm_body.h), each
-// of which exports its launch and its list of instantiations as one AdmmUnit (biconvex_kernels.h):
-//   biconvex_admm.hip, _e2           fp64, diagonal costs, E = 4, 2      launch_admm, AdmmInsts
-//   biconvex_admm_f32.hip, _f32_e2   fp32                                launch_f32, F32Insts
-//   biconvex_admm_bq.hip, _bq_e2     blocks (kBlocks)                    launch_shape<SHAPE, E>, ShapeInsts<SHAPE, E>
-//   biconvex_admm_kq.hip, _kq_e2     band (kBand)
-//   biconvex_admm_cone.hip, _cone_e2     Euclidean cone projection (kCone)
-//   biconvex_admm_conef.hip, _conef_e2   ... about per-contact normals (kConeFrame)
-// so that every unit is built with its own flags (bunmpc_amd/build.py), the units build in parallel and one feature's kernels cannot
-// disturb another's code object.  Which kernel a batch gets is decided once, for every unit, by plan_launch (biconvex_admm.hip).
+// namespace of biconvex_admm.hip (after biconvex_lanes.h and biconvex_admm_body.h), which is compiled once per cost shape, precision
+// and foot count and exports that unit's launch and list of instantiations as one AdmmUnit (biconvex_kernels.h: admm_unit_of):
+//   kDiag, fp64                      launch_admm, AdmmInsts
+//   kDiag, fp32                      launch_f32, F32Insts
+//   every other shape (fp64)         launch_shape<SHAPE, E>, ShapeInsts<SHAPE, E>
+// bunmpc_amd/build.py lists the units and gives each its flags.  Which kernel a batch gets is decided once, for every unit, by
+// plan_launch (biconvex_launch.hip).
 // A new cost shape is: its CostShape value with its row of kShapes and its struct in ShapeExtra (biconvex_kernels.h), its kernel
-// template below with its lines in shape_kernel / shape_extra, two unit files (and admm_unit's line), and its `if constexpr` code in
-// the body.
+// template below with its lines in shape_kernel / shape_extra, its name in bunmpc_amd/build.py, and its `if constexpr` code in the
+// body.
 #pragma once
 
 // fp64, WPE = 1: ONE wave per SIMD.  The body holds 294 registers; capped at 256 with the FISTA iterates in registers the compiler parks
@@ -36,7 +33,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     admm_body<AdmmCfg<double, 21, E, false, false, true, WPE == 2>>(a);
 }
 // fp32: TWO waves per SIMD -- this latency-bound loop gains a second wave to issue from while the first waits (one wave per SIMD:
-// 9.0 ms).  Instantiated only in the fp32 units (biconvex_admm_f32.hip explains their flags).
+// 9.0 ms).  Instantiated only in the fp32 units (bunmpc_amd/build.py explains their flags).
 template <int LPP, int E>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void biconvex_admm_kernel_f32(const BatchArgs a) {
     admm_body<AdmmCfg<float, LPP, E, false, false>>(a);

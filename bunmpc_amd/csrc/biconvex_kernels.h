@@ -158,16 +158,21 @@ struct AdmmLaunch {
     long steal_waves;    // ... its persistent grid
     CostArgs cost;
 };
-// The instantiations of one cost shape, precision and foot count: one translation unit each (biconvex_admm_inst.h lists them).
+// The instantiations of one cost shape, precision and foot count: one translation unit each (bunmpc_amd/build.py lists them).
 // launch: the launch plan_launch decided on (a.cmtab and, for the work-stealing kernel, a.queue set); scratch_bytes: the largest
 // private-segment bytes per lane over the unit's kernels, -1 on error
 struct AdmmUnit {
     hipError_t (*launch)(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream);
     int (*scratch_bytes)();
 };
-const AdmmUnit &admm_unit_e4(), &admm_unit_e2(), &admm_unit_f32_e4(), &admm_unit_f32_e2(), &admm_unit_bq_e4(), &admm_unit_bq_e2(), &admm_unit_kq_e4(), &admm_unit_kq_e2(),
-               &admm_unit_cone_e4(), &admm_unit_cone_e2(), &admm_unit_conef_e4(), &admm_unit_conef_e2();
-// ... of a combination the caller has validated: n_eff 2 or 4, precision 0 or 1 (blocks / band / cone / cone with normals: 0)
+// The combinations a unit is built for, by kShapes, and each one's accessor: every compilation of biconvex_admm.hip defines the
+// explicit specialisation it was built for, and biconvex_launch.hip's table refers to all of them.
+constexpr bool unit_is_built(int shape, int precision, int E) {
+    return shape >= 0 && shape < kNumShapes && (precision == 0 || (precision == 1 && !kShapes[shape].fp64_only)) && (E == 2 || E == 4);
+}
+template <CostShape SHAPE, int PRECISION, int E>
+const AdmmUnit &admm_unit_of();
+// ... of a combination the caller has validated: unit_is_built(shape, precision, n_eff)
 const AdmmUnit &admm_unit(CostShape shape, int precision, int n_eff);
 
 // The dispatch switches of the process (the set_* calls below) and what they decide: a pure function of the batch's sizes, the

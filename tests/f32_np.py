@@ -27,7 +27,7 @@ rule comes from (biconvex_admm_body.h unless another file is named; R is the ker
               (biconvex_lanes.h: seg_sum2) are fp64 additions; `rhs = (double)L * 0.5 * g2s`, `bt = cvs > rhs`, `done = g2s < tol * tol`,
               the reference's sqrt form inside the 1e-14 band.  BAND (the fp32 segment sums) is `sizeof(R) == sizeof(double)` only and
               CAN_CERT is false for R = float: every step of these kernels is tested, on fp64 sums.
-  momentum    `cm = (R)cmtab[i]`, the table of (t_k - 1) / t_{k+1} with t_{k+1} = 1 + sqrt(1 + 4 t_k^2) / 2 (biconvex_admm.hip:
+  momentum    `cm = (R)cmtab[i]`, the table of (t_k - 1) / t_{k+1} with t_{k+1} = 1 + sqrt(1 + 4 t_k^2) / 2 (biconvex_launch.hip:
               momentum_table_kernel, fp64); `y = fmaR(cm, xn - xo, xn)` and the image `ry = fmaR(cm, rn - ro, rn)` by linearity.
               A finishing problem's x_k is latched (`last`), its counters stop (`it_f += lanes(act)`).
   motion step make_bf (`sx += cc * fx * dt`, `b3 += -cc * fx * dt / m`, `b6 += (cc fy r2 - cc fz r1) * dt`, gravity on b5), the harness
@@ -85,7 +85,7 @@ def case_id(c):
 
 
 def momentum_table(n):
-    """(t_k - 1) / t_{k+1}, fp64 (biconvex_admm.hip: momentum_table_kernel)"""
+    """(t_k - 1) / t_{k+1}, fp64 (biconvex_launch.hip: momentum_table_kernel)"""
     tab, tk = np.empty(n), 1.0
     for i in range(n):
         tk1 = 1.0 + np.sqrt(1.0 + 4.0 * tk * tk) * 0.5

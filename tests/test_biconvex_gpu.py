@@ -253,7 +253,7 @@ def test_fp32_kernels_use_no_scratch_memory(hiplib):
 
 
 def test_fp32_variant_on_a_ragged_batch():
-    """The fp32 kernels are a translation unit of their own (biconvex_admm_f32.hip): the padding problems of a last, partly
+    """The fp32 kernels are a translation unit of their own (bunmpc_amd/build.py: the fp32 units): the padding problems of a last, partly
     filled wave (B = 7 at four problems per wave) read the wave's first problem and write nothing."""
     b = problems.make_batch("solo12_trot", 7, H=8)
     d64 = bb.solve_host(b, num_iters=3)

@@ -1,12 +1,11 @@
 #!/usr/bin/env python3
 """one line per kernel of a translation unit: registers, spills, scratch, occupancy, LDS (hipcc -Rpass-analysis=kernel-resource-usage).
-usage: python tools/kernel_usage.py ik_ddp.hip [extra hipcc flags]"""
+usage: python tools/kernel_usage.py JOB [extra hipcc flags]      (a job name of bunmpc_amd/build.py: ik_ddp, admm_band_f64_e4, ...)"""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from bunmpc_amd import build
-src = sys.argv[1]
-cmd = [build.HIPCC] + build.FLAGS + build.FILE_FLAGS.get(src, []) + sys.argv[2:] + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(build.CSRC, src), "-o", "/tmp/_usage.o"]
+cmd = build.compile_cmd(build.job(sys.argv[1]), sys.argv[2:]) + ["-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/tmp/_usage.o"]
 err = subprocess.run(cmd, stderr=subprocess.PIPE, text=True).stderr
 cur = None
 rows = {}

@@ -7,8 +7,8 @@ decisions), with that path's fp64 arithmetic (v_fma_f64, v_fmac_f64, v_mul_f64, 
 permlanes.  Also the kernel's registers, scratch and static LDS as the compiler reports them.
 
     python tools/loop_valu.py LISTING.s KERNEL_SUBSTRING [--through RE]... [--committing] [--blocks] [--mnemonics]
-    python tools/loop_valu.py --compile bunmpc_amd/csrc/biconvex_admm.hip KERNEL_SUBSTRING [--through RE]... [--committing] [--blocks] [--mnemonics]
-        (--compile: device code of the unit with bunmpc_amd/build.py's flags for it; --through RE: the cheapest path that runs an
+    python tools/loop_valu.py --compile admm_diag_f64_e4 KERNEL_SUBSTRING [--through RE]... [--committing] [--blocks] [--mnemonics]
+        (--compile: device code of that job of bunmpc_amd/build.py, with its flags; --through RE: the cheapest path that runs an
         instruction matching RE, e.g. 'permlane' for an iteration that reduces its sums -- in fp32 where it can; given more than
         once: a path that runs an instruction of every RE, each in a block of its own; --committing: --through ds_write2, the
         iteration that writes x_{k+1} and its image back to LDS.  The plain cheapest path of a certified loop is NOT an iteration
@@ -30,12 +30,11 @@ F64 = ("v_fma_f64", "v_fmac_f64", "v_mul_f64", "v_add_f64")
 NOT_VALU = ("global_", "buffer_", "flat_", "scratch_", "ds_", "s_")
 
 
-def compile_listing(src):
+def compile_listing(job):
     sys.path.insert(0, ROOT)
     from bunmpc_amd import build
-    out = os.path.join(tempfile.mkdtemp(), os.path.basename(src) + ".s")
-    cmd = [build.HIPCC] + build.FLAGS + build.FILE_FLAGS.get(os.path.basename(src), []) + \
-          ["--cuda-device-only", "-S", "-I", os.path.join(ROOT, "include"), src, "-o", out]
+    out = os.path.join(tempfile.mkdtemp(), job + ".s")
+    cmd = build.compile_cmd(build.job(job)) + ["--cuda-device-only", "-S", "-I", os.path.join(ROOT, "include"), "-o", out]
     subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
     return out
 
