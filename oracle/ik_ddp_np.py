@@ -151,7 +151,8 @@ def node_calc(prob, t, x, u, diff=False):
 def solve_ddp(prob, x0, maxiter=100, reg_min=1e-9, reg_max=1e9, verbose=False):
     """crocoddyl 1.9.0 SolverDDP::solve(init_xs={}, init_us={}, maxiter=100, is_feasible=false,
     reginit=NaN) as called by InverseKinematics::optimize (inverse_kinematics.cpp:56-58).
-    Returns dict(xs, us, iters, cost, stop, converged, reg, K, k)."""
+    Returns dict(xs, us, iters, cost, stop, converged, reg, K, k, trace); trace: one row per iteration [cost after it, regularisation
+    after it, accepted step length (0 = none accepted), stopping criterion], as the compiled twin and the kernels record it."""
     model, T = prob.model, prob.T
     nv = model.nv
     ndx = 2 * nv
@@ -169,6 +170,7 @@ def solve_ddp(prob, x0, maxiter=100, reg_min=1e-9, reg_max=1e9, verbose=False):
     data = [None] * (T + 1)
     K = [None] * T; k = [None] * T; Qu = [None] * T; Quuk = [None] * T
     stop, it_done, converged = np.inf, 0, False
+    trace = []
 
     def calc_diff():
         nonlocal cost, is_feasible
@@ -252,6 +254,7 @@ def solve_ddp(prob, x0, maxiter=100, reg_min=1e-9, reg_max=1e9, verbose=False):
         d2 = -sum(k[t] @ Quuk[t] for t in range(T))
         recalc = False
         alpha = alphas[-1]
+        alpha_acc = 0.0
         for alpha in alphas:
             try:
                 cost_try = forward(alpha)
@@ -267,6 +270,7 @@ def solve_ddp(prob, x0, maxiter=100, reg_min=1e-9, reg_max=1e9, verbose=False):
                     is_feasible = True
                     cost = cost_try
                     recalc = True
+                    alpha_acc = alpha
                     break
         if alpha > th_stepdec:
             xreg = ureg = max(xreg / 10.0, reg_min)
@@ -275,10 +279,11 @@ def solve_ddp(prob, x0, maxiter=100, reg_min=1e-9, reg_max=1e9, verbose=False):
             if xreg == reg_max:
                 return dict(xs=xs, us=us, iters=it_done, cost=cost, stop=stop, converged=False, reg=xreg)
         stop = sum(Qu[t] @ Qu[t] for t in range(T))
+        trace.append((cost, xreg, alpha_acc, stop))
         if verbose:
             print("iter %3d cost %.6e stop %.3e alpha %.4f reg %.1e feas %d" % (it, cost, stop, alpha, xreg, is_feasible))
         if was_feasible and stop < th_stop:
             converged = True
             break
     # K, k: the gains of the last backward pass (tests/test_ik_passes_cpu.py holds the stand-alone Riccati reference to them)
-    return dict(xs=xs, us=us, iters=it_done, cost=cost, stop=stop, converged=converged, reg=xreg, K=K, k=k)
+    return dict(xs=xs, us=us, iters=it_done, cost=cost, stop=stop, converged=converged, reg=xreg, K=K, k=k, trace=np.array(trace))

@@ -218,6 +218,11 @@ def riccati_bounds(data, fs, xreg, feasible):
 
 # ------------------------------------------------------------------------------- the cases ---
 def load_model(robot):
+    """"solo12" / "go2": the committed models; "skew", "skew_axes", "skew_one", "skew_absorbed": the robots of tests/skew_robot.py with
+    rotated joint placements / oblique axes, and the first of them with its placements folded into the child frames"""
+    if robot.startswith("skew"):
+        from tests import skew_robot
+        return skew_robot.robot(robot)
     return urdf_model.RobotModel.from_json(open(os.path.join(ROBOTS, robot + ".json")).read())
 
 
@@ -342,9 +347,9 @@ class Case:
 
 def cases(which="all"):
     """the fixed case set.  Horizons 1, 2, 7, 10, 64 (even and odd node counts), base orientation 0 .. 3.0 rad away from x_reg's,
-    both robots, the three weight layouts, both feasibility flags and regularisations, velocity scales 1 and 10; one case whose
-    Q_uu is indefinite until the regularisation has grown; one of 256 problems (1536 node pairs: the one-wave derivative kernel's
-    own launch size)."""
+    both robots and the skewed test robots (tests/skew_robot.py), the three weight layouts, both feasibility flags and regularisations,
+    velocity scales 1 and 10; one case whose Q_uu is indefinite until the regularisation has grown; one of 256 problems (1536 node
+    pairs: the one-wave derivative kernel's own launch size)."""
     small = [
         Case("solo12_T1_a0_shared", "solo12", 101, 5, 1, 0.0, "shared", 1.0, 0, 1e-9),
         Case("solo12_T2_a1e-9_problem_feas_xreg1", "solo12", 102, 5, 2, 1e-9, "problem", 10.0, 1, 1.0),
@@ -355,6 +360,15 @@ def cases(which="all"):
         Case("go2_T2_a3.0_shared_xreg1", "go2", 107, 5, 2, 3.0, "shared", 10.0, 0, 1.0),
         Case("go2_T1_a1e-4_node_feas", "go2", 108, 5, 1, 1e-4, "node", 1.0, 1, 1e-9),
         Case("solo12_T10_indefinite", "solo12", 109, 5, 10, 0.5, "shared", 1.0, 0, 1e-9, indefinite=True),
+    ]
+    # rotated joint placements and oblique axes (tests/skew_robot.py; compared pairwise in tests/test_skew_robot_gpu.py).  The absorbed
+    # case takes the seed of the skew case of its name: identical xs, us, tasks and weights on the kinematically identical robot
+    small += [
+        Case("skew_T1_a0_shared", "skew", 121, 5, 1, 0.0, "shared", 1.0, 0, 1e-9),
+        Case("skew_T7_a1.57_node_feas_xreg1", "skew", 122, 5, 7, np.pi / 2, "node", 10.0, 1, 1.0),
+        Case("skew_axes_T2_a3.0_problem", "skew_axes", 123, 5, 2, 3.0, "problem", 1.0, 0, 1e-9),
+        Case("skew_one_T7_a0.5_shared", "skew_one", 124, 5, 7, 0.5, "shared", 1.0, 0, 1e-9),
+        Case("skew_absorbed_T7_a1.57_node_feas_xreg1", "skew_absorbed", 122, 5, 7, np.pi / 2, "node", 10.0, 1, 1.0),
     ]
     if which == "small":
         return small

@@ -45,11 +45,12 @@ def np_problem(model, wb, i, X):
     return prob
 
 
-def test_kinematic_quantities_agree(solo):
-    model, m = solo
+def _kinematic_quantities_agree(model, m, joint_range=None):
+    """joint_range None: joint angles ~ N(0, 1) (the Solo12 test as it was); a number: uniform in +- that"""
     rng = np.random.default_rng(3)
     for _ in range(4):
-        q = rb.integrate(model, rb.neutral(model), np.concatenate([0.3 * rng.standard_normal(6), rng.standard_normal(12)]))
+        qj = rng.standard_normal(12) if joint_range is None else rng.uniform(-joint_range, joint_range, 12)
+        q = rb.integrate(model, rb.neutral(model), np.concatenate([0.3 * rng.standard_normal(6), qj]))
         x = np.concatenate([q, rng.standard_normal(18)])
         kq, kin = ic.kin_quantities(m, x), rb.Kin(model, x[:19], x[19:])
         assert np.abs(kq["com"] - kin.com).max() < 1e-14
@@ -63,6 +64,10 @@ def test_kinematic_quantities_agree(solo):
             assert np.abs(J - kin.frame_jacobian_lin(name)).max() < 1e-14
         c9 = ic.centroidal_state(m, x)[0]
         assert np.abs(c9 - np.concatenate([kin.com, kin.vcom(), kin.centroidal_momentum()[3:]])).max() < 1e-13
+
+
+def test_kinematic_quantities_agree(solo):
+    _kinematic_quantities_agree(*solo)
 
 
 def test_state_operators_and_se3_jacobians(solo):
@@ -94,7 +99,22 @@ def test_state_operators_and_se3_jacobians(solo):
 
 
 def test_node_derivatives_agree(solo):
-    model, m = solo
+    _node_derivatives_agree(*solo)
+
+
+@pytest.mark.parametrize("robot", ["skew", "skew_axes", "skew_one", "skew_absorbed"])
+def test_twins_agree_on_the_skewed_robots(robot):
+    """the same two checks, same bounds, on the robots of tests/skew_robot.py: rotated joint placements (m->R[i] in the compiled twin's
+    kinematics, model.R[i] in rbd_np.Kin) and oblique joint axes, joints in +-pi.  The per-node comparison on the fixed case set is
+    tests/test_ik_passes_cpu.py::test_twins_agree_on_the_cases[skew_*]."""
+    from tests import skew_robot
+    model = skew_robot.robot(robot)
+    m = ic.Model(model)
+    _kinematic_quantities_agree(model, m, joint_range=np.pi)
+    _node_derivatives_agree(model, m)
+
+
+def _node_derivatives_agree(model, m):
     wb = problems.make_wb_batch(model, 2)
     T = wb.ik_T
     X = np.tile(wb.dyn.x_init[1], (wb.dyn.H + 1, 1))

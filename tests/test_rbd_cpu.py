@@ -16,6 +16,16 @@ def model():
     return urdf_model.RobotModel.from_json(open(ROBOT).read())
 
 
+@pytest.fixture(scope="module", params=["solo12", "skew"])
+def any_model(request, model):
+    """Solo12 (identity joint placements, axes along x / y) and the skewed test robot (tests/skew_robot.py: every placement rotated,
+    every axis oblique, full inertias), which is the only one on which R[i] and the a[2] terms of the joint rotation matter"""
+    if request.param == "solo12":
+        return model
+    from tests import skew_robot
+    return skew_robot.robot(request.param)
+
+
 def rand_state(model, rng, scale=0.5):
     q = rb.integrate(model, rb.neutral(model), scale * rng.standard_normal(model.nv))
     q[7:] += np.tile([0.0, 0.8, -1.6], 4) * np.array([1] * 6 + [-1] * 6)
@@ -56,7 +66,8 @@ def test_se3_log_exp_roundtrip_and_jacobians():
             assert np.allclose(fd, Je[:, k], atol=1e-6)
 
 
-def test_kinematic_jacobians_by_finite_differences(model):
+def test_kinematic_jacobians_by_finite_differences(any_model):
+    model = any_model
     rng = np.random.default_rng(1)
     eps = 1e-6
     for _ in range(3):
@@ -76,7 +87,8 @@ def test_kinematic_jacobians_by_finite_differences(model):
             assert np.allclose((k1.centroidal_momentum() - h0) / eps, dh[:, c], atol=2e-5), c
 
 
-def test_state_operators(model):
+def test_state_operators(any_model):
+    model = any_model
     rng = np.random.default_rng(2)
     q0, v0 = rand_state(model, rng)
     q1, v1 = rand_state(model, rng)
