@@ -59,7 +59,7 @@ class Terrain(C.Structure):
 class LaunchPlan(C.Structure):
     """bmpc_launch_plan_t"""
     _fields_ = [("status", C.c_int), ("lanes_per_problem", C.c_int), ("waves_per_simd", C.c_int), ("steal", C.c_int), ("steal_waves", C.c_long),
-                ("kernel", C.c_char_p)]
+                ("kernel", C.c_char_p), ("loop_constants_in_lds", C.c_int)]
 
 
 class GaitParams(C.Structure):
@@ -128,6 +128,10 @@ _SIGS = {
     "bmpc_set_latency_mapping_max_batch": (_I, [_I]),
     "bmpc_set_exact_step_decisions": (_I, [_I]),
     "bmpc_set_certified_steps": (_I, [_I]),
+    "bmpc_set_loop_constants_in_lds": (_I, [_I]),
+    "bmpc_loop_constants_lds_bytes": (C.c_long, [_I, _I]),
+    "bmpc_loop_constants_fit": (_I, [_I, _I]),
+    "bmpc_loop_constants_resident_waves": (_I, [_I]),
     "bmpc_biconvex_fp32_scratch_bytes": (_I, []),
     "bmpc_biconvex_kernel_scratch_bytes": (_I, [_I, _I]),
     "bmpc_last_error": (C.c_char_p, []),

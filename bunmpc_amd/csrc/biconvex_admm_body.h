@@ -31,6 +31,10 @@
 // iterating, which is also the latch of a finishing problem.  36 registers less across the loops than two register copies whose
 // roles swap: both loops are free of scratch accesses at 256 registers.  Same operations in the same order: same bits.
 //
+// CLDS (a second build for two waves per SIMD: 32 lanes, four feet, harness form, fp64, 17 .. 21 knots): XLDS, except that in the two
+// CERTIFIED loops it is 18 constants of the phase that rest in LDS -- read early, never written -- while x_k and its image stay in
+// registers; the X / F / R blocks are written only when a problem finishes or hands over (see the motion step).  Same bits again.
+//
 // WAVES > 1 (round 4; horizons of 64 .. 255 knots: the reference's own sweep of solve times goes to 10 s horizons,
 // examples/analysis/solve_times_test.py): ONE problem per WORKGROUP of WAVES wave64s, knot t on thread t.  The knot t <-> t +- 1
 // exchanges cross the wave boundaries through LDS (lane 0 / lane 63 of every wave leave their values, one workgroup barrier, the
@@ -99,7 +103,7 @@ constexpr int sym_index(int n, int r, int c) { return r <= c ? r * n - r * (r - 
 // which projection -- one value, so a variant cannot be two shapes at once -- and with it which argument struct the variant's arrays
 // come in (Extra; kDiag: an empty one).  What a shape's kernels are built for is asserted here from the shape's row of kShapes, the
 // table the launches, plan_launch and the C-ABI read as well.
-template <typename R_, int LPP_, int E_, bool RAW_, bool HASQF_, bool STEAL_ = false, bool XLDS_ = false, int WAVES_ = 1, CostShape SHAPE_ = kDiag>
+template <typename R_, int LPP_, int E_, bool RAW_, bool HASQF_, bool STEAL_ = false, bool XLDS_ = false, int WAVES_ = 1, CostShape SHAPE_ = kDiag, bool CLDS_ = false>
 struct AdmmCfg {
     using R = R_;
     using Extra = ShapeExtra<SHAPE_>;
@@ -110,6 +114,8 @@ struct AdmmCfg {
     static constexpr bool PARK = XLDS && !MW;      // (the LDS header is written by lane 0 and read by the whole problem: across waves that would take barriers)
     static constexpr bool CAN_CERT = FP64 && kShapes[SHAPE_].certifies;      // (see `certify` in the body)
     static constexpr bool BAND = !MW && !STEAL && XLDS && !RAW && LPP == 32 && E == 4 && FP64;      // (the headline kernel: see "fp32 step decisions" in the body)
+    static constexpr bool CLDS = CLDS_;      // (the headline kernel with its certified loops' constants in LDS: see CLDS in the body)
+    static_assert(!CLDS || BAND, "loop constants in LDS: a build of the headline kernel");
     static_assert(!kShapes[SHAPE_].fp64_only || FP64, "this cost shape: fp64 only");
     static_assert(!kShapes[SHAPE_].raw_only || RAW, "this cost shape: raw form only");
     static_assert(LPP * WAVES <= kShapes[SHAPE_].max_knots, "this cost shape: more lanes per problem than it has kernels for");
@@ -245,6 +251,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
     // bytes per lane, reloads inside the FISTA loops), the rounding of the iterates (two feet, 21 lanes) or the time (the work-stealing
     // kernel, 27.6 -> 29.6 ms): they keep the fp64 sums, as do the workgroup kernels (MW) and the fp32 kernel.
     constexpr bool BAND = C::BAND;
+    [[maybe_unused]] constexpr bool CLDS = C::CLDS;
     constexpr double kBand = 1e-5;
     // (1 - kBand) x and (1 + kBand) x as floats, wave-uniform (scalar registers): thresholds that need no range check, g2 is confined
     auto band_u = [](double x, float &lo, float &hi) {
@@ -329,6 +336,19 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
         lds_fence();
         const double *Hd = header(); const int *Hi = reinterpret_cast<const int *>(Hd + 12);
         last_viol = Hd[11]; n_admm = Hi[2]; status = Hi[3]; L_f = (R)Hd[10]; it_f = Hi[4]; bt_f = Hi[5];
+    };
+    // CLDS (the loop-constants build, see the motion step): the lane number as the hardware counts it, counted where it is needed -- on an
+    // opaque zero, or it is counted once per kernel -- and from it, in the phase that uses them, the address of the constants of the lane's
+    // knot (as a byte offset into LDS; lanes outside `own` read the zeros) and of its record.  Made from `lane` they are values of the
+    // whole kernel, which hipcc parks in scratch memory and reads back inside the loops.
+    [[maybe_unused]] auto lane_id = [&]() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, opaque_zero())); };
+    [[maybe_unused]] auto consts_offset = [&](mask_t own) {
+        const unsigned ln = opaque_copy(lane_id());
+        return lanes(own) ? 8u * ((unsigned)(kLdsZeros + 2 * (kSegLds + (H + 1) * KL)) + (ln / (unsigned)LPP * (unsigned)(H + 1) + ln % (unsigned)LPP) * (unsigned)kLoopConstLds) : 0u;
+    };
+    [[maybe_unused]] auto knot_record = [&]() {      // (Xg, made again where a store needs it, as header() is: held across a loop it is one register too many)
+        const unsigned ln = opaque_copy(lane_id());
+        return reinterpret_cast<R *>(lds_raw) + kLdsZeros + (long)(ln / (unsigned)LPP) * (kSegLds + (long)(H + 1) * KL) + (long)(ln % (unsigned)LPP) * KL + kSegLds;
     };
     // the problem `sl` names (every offset set) comes on chip: step constants, iterates, counters (lanes of the segments in m)
     auto load_problem = [&](mask_t m) {
@@ -877,6 +897,147 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                 return maxit;
             };
             int i0 = 0;
+            if constexpr (CLDS) {
+                // CLDS: the certified loop with F_k and its image in registers (xa / ra and xb / rb, roles alternating) and 18 of the
+                // phase's constants -- the weights and bPk -- in LDS, as in the motion step (described there; the area is the same, the
+                // phases exclusive).  A lambda of its own: the shared `iterate` stays what every other kernel compiles.  Its certified
+                // trial, operation for operation: gradient, step, "SoC" projection, image, screen, the fp32 or fp64 decisions, momentum.
+                // A lane without a force knot reads zeros for its weights and bPk, which is what they are; its values stay zeros.
+                // The F / R blocks are written where they are read again: at a problem's `done` bit or at maxit - 1 (F_{k+1} and its
+                // image), and F_k and its image of the problems still iterating in front of a hand-over.  Lane-local stores under the
+                // lane's own problem's mask, as the shared loop's: a diverged wave-mate's NaNs stay its own.
+                if (cert) {
+                    const unsigned cb = consts_offset(rvalid_m);
+                    auto consts = [&]() { return reinterpret_cast<R *>(reinterpret_cast<char *>(lds_raw) + opaque_copy(cb)); };
+                    if (rvalid) { R *Cg = consts(); UNROLL for (int j = 0; j < NF; ++j) Cg[j] = wf[j]; UNROLL for (int k = 0; k < 6; ++k) Cg[NF + k] = bpk[k]; }
+                    park_f();      // (the step constant and the counters rest in the header across the loop, as across the motion step)
+                    R wc[NF];
+                    { const R *Cz = consts(); UNROLL for (int j = 0; j < NF; ++j) wc[j] = Cz[j]; }
+                    unsigned n0 = 0, n1 = 0;      // iterations of the wave's two problems, counted in scalar registers (act is segment-uniform)
+                    auto store_fr = [&](mask_t m, const R (&xv)[NF], const R (&rv)[6]) {
+                        if (lanes(m & rvalid_m)) {
+                            R *Xs = knot_record();
+                            UNROLL for (int j = 0; j < NF; ++j) Xs[18 + j] = xv[j];
+                            UNROLL for (int k = 0; k < 6; ++k) Xs[18 + NF + k] = rv[k];
+                        }
+                    };
+                    auto iterate_k = [&](const R (&xo)[NF], const R (&ro)[6], R (&xn)[NF], R (&rn)[6], int i) -> bool {
+                        const R cm = (R)cmtab[i];
+                        mask_t done;
+                        unsigned long long anycone = 0;     // lanes with a force on the cone branch, as a scalar mask
+                        R fr[NF];
+                        UNROLL for (int n = 0; n < E; ++n) {
+                            const R zx = an[n] * ry[0] - sp[n][2] * ry[4] + sp[n][1] * ry[5];
+                            const R zy = an[n] * ry[1] + sp[n][2] * ry[3] - sp[n][0] * ry[5];
+                            const R zz = an[n] * ry[2] - sp[n][1] * ry[3] + sp[n][0] * ry[4];
+                            R gx, gy, gz;
+                            gx = fmaR(wc[3 * n], y[3 * n], rho * zx); gy = fmaR(wc[3 * n + 1], y[3 * n + 1], rho * zy);
+                            gz = fmaR(wc[3 * n + 2], y[3 * n + 2], rho * zz);
+                            fr[3 * n] = fmaR(-gx, invL, y[3 * n]);
+                            fr[3 * n + 1] = fmaR(-gy, invL, y[3 * n + 1]);
+                            fr[3 * n + 2] = fmaR(-gz, invL, y[3 * n + 2]);
+                            const R s = fmaR(fr[3 * n], fr[3 * n], fr[3 * n + 1] * fr[3 * n + 1]);
+                            const R fz = fr[3 * n + 2];
+                            const bool zero = (s * mu < -fz) || (fz < 0);
+                            anycone |= __ballot(!zero && (s > mu * fz));
+                            const R keep = zero ? R(0) : R(1);
+                            xn[3 * n] = keep * fr[3 * n];
+                            xn[3 * n + 1] = keep * fr[3 * n + 1];
+                            xn[3 * n + 2] = keep * fz;
+                        }
+                        if (anycone != 0) {   // cone branch (fista.cpp:64-68); skipped while no lane needs it
+                            UNROLL for (int n = 0; n < E; ++n) {
+                                const R s = fmaR(fr[3 * n], fr[3 * n], fr[3 * n + 1] * fr[3 * n + 1]);
+                                const R fz = fr[3 * n + 2];
+                                const bool zero = (s * mu < -fz) || (fz < 0);
+                                const bool cone = !zero && (s > mu * fz);
+                                const R k = fast_div(fmaR(mu2, s, mu * fz), (mu2 + R(1)) * s);
+                                xn[3 * n] = cone ? fr[3 * n] * k : xn[3 * n];
+                                xn[3 * n + 1] = cone ? fr[3 * n + 1] * k : xn[3 * n + 1];
+                                xn[3 * n + 2] = cone ? fmaR(mu, s, fz) * imu : xn[3 * n + 2];
+                            }
+                        }
+                        {   // applyA, its bPk read behind the projection and used last
+                            R bk[6];
+                            const R *Cz = reinterpret_cast<const R *>(reinterpret_cast<const char *>(lds_raw) + opaque_copy_after(cb, xn[NF - 1]));
+                            UNROLL for (int k = 0; k < 6; ++k) bk[k] = Cz[NF + k];
+                            R s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0;
+                            UNROLL for (int n = 0; n < E; ++n) {
+                                const R vx = xn[3 * n], vy = xn[3 * n + 1], vz = xn[3 * n + 2];
+                                s0 += an[n] * vx; s1 += an[n] * vy; s2 += an[n] * vz;
+                                s3 += sp[n][2] * vy - sp[n][1] * vz;
+                                s4 += sp[n][0] * vz - sp[n][2] * vx;
+                                s5 += sp[n][1] * vx - sp[n][0] * vy;
+                            }
+                            rn[0] = s0 + bk[0]; rn[1] = s1 + bk[1]; rn[2] = s2 + bk[2];
+                            rn[3] = s3 + bk[3]; rn[4] = s4 + bk[4]; rn[5] = s5 + bk[5];
+                        }
+                        R g2 = 0;
+                        bool settled;      // the two-stage screen (see the shared loop)
+                        {
+                            R s = 0;
+                            UNROLL for (int k = 0; k < (int)(sizeof(kScreenTermsF) / sizeof(int)); ++k) { const R d = xn[kScreenTermsF[k]] - y[kScreenTermsF[k]]; s = fmaR(d, d, s); }
+                            settled = seg_covered<LPP>(__ballot(s > theta), act);
+                            if (!settled) {
+                                UNROLL for (int j = 0; j < NF; ++j) { const R d = xn[j] - y[j]; g2 = fmaR(d, d, g2); }
+                                settled = seg_covered<LPP>(__ballot(g2 > theta), act);
+                            }
+                        }
+                        if (settled) done = 0;
+                        else {
+                            mask_t unclear = ~mask_t(0);      // designated lanes of live problems whose fp32 decisions are not clear
+                            if (banded != 0) {      // the fp32 decisions, if every live problem's are clear (see BAND)
+                                float gf = (float)g2;
+                                seg_sum1_f32<LPP>(gf);
+                                const mask_t yes = __ballot(gf < flo), no = __ballot(gf > fhi);
+                                const mask_t dyes = __ballot(gf < t2lo), dno = __ballot(gf > t2hi);
+                                const mask_t clear = (yes | no) & (dyes | dno) & __ballot(gf >= 1e-24f) & __ballot(gf <= 1e30f);
+                                unclear = ~clear & act;
+                                if (unclear == 0) {
+                                    if ((yes & act) != 0) { store_fr(act, xo, ro); return false; }
+                                    done = dyes;
+                                }
+                            }
+                            if (unclear != 0) {
+                                double g2s = (double)g2;
+                                sum1(g2s);
+                                // a live problem's step below the floor: nothing of this iteration is kept, the tested loop runs it again
+                                if ((__ballot(g2s < floor2) & act) != 0) { store_fr(act, xo, ro); return false; }
+                                done = __ballot(g2s < tol2);      // (see the shared loop for the sqrt-free form)
+                                if (__ballot(fabs(g2s - tol2) <= 1e-14 * tol2) != 0) done = __ballot(sqrt(g2s) < tol);
+                            }
+                        }
+                        const mask_t latch = act & (i == maxit - 1 ? ~mask_t(0) : done);
+                        if (latch != 0) store_fr(latch, xn, rn);
+                        { const R *Cz = consts(); UNROLL for (int j = 0; j < NF; ++j) wc[j] = Cz[j]; }      // (the next iteration's)
+                        UNROLL for (int j = 0; j < NF; ++j) y[j] = fma3(cm, xn[j] - xo[j], xn[j]);
+                        UNROLL for (int k = 0; k < 6; ++k) ry[k] = fmaR(cm, rn[k] - ro[k], rn[k]);
+                        UNROLL for (int j = 0; j < NF; ++j) keep_here(wc[j]);      // (a use that stays here: the loads are not sunk to the gradient step)
+                        n0 += (unsigned)act != 0u ? 1u : 0u;
+                        n1 += (unsigned)(act >> 32) != 0u ? 1u : 0u;
+                        act &= ~done;
+                        return true;
+                    };
+                    i0 = maxit;
+                    for (int i = 0; i < maxit; i += 2) {
+                        if (act == 0) break;
+                        if (!iterate_k(xa, ra, xb, rb, i)) { i0 = i; break; }
+                        if (i + 1 >= maxit || act == 0) break;
+                        if (!iterate_k(xb, rb, xa, ra, i + 1)) { i0 = i + 1; break; }
+                    }
+                    {   // what the tested loop and the rest of the phase work on comes back (read whether the tested loop runs or not: a
+                        // condition here and the registers stay occupied across the loop above)
+                        lds_fence();
+                        const double *Hd = header(); const int *Hi = reinterpret_cast<const int *>(Hd + 12);
+                        L_f = (R)Hd[10]; it_f = Hi[4]; bt_f = Hi[5];
+                        it_f += (int)(lane < LPP ? n0 : n1);
+                        if (banded != 0) band_L((double)L_f * 0.5, Llo, Lhi);
+                        const R *Cz = consts();
+                        UNROLL for (int j = 0; j < NF; ++j) wf[j] = Cz[j];
+                        UNROLL for (int k = 0; k < 6; ++k) bpk[k] = Cz[NF + k];
+                    }
+                }
+            } else
             if constexpr (CAN_CERT) { if (cert) i0 = loop(0, std::true_type{}); }
             if (i0 < maxit) {
                 if (!XLDS && (i0 & 1)) { UNROLL for (int j = 0; j < NF; ++j) xa[j] = xb[j]; UNROLL for (int k = 0; k < 6; ++k) ra[k] = rb[k]; }
@@ -1272,6 +1433,130 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                     return true;
                 };
                 int i0 = 0;
+                if constexpr (CLDS) {
+                    // CLDS: the certified loop with x_k and its image in REGISTERS (xa / ra and xb / rb, roles alternating as in the tested
+                    // loop of the one-wave build) and 18 of the phase's constants -- q and bPk -- in LDS: the knot's record of kLoopConstLds
+                    // doubles behind the wave's two problems (lanes without a knot read the zeros, which is what their q and bPk are up to
+                    // the sign of a zero that only their own unused values see).  A constant has no producer inside the loop: q comes in
+                    // during the previous iteration's momentum step, bPk behind the gradient step (used last in A x+, after the step
+                    // decisions), and nothing is written back.  The address passes through opaque_copy in every iteration, or the loads
+                    // leave the loop and their values spill.  What the tested loop needs behind this one (q, bPk, L_x, the counters, the
+                    // thresholds of L) is read back from LDS, so that it does not occupy registers across the loop.
+                    // iterate_c's operations on the same operands in the same order: the same bits.
+                    // What the X / R blocks of LDS hold is now written only where it is read again:
+                    //   * a problem whose `done` bit rises, or one still iterating at maxit - 1, stores x_{k+1} and its image there (what
+                    //     iterate_c leaves under `act` in every iteration: the phase's result, and what a later hand-over finds);
+                    //   * a hand-over (a live problem's step below the floor) first stores x_k and its image for the problems still
+                    //     iterating, so the tested loop -- in the XLDS form -- finds what iterate_c would have left.
+                    // A lane stores its own values to its own record under its own problem's mask, and the R block only where it owns a
+                    // dynamics row: knot H's R block and ry keep the exact zeros applyA_c's argument rests on, and what a wave shift brings
+                    // across a segment's end still ends in the image of a lane with t >= H, which is neither advanced into ry nor stored.
+                    const unsigned cb = consts_offset(kvalid_m);
+                    auto consts = [&]() { return reinterpret_cast<R *>(reinterpret_cast<char *>(lds_raw) + opaque_copy(cb)); };
+                    if (cert) {
+                        if (kvalid) { R *Cg = consts(); UNROLL for (int l = 0; l < 9; ++l) { Cg[l] = q[l]; Cg[9 + l] = bpk[l]; } }
+                        lds_fence();
+                        R qc[9];
+                        { const R *Cz = consts(); UNROLL for (int l = 0; l < 9; ++l) qc[l] = Cz[l]; }
+                        unsigned n0 = 0, n1 = 0;      // iterations of the wave's two problems, counted in scalar registers (act is segment-uniform)
+                        auto store_xr = [&](mask_t m, const R (&xv)[9], const R (&rv)[9]) {
+                            R *Xs = knot_record();
+                            if (lanes(m & kvalid_m)) { UNROLL for (int l = 0; l < 9; ++l) Xs[l] = xv[l]; }
+                            if (lanes(m & rvalid_m)) { UNROLL for (int l = 0; l < 9; ++l) Xs[18 + NF + l] = rv[l]; }
+                        };
+                        auto hand_over = [&](const R (&xo)[9], const R (&ro)[9]) { store_xr(act, xo, ro); };
+                        auto iterate_k = [&](const R (&xo)[9], const R (&ro)[9], R (&xn)[9], R (&rn)[9], int i) -> bool {
+                            const R cm = (R)cmtab[i];
+                            mask_t done;
+                            {
+                                R z[9], wp[9];
+                                shift_prev(ry, wp);  // row-block t-1 (0 for t == 0)
+                                UNROLL for (int l = 0; l < 9; ++l) z[l] = ry[l] - wp[l];
+                                UNROLL for (int k = 0; k < 3; ++k) z[3 + k] = fmaR(dtp, wp[k], z[3 + k]);
+                                z[0] += SZ * ry[7] - SY * ry[8];
+                                z[1] += SX * ry[8] - SZ * ry[6];
+                                z[2] += SY * ry[6] - SX * ry[7];
+                                UNROLL for (int l = 0; l < 9; ++l) {
+                                    R g = fmaR(rho, z[l], qc[l]);
+                                    g = fmaR(qd[l], y[l], g);
+                                    R v = fmaR(-g, invL, y[l]);
+                                    if (l < NB) v = clamp_box(v, lb[l], ub[l]);
+                                    xn[l] = v;
+                                }
+                            }
+                            {   // applyA_c, its bPk read behind the gradient step (z and its neighbour's image are dead by then) and used last
+                                R bk[9];
+                                const R *Cz = reinterpret_cast<const R *>(reinterpret_cast<const char *>(lds_raw) + opaque_copy_after(cb, xn[8]));
+                                UNROLL for (int l = 0; l < 9; ++l) bk[l] = Cz[9 + l];
+                                R vn[9], w[9];
+                                shift_next(xn, vn);
+                                UNROLL for (int l = 0; l < 9; ++l) w[l] = xn[l] - vn[l];
+                                UNROLL for (int k = 0; k < 3; ++k) w[k] += dt * vn[3 + k];
+                                w[6] += SY * xn[2] - SZ * xn[1];
+                                w[7] += SZ * xn[0] - SX * xn[2];
+                                w[8] += SX * xn[1] - SY * xn[0];
+                                UNROLL for (int l = 0; l < 9; ++l) rn[l] = w[l] + bk[l];
+                            }
+                            R g2 = 0, s = 0;
+                            UNROLL for (int k = 0; k < (int)(sizeof(kScreenTermsX) / sizeof(int)); ++k) { const R d = xn[kScreenTermsX[k]] - y[kScreenTermsX[k]]; s = fmaR(d, d, s); }
+                            bool settled = seg_covered<LPP>(__ballot(s > theta), act);      // the screen, stage 1 (see the force step)
+                            if (!settled) {      // stage 2: the whole partial, with the bits it always had
+                                UNROLL for (int l = 0; l < 9; ++l) { const R d = xn[l] - y[l]; g2 = fmaR(d, d, g2); }
+                                settled = seg_covered<LPP>(__ballot(g2 > theta), act);
+                            }
+                            if (settled) done = 0;
+                            else {
+                                mask_t unclear = ~mask_t(0);
+                                if (banded != 0) {      // the fp32 decisions -- floor and exit -- if every live problem's are clear (see the force step)
+                                    float gf = (float)g2;
+                                    seg_sum1_f32<LPP>(gf);
+                                    const mask_t yes = __ballot(gf < flo), no = __ballot(gf > fhi);
+                                    const mask_t dyes = __ballot(gf < t2lo), dno = __ballot(gf > t2hi);
+                                    const mask_t clear = (yes | no) & (dyes | dno) & __ballot(gf >= 1e-24f) & __ballot(gf <= 1e30f);
+                                    unclear = ~clear & act;
+                                    if (unclear == 0) {
+                                        if ((yes & act) != 0) { hand_over(xo, ro); return false; }
+                                        done = dyes;
+                                    }
+                                }
+                                if (unclear != 0) {
+                                    double g2s = (double)g2;
+                                    sum1(g2s);
+                                    if ((__ballot(g2s < floor2) & act) != 0) { hand_over(xo, ro); return false; }
+                                    done = __ballot(g2s < tol2);      // the tested loop's exit rule (see the force loop for the sqrt-free form)
+                                    if (__ballot(fabs(g2s - tol2) <= 1e-14 * tol2) != 0) done = __ballot(sqrt(g2s) < tol);
+                                }
+                            }
+                            const mask_t latch = act & (i == maxit - 1 ? ~mask_t(0) : done);
+                            if (latch != 0) store_xr(latch, xn, rn);
+                            { const R *Cz = consts(); UNROLL for (int l = 0; l < 9; ++l) qc[l] = Cz[l]; }      // (the next iteration's)
+                            UNROLL for (int l = 0; l < 9; ++l) y[l] = fma3(cm, xn[l] - xo[l], xn[l]);      // (no copies at the loop's end: see fma3)
+                            if (rvalid) { UNROLL for (int l = 0; l < 9; ++l) ry[l] = fmaR(cm, rn[l] - ro[l], rn[l]); }      // (see applyA_c)
+                            UNROLL for (int l = 0; l < 9; ++l) keep_here(qc[l]);      // (a use that stays here: the loads are not sunk to the gradient step)
+                            n0 += (unsigned)act != 0u ? 1u : 0u;
+                            n1 += (unsigned)(act >> 32) != 0u ? 1u : 0u;
+                            act &= ~done;
+                            return true;
+                        };
+                        i0 = maxit;
+                        for (int i = 0; i < maxit; i += 2) {
+                            if (act == 0) break;
+                            if (!iterate_k(xa, ra, xb, rb, i)) { i0 = i; break; }
+                            if (i + 1 >= maxit || act == 0) break;
+                            if (!iterate_k(xb, rb, xa, ra, i + 1)) { i0 = i + 1; break; }
+                        }
+                        // (the step constant and the counters are read again from the header, where they have not changed: not held across the loop)
+                        load_xloop();
+                        if (banded != 0) band_L((double)L_x * 0.5, Llo, Lhi);
+                        it_x += (int)(lane < LPP ? n0 : n1);
+                        {   // the tested loop takes q and bPk from where the certified one had them (read whether it runs or not: a
+                            // condition here and their registers stay occupied across the loop above)
+                            lds_fence();
+                            const R *Cz = consts();
+                            UNROLL for (int l = 0; l < 9; ++l) { q[l] = Cz[l]; bpk[l] = Cz[9 + l]; }
+                        }
+                    }
+                } else
                 if (cert) {
                     for (; i0 < maxit; ++i0) {
                         if (act == 0) break;

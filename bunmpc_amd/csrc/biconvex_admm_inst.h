@@ -22,6 +22,12 @@ template <typename R, int LPP, int E, bool RAW, bool HASQF, int WPE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void biconvex_admm_kernel(const BatchArgs a) {
     admm_body<AdmmCfg<R, LPP, E, RAW, HASQF, false, WPE == 2>>(a);
 }
+// ... and the WPE = 2 build of the 32-lane harness-form kernel whose certified loops keep x_k in registers and 18 phase constants in LDS
+// (biconvex_admm_body.h: CLDS; 17 .. 21 knots at four feet: loop_constants_fit)
+template <int E>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void biconvex_admm_clds_kernel(const BatchArgs a) {
+    admm_body<AdmmCfg<double, 32, E, false, false, false, true, 1, kDiag, true>>(a);
+}
 // horizons of 64 .. 255 knots: one problem per workgroup of WAVES waves (biconvex_admm_body.h: WAVES)
 template <int E, int WAVES, bool RAW, bool HASQF, int WPE>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void biconvex_admm_wg_kernel(const BatchArgs a) {
@@ -66,13 +72,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 
 // One instantiation of a unit: its kernel and the plan that takes it -- lanes per problem (above 64: the workgroup kernel of LPP / 64
 // waves), form (0 harness, 1 raw, 2 raw with qf), AdmmLaunch::w2 and ::steal.
-template <auto K, int LPP_, int FORM, bool W2 = false, bool STEAL_ = false>
+template <auto K, int LPP_, int FORM, bool W2 = false, bool STEAL_ = false, bool CLDS_ = false>
 struct Inst {
     static constexpr auto kernel = K;
     static constexpr int LPP = LPP_;
-    static constexpr bool STEAL = STEAL_;
+    static constexpr bool STEAL = STEAL_, CLDS = CLDS_;
     static bool planned(const BatchArgs &a, const AdmmLaunch &l) {
-        return l.lpp == LPP && l.steal == STEAL && l.w2 == W2 && (a.raw ? (a.qf ? 2 : 1) : 0) == FORM;
+        return l.lpp == LPP && l.steal == STEAL && l.w2 == W2 && l.clds == CLDS && (a.raw ? (a.qf ? 2 : 1) : 0) == FORM;
     }
 };
 // f(std::integral_constant<int, V>) for every V of a list
@@ -95,6 +101,7 @@ struct AdmmInsts {
         }); });
         v(Inst<&biconvex_admm_steal_kernel<E, 1>, 21, 0, false, true>{});
         v(Inst<&biconvex_admm_steal_kernel<E, 2>, 21, 0, true, true>{});
+        if constexpr (E == 4) v(Inst<&biconvex_admm_clds_kernel<E>, 32, 0, true, false, true>{});
     }
 };
 // fp32 (the units built without the SLP vectoriser): harness form, 16 / 32 / 64 lanes per problem
@@ -153,6 +160,9 @@ hipError_t launch_inst(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stre
             }
         }
         hipLaunchKernelGGL(kernel, dim3(launch_grid(a.B, 1)), dim3(I::LPP), launch_lds_bytes(elem, 1, E, a.H, (size_t)(I::LPP / 64) * 40), stream, a);
+    } else if constexpr (I::CLDS) {
+        if (!loop_constants_fit(E, a.H)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(kernel, dim3(launch_grid(a.B, 2)), dim3(64), loop_constants_lds_bytes(E, a.H), stream, a);
     } else {
         hipLaunchKernelGGL(kernel, dim3(launch_grid(a.B, 64 / I::LPP)), dim3(64), launch_lds_bytes(elem, 64 / I::LPP, E, a.H), stream, a, extra...);
     }
@@ -195,4 +205,20 @@ int scratch_bytes() {
         else worst = (long)at.localSizeBytes > worst ? (long)at.localSizeBytes : worst;
     });
     return (int)worst;
+}
+
+// waves of the unit's loop-constants build that one CU holds at once with the LDS a horizon of H takes (the runtime's occupancy query:
+// at k = 21 eight waves fill the CU's LDS to the allocation granule, so the arithmetic alone does not settle it); 0: no such build
+template <typename Insts>
+int loop_constants_resident_waves(int H) {
+    int waves = 0;
+    Insts::each([&](auto inst) {
+        using I = decltype(inst);
+        if constexpr (I::CLDS) {
+            int n = 0;
+            const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, I::kernel, 64, loop_constants_lds_bytes(Insts::E, H));
+            waves = e == hipSuccess ? n : -1;
+        }
+    });
+    return waves;
 }

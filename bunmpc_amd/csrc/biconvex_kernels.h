@@ -148,6 +148,20 @@ using ShapeExtra = std::tuple_element_t<SHAPE, std::tuple<NoArgs, BlockArgs, Ban
 constexpr size_t launch_lds_bytes(size_t elem, int per_wg, int E, int H, size_t extra = 0) {
     return elem * (kLdsZeros + (size_t)per_wg * ((size_t)kSegLds + (size_t)knot_lds(E) * (size_t)(H + 1)) + extra);
 }
+// The loop-constants build of the headline kernel (biconvex_admm_body.h: CLDS) parks kLoopConstLds doubles per knot behind the records of
+// a wave's two problems: 18 phase constants of the knot's lane in an odd stride (no two lanes of a segment share a bank)
+constexpr int kLoopConstLds = 19;
+constexpr size_t loop_constants_extra(int H) { return 2 * (size_t)(H + 1) * kLoopConstLds; }
+// ... and its wave's LDS bytes: 8 (84 + (78 + 2 x 19) k) for k = H + 1 knots at four feet
+constexpr size_t loop_constants_lds_bytes(int E, int H) { return launch_lds_bytes(sizeof(double), 2, E, H, loop_constants_extra(H)); }
+// eight such waves share a CU's 160 KB (two per SIMD): 20480 bytes each -- at four feet, k <= 21
+constexpr bool loop_constants_fit(int E, int H) { return H >= 1 && 8 * loop_constants_lds_bytes(E, H) <= 160 * 1024; }
+// what mode 2 of set_loop_constants_in_lds ("when it pays") resolves to wherever the build fits: "always", by the measurement in
+// EXPERIMENTS.md ("Headline kernel: iterates in registers, loop constants in LDS": 2.82 -> 2.55 ms at B = 4096, H = 20)
+#ifndef BMPC_LOOP_CONSTANTS_PAY      // (side-by-side experiment builds: BUNMPC_EXTRA_FLAGS=-DBMPC_LOOP_CONSTANTS_PAY=0)
+#define BMPC_LOOP_CONSTANTS_PAY 1
+#endif
+constexpr bool kLoopConstantsPay = BMPC_LOOP_CONSTANTS_PAY != 0;
 constexpr unsigned launch_grid(int B, int per_wg) { return (unsigned)((B + per_wg - 1) / per_wg); }
 
 // The kernel a batch gets.  Set by plan_launch, except the cost arrays: launch_biconvex_admm adds those.
@@ -157,13 +171,15 @@ struct AdmmLaunch {
     bool steal;          // the work-stealing kernel (lpp 21, harness form, fp64)
     long steal_waves;    // ... its persistent grid
     CostArgs cost;
+    bool clds;           // the two-waves build with the certified loops' constants in LDS (32 lanes, four feet, harness form, fp64)
 };
 // The instantiations of one cost shape, precision and foot count: one translation unit each (bunmpc_amd/build.py lists them).
 // launch: the launch plan_launch decided on (a.cmtab and, for the work-stealing kernel, a.queue set); scratch_bytes: the largest
-// private-segment bytes per lane over the unit's kernels, -1 on error
+// private-segment bytes per lane over the unit's kernels, -1 on error; loop_constants_resident_waves: see the member
 struct AdmmUnit {
     hipError_t (*launch)(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream);
     int (*scratch_bytes)();
+    int (*loop_constants_resident_waves)(int H);      // of the unit's loop-constants build, by the occupancy query: waves one CU holds at once; 0: the unit has no such build, -1 on error
 };
 // The combinations a unit is built for, by kShapes, and each one's accessor: every compilation of biconvex_admm.hip defines the
 // explicit specialisation it was built for, and biconvex_launch.hip's table refers to all of them.
@@ -185,6 +201,7 @@ struct DispatchKnobs {
     int latency_max_batch = 1024;      // the one-problem-per-wave kernel up to this many problems
     int exact_step_decisions = 0;      // 1: every step decision from the fp64 sums, in every centroidal kernel; 2: the headline kernel without its lane-local screen (tests)
     int certified_steps = 1;           // the fp64 batch kernels' per-phase step certificate: 0 off, 1 on, 2 force phases only
+    int loop_constants_in_lds = 2;     // the headline kernel's build with loop constants in LDS and x_k in registers: 0 never, 1 whenever it fits, 2 when it pays
 };
 struct LaunchPlan {
     hipError_t status;       // hipErrorInvalidValue: a shape no kernel is built for
@@ -214,6 +231,7 @@ int set_steal_grid(int waves);                       // waves of the work-steali
 int set_work_stealing(int on);                       // the segment-level work-stealing kernel for num_iters >= 25 (default on); returns the old value
 int biconvex_last_lanes_per_problem();               // of the calling host thread's latest launch: 16 / 21 / 32 / 64, 0 = one problem per wave
 int set_exact_step_decisions(int on);                // 1: every step decision from the fp64 sums, in every centroidal kernel; 2: fp32 decisions without the headline kernel's lane-local screen; returns the old value
+int set_loop_constants_in_lds(int mode);             // the headline kernel's certified loops with their constants in LDS and x_k in registers: 0 never, 1 whenever it fits, 2 when it pays (default); returns the old value
 int set_certified_steps(int on);                     // the fp64 batch kernels' per-phase step certificate: 0 off, 1 on (default), 2 force phases only; returns the old value
 
 // Lane-exchange self test (DPP shifts and segment sums used by the kernel).

@@ -263,6 +263,8 @@ __device__ __forceinline__ double *at(double *ubase, unsigned byte_off) {
 __device__ __forceinline__ unsigned opaque_zero() { unsigned z = 0; asm volatile("" : "+v"(z)); return z; }
 // v, as a value the optimiser knows nothing about (no instruction): what is computed from it stays where it is written
 __device__ __forceinline__ unsigned opaque_copy(unsigned v) { asm volatile("" : "+v"(v)); return v; }
+// ... and which it cannot make before `dep` is: a load from an address built on the result is issued behind dep's producer (no instruction)
+__device__ __forceinline__ unsigned opaque_copy_after(unsigned v, const double &dep) { asm volatile("" : "+v"(v) : "v"(dep)); return v; }
 // a use of v the optimiser cannot move or remove (no instruction)
 __device__ __forceinline__ void keep_here(double &v) { asm volatile("" : "+v"(v)); }
 __device__ __forceinline__ void keep_here(float &v) { asm volatile("" : "+v"(v)); }

@@ -117,6 +117,14 @@ bool two_per_simd_pays(const BatchArgs &a, int per_wave, long simds, const Dispa
     return (a.B + per_wave - 1) / per_wave > simds;
 }
 
+// The loop-constants build (biconvex_admm_body.h: CLDS) in place of the two-waves build of the 32-lane kernel: four feet, harness
+// form, fp64, diagonal costs (the one instantiation it exists in), and a wave's LDS with the constants' area such that eight waves
+// still share a CU (loop_constants_fit: 17 .. 21 knots).  Mode 2, "when it pays": see kLoopConstantsPay.  Results do not depend on it.
+bool loop_constants_pay(const BatchArgs &a, int n_eff, const DispatchKnobs &kn) {
+    if (kn.loop_constants_in_lds == 0 || (kn.loop_constants_in_lds != 1 && !kLoopConstantsPay)) return false;
+    return n_eff == 4 && !a.raw && a.precision == 0 && loop_constants_fit(n_eff, a.H);
+}
+
 // The units' accessors at 4 * shape + 2 * precision + (two feet), null where kShapes[shape] builds no unit.  Made from kShapes alone: a
 // row without its units (bunmpc_amd/build.py lists them) is an undefined symbol when the library loads.
 using UnitAccessor = const AdmmUnit &(*)();
@@ -145,6 +153,7 @@ int set_work_stealing(int on) { return set_knob(g_knobs.work_stealing, on); }
 int set_latency_mapping_max_batch(int max_batch) { return set_knob(g_knobs.latency_max_batch, max_batch); }
 int set_exact_step_decisions(int on) { return set_knob(g_knobs.exact_step_decisions, on); }
 int set_certified_steps(int on) { return set_knob(g_knobs.certified_steps, on); }
+int set_loop_constants_in_lds(int mode) { return set_knob(g_knobs.loop_constants_in_lds, mode); }
 int biconvex_last_waves_per_simd() { return t_last_wpe; }
 int biconvex_last_lanes_per_problem() { return t_last_lpp; }
 const char *biconvex_last_kernel_name() { return t_last_kernel; }
@@ -154,7 +163,7 @@ const char *biconvex_last_kernel_name() { return t_last_kernel; }
 // the fp64 sums; the lanes per problem are chosen as for diagonal costs.  The Euclidean cone projection (kCone): likewise, in either form
 // (those other kernels restate the reference's projection only); about per-contact normals (kConeFrame): exactly as kCone.
 LaunchPlan plan_launch(const BatchArgs &a, CostShape shape, int n_eff, long simds, const DispatchKnobs &kn) {
-    LaunchPlan p = {hipErrorInvalidValue, nullptr, {0, false, false, 0, {}}, false, a.certified_steps};
+    LaunchPlan p = {hipErrorInvalidValue, nullptr, {0, false, false, 0, {}, false}, false, a.certified_steps};
     if (shape < 0 || shape >= kNumShapes) return p;
     const ShapeInfo &s = kShapes[shape];
     const bool diag = shape == kDiag;
@@ -177,7 +186,12 @@ LaunchPlan plan_launch(const BatchArgs &a, CostShape shape, int n_eff, long simd
     p.certified_steps = !s.certifies ? 0 : (kn.certified_steps == 2 ? 2 : (kn.certified_steps != 0 ? 1 : 0));      // (2: force phases only)
     p.kernel = diag && a.precision == 1 ? "biconvex_admm_kernel_f32" : s.kernel;
     // the same decisions for two feet as for four, with the LDS record of the foot count (knot_lds)
-    auto segments = [&](int lpp) { p.l.lpp = lpp; p.l.w2 = diag && two_per_simd_pays(a, 64 / lpp, simds, kn); return p; };
+    auto segments = [&](int lpp) {
+        p.l.lpp = lpp;
+        p.l.w2 = diag && two_per_simd_pays(a, 64 / lpp, simds, kn);
+        p.l.clds = p.l.w2 && lpp == 32 && loop_constants_pay(a, n_eff, kn);
+        return p;
+    };
     if (k <= 16) return segments(16);
     // 17..21 knots (the headline shape): three problems per wave in 21-lane segments (fp64; the fp32 kernels keep 32-lane segments)
     if (k <= 21 && a.precision == 0 && three_per_wave_pays(a, simds, kn)) {
@@ -191,7 +205,7 @@ LaunchPlan plan_launch(const BatchArgs &a, CostShape shape, int n_eff, long simd
             // 1024 .. 2048 waves 34.2 .. 37.3 ms -- the stealing itself already fills the gaps the second wave would)
             const bool w2 = kn.two_per_simd == 1;
             // the persistent grid: as many waves as the chip holds at once (one or two per SIMD)
-            p.l = {21, w2, true, kn.steal_grid > 0 ? std::min<long>(kn.steal_grid, (a.B + 2) / 3) : (w2 ? 2 * simds : simds), {}};
+            p.l = {21, w2, true, kn.steal_grid > 0 ? std::min<long>(kn.steal_grid, (a.B + 2) / 3) : (w2 ? 2 * simds : simds), {}, false};
             return p;
         }
         return segments(21);
@@ -203,7 +217,7 @@ LaunchPlan plan_launch(const BatchArgs &a, CostShape shape, int n_eff, long simd
         // LDS fits a CU (at 127 knots only three do: 9.2 ms against 6.9 at B = 1024); four waves per problem: always (11.4-12.6 ms
         // against 15.9-16.8: tools/horizon_sweep.py)
         const bool fits = k > 128 || 4 * launch_lds_bytes(sizeof(double), 1, n_eff, a.H, (size_t)(lpp / 64) * 40) <= 160 * 1024;
-        p.l = {lpp, kn.two_per_simd == 1 || (kn.two_per_simd == 2 && fits && (long)a.B * (lpp / 64) > simds), false, 0, {}};
+        p.l = {lpp, kn.two_per_simd == 1 || (kn.two_per_simd == 2 && fits && (long)a.B * (lpp / 64) > simds), false, 0, {}, false};
         return p;
     }
     return segments(k <= 32 ? 32 : 64);

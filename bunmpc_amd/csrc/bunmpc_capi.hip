@@ -261,6 +261,13 @@ int bmpc_biconvex_last_lanes_per_problem(void) { return bunmpc::biconvex_last_la
 int bmpc_set_latency_mapping_max_batch(int max_batch) { return bunmpc::set_latency_mapping_max_batch(max_batch); }
 int bmpc_set_exact_step_decisions(int on) { return bunmpc::set_exact_step_decisions(on); }
 int bmpc_set_certified_steps(int on) { return bunmpc::set_certified_steps(on); }
+int bmpc_set_loop_constants_in_lds(int mode) { return bunmpc::set_loop_constants_in_lds(mode); }
+long bmpc_loop_constants_lds_bytes(int n_eff, int n_col) { return n_col >= 1 && (n_eff == 2 || n_eff == 4) ? (long)bunmpc::loop_constants_lds_bytes(n_eff, n_col) : -1; }
+int bmpc_loop_constants_resident_waves(int n_col) {
+    if (!bunmpc::loop_constants_fit(4, n_col)) return fail(BMPC_BAD_ARG, "the loop-constants build does not fit this horizon"), -1;
+    return bunmpc::admm_unit(bunmpc::kDiag, 0, 4).loop_constants_resident_waves(n_col);
+}
+int bmpc_loop_constants_fit(int n_eff, int n_col) { return (n_eff == 2 || n_eff == 4) && bunmpc::loop_constants_fit(n_eff, n_col) ? 1 : 0; }
 int bmpc_biconvex_fp32_scratch_bytes(void) { return bunmpc::admm_unit(bunmpc::kDiag, 1, 4).scratch_bytes(); }
 int bmpc_block_cost_struct_size(void) { return (int)sizeof(bmpc_block_cost_t); }
 int bmpc_band_cost_struct_size(void) { return (int)sizeof(bmpc_band_cost_t); }
@@ -299,6 +306,7 @@ int bmpc_biconvex_plan_launch(const bmpc_batch_t *d, int cost_shape, long simds,
     out->waves_per_simd = p.latency ? 0 : (p.l.w2 ? 2 : 1);
     out->steal = p.l.steal;
     out->steal_waves = p.l.steal_waves;
+    out->loop_constants_in_lds = p.l.clds;
     return BMPC_OK;
 }
 const char *bmpc_last_error(void) { return g_err.c_str(); }

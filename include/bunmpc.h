@@ -206,6 +206,23 @@ int bmpc_set_exact_step_decisions(int on);
  * steps where a kernel has them; 2: the force step only (test switches: results must be bit-identical whatever the value).
  * Returns the old value. */
 int bmpc_set_certified_steps(int on);
+/* The benchmark's kernel (two waves per SIMD, 32 lanes per problem, four feet, harness form, fp64, diagonal costs) exists in a second
+ * two-waves build whose certified FISTA loops keep x_k and its image in registers and read 18 constants of the phase from LDS instead
+ * (DESIGN.md section 4): same operations in the same order, bit-identical results.  Its wave needs bmpc_loop_constants_lds_bytes of LDS,
+ * and eight waves share a CU's 160 KB: bmpc_loop_constants_fit, n_col = 16 .. 20 at four feet.  mode 0: never that build; 1: wherever
+ * the two-waves build is taken and it fits; 2 (default): when it pays -- which the measurement recorded in EXPERIMENTS.md resolves to
+ * "wherever it fits" (B = 4096, n_col = 20: 2.82 -> 2.55 ms).  Only the kernel behind the record changes: bmpc_biconvex_last_kernel_name / _lanes_per_problem / _waves_per_simd and the
+ * same fields of bmpc_biconvex_plan_launch report what they report for the two-waves build; the plan's loop_constants_in_lds tells
+ * them apart.  Returns the old value. */
+int bmpc_set_loop_constants_in_lds(int mode);
+/* LDS bytes of a wave of that build for n_col + 1 knots (two problems per wave; -1 for another n_eff or n_col < 1) and whether eight of
+ * them fit a CU: 8 (84 + (78 + 2 x 19) (n_col + 1)) <= 20480 at four feet.  Pure functions. */
+long bmpc_loop_constants_lds_bytes(int n_eff, int n_col);
+int bmpc_loop_constants_fit(int n_eff, int n_col);
+/* Waves of that build one CU holds at once at this n_col, as the runtime's occupancy query answers for the loaded code object and the
+ * current device: 8 is what two waves per SIMD need (at n_col = 20 the LDS of eight waves fills the CU to the allocation granule).
+ * -1 (BMPC_BAD_ARG) where the build does not fit, or on error.  Needs a GPU. */
+int bmpc_loop_constants_resident_waves(int n_col);
 /* Scratch (private-segment) bytes per lane of the fp32 kernels as the loaded code object reports them, -1 on error.  0 is what
  * the build is set up for (bunmpc_amd/build.py: their translation unit is compiled without the SLP vectoriser); a compiler that
  * spills again shows up here, and in 4x the HBM traffic. */
@@ -235,6 +252,7 @@ typedef struct {
     int steal;
     long steal_waves;
     const char *kernel;
+    int loop_constants_in_lds;      /* 1: the build of bmpc_set_loop_constants_in_lds behind this record */
 } bmpc_launch_plan_t;
 int bmpc_biconvex_plan_launch(const bmpc_batch_t *d, int cost_shape, long simds, bmpc_launch_plan_t *out);
 
