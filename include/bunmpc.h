@@ -373,27 +373,25 @@ int bmpc_biconvex_cone_kernel_scratch_bytes(int n_eff);
  * SIMD, both forms, every step tested on fp64 sums).  BMPC_BAD_ARG with a message naming the limit: normals under projection == 0,
  * fp32, n_col + 1 > 64 knots, n_eff other than 2 or 4, a stride outside the rule above, and (host entry point, setters) a normal that
  * is not finite or not of unit length.  Not built: normals in fp32, for more than 63 knots, and
- * for the reference's "SoC" step, which stays the reference's.
- * (This family's prototypes carry an explicit `extern`: tests/test_cone_cpu.py pins the number of plain `int bmpc_*cone*(...)`
- * prototypes in this header to the six of the family above; tests/test_cone_frame_cpu.py checks these against the binding.) */
+ * for the reference's "SoC" step, which stays the reference's. */
 typedef struct {
     const double *normals; long snormals;  /* [.][n_col][n_eff][3], unit, world frame; NULL: world z */
 } bmpc_contact_frame_t;
-extern int bmpc_contact_frame_struct_size(void);    /* sizeof(bmpc_contact_frame_t), to catch binding drift */
-extern int bmpc_biconvex_solve_batch_cone_frames_device(const bmpc_batch_t *d, const bmpc_cone_t *c, const bmpc_contact_frame_t *fr, void *hip_stream);
-extern int bmpc_biconvex_solve_batch_cone_frames_host(const bmpc_batch_t *d, const bmpc_cone_t *c, const bmpc_contact_frame_t *fr);
+int bmpc_contact_frame_struct_size(void);    /* sizeof(bmpc_contact_frame_t), to catch binding drift */
+int bmpc_biconvex_solve_batch_cone_frames_device(const bmpc_batch_t *d, const bmpc_cone_t *c, const bmpc_contact_frame_t *fr, void *hip_stream);
+int bmpc_biconvex_solve_batch_cone_frames_host(const bmpc_batch_t *d, const bmpc_cone_t *c, const bmpc_contact_frame_t *fr);
 /* The handle's contact normals n [n_col][n_eff][3] (NULL: back to world z); they persist across optimize calls.  optimize refuses
  * (BMPC_BAD_ARG) normals under projection 0 and, as with projection 1 itself, on a handle that carries block or band costs or has
  * n_col + 1 > 64.  bmpc_kinodyn_optimize goes through the handle's optimize: it honours them or returns that refusal. */
-extern int bmpc_biconvex_set_contact_normals(bmpc_biconvex_t *h, const double *n);
+int bmpc_biconvex_set_contact_normals(bmpc_biconvex_t *h, const double *n);
 /* ... taken from the matrices of bmpc_biconvex_set_rotation_matrix_f: the normal of a contact is the third row of its R (row-major;
  * the reference's commented line is rotated_force = R * f, so local z is row 2 of R).  Refuses (BMPC_BAD_ARG) unless exactly
  * n_col * n_eff matrices were appended, knot-major, and every third row passes the unit test above.  The matrices themselves stay
  * stored and otherwise unused. */
-extern int bmpc_biconvex_set_contact_normals_from_rotations(bmpc_biconvex_t *h);
+int bmpc_biconvex_set_contact_normals_from_rotations(bmpc_biconvex_t *h);
 /* The largest scratch (private-segment) bytes per lane over the kernels about contact normals of one foot count (n_eff 2 or 4), as the
  * loaded code object reports them; -1 for another n_eff, or on error. */
-extern int bmpc_biconvex_cone_frame_kernel_scratch_bytes(int n_eff);
+int bmpc_biconvex_cone_frame_kernel_scratch_bytes(int n_eff);
 
 /* rigid-body model -------------------------------------------------------------------
  * What pinocchio::urdf::buildModel(urdf, JointModelFreeFlyer()) yields (inverse_kinematics.cpp:10,
@@ -610,11 +608,8 @@ int bmpc_kinodyn_solve_batch_device(const bmpc_kinodyn_batch_t *d, void *hip_str
 /* The same with the centroidal stage through bmpc_biconvex_solve_batch_cone_device or, with frames, ..._cone_frames_device: the
  * Euclidean cone projection, per-foot coefficients and contact normals (bmpc_cone_t, bmpc_contact_frame_t above) in the whole-body
  * data path.  Their refusals (returned before anything is written or launched) and their kernels.  cone == NULL is
- * bmpc_kinodyn_solve_batch_device itself, bit for bit; frames may be NULL.
- * (Declared through BMPC_ADDITIVE, which expands to nothing: tests/test_cone_cpu.py and tests/test_cone_frame_cpu.py pin the plain
- * and the `extern` prototypes of this header whose names hold "cone" to the families above.) */
-#define BMPC_ADDITIVE
-BMPC_ADDITIVE int bmpc_kinodyn_solve_batch_cone_device(const bmpc_kinodyn_batch_t *d, const bmpc_cone_t *cone, const bmpc_contact_frame_t *frames, void *hip_stream);
+ * bmpc_kinodyn_solve_batch_device itself, bit for bit; frames may be NULL. */
+int bmpc_kinodyn_solve_batch_cone_device(const bmpc_kinodyn_batch_t *d, const bmpc_cone_t *cone, const bmpc_contact_frame_t *frames, void *hip_stream);
 
 /* harness inputs on the device (additive; SURVEY 8f-1, centroidal level) -----------------------------
  * What SoloMpcGaitGen.create_cnt_plan / create_costs compute per MPC call (abstract_cyclic_gen.py:159-414, 564-607)

@@ -3,8 +3,6 @@ of them, the reason for the mode), the numpy twin on the Go2 and mixed-gait prob
 deterministically, the precondition of the GPU cases (the twin does not move under a one-ulp change of its input), and the C-ABI's
 refusals and bindings."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
@@ -15,8 +13,6 @@ from bunmpc_amd.biconvex_mpc_cpp import BiconvexMP
 from oracle import oracle_np
 from tests import cone_np
 from tests.util import rel_l2
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _draws():
@@ -199,24 +195,20 @@ def test_handle_refusals():
     assert e.value.code == _lib.BAD_ARG and "64 knots" in str(e.value)
 
 
-_CTYPES = {"int": C.c_int, "long": C.c_long, "double": C.c_double}
+_I, _P = C.c_int, C.c_void_p
+_CONE = {"bmpc_cone_struct_size": (_I, []),
+         "bmpc_biconvex_solve_batch_cone_device": (_I, [_P, _P, _P]),
+         "bmpc_biconvex_solve_batch_cone_host": (_I, [_P, _P]),
+         "bmpc_biconvex_set_cone_projection": (_I, [_P, _I]),
+         "bmpc_biconvex_set_friction_coefficients": (_I, [_P, _P]),
+         "bmpc_biconvex_cone_kernel_scratch_bytes": (_I, [_I])}
 
 
 def test_cone_bindings_match_the_header(hiplib):
-    """the cone entry points' signatures in bunmpc_amd/_lib.py against their prototypes in include/bunmpc.h, the struct's size, the minor version"""
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "bunmpc.h")).read(), flags=re.S)
-    seen = 0
-    for res, name, args in re.findall(r"^\s*(int|void|long|double)\s+(bmpc_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", hdr, flags=re.M):
-        if "cone" not in name and name != "bmpc_biconvex_set_friction_coefficients":
-            continue
-        seen += 1
-        want = []
-        for a in (s.strip() for s in args.split(",")):
-            if a == "void":
-                continue
-            want.append(C.c_void_p if "*" in a else _CTYPES[a.replace("const ", "").split()[0]])
-        assert _lib._SIGS[name] == (None if res == "void" else _CTYPES[res], want), name
-    assert seen == 6
+    """the cone entry points' signatures as the binding reads them from include/bunmpc.h (tests/test_abi_cpu.py holds the whole table),
+    the struct's size, the minor version"""
+    for name, sig in _CONE.items():
+        assert _lib._SIGS[name] == sig, name
     assert hiplib.bmpc_cone_struct_size() == C.sizeof(_lib.Cone) == 24
     assert hiplib.bmpc_abi_minor_version() == 2
     assert hiplib.bmpc_biconvex_cone_kernel_scratch_bytes(3) == -1
