@@ -71,7 +71,8 @@ def compile_jobs():
              (_FP32_ADMM_FLAGS if precision else _FP64_ADMM_FLAGS)) for shape, precision, feet in units]
     # biconvex_launch.hip: host code and two helper kernels, which are held to the code the fp64 units' flags give them
     others = {"biconvex_launch.hip": _FP64_ADMM_FLAGS, "biconvex_latency.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], "bunmpc_capi.hip": [],
-              "ik_ddp.hip": ["-ffp-contract=on"], "bunmpc_ik_capi.hip": [], "plan_gen.hip": [], "id_ctrl.hip": [], "perturb.hip": []}
+              "ik_ddp.hip": ["-ffp-contract=on"], "bunmpc_ik_capi.hip": [], "plan_gen.hip": [], "id_ctrl.hip": [], "perturb.hip": [],
+              "cc_goals.hip": []}
     return jobs + [(src[:-len(".hip")], src, flags) for src, flags in others.items()]
 
 
@@ -90,8 +91,11 @@ def object_path(job, flags):
 
 
 def dependencies():
-    """every source of a job, every header of csrc/, the public header and this file (the flags live here)"""
-    return sorted({os.path.join(CSRC, src) for _, src, _ in compile_jobs()}) + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [INCLUDE, os.path.abspath(__file__)]
+    """every source of a job, every header of csrc/, the public header, every other header beside it (bunmpc_goals.h) and this file
+    (the flags live here)"""
+    beside = sorted(h for h in glob.glob(os.path.join(os.path.dirname(INCLUDE), "*.h")) if h != INCLUDE)
+    return (sorted({os.path.join(CSRC, src) for _, src, _ in compile_jobs()}) + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [INCLUDE] + beside +
+            [os.path.abspath(__file__)])
 
 
 def _without_mllvm(cmd):

@@ -9,6 +9,7 @@
 namespace bunmpc {
 int launch_wb_plan(const RobotModelDev *model, const bmpc_wb_plan_batch_t &d, const bmpc_terrain_t *t, double *normals, hipStream_t st);   // plan_gen.hip
 int check_terrain(const bmpc_terrain_t *t);                                                     // plan_gen.hip
+int model_on_device(const void *model, int *nframes, const RobotModelDev **dev);                // defined below, for cc_goals.hip
 int check_cone_batch(const bmpc_batch_t *d, const bmpc_cone_t *c, const bmpc_contact_frame_t *fr);   // bunmpc_capi.hip
 }
 
@@ -924,3 +925,15 @@ int bmpc_kinodyn_optimize(bmpc_kinodyn_t *h, const double *q, const double *v, i
 }
 
 }  // extern "C"
+
+// cc_goals.hip (include/bunmpc_goals.h takes the model as an opaque pointer): the model's frame count and, with dev != nullptr,
+// its device copy, uploaded on first use
+int bunmpc::model_on_device(const void *model, int *nframes, const RobotModelDev **dev) {
+    bmpc_model *m = const_cast<bmpc_model *>(static_cast<const bmpc_model *>(model));
+    *nframes = m->host.nframes;
+    if (dev) {
+        if (int rc = m->upload()) return rc;
+        *dev = m->dptr();
+    }
+    return BMPC_OK;
+}
