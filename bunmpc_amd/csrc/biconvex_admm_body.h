@@ -295,7 +295,8 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
 
     if (lane < kLdsZeros) zeros[lane] = R(0);
     __syncthreads();
-    const double *const cmtab = a.cmtab;      // (wave-uniform reads: through the scalar cache)
+    const double *const cmtab = a.cmtab;      // (wave-uniform reads.  The loop-constants build takes them through the scalar cache, uniform_load; as plain
+                                              // loads, everywhere else, hipcc makes them per-lane global loads of one address)
 
     R dt = ldz<R>(a.dt + wave0 * H, oK, 0, rvalid);
     R dtp;  // dt of knot t-1 (0 for t == 0: previous lane is a dead/terminal lane)
@@ -342,9 +343,16 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
     // knot (as a byte offset into LDS; lanes outside `own` read the zeros) and of its record.  Made from `lane` they are values of the
     // whole kernel, which hipcc parks in scratch memory and reads back inside the loops.
     [[maybe_unused]] auto lane_id = [&]() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, opaque_zero())); };
+    // A lane outside `own` reads its zeros where the record of the knot it would own -- the stride going on past the horizon -- falls in
+    // the LDS banks: element (that record's element index) mod 32 of the zeros at the front of LDS.  The lanes of a 32-lane segment then
+    // sit on 32 different bank pairs in every read of the constants, and those of each group of 16 on 16 (19 is odd; DESIGN.md section
+    // 4 and tools/lds_bank_model.py).  At one address for all of them -- element 0 -- they met a knot lane's bank in most of these
+    // reads.  The last element read is 31 + 18 < kLdsZeros.
+    static_assert(!CLDS || (kLoopConstLds % 2 == 1 && 31 + kLoopConstLds <= kLdsZeros), "idle lanes read exact zeros, on banks of their own");
     [[maybe_unused]] auto consts_offset = [&](mask_t own) {
         const unsigned ln = opaque_copy(lane_id());
-        return lanes(own) ? 8u * ((unsigned)(kLdsZeros + 2 * (kSegLds + (H + 1) * KL)) + (ln / (unsigned)LPP * (unsigned)(H + 1) + ln % (unsigned)LPP) * (unsigned)kLoopConstLds) : 0u;
+        const unsigned e = (unsigned)(kLdsZeros + 2 * (kSegLds + (H + 1) * KL)) + (ln / (unsigned)LPP * (unsigned)(H + 1) + ln % (unsigned)LPP) * (unsigned)kLoopConstLds;
+        return 8u * (lanes(own) ? e : e & 31u);
     };
     [[maybe_unused]] auto knot_record = [&]() {      // (Xg, made again where a store needs it, as header() is: held across a loop it is one register too many)
         const unsigned ln = opaque_copy(lane_id());
@@ -913,7 +921,13 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                     park_f();      // (the step constant and the counters rest in the header across the loop, as across the motion step)
                     R wc[NF];
                     { const R *Cz = consts(); UNROLL for (int j = 0; j < NF; ++j) wc[j] = Cz[j]; }
-                    unsigned n0 = 0, n1 = 0;      // iterations of the wave's two problems, counted in scalar registers (act is segment-uniform)
+                    // (the scalar side of the loop -- counts from the exit index, `act` and the screen's words changed only where `done`
+                    // has a bit, the last iteration's store at the loop's exits, a scalar momentum coefficient, the return value that says
+                    // how the loop goes on: described at the motion step's loop)
+                    int c0 = 0, c1 = 0;      // iterations of the wave's two problems that have left the loop (scalar registers)
+                    unsigned dead0, dead1;
+                    seg_dead32(act, dead0, dead1);
+                    R cmn = uniform_load(cmtab, 0u);
                     auto store_fr = [&](mask_t m, const R (&xv)[NF], const R (&rv)[6]) {
                         if (lanes(m & rvalid_m)) {
                             R *Xs = knot_record();
@@ -921,9 +935,45 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                             UNROLL for (int k = 0; k < 6; ++k) Xs[18 + NF + k] = rv[k];
                         }
                     };
-                    auto iterate_k = [&](const R (&xo)[NF], const R (&ro)[6], R (&xn)[NF], R (&rn)[6], int i) -> bool {
-                        const R cm = (R)cmtab[i];
-                        mask_t done;
+                    constexpr int kGo = 0, kHandOver = 1, kAllLeft = 2;
+                    // an iteration that the screen does not settle: the step decisions from the sums, a hand-over, or problems that finish
+                    auto unsettled = [&](const R (&xo)[NF], const R (&ro)[6], const R (&xn)[NF], const R (&rn)[6], int i, R g2) -> int {
+                        mask_t done = 0;
+                        mask_t unclear = ~mask_t(0);      // designated lanes of live problems whose fp32 decisions are not clear
+                        if (banded != 0) {      // the fp32 decisions, if every live problem's are clear (see BAND)
+                            float gf = (float)g2;
+                            seg_sum1_f32<LPP>(gf);
+                            const mask_t yes = __ballot(gf < flo), no = __ballot(gf > fhi);
+                            const mask_t dyes = __ballot(gf < t2lo), dno = __ballot(gf > t2hi);
+                            const mask_t clear = (yes | no) & (dyes | dno) & __ballot(gf >= 1e-24f) & __ballot(gf <= 1e30f);
+                            unclear = ~clear & act;
+                            if (unclear == 0) {
+                                if ((yes & act) != 0) { store_fr(act, xo, ro); return kHandOver; }
+                                done = dyes;
+                            }
+                        }
+                        if (unclear != 0) {
+                            double g2s = (double)g2;
+                            sum1(g2s);
+                            // a live problem's step below the floor: nothing of this iteration is kept, the tested loop runs it again
+                            if ((__ballot(g2s < floor2) & act) != 0) { store_fr(act, xo, ro); return kHandOver; }
+                            done = __ballot(g2s < tol2);      // (see the shared loop for the sqrt-free form)
+                            if (__ballot(fabs(g2s - tol2) <= 1e-14 * tol2) != 0) done = __ballot(sqrt(g2s) < tol);
+                        }
+                        const mask_t latch = act & done;
+                        if (latch != 0) {      // problems that finish here: F_{k+1} and its image, their counts, and what follows from `act`
+                            store_fr(latch, xn, rn);
+                            if ((unsigned)latch != 0u) c0 = i + 1;
+                            if ((unsigned)(latch >> 32) != 0u) c1 = i + 1;
+                            act &= ~done;
+                            if (act == 0) return kAllLeft;      // (nothing reads y behind the loop)
+                            seg_dead32(act, dead0, dead1);
+                        }
+                        return kGo;
+                    };
+                    auto iterate_k = [&](const R (&xo)[NF], const R (&ro)[6], R (&xn)[NF], R (&rn)[6], int i) -> int {
+                        const R cm = cmn;
+                        cmn = uniform_load(cmtab, min((unsigned)i + 1u, (unsigned)kMaxFistaIters - 1u));      // (the next iteration's)
                         unsigned long long anycone = 0;     // lanes with a force on the cone branch, as a scalar mask
                         R fr[NF];
                         UNROLL for (int n = 0; n < E; ++n) {
@@ -957,7 +1007,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                                 xn[3 * n + 2] = cone ? fmaR(mu, s, fz) * imu : xn[3 * n + 2];
                             }
                         }
-                        {   // applyA, its bPk read behind the projection and used last
+                        {   // applyA, its bPk read behind the projection and used last, behind one wait for all six
                             R bk[6];
                             const R *Cz = reinterpret_cast<const R *>(reinterpret_cast<const char *>(lds_raw) + opaque_copy_after(cb, xn[NF - 1]));
                             UNROLL for (int k = 0; k < 6; ++k) bk[k] = Cz[NF + k];
@@ -969,62 +1019,43 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                                 s4 += sp[n][0] * vz - sp[n][2] * vx;
                                 s5 += sp[n][1] * vx - sp[n][0] * vy;
                             }
+                            keep_here(bk);
                             rn[0] = s0 + bk[0]; rn[1] = s1 + bk[1]; rn[2] = s2 + bk[2];
                             rn[3] = s3 + bk[3]; rn[4] = s4 + bk[4]; rn[5] = s5 + bk[5];
                         }
-                        R g2 = 0;
-                        bool settled;      // the two-stage screen (see the shared loop)
-                        {
+                        {   // the two-stage screen (see the shared loop), as nested branches (see the motion step's loop)
                             R s = 0;
                             UNROLL for (int k = 0; k < (int)(sizeof(kScreenTermsF) / sizeof(int)); ++k) { const R d = xn[kScreenTermsF[k]] - y[kScreenTermsF[k]]; s = fmaR(d, d, s); }
-                            settled = seg_covered<LPP>(__ballot(s > theta), act);
-                            if (!settled) {
+                            if (!seg_covered32(__ballot(s > theta), dead0, dead1)) {
+                                R g2 = 0;
                                 UNROLL for (int j = 0; j < NF; ++j) { const R d = xn[j] - y[j]; g2 = fmaR(d, d, g2); }
-                                settled = seg_covered<LPP>(__ballot(g2 > theta), act);
-                            }
-                        }
-                        if (settled) done = 0;
-                        else {
-                            mask_t unclear = ~mask_t(0);      // designated lanes of live problems whose fp32 decisions are not clear
-                            if (banded != 0) {      // the fp32 decisions, if every live problem's are clear (see BAND)
-                                float gf = (float)g2;
-                                seg_sum1_f32<LPP>(gf);
-                                const mask_t yes = __ballot(gf < flo), no = __ballot(gf > fhi);
-                                const mask_t dyes = __ballot(gf < t2lo), dno = __ballot(gf > t2hi);
-                                const mask_t clear = (yes | no) & (dyes | dno) & __ballot(gf >= 1e-24f) & __ballot(gf <= 1e30f);
-                                unclear = ~clear & act;
-                                if (unclear == 0) {
-                                    if ((yes & act) != 0) { store_fr(act, xo, ro); return false; }
-                                    done = dyes;
+                                if (!seg_covered32(__ballot(g2 > theta), dead0, dead1)) {
+                                    const int r = unsettled(xo, ro, xn, rn, i, g2);
+                                    if (r != kGo) return r;
                                 }
                             }
-                            if (unclear != 0) {
-                                double g2s = (double)g2;
-                                sum1(g2s);
-                                // a live problem's step below the floor: nothing of this iteration is kept, the tested loop runs it again
-                                if ((__ballot(g2s < floor2) & act) != 0) { store_fr(act, xo, ro); return false; }
-                                done = __ballot(g2s < tol2);      // (see the shared loop for the sqrt-free form)
-                                if (__ballot(fabs(g2s - tol2) <= 1e-14 * tol2) != 0) done = __ballot(sqrt(g2s) < tol);
-                            }
                         }
-                        const mask_t latch = act & (i == maxit - 1 ? ~mask_t(0) : done);
-                        if (latch != 0) store_fr(latch, xn, rn);
                         { const R *Cz = consts(); UNROLL for (int j = 0; j < NF; ++j) wc[j] = Cz[j]; }      // (the next iteration's)
-                        UNROLL for (int j = 0; j < NF; ++j) y[j] = fma3(cm, xn[j] - xo[j], xn[j]);
+                        UNROLL for (int j = 0; j < NF; ++j) y[j] = fma3_s(cm, xn[j] - xo[j], xn[j]);
                         UNROLL for (int k = 0; k < 6; ++k) ry[k] = fmaR(cm, rn[k] - ro[k], rn[k]);
-                        UNROLL for (int j = 0; j < NF; ++j) keep_here(wc[j]);      // (a use that stays here: the loads are not sunk to the gradient step)
-                        n0 += (unsigned)act != 0u ? 1u : 0u;
-                        n1 += (unsigned)(act >> 32) != 0u ? 1u : 0u;
-                        act &= ~done;
-                        return true;
+                        keep_here(wc);      // (a use that stays here: the loads are not sunk to the gradient step; one statement, one wait)
+                        return kGo;
                     };
                     i0 = maxit;
-                    for (int i = 0; i < maxit; i += 2) {
-                        if (act == 0) break;
-                        if (!iterate_k(xa, ra, xb, rb, i)) { i0 = i; break; }
-                        if (i + 1 >= maxit || act == 0) break;
-                        if (!iterate_k(xb, rb, xa, ra, i + 1)) { i0 = i + 1; break; }
+                    // (where the loop ends by maxit, the problems still iterating store the last iteration's F_{k+1} and its image from the
+                    // register set that iteration wrote -- at the exit itself: asked behind the loop which set that was, both stay live through it)
+                    if (act != 0 && maxit > 0) {
+                        for (int i = 0;;) {
+                            const int r = iterate_k(xa, ra, xb, rb, i);
+                            if (r != kGo) { if (r == kHandOver) i0 = i; break; }
+                            if (i + 1 >= maxit) { store_fr(act, xb, rb); break; }
+                            const int r1 = iterate_k(xb, rb, xa, ra, i + 1);
+                            if (r1 != kGo) { if (r1 == kHandOver) i0 = i + 1; break; }
+                            i += 2;
+                            if (i >= maxit) { store_fr(act, xa, ra); break; }
+                        }
                     }
+                    const int n0 = (unsigned)act != 0u ? i0 : c0, n1 = (unsigned)(act >> 32) != 0u ? i0 : c1;
                     {   // what the tested loop and the rest of the phase work on comes back (read whether the tested loop runs or not: a
                         // condition here and the registers stay occupied across the loop above)
                         lds_fence();
@@ -1458,16 +1489,63 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                         lds_fence();
                         R qc[9];
                         { const R *Cz = consts(); UNROLL for (int l = 0; l < 9; ++l) qc[l] = Cz[l]; }
-                        unsigned n0 = 0, n1 = 0;      // iterations of the wave's two problems, counted in scalar registers (act is segment-uniform)
+                        // What an iteration that settles at the screen runs beside its arithmetic is kept to a few scalar instructions:
+                        //   * a problem's iteration count is the index at which its bit left `act` (plus one), or the index at which the
+                        //     loop ended -- `act` only loses bits here -- noted where `done` has a bit and behind the loop;
+                        //   * `act`, the latch of a finishing problem and the words of the screen change only where `done` has a bit;
+                        //   * x_{k+1} and its image of the problems still iterating when the loop ends by maxit are stored at that exit of
+                        //     the loop, from the register set the copy in front of it wrote;
+                        //   * the momentum coefficient is a scalar, loaded one iteration ahead (uniform_load);
+                        //   * iterate_k says how the loop goes on by its return value alone: kGo, kHandOver (a live problem's step below
+                        //     the floor: nothing of this iteration is kept, the tested loop runs it again) or kAllLeft.
+                        int c0 = 0, c1 = 0;      // iterations of the wave's two problems that have left the loop (scalar registers)
+                        unsigned dead0, dead1;
+                        seg_dead32(act, dead0, dead1);
+                        R cmn = uniform_load(cmtab, 0u);
                         auto store_xr = [&](mask_t m, const R (&xv)[9], const R (&rv)[9]) {
                             R *Xs = knot_record();
                             if (lanes(m & kvalid_m)) { UNROLL for (int l = 0; l < 9; ++l) Xs[l] = xv[l]; }
                             if (lanes(m & rvalid_m)) { UNROLL for (int l = 0; l < 9; ++l) Xs[18 + NF + l] = rv[l]; }
                         };
                         auto hand_over = [&](const R (&xo)[9], const R (&ro)[9]) { store_xr(act, xo, ro); };
-                        auto iterate_k = [&](const R (&xo)[9], const R (&ro)[9], R (&xn)[9], R (&rn)[9], int i) -> bool {
-                            const R cm = (R)cmtab[i];
-                            mask_t done;
+                        constexpr int kGo = 0, kHandOver = 1, kAllLeft = 2;
+                        // an iteration that the screen does not settle: the step decisions from the sums, a hand-over, or problems that finish
+                        auto unsettled = [&](const R (&xo)[9], const R (&ro)[9], const R (&xn)[9], const R (&rn)[9], int i, R g2) -> int {
+                            mask_t done = 0;
+                            mask_t unclear = ~mask_t(0);
+                            if (banded != 0) {      // the fp32 decisions -- floor and exit -- if every live problem's are clear (see the force step)
+                                float gf = (float)g2;
+                                seg_sum1_f32<LPP>(gf);
+                                const mask_t yes = __ballot(gf < flo), no = __ballot(gf > fhi);
+                                const mask_t dyes = __ballot(gf < t2lo), dno = __ballot(gf > t2hi);
+                                const mask_t clear = (yes | no) & (dyes | dno) & __ballot(gf >= 1e-24f) & __ballot(gf <= 1e30f);
+                                unclear = ~clear & act;
+                                if (unclear == 0) {
+                                    if ((yes & act) != 0) { hand_over(xo, ro); return kHandOver; }
+                                    done = dyes;
+                                }
+                            }
+                            if (unclear != 0) {
+                                double g2s = (double)g2;
+                                sum1(g2s);
+                                if ((__ballot(g2s < floor2) & act) != 0) { hand_over(xo, ro); return kHandOver; }
+                                done = __ballot(g2s < tol2);      // the tested loop's exit rule (see the force loop for the sqrt-free form)
+                                if (__ballot(fabs(g2s - tol2) <= 1e-14 * tol2) != 0) done = __ballot(sqrt(g2s) < tol);
+                            }
+                            const mask_t latch = act & done;
+                            if (latch != 0) {      // problems that finish here: x_{k+1} and its image, their counts, and what follows from `act`
+                                store_xr(latch, xn, rn);
+                                if ((unsigned)latch != 0u) c0 = i + 1;
+                                if ((unsigned)(latch >> 32) != 0u) c1 = i + 1;
+                                act &= ~done;
+                                if (act == 0) return kAllLeft;      // (nothing reads y behind the loop)
+                                seg_dead32(act, dead0, dead1);
+                            }
+                            return kGo;
+                        };
+                        auto iterate_k = [&](const R (&xo)[9], const R (&ro)[9], R (&xn)[9], R (&rn)[9], int i) -> int {
+                            const R cm = cmn;
+                            cmn = uniform_load(cmtab, min((unsigned)i + 1u, (unsigned)kMaxFistaIters - 1u));      // (the next iteration's)
                             {
                                 R z[9], wp[9];
                                 shift_prev(ry, wp);  // row-block t-1 (0 for t == 0)
@@ -1484,7 +1562,8 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                                     xn[l] = v;
                                 }
                             }
-                            {   // applyA_c, its bPk read behind the gradient step (z and its neighbour's image are dead by then) and used last
+                            {   // applyA_c, its bPk read behind the gradient step (z and its neighbour's image are dead by then) and used last,
+                                // behind one wait for all nine
                                 R bk[9];
                                 const R *Cz = reinterpret_cast<const R *>(reinterpret_cast<const char *>(lds_raw) + opaque_copy_after(cb, xn[8]));
                                 UNROLL for (int l = 0; l < 9; ++l) bk[l] = Cz[9 + l];
@@ -1495,56 +1574,42 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                                 w[6] += SY * xn[2] - SZ * xn[1];
                                 w[7] += SZ * xn[0] - SX * xn[2];
                                 w[8] += SX * xn[1] - SY * xn[0];
+                                keep_here(bk);
                                 UNROLL for (int l = 0; l < 9; ++l) rn[l] = w[l] + bk[l];
                             }
-                            R g2 = 0, s = 0;
+                            R s = 0;
                             UNROLL for (int k = 0; k < (int)(sizeof(kScreenTermsX) / sizeof(int)); ++k) { const R d = xn[kScreenTermsX[k]] - y[kScreenTermsX[k]]; s = fmaR(d, d, s); }
-                            bool settled = seg_covered<LPP>(__ballot(s > theta), act);      // the screen, stage 1 (see the force step)
-                            if (!settled) {      // stage 2: the whole partial, with the bits it always had
+                            // the screen (see the force step); its two stages and what follows a miss are nested branches: as a bool
+                            // that the stages share, `settled` is made a 64-bit mask and tested again
+                            if (!seg_covered32(__ballot(s > theta), dead0, dead1)) {
+                                R g2 = 0;      // stage 2: the whole partial, with the bits it always had
                                 UNROLL for (int l = 0; l < 9; ++l) { const R d = xn[l] - y[l]; g2 = fmaR(d, d, g2); }
-                                settled = seg_covered<LPP>(__ballot(g2 > theta), act);
-                            }
-                            if (settled) done = 0;
-                            else {
-                                mask_t unclear = ~mask_t(0);
-                                if (banded != 0) {      // the fp32 decisions -- floor and exit -- if every live problem's are clear (see the force step)
-                                    float gf = (float)g2;
-                                    seg_sum1_f32<LPP>(gf);
-                                    const mask_t yes = __ballot(gf < flo), no = __ballot(gf > fhi);
-                                    const mask_t dyes = __ballot(gf < t2lo), dno = __ballot(gf > t2hi);
-                                    const mask_t clear = (yes | no) & (dyes | dno) & __ballot(gf >= 1e-24f) & __ballot(gf <= 1e30f);
-                                    unclear = ~clear & act;
-                                    if (unclear == 0) {
-                                        if ((yes & act) != 0) { hand_over(xo, ro); return false; }
-                                        done = dyes;
-                                    }
-                                }
-                                if (unclear != 0) {
-                                    double g2s = (double)g2;
-                                    sum1(g2s);
-                                    if ((__ballot(g2s < floor2) & act) != 0) { hand_over(xo, ro); return false; }
-                                    done = __ballot(g2s < tol2);      // the tested loop's exit rule (see the force loop for the sqrt-free form)
-                                    if (__ballot(fabs(g2s - tol2) <= 1e-14 * tol2) != 0) done = __ballot(sqrt(g2s) < tol);
+                                if (!seg_covered32(__ballot(g2 > theta), dead0, dead1)) {
+                                    const int r = unsettled(xo, ro, xn, rn, i, g2);
+                                    if (r != kGo) return r;
                                 }
                             }
-                            const mask_t latch = act & (i == maxit - 1 ? ~mask_t(0) : done);
-                            if (latch != 0) store_xr(latch, xn, rn);
                             { const R *Cz = consts(); UNROLL for (int l = 0; l < 9; ++l) qc[l] = Cz[l]; }      // (the next iteration's)
-                            UNROLL for (int l = 0; l < 9; ++l) y[l] = fma3(cm, xn[l] - xo[l], xn[l]);      // (no copies at the loop's end: see fma3)
+                            UNROLL for (int l = 0; l < 9; ++l) y[l] = fma3_s(cm, xn[l] - xo[l], xn[l]);      // (no copies at the loop's end: see fma3)
                             if (rvalid) { UNROLL for (int l = 0; l < 9; ++l) ry[l] = fmaR(cm, rn[l] - ro[l], rn[l]); }      // (see applyA_c)
-                            UNROLL for (int l = 0; l < 9; ++l) keep_here(qc[l]);      // (a use that stays here: the loads are not sunk to the gradient step)
-                            n0 += (unsigned)act != 0u ? 1u : 0u;
-                            n1 += (unsigned)(act >> 32) != 0u ? 1u : 0u;
-                            act &= ~done;
-                            return true;
+                            keep_here(qc);      // (a use that stays here: the loads are not sunk to the gradient step; one statement, one wait)
+                            return kGo;
                         };
                         i0 = maxit;
-                        for (int i = 0; i < maxit; i += 2) {
-                            if (act == 0) break;
-                            if (!iterate_k(xa, ra, xb, rb, i)) { i0 = i; break; }
-                            if (i + 1 >= maxit || act == 0) break;
-                            if (!iterate_k(xb, rb, xa, ra, i + 1)) { i0 = i + 1; break; }
+                        // (where the loop ends by maxit, the problems still iterating store the last iteration's x_{k+1} and its image from the
+                        // register set that iteration wrote -- at the exit itself: asked behind the loop which set that was, both stay live through it)
+                        if (act != 0 && maxit > 0) {
+                            for (int i = 0;;) {
+                                const int r = iterate_k(xa, ra, xb, rb, i);
+                                if (r != kGo) { if (r == kHandOver) i0 = i; break; }
+                                if (i + 1 >= maxit) { store_xr(act, xb, rb); break; }
+                                const int r1 = iterate_k(xb, rb, xa, ra, i + 1);
+                                if (r1 != kGo) { if (r1 == kHandOver) i0 = i + 1; break; }
+                                i += 2;
+                                if (i >= maxit) { store_xr(act, xa, ra); break; }
+                            }
                         }
+                        const int n0 = (unsigned)act != 0u ? i0 : c0, n1 = (unsigned)(act >> 32) != 0u ? i0 : c1;
                         // (the step constant and the counters are read again from the header, where they have not changed: not held across the loop)
                         load_xloop();
                         if (banded != 0) band_L((double)L_x * 0.5, Llo, Lhi);

@@ -225,6 +225,18 @@ __device__ __forceinline__ bool seg_covered(mask_t have, mask_t need) {
     return ok;
 }
 
+// ... for the two 32-lane segments of a wave with `need` kept as two scalar words, made where `need` changes and not where it is asked:
+// d0 / d1 are all ones where the segment has no bit in `need` (seg_dead32).  A segment is covered if its word of `have`, or'ed with
+// its d, is non-zero; both are if the smaller of the two or's is: four 32-bit scalar operations and a compare, no 64-bit boolean.
+__device__ __forceinline__ void seg_dead32(mask_t need, unsigned &d0, unsigned &d1) {
+    d0 = (unsigned)need == 0u ? ~0u : 0u;
+    d1 = (unsigned)(need >> 32) == 0u ? ~0u : 0u;
+}
+__device__ __forceinline__ bool seg_covered32(mask_t have, unsigned d0, unsigned d1) {
+    const unsigned t0 = (unsigned)have | d0, t1 = (unsigned)(have >> 32) | d1;
+    return (t0 < t1 ? t0 : t1) != 0u;
+}
+
 // The two decisions of a FISTA step -- retry (cv > (L/2) g2) and exit (g2 < tol^2) -- from WAVE sums of g2 and cv taken in fp32:
 // 4 DPP-fused v_add_f32 per value, one v_permlane16_swap that leaves the sums of g2 in rows 0 / 2 and of cv in rows 1 / 3, one
 // v_permlane32_swap, two v_readlane: 19 instructions against the 36 of the fp64 butterfly (seg_sum2<64>).  The fp32 sums of
@@ -268,6 +280,17 @@ __device__ __forceinline__ unsigned opaque_copy_after(unsigned v, const double &
 // a use of v the optimiser cannot move or remove (no instruction)
 __device__ __forceinline__ void keep_here(double &v) { asm volatile("" : "+v"(v)); }
 __device__ __forceinline__ void keep_here(float &v) { asm volatile("" : "+v"(v)); }
+// ... of a whole batch of values in ONE statement: values that come from LDS are then waited for once (lgkmcnt of the last), where a
+// statement per value makes hipcc wait for each in turn, a ladder of s_waitcnt with nothing between its rungs
+__device__ __forceinline__ void keep_here(double (&v)[6]) {
+    asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]));
+}
+__device__ __forceinline__ void keep_here(double (&v)[9]) {
+    asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]));
+}
+__device__ __forceinline__ void keep_here(double (&v)[12]) {
+    asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]));
+}
 // HBM holds fp64 whatever the arithmetic type R of the kernel; conversion happens at the load / store
 // (the constant element index stays outside the 32-bit offset: it folds into the instruction's immediate)
 // The load is UNCONDITIONAL (the caller's offset names an existing element in every lane); `ok` only decides what is kept.
@@ -309,6 +332,21 @@ __device__ __forceinline__ double fma3(double a, double b, double c) {
     double r;
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
+}
+
+// ... with a wave-uniform a taken from scalar registers (the momentum coefficient: no copy of it into vector registers)
+__device__ __forceinline__ double fma3_s(double a, double b, double c) {
+    double r;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "s"(a), "v"(b), "v"(c));
+    return r;
+}
+// Element i (wave-uniform) of a table that no kernel writes while this one runs, read through the scalar cache: the constant address
+// space is what lets hipcc select s_load_dwordx2.  A plain global load of a uniform address stays a per-lane global_load wherever the
+// kernel also stores to global memory, since the compiler cannot show that the table is not among the stores' targets.
+__device__ __forceinline__ double uniform_load(const double *table, unsigned i) {
+    typedef const char __attribute__((address_space(4))) *const_bytes;
+    typedef const double __attribute__((address_space(4))) *const_ptr;
+    return *(const_ptr)((const_bytes)table + 8u * i);      // (a 32-bit byte offset: the instruction takes it as it is, no 64-bit address is made)
 }
 
 // The box projection max(min(v, hi), lo) as the two bare instructions.  Through fmin / fmax hipcc re-quiets the bounds inside

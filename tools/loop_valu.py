@@ -6,8 +6,8 @@ iteration that takes none of the branches it can skip -- the cone step, the retr
 decisions), with that path's fp64 arithmetic (v_fma_f64, v_fmac_f64, v_mul_f64, v_add_f64), DPP moves, DPP-fused operations and
 permlanes.  Also the kernel's registers, scratch and static LDS as the compiler reports them.
 
-    python tools/loop_valu.py LISTING.s KERNEL_SUBSTRING [--through RE]... [--committing] [--blocks] [--mnemonics]
-    python tools/loop_valu.py --compile admm_diag_f64_e4 KERNEL_SUBSTRING [--through RE]... [--committing] [--blocks] [--mnemonics]
+    python tools/loop_valu.py LISTING.s KERNEL_SUBSTRING [--through RE]... [--committing] [--momentum] [--scalar] [--blocks] [--mnemonics]
+    python tools/loop_valu.py --compile admm_diag_f64_e4 KERNEL_SUBSTRING [--through RE]... [--committing] [--momentum] [--scalar] [--blocks] [--mnemonics]
         (--compile: device code of that job of bunmpc_amd/build.py, with its flags; --through RE: the cheapest path that runs an
         instruction matching RE, e.g. 'permlane' for an iteration that reduces its sums -- in fp32 where it can; given more than
         once: a path that runs an instruction of every RE, each in a block of its own; --committing: --through ds_write2, the
@@ -15,7 +15,15 @@ permlanes.  Also the kernel's registers, scratch and static LDS as the compiler 
         that commits: it leaves the loop before applyA(xn), the momentum step and the write-back.  The headline kernel's certified
         loops: --committing is the screened iteration, --committing --through permlane16 the one that takes the fp32 sum; in the
         force loop, whose two unrolled copies are one loop here, the path runs one copy and leaves by the other's exit test;
-        --mnemonics: the path's vector instructions counted by mnemonic -- is a select or a mask operation on it?)
+        --mnemonics: the path's vector instructions counted by mnemonic -- is a select or a mask operation on it?
+        --momentum: --through the re-read of the loop constants' first pair (`ds_read2_b64 ... offset1:1`), which the loop-constants
+        build issues at the head of its momentum step: the iteration that commits in `biconvex_admm_clds_kernel`, whose only
+        ds_write2 is the rare latch; --momentum alone is the settled iteration, --momentum --through permlane16 the one that
+        takes the fp32 sum; with it the path also runs every exec-masked region it meets (no s_cbranch_execz edge), as the hardware
+        does while one lane is in it -- the rvalid half of the motion loop's momentum step is such a region;
+        --scalar: the path's instructions that are NOT vector ALU, by class -- SALU (arithmetic, compares, selects, moves, mask
+        operations), branches, s_waitcnt, s_nop, scalar memory, LDS, vector memory, other -- and the SALU ones by mnemonic.  In an
+        issue-bound kernel with two waves per SIMD each of them is an issue turn that is not a VALU turn.)
 
 The headline kernel: 'biconvex_admm_kernelIdLi32ELi4ELb0ELb0ELi2E' (biconvex_admm_kernel<double, 32, 4, false, false, 2>)."""
 import collections
@@ -41,6 +49,28 @@ def compile_listing(job):
 
 def is_valu(mn):
     return mn.startswith("v_") and not mn.startswith(NOT_VALU)
+
+
+def scalar_class(mn):
+    """the class of an instruction that is not VALU, as --scalar reports it"""
+    if mn.startswith(("s_branch", "s_cbranch")):
+        return "branch"
+    if mn.startswith("s_waitcnt"):
+        return "s_waitcnt"
+    if mn.startswith("s_nop"):
+        return "s_nop"
+    if mn.startswith(("s_load", "s_buffer_load", "s_scratch_load")):
+        return "scalar memory"
+    if mn.startswith("ds_"):
+        return "LDS"
+    if mn.startswith(("global_", "buffer_", "flat_", "scratch_")):
+        return "vector memory"
+    if mn.startswith("s_") and not mn.startswith(("s_barrier", "s_endpgm", "s_sleep", "s_set", "s_sendmsg", "s_trap")):
+        return "SALU"
+    return "other"
+
+
+SCALAR_CLASSES = ("SALU", "branch", "s_waitcnt", "s_nop", "scalar memory", "LDS", "vector memory", "other")
 
 
 def base(mn):
@@ -81,10 +111,13 @@ def resources(lines, end):
 def main():
     argv = sys.argv[1:]
     through = ["ds_write2"] if "--committing" in argv else []
+    if "--momentum" in argv:
+        through.append(r"ds_read2_b64 \S+ \S+ offset1:1$")
     while "--through" in argv:
         through.append(argv[argv.index("--through") + 1])
         del argv[argv.index("--through"):argv.index("--through") + 2]
     want = (1 << len(through)) - 1
+    run_masked = "--momentum" in argv      # (an exec-masked region is run, not skipped: its s_cbranch_execz is never taken while a lane is in it)
     args = [a for a in argv if not a.startswith("--")]
     listing = compile_listing(args[0]) if "--compile" in sys.argv else args[0]
     lines = open(listing).read().split("\n")
@@ -130,8 +163,8 @@ def main():
             ins = blocks[k][2]
             if not (ins and ins[-1][0] == "s_branch") and k + 1 in inside:
                 succ[k].add(k + 1)
-        for src, dst, _ in edges:
-            if src in inside and dst in inside:
+        for src, dst, mn in edges:
+            if src in inside and dst in inside and not (run_masked and mn == "s_cbranch_execz"):
                 succ[src].add(dst)
         latches = [k for k in members if head in succ[k]]
         for k in members:
@@ -168,6 +201,10 @@ def main():
                                 sum(1 for mn, _ in hot if is_valu(mn)), " ".join("%s %d" % (f, f64[f]) for f in F64), dpp_mov, dpp_op, perm))
         if "--mnemonics" in sys.argv:
             print("    on the path: " + ", ".join("%s %d" % kv for kv in sorted(collections.Counter(base(mn) for mn, _ in hot if is_valu(mn)).items())))
+        if "--scalar" in sys.argv:
+            cls = collections.Counter(scalar_class(mn) for mn, _ in hot if not is_valu(mn))
+            print("    not VALU on the path: %d | %s" % (sum(cls.values()), ", ".join("%s %d" % (c, cls[c]) for c in SCALAR_CLASSES)))
+            print("    SALU on the path: " + ", ".join("%s %d" % kv for kv in sorted(collections.Counter(mn for mn, _ in hot if scalar_class(mn) == "SALU" and not is_valu(mn)).items())))
         if "--blocks" in sys.argv:
             for k in members:
                 br = [t for mn, t in blocks[k][2] if mn.startswith(("s_branch", "s_cbranch"))]
