@@ -2,12 +2,15 @@
 // Mirrors (behaviour, not code) ISL/include/ik/inverse_kinematics.hpp + ISL/src/ik/*.cpp and
 // ISL/src/motion_planner/kino_dyn.cpp; all numerics run in ik_ddp.hip / biconvex_admm.hip.
 #include "../../include/bunmpc.h"
+#include "../../include/bunmpc_turn.h"
 #include "ik_types.h"
 #include "id_types.h"
 #include "perturb_types.h"
 
 namespace bunmpc {
-int launch_wb_plan(const RobotModelDev *model, const bmpc_wb_plan_batch_t &d, const bmpc_terrain_t *t, double *normals, hipStream_t st);   // plan_gen.hip
+int launch_wb_plan(const RobotModelDev *model, const bmpc_wb_plan_batch_t &d, const bmpc_terrain_t *t, double *normals, const bmpc_turn_t *turn,
+                   hipStream_t st);                                                             // plan_gen.hip
+int check_turn(const bmpc_turn_t *turn, bool wb);                                               // plan_gen.hip
 int check_terrain(const bmpc_terrain_t *t);                                                     // plan_gen.hip
 int model_on_device(const void *model, int *nframes, const RobotModelDev **dev);                // defined below, for cc_goals.hip
 int check_cone_batch(const bmpc_batch_t *d, const bmpc_cone_t *c, const bmpc_contact_frame_t *fr);   // bunmpc_capi.hip
@@ -447,8 +450,9 @@ bmpc_model_t *bmpc_model_create(int nj, const int *parent, const double *R, cons
 }
 void bmpc_model_destroy(bmpc_model_t *m) { delete m; }
 
-// t == nullptr with terrain == false: flat ground (bmpc_wb_plan_batch_device)
-static int wb_plan_batch(const bmpc_wb_plan_batch_t *d, bool terrain, const bmpc_terrain_t *t, double *normals, void *hip_stream) {
+// t == nullptr with terrain == false: flat ground (bmpc_wb_plan_batch_device); turn == nullptr: w_des = 0 (the calls of bunmpc.h)
+static int wb_plan_batch(const bmpc_wb_plan_batch_t *d, bool terrain, const bmpc_terrain_t *t, double *normals, const bmpc_turn_t *turn,
+                         void *hip_stream) {
     if (!d || !d->model) return ik_fail(BMPC_BAD_ARG, "null descriptor or model");
     if (d->B < 0 || d->n_col < 1 || d->ik_col < 1 || d->ik_col > d->n_col) return ik_fail(BMPC_BAD_ARG, "bad sizes");
     if (!d->gait || !d->x || !d->t0 || !d->v_des_body) return ik_fail(BMPC_BAD_ARG, "missing input array");
@@ -459,14 +463,21 @@ static int wb_plan_batch(const bmpc_wb_plan_batch_t *d, bool terrain, const bmpc
         if (d->foot_frame[j] < 0 || d->foot_frame[j] >= d->model->host.nframes) return ik_fail(BMPC_BAD_ARG, "foot frame out of range");
     if (terrain)
         if (int rc = bunmpc::check_terrain(t)) return rc;
+    if (turn)
+        if (int rc = bunmpc::check_turn(turn, true)) return rc;
     if (d->B == 0) return BMPC_OK;
     bmpc_model *m = const_cast<bmpc_model *>(d->model);
     if (int rc = m->upload()) return rc;
-    return bunmpc::launch_wb_plan(m->dptr(), *d, t, normals, static_cast<hipStream_t>(hip_stream));
+    return bunmpc::launch_wb_plan(m->dptr(), *d, t, normals, turn, static_cast<hipStream_t>(hip_stream));
 }
-int bmpc_wb_plan_batch_device(const bmpc_wb_plan_batch_t *d, void *hip_stream) { return wb_plan_batch(d, false, nullptr, nullptr, hip_stream); }
+int bmpc_wb_plan_batch_device(const bmpc_wb_plan_batch_t *d, void *hip_stream) { return wb_plan_batch(d, false, nullptr, nullptr, nullptr, hip_stream); }
 int bmpc_wb_plan_batch_terrain_device(const bmpc_wb_plan_batch_t *d, const bmpc_terrain_t *t, double *normals, void *hip_stream) {
-    return wb_plan_batch(d, true, t, normals, hip_stream);
+    return wb_plan_batch(d, true, t, normals, nullptr, hip_stream);
+}
+// include/bunmpc_turn.h; a NULL terrain is flat ground here, and its normals are then not looked at
+int bmpc_wb_plan_batch_turn_device(const void *wb_plan, const void *terrain, double *normals, const bmpc_turn_t *turn, void *hip_stream) {
+    return wb_plan_batch(static_cast<const bmpc_wb_plan_batch_t *>(wb_plan), terrain != nullptr, static_cast<const bmpc_terrain_t *>(terrain),
+                         terrain ? normals : nullptr, turn, hip_stream);
 }
 int bmpc_id_batch_device(const bmpc_id_batch_t *d, void *hip_stream) {
     using namespace bunmpc;

@@ -12,12 +12,17 @@
 // On a terrain (bmpc_plan_batch_terrain_device, bmpc_wb_plan_batch_terrain_device): the same walk with the reference's height-map
 // lines (:333-337, :370-374) -- bilinear height of a regular grid under every new stance and swing location -- and the unit normal
 // of the terrain under every knot, for the friction cones (bunmpc_amd/terrain.py is the numpy restatement).
+//
+// With turning commands (include/bunmpc_turn.h: bmpc_plan_batch_turn_device, bmpc_wb_plan_batch_turn_device): the reference's
+// w_des != 0 branch per problem -- ori_des = q[3:7] in the orientation correction (:636-639, 585-591) and the yaw-momentum reference
+// yaw_inertia * w_des (:602-607); the centrifugal step (:285-286) is in the walk already.
 #include <cmath>
 #include <string>
 
 #include <hip/hip_runtime.h>
 
 #include "../../include/bunmpc.h"
+#include "../../include/bunmpc_turn.h"
 #include "ik_types.h"
 #include "rbd_quad.h"
 
@@ -131,7 +136,18 @@ __global__ void plan_feet_kernel(const bmpc_plan_batch_t d, const TerrainArgs<kT
 }
 
 
-__global__ void plan_costs_kernel(const bmpc_plan_batch_t d) {
+// the turn kernels' extra arguments (include/bunmpc_turn.h): the yaw inertia of the cost references, the commands of the whole-body
+// front end.  Nothing without turning.
+template <bool kTurn> struct TurnCostArgs {};
+template <> struct TurnCostArgs<true> { double yaw_inertia; };
+template <bool kTurn> struct TurnStateArgs {};
+template <> struct TurnStateArgs<true> { const double *w_des; };
+
+// kTurn = false: the yaw-momentum reference is the orientation correction amom[2] ori_correction[2], whatever w_des is (every turn
+// statement is discarded: the kernel of bmpc_plan_batch_device).  true: a problem with w_des != 0 gets yaw_inertia * w_des in X_nom[8::9]
+// and X_ter[8] (abstract_cyclic_gen.py:602-607); one with w_des == 0 is written as above.
+template <bool kTurn>
+__global__ void plan_costs_kernel(const bmpc_plan_batch_t d, const TurnCostArgs<kTurn> ta) {
     const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= d.B) return;
     const int H = d.n_col;
@@ -149,21 +165,33 @@ __global__ void plan_costs_kernel(const bmpc_plan_batch_t d) {
     const double am[3] = {d.amom ? d.amom[b * 3] : 0.0, d.amom ? d.amom[b * 3 + 1] : 0.0, d.amom ? d.amom[b * 3 + 2] : 0.0};
     double *Xn = d.X_nom + b * 9L * H, *Xt = d.X_ter + b * 9;
     double nx = x0[0], ny = 0.0;                               // X_nom[0::9] = X_init[0]; y starts at 0 (:574-577)
+    [[maybe_unused]] bool turning = false;
+    [[maybe_unused]] double lz = 0.0;
+    if constexpr (kTurn) {
+        const double w = d.w_des[b];
+        turning = w != 0.0;                                    // NaN != 0: a non-finite command gives a non-finite reference
+        lz = ta.yaw_inertia * w;                               // (I_composite_b [0, 0, w])[2]      (:604)
+    }
     for (int i = 0; i < H; ++i) {
         if (i > 0) { nx = nx + vd[0] * dt[i]; ny = ny + vd[1] * dt[i]; }
         double *r = Xn + 9L * i;
         r[0] = i == 0 ? x0[0] : nx; r[1] = i == 0 ? 0.0 : ny; r[2] = g.nom_ht;
         r[3] = vd[0]; r[4] = vd[1]; r[5] = vd[2];
         r[6] = am[0] * g.ori_correction[0]; r[7] = am[1] * g.ori_correction[1]; r[8] = am[2] * g.ori_correction[2];
+        if constexpr (kTurn) if (turning) r[8] = lz;
     }
     Xt[0] = x0[0] + g.gait_horizon * g.gait_period * vd[0];
     Xt[1] = x0[1] + g.gait_horizon * g.gait_period * vd[1];
     Xt[2] = g.nom_ht; Xt[3] = vd[0]; Xt[4] = vd[1]; Xt[5] = vd[2];
     Xt[6] = am[0]; Xt[7] = am[1]; Xt[8] = am[2];
+    if constexpr (kTurn) if (turning) Xt[8] = lz;
 }
 
-// whole-body front end: kinematics of x = [q, v] and the quantities the plan builders take
-__global__ void wb_state_kernel(const RobotModelDev *model, const bmpc_wb_plan_batch_t d) {
+// whole-body front end: kinematics of x = [q, v] and the quantities the plan builders take.  kTurn = false: w_des = 0 and
+// amom = log3(R_q^T) (bmpc_wb_plan_batch_device's kernel: every turn statement is discarded).  true: w_des[b] is the caller's command
+// and, where it is not 0, ori_des = q[3:7] (:636-639): R_des = Rz(yaw of R_q) and amom = log3(R_des R_q^T) (:585-591, 616-627).
+template <bool kTurn>
+__global__ void wb_state_kernel(const RobotModelDev *model, const bmpc_wb_plan_batch_t d, const TurnStateArgs<kTurn> ta) {
     const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= d.B) return;
     const double *x = d.x + b * kNX;
@@ -179,7 +207,9 @@ __global__ void wb_state_kernel(const RobotModelDev *model, const bmpc_wb_plan_b
     for (int j = 0; j < 4; ++j) for (int c = 0; c < 3; ++c) d.feet0[(b * 4 + j) * 3 + c] = p1.fx[j][c];
     const double *vb = d.v_des_body + b * 3;
     for (int c = 0; c < 3; ++c) d.v_des[b * 3 + c] = p1.Rb[3 * c] * vb[0] + p1.Rb[3 * c + 1] * vb[1] + p1.Rb[3 * c + 2] * vb[2];   // :642-643
-    d.w_des[b] = 0.0;
+    [[maybe_unused]] double wt = 0.0;
+    if constexpr (kTurn) { wt = ta.w_des[b]; d.w_des[b] = wt; }
+    else d.w_des[b] = 0.0;
     const double yaw = atan2(p1.Rb[3], p1.Rb[0]), cy = cos(yaw), sy = sin(yaw);    // matrixToRpy, roll = pitch = 0 (:173-177)
     for (int j = 0; j < 4; ++j) {
         const double ox = d.gait->offsets_xy[j][0], oy = d.gait->offsets_xy[j][1];
@@ -188,7 +218,15 @@ __global__ void wb_state_kernel(const RobotModelDev *model, const bmpc_wb_plan_b
     }
     double Rt[9], w[3];
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Rt[3 * i + j] = p1.Rb[3 * j + i];
-    rbd::log3(Rt, w);                                                              // log3(R_des R_q^T), R_des = I (:616-627)
+    if constexpr (kTurn) {
+        if (wt != 0.0) {                                                           // R_des = Rz(yaw): rows 0 and 1 of R_des R_q^T turn
+            for (int j = 0; j < 3; ++j) {
+                Rt[j] = cy * p1.Rb[3 * j] - sy * p1.Rb[3 * j + 1];
+                Rt[3 + j] = sy * p1.Rb[3 * j] + cy * p1.Rb[3 * j + 1];
+            }
+        }
+    }
+    rbd::log3(Rt, w);                                                              // log3(R_des R_q^T), R_des = I unless turning (:616-627)
     for (int c = 0; c < 3; ++c) d.amom[b * 3 + c] = w[c];
 }
 
@@ -258,6 +296,12 @@ void launch_plan_feet(const bmpc_plan_batch_t &p, const bmpc_terrain_t *t, doubl
     if (t) hipLaunchKernelGGL(plan_feet_kernel<true>, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, p, TerrainArgs<true>{*t, normals});
     else hipLaunchKernelGGL(plan_feet_kernel<false>, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, p, TerrainArgs<false>{});
 }
+// turn == nullptr: the cost references of the plain calls
+void launch_plan_costs(const bmpc_plan_batch_t &p, const bmpc_turn_t *turn, hipStream_t st) {
+    const dim3 grid((unsigned)((p.B + 255) / 256)), block(256);
+    if (turn) hipLaunchKernelGGL(plan_costs_kernel<true>, grid, block, 0, st, p, TurnCostArgs<true>{turn->yaw_inertia});
+    else hipLaunchKernelGGL(plan_costs_kernel<false>, grid, block, 0, st, p, TurnCostArgs<false>{});
+}
 }  // namespace
 
 // what the terrain entry points refuse of a bmpc_terrain_t (the heights themselves are device memory: not looked at)
@@ -273,8 +317,21 @@ int check_terrain(const bmpc_terrain_t *t) {
     return BMPC_OK;
 }
 
-int launch_wb_plan(const RobotModelDev *model, const bmpc_wb_plan_batch_t &d, const bmpc_terrain_t *t, double *normals, hipStream_t st) {
-    hipLaunchKernelGGL(wb_state_kernel, dim3((unsigned)((d.B + 63) / 64)), dim3(64), 0, st, model, d);
+// what the turn entry points refuse of a bmpc_turn_t (include/bunmpc_turn.h); wb: the whole-body call, which takes the commands from it
+int check_turn(const bmpc_turn_t *turn, bool wb) {
+    if (!std::isfinite(turn->yaw_inertia) || !(turn->yaw_inertia > 0.0)) return set_error(BMPC_BAD_ARG, "bmpc_turn_t.yaw_inertia must be finite and > 0");
+    if (wb && !turn->w_des) return set_error(BMPC_BAD_ARG, "the whole-body turn call needs the commands (bmpc_turn_t.w_des is NULL)");
+    if (!wb && turn->w_des)
+        return set_error(BMPC_BAD_ARG, "bmpc_turn_t.w_des must be NULL in the centroidal-level turn call: the yaw rate is bmpc_plan_batch_t.w_des");
+    return BMPC_OK;
+}
+
+// turn == nullptr: w_des = 0 (bmpc_wb_plan_batch_device, bmpc_wb_plan_batch_terrain_device)
+int launch_wb_plan(const RobotModelDev *model, const bmpc_wb_plan_batch_t &d, const bmpc_terrain_t *t, double *normals, const bmpc_turn_t *turn,
+                   hipStream_t st) {
+    const dim3 sgrid((unsigned)((d.B + 63) / 64)), sblock(64);
+    if (turn) hipLaunchKernelGGL(wb_state_kernel<true>, sgrid, sblock, 0, st, model, d, TurnStateArgs<true>{turn->w_des});
+    else hipLaunchKernelGGL(wb_state_kernel<false>, sgrid, sblock, 0, st, model, d, TurnStateArgs<false>{});
     bmpc_plan_batch_t p;
     p.B = d.B; p.n_col = d.n_col; p.n_gaits = 1; p.reserved_ = 0;
     p.gaits = d.gait; p.gait_id = nullptr;
@@ -282,7 +339,7 @@ int launch_wb_plan(const RobotModelDev *model, const bmpc_wb_plan_batch_t &d, co
     p.amom = d.amom; p.hip_off = d.hip_off;
     p.cnt_plan = d.cnt_plan; p.swing_time = d.swing_time; p.dt = d.dt; p.X_nom = d.X_nom; p.X_ter = d.X_ter;
     launch_plan_feet(p, t, normals, st);
-    hipLaunchKernelGGL(plan_costs_kernel, dim3((unsigned)((d.B + 255) / 256)), dim3(256), 0, st, p);
+    launch_plan_costs(p, turn, st);
     const long nt = (long)d.B * (d.ik_col + 1);
     hipLaunchKernelGGL(wb_tasks_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, d);
     const hipError_t e = hipGetLastError();
@@ -306,8 +363,8 @@ extern "C" int bmpc_interp_batch_device(const bmpc_interp_batch_t *d, void *hip_
 }
 
 namespace {
-// t == nullptr: flat ground (bmpc_plan_batch_device)
-int plan_batch(const bmpc_plan_batch_t *d, bool terrain, const bmpc_terrain_t *t, double *normals, void *hip_stream) {
+// t == nullptr: flat ground (bmpc_plan_batch_device); turn == nullptr: no yaw-momentum branch (the calls of bunmpc.h)
+int plan_batch(const bmpc_plan_batch_t *d, bool terrain, const bmpc_terrain_t *t, double *normals, const bmpc_turn_t *turn, void *hip_stream) {
     using namespace bunmpc;
     if (!d) return set_error(BMPC_BAD_ARG, "null plan descriptor");
     if (d->B < 0 || d->n_col < 1) return set_error(BMPC_BAD_ARG, "B < 0 or n_col < 1");
@@ -317,18 +374,26 @@ int plan_batch(const bmpc_plan_batch_t *d, bool terrain, const bmpc_terrain_t *t
     if (!d->cnt_plan || !d->swing_time || !d->dt || !d->X_nom || !d->X_ter) return set_error(BMPC_BAD_ARG, "missing output array");
     if (terrain)
         if (int rc = check_terrain(t)) return rc;
+    if (turn)
+        if (int rc = check_turn(turn, false)) return rc;
     if (d->B == 0) return BMPC_OK;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     launch_plan_feet(*d, t, normals, st);
-    hipLaunchKernelGGL(plan_costs_kernel, dim3((unsigned)((d->B + 255) / 256)), dim3(256), 0, st, *d);
+    launch_plan_costs(*d, turn, st);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error(BMPC_DEVICE_ERROR, std::string("plan kernels: ") + hipGetErrorString(e));
     return BMPC_OK;
 }
 }  // namespace
 
-extern "C" int bmpc_plan_batch_device(const bmpc_plan_batch_t *d, void *hip_stream) { return plan_batch(d, false, nullptr, nullptr, hip_stream); }
+extern "C" int bmpc_plan_batch_device(const bmpc_plan_batch_t *d, void *hip_stream) { return plan_batch(d, false, nullptr, nullptr, nullptr, hip_stream); }
 extern "C" int bmpc_plan_batch_terrain_device(const bmpc_plan_batch_t *d, const bmpc_terrain_t *t, double *normals, void *hip_stream) {
-    return plan_batch(d, true, t, normals, hip_stream);
+    return plan_batch(d, true, t, normals, nullptr, hip_stream);
 }
 extern "C" int bmpc_terrain_struct_size(void) { return (int)sizeof(bmpc_terrain_t); }
+// include/bunmpc_turn.h; a NULL terrain is flat ground here, and its normals are then not looked at
+extern "C" int bmpc_plan_batch_turn_device(const void *plan, const void *terrain, double *normals, const bmpc_turn_t *turn, void *hip_stream) {
+    return plan_batch(static_cast<const bmpc_plan_batch_t *>(plan), terrain != nullptr, static_cast<const bmpc_terrain_t *>(terrain),
+                      terrain ? normals : nullptr, turn, hip_stream);
+}
+extern "C" int bmpc_turn_struct_size(void) { return (int)sizeof(bmpc_turn_t); }

@@ -1,6 +1,7 @@
 """One device-resident pass of the reference's data generation, from nominal states to training rows:
 
-    nominal (q, v), t0, desired velocity
+    nominal (q, v), t0, desired velocity (and, with step(..., w_des=...), desired yaw rate: the turning commands of the reference's
+    sampler, utils.get_des_velocities)
       -> contact flags of the current knot                      (bmpc_wb_plan_batch_device, plan of the nominal state)
       -> contact-conditioned perturbation + foot-height rejection    (bmpc_perturb_batch_device; data_collection.py:188-262)
       -> plan inputs of the perturbed state, KinoDynMP.optimize, 1 kHz plan   (BatchedMpc; abstract_cyclic_gen.py:629-698)
@@ -41,8 +42,10 @@ class PlanLabelGenerator:
         self.rows_per_plan = int(round(planning_time / 0.001))
         self._nominal = None
 
-    def step(self, q_nom, v_nom, t0, v_des_body, generator=None, perturb=True, episode_length=None):
-        """q_nom (B,19), v_nom (B,18), t0 (B,), v_des_body (B,3): device tensors.  Returns device tensors
+    def step(self, q_nom, v_nom, t0, v_des_body, generator=None, perturb=True, episode_length=None, w_des=None):
+        """q_nom (B,19), v_nom (B,18), t0 (B,), v_des_body (B,3): device tensors.  w_des (B,): desired yaw rates, a device tensor --
+        they reach the nominal plan, the MPC call and the cc_goals, and fill vc_goals[:, :, 3] (the row is [phase, v_x, v_y, w_des, gait],
+        simulation.py:494); None: w_des = 0 everywhere, through the calls that take no command.  Returns device tensors
         states (B,R,43), actions (B,R,12), vc_goals (B,R,5), and q0 / v0 (the perturbed initial states), `rejected`
         (indices whose draws were all refused: those keep their nominal state).  With goal_horizon >= 1 also cc_goals
         (B,R,12 goal_horizon), goal_rows (B,) int32 -- rows of cc_goals[b] that hold goals, zeros behind them -- and goal_status (B,)
@@ -57,14 +60,14 @@ class PlanLabelGenerator:
             x = torch.cat([q_nom, v_nom], dim=1)
             x[:, 0:2] = 0.0
             if self._nominal is not None and self._nominal.B == B:
-                nominal = self._nominal.update(x, t0, v_des_body).build()
+                nominal = self._nominal.update(x, t0, v_des_body, w_des=w_des).build()
             else:
                 nominal = self._nominal = DeviceWbPlan(m.dm, m.gait, m.offsets_xy, m.wb.feet, m.ik, x, t0, v_des_body, m.H, m.T,
-                                                       device=m.device).build()
+                                                       device=m.device, w_des=w_des, yaw_inertia=m.yaw_inertia).build()
             q0, v0, rejected = self.sampler.sample(q_nom, v_nom, nominal.cnt_plan[:, 0, :, 0], generator=generator)
         else:
             q0, v0 = q_nom, v_nom
-        sol = m.optimize(torch.cat([q0, v0], dim=1), t0, v_des_body)
+        sol = m.optimize(torch.cat([q0, v0], dim=1), t0, v_des_body, w_des=w_des)
         R = min(self.rows_per_plan, int(sol["rows"].min()))
         xs = sol["xs_int"][:, :R].reshape(B * R, 37)
         us = sol["us_int"][:, :R].reshape(B * R, 18)
@@ -74,21 +77,24 @@ class PlanLabelGenerator:
         vc = torch.zeros((B, R, dataset.VC_GOAL_WIDTH), dtype=torch.float64, device=t0.device)
         vc[:, :, 0] = torch.remainder(t, self.gait.gait_period) / self.gait.gait_period
         vc[:, :, 1:3] = v_des_body[:, None, 0:2]
+        if w_des is not None:
+            vc[:, :, 3] = w_des[:, None]
         vc[:, :, 4] = dataset.GAIT_VALUE.get(self.gait.name, 0.0)
         res = dict(states=out["state"].reshape(B, R, 43), actions=out["action"].reshape(B, R, 12), vc_goals=vc, q0=q0, v0=v0,
                    rejected=rejected, solution=sol)
         if self.goal_horizon:
-            res.update(self._cc_goals(torch.cat([q0, v0], dim=1), t0, v_des_body, xs, R, int(episode_length or self.episode_length)))
+            res.update(self._cc_goals(torch.cat([q0, v0], dim=1), t0, v_des_body, xs, R, int(episode_length or self.episode_length), w_des))
         return res
 
-    def _cc_goals(self, x0, t0, v_des, xs, R, episode_length):
+    def _cc_goals(self, x0, t0, v_des, xs, R, episode_length, w_des=None):
         """planner-derived goals of the perturbed states: row r is step int(t0 / 0.001) + r, the step of states[:, r]"""
         import ctypes as C
         import torch
         from . import _lib
         from .cc_goal_batch import DeviceWbCcGoals
         m, B = self.mpc, x0.shape[0]
-        w_des = torch.zeros(B, dtype=torch.float64, device=x0.device)      # the data path: w_des = 0, as in vc_goals
+        if w_des is None:
+            w_des = torch.zeros(B, dtype=torch.float64, device=x0.device)      # no command: w_des = 0, as in vc_goals
         g = self._goals
         if g is not None and g.B == B and g.episode_length == episode_length:
             g.update(x0, t0, v_des, w_des)

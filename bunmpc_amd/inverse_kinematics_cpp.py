@@ -17,9 +17,10 @@ from . import _lib, urdf_model
 class DeviceModel:
     """bmpc_model_t built from a urdf_model.RobotModel (kept alive by whoever uses the handle)."""
 
-    def __init__(self, model):
+    def __init__(self, model, lib=None):
+        """lib: another build of the library with bunmpc.h's signatures on it (tools that time two builds side by side); None: this one"""
         self.model = model
-        lib = _lib.lib()
+        lib = _lib.lib() if lib is None else lib
         fr = list(model.frames.values())
         fbody = np.array([f[0] for f in fr], dtype=np.int32)
         fp = np.ascontiguousarray([f[2] for f in fr], dtype=np.float64)

@@ -6,11 +6,13 @@ resident from the raw states to the 1 kHz plans:
       -> bmpc_kinodyn_solve_batch_device   (centroidal ADMM + whole-body IK-DDP)
       -> bmpc_interp_batch_device    (xs_int, us_int, f_int)
 
-Everything in between stays in HBM; torch holds the memory and the stream.  w_des = 0 (the data path of the reference's
-data generation)."""
+Everything in between stays in HBM; torch holds the memory and the stream.  optimize(..., w_des=...) takes a desired yaw rate per
+robot (bmpc_wb_plan_batch_turn_device, include/bunmpc_turn.h: the reference's turning branch, centrifugal steps and yaw-momentum
+reference); without it w_des = 0, the straight-line commands of the reference's data generation."""
 import numpy as np
 
 from . import fk_np, problems
+from .cyclic_gen import composite_inertia_base
 from .inverse_kinematics_cpp import as_device_model
 from .kinodyn_batch import KinoDynDeviceBatch
 from .plan_batch import DeviceWbPlan, interpolate_on_device
@@ -39,10 +41,13 @@ class BatchedMpc:
         offs = np.round(fk_np.frame_positions(model, k0, wb.hips)[0] - k0["com"][0], 3)                     # :56-59
         offs[:, 1] += np.array([0.04, -0.04, 0.04, -0.04])                                                 # :61-72
         self.offsets_xy = offs[:, :2]
+        self.yaw_inertia = float(composite_inertia_base(model, wb.q0)[2, 2])                               # :48-49, :604
         self._kb = self._plan = None
 
-    def optimize(self, x, t0, v_des_body, same_rollouts=False):
-        """same_rollouts=True: this call replans the rollouts of the previous call with the same batch size (the reference keeps
+    def optimize(self, x, t0, v_des_body, same_rollouts=False, w_des=None):
+        """w_des (B,): desired yaw rates, numpy or device tensor (abstract_cyclic_gen.py:636-639, 602-607, 285-286); None: all zero,
+        through the call that takes no command.
+        same_rollouts=True: this call replans the rollouts of the previous call with the same batch size (the reference keeps
         one KinoDynMP per rollout, whose FISTA step constants persist from replan to replan: fista.hpp:52); False: B fresh
         rollouts (the data-generation passes).
         x (B,37), t0 (B,), v_des_body (B,3) numpy arrays or device tensors -> dict of device tensors: xs_int (B,R,37), us_int (B,R,18),
@@ -55,11 +60,11 @@ class BatchedMpc:
         if self._kb is not None and self._kb.wb.dyn.B == B:
             # same batch size as the last call: the plan tensors, the solver's workspace and its descriptors are reused
             plan, kb = self._plan, self._kb
-            plan.update(x, t0, v_des_body).build()
+            plan.update(x, t0, v_des_body, w_des=w_des).build()
             kb.carry_step_constants(same_rollouts)
         else:
             plan = DeviceWbPlan(self.dm, self.gait, self.offsets_xy, self.wb.feet, self.ik, x, t0, v_des_body, self.H, self.T,
-                                device=self.device, terrain=self.terrain).build()
+                                device=self.device, terrain=self.terrain, w_des=w_des, yaw_inertia=self.yaw_inertia).build()
             kb = KinoDynDeviceBatch(self._weights_only_batch(B), self.model, device=self.device, num_iters=self.dyn_iters, plan=plan,
                                     cone=self._cone_of(plan))
         kb.solve()

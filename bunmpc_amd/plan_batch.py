@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _lib_turn
 
 
 def gait_struct(gait, offsets_xy):
@@ -38,16 +38,25 @@ class DeviceTerrain:
         self.desc = t
 
 
+def _turn_call(fn, plan, stream):
+    """a call of include/bunmpc_turn.h for a DevicePlan / DeviceWbPlan: (descriptor, terrain or NULL, normals or NULL, turn, stream)"""
+    on = plan.terrain is not None
+    return fn(C.byref(plan.desc), C.byref(plan.terrain.desc) if on else None, C.c_void_p(plan.normals.data_ptr()) if on else None,
+              C.byref(plan.turn), C.c_void_p(stream))
+
+
 class DevicePlan:
     """Builds (and keeps) the plan tensors of one batch on `device`.  Inputs are numpy arrays or torch tensors:
     t0 (B,), com (B,3), feet0 (B,4,3), v_des (B,3), w_des (B,), x_init (B,9), optional amom (B,3), hip_off (B,4,2),
     gait_id (B,) into `gaits` (list of GaitParams with the robot's hip offsets).
     terrain: a terrain.HeightMap (uploaded once) -- the plan stands on it (bmpc_plan_batch_terrain_device) and `normals` (B, H, 4, 3),
     a device tensor, holds the terrain's unit normal under every knot's (x, y): DeviceBatch(cone=dict(..., normals=plan.normals))
-    takes it as it is.  None: flat ground (bmpc_plan_batch_device), no `normals`."""
+    takes it as it is.  None: flat ground (bmpc_plan_batch_device), no `normals`.
+    yaw_inertia: the turning harness' yaw-momentum reference (bmpc_plan_batch_turn_device, include/bunmpc_turn.h): a problem with
+    w_des != 0 gets X_nom[8::9] = X_ter[8] = yaw_inertia * w_des.  None: today's call, whose w_des only moves the steps."""
 
     def __init__(self, gaits, offsets_xy, H, t0, com, feet0, v_des, w_des, x_init, amom=None, hip_off=None, gait_id=None,
-                 device="cuda", terrain=None):
+                 device="cuda", terrain=None, yaw_inertia=None):
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("DevicePlan needs a GPU")
@@ -78,11 +87,14 @@ class DevicePlan:
         for k in ("cnt_plan", "swing_time", "dt", "X_nom", "X_ter"):
             setattr(d, k, getattr(self, k).data_ptr())
         self.desc = d
+        self.turn = None if yaw_inertia is None else _lib_turn.turn_struct(yaw_inertia)
 
     def build(self):
         """asynchronous on torch's current stream"""
         stream = self.torch.cuda.current_stream(self.device).cuda_stream
-        if self.terrain is None:
+        if self.turn is not None:
+            _lib.check(_turn_call(_lib_turn.lib().bmpc_plan_batch_turn_device, self, stream))
+        elif self.terrain is None:
             _lib.check(_lib.lib().bmpc_plan_batch_device(C.byref(self.desc), C.c_void_p(stream)))
         else:
             _lib.check(_lib.lib().bmpc_plan_batch_terrain_device(C.byref(self.desc), C.byref(self.terrain.desc), C.c_void_p(self.normals.data_ptr()),
@@ -94,9 +106,13 @@ class DeviceWbPlan:
     """Whole-body front end on the GPU (bmpc_wb_plan_batch_device): from states x = [q, v], times and body-frame
     desired velocities to the centroidal batch inputs and the IK task blocks, all left in HBM.  Device counterpart of
     problems.make_wb_batch (weights / regularisation references stay small host-provided arrays).  terrain: as for DevicePlan
-    (bmpc_wb_plan_batch_terrain_device; the via tasks keep the absolute step_ht, as in the reference)."""
+    (bmpc_wb_plan_batch_terrain_device; the via tasks keep the absolute step_ht, as in the reference).
+    w_des (B,): desired yaw rates, with yaw_inertia = composite_inertia_base(model, q0)[2, 2] (bmpc_wb_plan_batch_turn_device,
+    include/bunmpc_turn.h): what SoloMpcGaitGen.optimize does with w_des, problem by problem; a problem with w_des == 0 is planned as
+    without.  w_des=None: today's call (w_des = 0).  yaw_inertia alone keeps the plan ready for update(..., w_des=...)."""
 
-    def __init__(self, dev_model, gait, offsets_xy, feet, ik, x, t0, v_des_body, H, T, device="cuda", terrain=None):
+    def __init__(self, dev_model, gait, offsets_xy, feet, ik, x, t0, v_des_body, H, T, device="cuda", terrain=None, w_des=None,
+                 yaw_inertia=None):
         import torch
         self.torch, self.device = torch, torch.device(device)
         f64 = torch.float64
@@ -135,18 +151,39 @@ class DeviceWbPlan:
             setattr(d, k, getattr(self, k).data_ptr())
         self.desc = d
         self.dev_model = dev_model
+        # the commands live in a tensor of their own (bmpc_turn_t.w_des); self.w_des is the struct's intermediate the kernels fill
+        self.turn = self.w_cmd = None
+        if yaw_inertia is not None:
+            self.w_cmd = z(B).zero_()
+            self.turn = _lib_turn.turn_struct(yaw_inertia, self.w_cmd)
+        self._set_commands(w_des)
 
-    def update(self, x, t0, v_des_body):
-        """new states / times / desired velocities for the same batch size, copied into the tensors the descriptor points
-        at (nothing is allocated: the steady state of a generator that plans batch after batch)"""
+    def _set_commands(self, w_des):
+        """w_des=None: the next build() is today's call"""
+        self.turning = w_des is not None
+        if self.turning:
+            if self.turn is None:
+                raise ValueError("w_des needs yaw_inertia (DeviceWbPlan(..., yaw_inertia=...))")
+            torch = self.torch
+            src = w_des if isinstance(w_des, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(w_des), dtype=torch.float64)
+            if tuple(src.shape) != (self.B,):
+                raise ValueError("w_des: expected shape (%d,), got %r" % (self.B, tuple(src.shape)))
+            self.w_cmd.copy_(src)
+
+    def update(self, x, t0, v_des_body, w_des=None):
+        """new states / times / desired velocities (and yaw rates; None: w_des = 0, today's call) for the same batch size, copied
+        into the tensors the descriptor points at (nothing is allocated: the steady state of a generator that plans batch after batch)"""
         torch = self.torch
         for dst, src in ((self.x, x), (self.t0, t0), (self.v_des_body, v_des_body)):
             dst.copy_(src if isinstance(src, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(src), dtype=torch.float64))
+        self._set_commands(w_des)
         return self
 
     def build(self):
         stream = self.torch.cuda.current_stream(self.device).cuda_stream
-        if self.terrain is None:
+        if self.turning:
+            _lib.check(_turn_call(_lib_turn.lib().bmpc_wb_plan_batch_turn_device, self, stream))
+        elif self.terrain is None:
             _lib.check(_lib.lib().bmpc_wb_plan_batch_device(C.byref(self.desc), C.c_void_p(stream)))
         else:
             _lib.check(_lib.lib().bmpc_wb_plan_batch_terrain_device(C.byref(self.desc), C.byref(self.terrain.desc), C.c_void_p(self.normals.data_ptr()),

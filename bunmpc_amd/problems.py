@@ -72,6 +72,11 @@ TROT = GaitParams(
     np.array([1e-5, 1e-5, 1e5, 1e1, 1e1, 2e2, 1e4, 1e4, 1e4]),
     10 * np.array([1e5, 1e-5, 1e5, 1e1, 1e1, 2e2, 1e5, 1e5, 1e5]),
     np.array(4 * [1e1, 1e1, 1e1]), 0.2, step_ht=0.075, ori_correction=(0.3, 0.5, 0.4))
+# motions/cyclic/solo12_trot.py:46-74 (trot_turn): the second pair 0.4 of a period behind, one period of horizon (H = 10, H_ik = 5), no
+# roll correction; dataset.GAIT_VALUE has no entry for its name, so its gait value in vc_goals is that of an unknown gait
+TROT_TURN = GaitParams(
+    "trot_turn", 0.5, (0.6,) * 4, (0.0, 0.4, 0.4, 0.0), 1.0,
+    TROT.W_X.copy(), TROT.W_X_ter.copy(), TROT.W_F.copy(), 0.2, step_ht=0.05, ori_correction=(0.0, 0.5, 0.4))
 # motions/cyclic/solo12_bound.py:16-44
 BOUND = GaitParams(
     "bound", 0.3, (0.5,) * 4, (0.0, 0.0, 0.5, 0.5), 4.0,
@@ -498,6 +503,8 @@ GO2_WB = WholeBodyRobot("go2", GO2_Q0, ("FL_foot", "FR_foot", "RL_foot", "RR_foo
 TROT_IK = dict(state_wt=np.array([0., 0, 10] + [1000] * 3 + [1.0] * 12 + [0.] * 3 + [100] * 3 + [0.5] * 12),
                ctrl_wt=np.array([0, 0, 1000] + [5e2] * 3 + [1.0] * 12), swing_wt=(1e4, 1e4), cent_wt=(0.0, 5e2),
                reg_wt=(5e-2, 1e-5))
+# IK weights of the turning trot (motions/cyclic/solo12_trot.py:55-64): the yaw entries of state_wt 10 in place of 1000 and 100
+TROT_TURN_IK = dict(TROT_IK, state_wt=np.array([0., 0, 10] + [1000, 1000, 10] + [1.0] * 12 + [0.] * 3 + [100, 100, 10] + [0.5] * 12))
 
 
 @dataclass
@@ -528,18 +535,16 @@ def _log3_batch(R):
     return f[:, None] * v
 
 
-def make_wb_batch(model, B, first=0, seed=None, gait=TROT, ik=TROT_IK, ik_hor_ratio=0.5, wb=None, height_map=None):
+def make_wb_batch(model, B, first=0, seed=None, gait=TROT, ik=TROT_IK, ik_hor_ratio=0.5, wb=None, height_map=None, w_des=None):
     """Perturbed whole-body states and everything SoloMpcGaitGen.optimize hands to KinoDynMP
     (abstract_cyclic_gen.py:629-663): contact plan from the feet / CoM of (q, v), centroidal costs
     (create_costs :564-614) and the IK task list (:545-562).  Solo12 trot by default.  height_map: the terrain of the contact
-    plan (contact_plan explains it; kept in meta); the via-point height step_ht and nom_ht stay absolute, as in the reference."""
-    from . import fk_np
-    wb = SOLO12_WB if wb is None else wb
-    Q0, FEET, HIPS = wb.q0, wb.feet, wb.hips
+    plan (contact_plan explains it; kept in meta); the via-point height step_ht and nom_ht stay absolute, as in the reference.
+    w_des (B,): desired yaw rates.  A problem with w_des != 0 takes the reference's turning branch: centrifugal steps (:285-286),
+    ori_des = q[3:7] (:636-639) and the yaw-momentum reference yaw_inertia * w_des (:602-607), yaw_inertia =
+    composite_inertia_base(model, q0)[2, 2] (kept in meta); None or zeros: the arrays without it, bit for bit."""
+    Q0 = (SOLO12_WB if wb is None else wb).q0
     seed = BASE_SEED + 5 if seed is None else seed
-    H = gait.horizon
-    T = int(np.round(ik_hor_ratio * gait.gait_horizon * gait.gait_period / gait.gait_dt, 2))   # :128
-    E = 4
     u, nrm = _draws(seed, first, B, 48)
     # state perturbation in the tangent space of q0
     dq = np.zeros((B, 18))
@@ -559,6 +564,17 @@ def make_wb_batch(model, B, first=0, seed=None, gait=TROT, ik=TROT_IK, ik_hor_ra
     t0 = np.round(0.05 * np.floor(u[:, 0] * 10), 3)
     v_des_b = np.zeros((B, 3))
     v_des_b[:, 0] = 0.3 * u[:, 1]
+    return wb_batch_of_states(model, q, v, t0, v_des_b, gait, ik, ik_hor_ratio, wb, height_map, w_des, dict(seed=seed, first=first))
+
+
+def wb_batch_of_states(model, q, v, t0, v_des_b, gait=TROT, ik=TROT_IK, ik_hor_ratio=0.5, wb=None, height_map=None, w_des=None, meta=None):
+    """make_wb_batch for the caller's states q (B,19) (base x, y as SoloMpcGaitGen.optimize leaves them: 0), v (B,18), times t0 (B,)
+    and body-frame desired velocities v_des_b (B,3); meta: what the batch's meta should hold beside the inputs"""
+    from . import fk_np
+    wb = SOLO12_WB if wb is None else wb
+    Q0, FEET, HIPS = wb.q0, wb.feet, wb.hips
+    B, E, H = q.shape[0], 4, gait.horizon
+    T = int(np.round(ik_hor_ratio * gait.gait_horizon * gait.gait_period / gait.gait_dt, 2))   # :128
     kin = fk_np.kinematics(model, q, v)
     Rb = kin["oR"][0]
     v_des = np.einsum("bij,bj->bi", Rb, v_des_b)                    # :642-643
@@ -574,14 +590,26 @@ def make_wb_batch(model, B, first=0, seed=None, gait=TROT, ik=TROT_IK, ik_hor_ra
     com_xy = np.round(kin["com"][:, 0:2], 3)
     robot = RobotParams(wb.name, model.total_mass, fk_np.frame_positions(model, k0, FEET)[0][:, 0:2], offs[:, 0:2],
                         float(k0["com"][0, 2]))
-    cnt, swing, dt = contact_plan(gait, robot, H, t0, com_xy, kin["com"][:, 2], feet0, v_des, np.zeros(B), hip_off, height_map=height_map)
+    w_des = np.zeros(B) if w_des is None else np.array(w_des, dtype=np.float64).reshape(B)
+    turning = w_des != 0                                              # the reference's test (:603, :636): a NaN turns
+    cnt, swing, dt = contact_plan(gait, robot, H, t0, com_xy, kin["com"][:, 2], feet0, v_des, w_des, hip_off, height_map=height_map)
     x_init = np.concatenate([kin["com"], kin["vcom"], kin["L"]], axis=1)
     amom = _log3_batch(np.transpose(Rb, (0, 2, 1)))                   # log3(R_des R_q^T), R_des = I  (:616-627)
+    yaw_inertia = None
+    if turning.any():
+        from .cyclic_gen import composite_inertia_base
+        yaw_inertia = float(composite_inertia_base(model, Q0)[2, 2])  # rdata.Ycrb[1].inertia of q0 (:48-49)
+        z, o = np.zeros(B), np.ones(B)
+        R_des = np.stack([np.stack([cy, -sy, z], axis=1), np.stack([sy, cy, z], axis=1), np.stack([z, z, o], axis=1)], axis=1)   # :588-591
+        amom = np.where(turning[:, None], _log3_batch(R_des @ np.transpose(Rb, (0, 2, 1))), amom)
     X_nom, X_ter = centroidal_costs(gait, H, x_init, v_des, dt, amom)
+    if turning.any():                                                 # :602-607
+        X_nom[turning, 8::9] = (yaw_inertia * w_des[turning])[:, None]
+        X_ter[turning, 8] = yaw_inertia * w_des[turning]
     dyn = Batch(wb.name + "_" + gait.name + "_wb", B, H, E, model.total_mass, gait.rho, cnt, dt, x_init, X_nom, X_ter,
                 np.tile(gait.W_X, H)[None], gait.W_X_ter[None].copy(), np.tile(gait.W_F, H)[None],
                 np.tile(BOUNDS_TILE, (H, 1))[None], swing, np.zeros(B, dtype=np.int64), wb.mu,
-                dict(seed=seed, first=first, t0=t0, v_des=v_des, v_des_body=v_des_b, height_map=height_map))
+                dict(meta or {}, t0=t0, v_des=v_des, v_des_body=v_des_b, height_map=height_map, w_des=w_des, yaw_inertia=yaw_inertia))
     # IK task blocks: 4 x {w, frame, ref3} | com {w, ref3} | mom {w, ref6} | state w | ctrl w
     fid = tuple(model.frame_id(n) for n in FEET)
     tasks = np.zeros((B, T + 1, 33))
