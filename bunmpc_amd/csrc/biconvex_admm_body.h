@@ -319,13 +319,17 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
         return reinterpret_cast<double *>(zeros) + kLdsZeros + (long)(sg < 64 / LPP ? sg : 0) * (kSegLds + (long)(H + 1) * KL);
     };
     auto lds_fence = [&]() { asm volatile("" ::: "memory"); };       // (the compiler may not carry a parked value past this in a register)
+    // (CLDS: lane 0's stores too take the address from header(), not from Sg, which is a value of the whole kernel that hipcc reloads from
+    // scratch memory in front of every use -- see "phase prologues" below)
     auto park_x = [&]() {      // before the force loop: everything the motion step and the end of the ADMM iteration work on
-        if (l0) { double *Hd = reinterpret_cast<double *>(Sg); int *Hi = reinterpret_cast<int *>(Hd + 12);      // (lane 0's record starts at the header)
+        if (l0) { double *Hd; if constexpr (C::CLDS) Hd = header(); else Hd = reinterpret_cast<double *>(Sg);      // (lane 0's record starts at the header)
+                  int *Hi = reinterpret_cast<int *>(Hd + 12);
                   Hd[9] = (double)L_x; Hd[11] = last_viol; Hi[0] = it_x; Hi[1] = bt_x; Hi[2] = n_admm; Hi[3] = status; }
         lds_fence();
     };
     auto park_f = [&]() {      // before the motion step: what the force loop works on
-        if (l0) { double *Hd = reinterpret_cast<double *>(Sg); int *Hi = reinterpret_cast<int *>(Hd + 12); Hd[10] = (double)L_f; Hi[4] = it_f; Hi[5] = bt_f; }
+        if (l0) { double *Hd; if constexpr (C::CLDS) Hd = header(); else Hd = reinterpret_cast<double *>(Sg);
+                  int *Hi = reinterpret_cast<int *>(Hd + 12); Hd[10] = (double)L_f; Hi[4] = it_f; Hi[5] = bt_f; }
         lds_fence();
     };
     auto load_xloop = [&]() {      // in front of the motion loop
@@ -357,6 +361,20 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
     [[maybe_unused]] auto knot_record = [&]() {      // (Xg, made again where a store needs it, as header() is: held across a loop it is one register too many)
         const unsigned ln = opaque_copy(lane_id());
         return reinterpret_cast<R *>(lds_raw) + kLdsZeros + (long)(ln / (unsigned)LPP) * (kSegLds + (long)(H + 1) * KL) + (long)(ln % (unsigned)LPP) * KL + kSegLds;
+    };
+    // CLDS, phase prologues (everything of the ADMM iteration outside the FISTA loops: DESIGN.md section 4, "Phase prologues").  The blocks of
+    // the lane's record are read there UNCONDITIONALLY, as one batch per block behind one wait (lds_block, biconvex_lanes.h), from one
+    // address per region of the code, made in that region: record_or_front.  Written as `kvalid ? Xg[l] : 0` every element was an
+    // exec-masked block of its own that first reloaded the record's address from scratch memory and waited for it (about 140 dependent
+    // round trips per ADMM iteration).  A lane in `own` gets its record (its X block; P, F, R behind it as in Xg); a lane outside reads
+    // at the front of LDS, where consts_offset sends its idle lanes: element (its record's element index) mod 32, so the lanes of a
+    // segment stay on 32 different bank pairs.  What it finds there -- zeros, then the first problem's header: at most element
+    // 31 + 18 + NF < kLdsZeros + kSegLds -- is never used: every block read this way goes through a select on the lane's own predicate.
+    static_assert(!CLDS || 31 + 18 + NF <= kLdsZeros + kSegLds, "lanes without a knot read inside the wave's LDS");
+    [[maybe_unused]] auto record_or_front = [&](mask_t own) {
+        const unsigned ln = opaque_copy(lane_id());
+        const unsigned e = (unsigned)(kLdsZeros + kSegLds) + ln / (unsigned)LPP * (unsigned)(kSegLds + (H + 1) * KL) + ln % (unsigned)LPP * (unsigned)KL;
+        return reinterpret_cast<R *>(reinterpret_cast<char *>(lds_raw) + 8u * (lanes(own) ? e : e & 31u));
     };
     // the problem `sl` names (every offset set) comes on chip: step constants, iterates, counters (lanes of the segments in m)
     auto load_problem = [&](mask_t m) {
@@ -449,6 +467,10 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
     // phase, in front of its FISTA loop; written out once, behind the last ADMM iteration.
     [[maybe_unused]] int *const certn = reinterpret_cast<int *>(Sg + kSegLds + (long)H * KL + 18);      // (lane 0's: its record is the segment's first)
     if constexpr (BAND) { if (l0) { certn[0] = 0; certn[1] = 0; } }
+    [[maybe_unused]] auto cert_count = [&]() -> int * {      // certn where a phase counts (CLDS: from header(), see "phase prologues")
+        if constexpr (CLDS) return reinterpret_cast<int *>(header() + kSegLds + (long)H * KL + 18);
+        else return certn;
+    };
 
     for (int it = 0; STEAL || it < a.c.num_iters; ++it) {
         if (alive == 0) break;
@@ -471,7 +493,16 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                 UNROLL for (int k = 0; k < 3; ++k) r[n][k] = ldz<R>(cnt_u, oC + ph, 4 * n + 1 + k, rvalid);
             }
             R X[9];
+            [[maybe_unused]] R *rec = nullptr;      // CLDS: the lane's record, or the front of LDS (see "phase prologues"): this prologue's one address
+            [[maybe_unused]] R Pv[CLDS ? 6 : 1], F0[CLDS ? NF : 1];
+            if constexpr (CLDS) {
+                rec = record_or_front(kvalid_m);
+                lds_block(rec, X, kvalid);
+                lds_batch(rec + 9 + 3, Pv);      // (selected with the sum it enters, below)
+                lds_block(rec + 18, F0, rvalid);
+            } else {
             UNROLL for (int l = 0; l < 9; ++l) X[l] = kvalid ? Xg[l] : R(0);
+            }
             // bPk rows 9t+3..8 = -b_x + P, b_x = X_{t+1} - X_t (+g dt)   (centroidal.cpp:60-65)
             R bpk[6], Xv[6], Xvn[6];
             UNROLL for (int k = 0; k < 6; ++k) Xv[k] = X[3 + k];
@@ -480,7 +511,8 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                 const R xn = Xvn[k];
                 R bx = xn - X[3 + k];
                 if (k == 2) bx += R(kGravity) * dt;
-                bpk[k] = rvalid ? (-bx + Pg[3 + k]) : R(0);
+                if constexpr (CLDS) bpk[k] = rvalid ? (-bx + Pv[k]) : R(0);
+                else bpk[k] = rvalid ? (-bx + Pg[3 + k]) : R(0);
             }
             // A_x entries of this knot (centroidal.cpp:67-81)
             R an[E], sp[E][3];
@@ -552,12 +584,14 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                     const double v[3] = {a0 * u[0] + s2 * u[4] + s1 * u[5], a0 * u[1] + s2 * u[3] + s0 * u[5], a0 * u[2] + s1 * u[3] + s0 * u[4]};
                     UNROLL for (int k = 0; k < 3; ++k) ok = ok && (double)wf[3 * n + k] * dg[3 * n + k] + (double)rho * v[k] <= T * dg[3 * n + k];
                 }
+                if constexpr (CLDS) { UNROLL for (int j = 0; j < NF; ++j) x2 += (double)F0[j] * (double)F0[j]; }      // (a lane without forces: exact zeros, x2 stays +0.0)
+                else
                 if (rvalid) { UNROLL for (int j = 0; j < NF; ++j) x2 += (double)Fg[j] * (double)Fg[j]; }      // (x_0: the F block)
                 UNROLL for (int k = 0; k < 6; ++k) b2 += (double)bpk[k] * (double)bpk[k];
                 cert = certify(ok, alive);
                 if (cert) floor2 = cert_floor(b2 + (T / (double)rho) * x2, Lh0, alive);
             }
-            if constexpr (BAND) { if (cert && l0 && lanes(alive)) ++certn[0]; }
+            if constexpr (BAND) { if (cert && l0 && lanes(alive)) ++cert_count()[0]; }
             // u = A v + bPk on rows 9t+3..8
             auto applyA = [&](const R (&v)[NF], R (&u)[6]) {
                 R s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0;
@@ -575,9 +609,12 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
             // FISTA state.  x lives in two buffers (xa/xb, A-images ra/rb) whose roles swap every
             // iteration, so "x_k = x_k_1" (fista.cpp:37) costs no register moves.
             R xa[NF], xb[NF], y[NF], ra[6], rb[6], ry[6];
-            UNROLL for (int j = 0; j < NF; ++j) { xa[j] = rvalid ? Fg[j] : R(0); y[j] = xa[j]; }
+            if constexpr (CLDS) { UNROLL for (int j = 0; j < NF; ++j) { xa[j] = F0[j]; y[j] = xa[j]; } }
+            else { UNROLL for (int j = 0; j < NF; ++j) { xa[j] = rvalid ? Fg[j] : R(0); y[j] = xa[j]; } }
             applyA(y, ry);
             UNROLL for (int k = 0; k < 6; ++k) ra[k] = ry[k];
+            if constexpr (CLDS) { if (rvalid) { UNROLL for (int k = 0; k < 6; ++k) rec[18 + NF + k] = ry[k]; } }
+            else
             if (XLDS && rvalid) { UNROLL for (int k = 0; k < 6; ++k) Rg[k] = ry[k]; }      // (x_0 itself is in the F block already)
             const R mu2 = mu * mu, imu = R(1) / (mu * mu + R(1));
             const double tol2 = tol * tol;
@@ -1090,12 +1127,14 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
             }
             // A_f / b_f entries of this knot from the new forces (centroidal.cpp:86-127)
             R SX = 0, SY = 0, SZ = 0, bf[9];
-            auto make_bf = [&](const R (&cc)[E], const R (&rr)[E][3], R (&b)[9], R &sx, R &sy, R &sz) {
+            // (CLDS: the forces come as fv, the F block read in one batch by the caller -- see "phase prologues")
+            auto make_bf = [&](const R (&cc)[E], const R (&rr)[E][3], R (&b)[9], R &sx, R &sy, R &sz, [[maybe_unused]] const R *fv) {
                 R b3 = 0, b4 = 0, b5 = 0, b6 = 0, b7 = 0, b8 = 0;
                 sx = 0; sy = 0; sz = 0;
                 UNROLL for (int n = 0; n < E; ++n) {
-                    const R fx = rvalid ? Fg[3 * n] : R(0), fy = rvalid ? Fg[3 * n + 1] : R(0),
-                            fz = rvalid ? Fg[3 * n + 2] : R(0);
+                    R fx, fy, fz;
+                    if constexpr (CLDS) { fx = fv[3 * n]; fy = fv[3 * n + 1]; fz = fv[3 * n + 2]; }
+                    else { fx = rvalid ? Fg[3 * n] : R(0); fy = rvalid ? Fg[3 * n + 1] : R(0); fz = rvalid ? Fg[3 * n + 2] : R(0); }
                     sx += cc[n] * fx * dt; sy += cc[n] * fy * dt; sz += cc[n] * fz * dt;
                     b3 += -cc[n] * fx * dt / m; b4 += -cc[n] * fy * dt / m; b5 += -cc[n] * fz * dt / m;
                     b6 += (cc[n] * fy * rr[n][2] - cc[n] * fz * rr[n][1]) * dt;
@@ -1106,9 +1145,19 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                 b[3] = b3; b[4] = b4; b[5] = b5 + R(kGravity) * dt;
                 b[6] = b6; b[7] = b7; b[8] = b8;
             };
-            make_bf(c, r, bf, SX, SY, SZ);
+            [[maybe_unused]] R *rec = nullptr;      // CLDS: this prologue's one address of the lane's record (see "phase prologues")
+            [[maybe_unused]] R Fv[CLDS ? NF : 1], Pv[CLDS ? 9 : 1];
+            if constexpr (CLDS) {
+                rec = record_or_front(kvalid_m);
+                lds_block(rec + 18, Fv, rvalid);
+                lds_batch(rec + 9, Pv);      // (selected with the sum it enters, below)
+            }
+            make_bf(c, r, bf, SX, SY, SZ, Fv);
             R bpk[9];
-            UNROLL for (int l = 0; l < 9; ++l) bpk[l] = rvalid ? (-bf[l] + Pg[l]) : R(0);
+            UNROLL for (int l = 0; l < 9; ++l) {
+                if constexpr (CLDS) bpk[l] = rvalid ? (-bf[l] + Pv[l]) : R(0);
+                else bpk[l] = rvalid ? (-bf[l] + Pg[l]) : R(0);
+            }
             // cost and bounds of this knot
             R qd[9], q[9], lb[NB], ub[NB];
             if (RAW) {
@@ -1152,10 +1201,18 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
             // x_init rows folded into lane 0's diagonal cost:  rho |X_0 + (P_H - x_init)|^2   (q holds q/2: half-gradient form,
             // see the force step)
             R pi[9];
+            [[maybe_unused]] R xi9[CLDS ? 9 : 1];
+            if constexpr (CLDS) {      // the segment's header holds the x_init rows' multipliers: one address for all its lanes, read by all, kept by lane 0;
+                lds_block(header(), pi, l0);      // x_init likewise, as one batch of loads (as `l0 ? pi - xi : 0` alone: nine masked loads, each waited for)
+                UNROLL for (int l = 0; l < 9; ++l) xi9[l] = (R)at(xinit_u, o.P9 + ph)[l];
+                keep_here(xi9);
+            } else {
             UNROLL for (int l = 0; l < 9; ++l) pi[l] = R(0);
             if (l0) { UNROLL for (int l = 0; l < 9; ++l) pi[l] = PIg[l]; }
+            }
             UNROLL for (int l = 0; l < 9; ++l) {
-                const R xi = (R)at(xinit_u, o.P9 + ph)[l];
+                R xi;
+                if constexpr (CLDS) xi = xi9[l]; else xi = (R)at(xinit_u, o.P9 + ph)[l];
                 const R bpi = l0 ? (pi[l] - xi) : R(0);
                 qd[l] += l0 ? rho : R(0);
                 q[l] = fmaR(rho, bpi, q[l]);
@@ -1207,9 +1264,12 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
             };
 
             R xa[9], xb[9], y[9], ra[9], rb[9], ry[9];
-            UNROLL for (int l = 0; l < 9; ++l) { xa[l] = kvalid ? Xg[l] : R(0); y[l] = xa[l]; }
+            if constexpr (CLDS) { lds_block(rec, xa, kvalid); UNROLL for (int l = 0; l < 9; ++l) y[l] = xa[l]; }
+            else { UNROLL for (int l = 0; l < 9; ++l) { xa[l] = kvalid ? Xg[l] : R(0); y[l] = xa[l]; } }
             applyA(y, ry);
             UNROLL for (int l = 0; l < 9; ++l) ra[l] = ry[l];
+            if constexpr (CLDS) { if (kvalid) { UNROLL for (int l = 0; l < 9; ++l) rec[18 + NF + l] = ry[l]; } }
+            else
             if (XLDS && kvalid) { UNROLL for (int l = 0; l < 9; ++l) Rg[l] = ry[l]; }
             const double tol2 = tol * tol;
             if (PARK) load_xloop();
@@ -1373,12 +1433,14 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                     v[2] += ay * u[6] + ax * u[7];
                     bool ok = true;
                     UNROLL for (int l = 0; l < 9; ++l) ok = ok && (double)qd[l] * dg[l] + (double)rho * v[l] <= T * dg[l];
+                    if constexpr (CLDS) { UNROLL for (int l = 0; l < 9; ++l) x2 += (double)xa[l] * (double)xa[l]; }      // (x_0, still in xa; a lane without a knot: exact zeros)
+                    else
                     if (kvalid) { UNROLL for (int l = 0; l < 9; ++l) x2 += (double)Xg[l] * (double)Xg[l]; }      // (x_0: the X block)
                     UNROLL for (int l = 0; l < 9; ++l) b2 += (double)bpk[l] * (double)bpk[l];
                     cert = certify(ok, alive);
                     if (cert) floor2 = cert_floor(b2 + (T / (double)rho) * x2, Lh0, alive);
                 }
-                if (cert && l0 && lanes(alive)) ++certn[1];
+                if (cert && l0 && lanes(alive)) ++cert_count()[1];
                 float flo = 0.0f, fhi = 0.0f;
                 if (banded != 0) band_u(floor2, flo, fhi);
                 const double theta = cert && a.exact_step_decisions == 0 ? screen_theta(tol2, floor2) : __builtin_inf();      // (see the force step)
@@ -1644,7 +1706,15 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
             }
             }
             R fin[9];
+            [[maybe_unused]] R *rec2 = nullptr;      // CLDS: the record's address again, for what follows the loops (not held across them)
+            [[maybe_unused]] R Fv2[CLDS ? NF : 1];
+            if constexpr (CLDS) {
+                rec2 = record_or_front(kvalid_m);
+                lds_block(rec2, fin, kvalid);
+                lds_block(rec2 + 18, Fv2, rvalid);
+            } else {
             UNROLL for (int l = 0; l < 9; ++l) fin[l] = kvalid ? Xg[l] : R(0);
+            }
             if (PARK) load_rest();
             if (XLDS) {     // b_f made again from the contact plan and the forces (same expressions, same bits) instead of six registers held
                             // across the FISTA loop -- which the 256-register build held in scratch memory
@@ -1654,7 +1724,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                     c2[n] = ldz<R>(cnt_u, oC + ph2, 4 * n, rvalid);
                     UNROLL for (int k = 0; k < 3; ++k) r2[n][k] = ldz<R>(cnt_u, oC + ph2, 4 * n + 1 + k, rvalid);
                 }
-                make_bf(c2, r2, bf, s0, s1, s2);
+                make_bf(c2, r2, bf, s0, s1, s2, Fv2);
             }
 
             // dyn_violation = A_f X - b_f ; P += dyn_violation          (biconvex.cpp:98-99)
@@ -1669,15 +1739,31 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                 w[8] += SX * fin[1] - SY * fin[0];
                 const bool al = lanes(alive);
                 R dr[9], dx0[9];
+                [[maybe_unused]] R xi9[CLDS ? 9 : 1];
+                if constexpr (CLDS) {      // (x_init as one batch of loads: see the prologue)
+                    const unsigned ph3 = opaque_zero();
+                    UNROLL for (int l = 0; l < 9; ++l) xi9[l] = (R)at(xinit_u, o.P9 + ph3)[l];
+                    keep_here(xi9);
+                }
                 UNROLL for (int l = 0; l < 9; ++l) {
                     const R d = rvalid ? (w[l] - bf[l]) : R(0);
-                    const R xi = (R)at(xinit_u, o.P9 + ph)[l];
+                    R xi;
+                    if constexpr (CLDS) xi = xi9[l]; else xi = (R)at(xinit_u, o.P9 + ph)[l];
                     const R di = l0 ? (fin[l] - xi) : R(0);
                     dr[l] = d; dx0[l] = di;
+                    // (CLDS: the sum as every build has compiled it, spelled out -- d d + (di di) with the first product fused; left to the
+                    // compiler's contraction, the straight-line form of this block fused the other product: 1 ulp in dyn_viol)
+                    if constexpr (CLDS) v2 += __builtin_fma((double)d, (double)d, (double)di * (double)di);
+                    else
                     v2 += (double)d * (double)d + (double)di * (double)di;
                 }
+                if constexpr (CLDS) {      // (the multipliers' read-modify-write stays under its masks, one region per block)
+                    if (al && rvalid) { UNROLL for (int l = 0; l < 9; ++l) rec2[9 + l] += dr[l]; }
+                    if (al && l0) { double *Hs = header(); UNROLL for (int l = 0; l < 9; ++l) Hs[l] += dx0[l]; }
+                } else {
                 if (al && rvalid) { UNROLL for (int l = 0; l < 9; ++l) Pg[l] += dr[l]; }
                 if (al && l0) { UNROLL for (int l = 0; l < 9; ++l) PIg[l] += dx0[l]; }
+                }
             }
             if (MW) { double z2 = 0.0; sum2(v2, z2); } else v2 = seg_sum<LPP>(v2);
             const double nrm = sqrt(v2);
@@ -1717,6 +1803,28 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
             }
         }
     }
+    if constexpr (CLDS) {     // ---- results, with the record's address and the offsets made here (held from the kernel's start they are registers -- or scratch reloads -- of every phase)
+        const R *re = record_or_front(kvalid_m);
+        const double *He = header();
+        const unsigned sle = opaque_copy(sl);
+        const Off oe = make_off(sle);
+        if (kvalid) { UNROLL for (int l = 0; l < 9; ++l) at(Xu, oe.X)[l] = (double)re[l]; }
+        if (rvalid) {
+            UNROLL for (int j = 0; j < NF; ++j) at(Fu, oe.F)[j] = (double)re[18 + j];
+            UNROLL for (int l = 0; l < 9; ++l) at(Pu, oe.X)[l] = (double)re[9 + l];
+        }
+        if (l0) { UNROLL for (int l = 0; l < 9; ++l) at(Pu, oe.PI)[l] = (double)He[l]; }
+        if (l0) {
+            *at(a.L_x + wave0, 8u * sle) = (double)L_x;
+            *at(a.L_f + wave0, 8u * sle) = (double)L_f;
+            if (a.dyn_viol) *at(a.dyn_viol + wave0, 8u * sle) = last_viol;
+            if (a.stats) {
+                int *s = a.stats + (wave0 + sle) * kStats;
+                s[0] = n_admm; s[1] = it_f; s[2] = it_x; s[3] = bt_f; s[4] = bt_x; s[5] = status;
+            }
+            if (a.cert_phases) { int *o = a.cert_phases + (wave0 + sle) * 2; const int *cn = cert_count(); o[0] = cn[0]; o[1] = cn[1]; }
+        }
+    } else
     if (!STEAL) {     // ---- results: one pass from LDS to the output blocks
         if (kvalid) { UNROLL for (int l = 0; l < 9; ++l) at(Xu, oX)[l] = (double)Xg[l]; }
         if (rvalid) {

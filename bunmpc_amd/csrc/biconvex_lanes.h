@@ -291,6 +291,18 @@ __device__ __forceinline__ void keep_here(double (&v)[9]) {
 __device__ __forceinline__ void keep_here(double (&v)[12]) {
     asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]));
 }
+// N consecutive doubles at p, read UNCONDITIONALLY, in straight-line code, and waited for once (keep_here on the whole array): every lane's
+// p names memory it may read.  What a lane has no business with is replaced behind the read -- lds_block: by +0.0, a select, which also
+// wipes the NaN of somebody else's record (a multiply by 0 / 1 would not).  Written as `ok ? p[l] : 0` hipcc makes an exec-masked block
+// per element, each with its own address reload and its own wait (the loop-constants build's phase prologues).
+template <int N> __device__ __forceinline__ void lds_batch(const double *p, double (&v)[N]) {
+    UNROLL for (int l = 0; l < N; ++l) v[l] = p[l];
+    keep_here(v);
+}
+template <int N> __device__ __forceinline__ void lds_block(const double *p, double (&v)[N], bool ok) {
+    lds_batch(p, v);
+    UNROLL for (int l = 0; l < N; ++l) v[l] = ok ? v[l] : 0.0;
+}
 // HBM holds fp64 whatever the arithmetic type R of the kernel; conversion happens at the load / store
 // (the constant element index stays outside the 32-bit offset: it folds into the instruction's immediate)
 // The load is UNCONDITIONAL (the caller's offset names an existing element in every lane); `ok` only decides what is kept.
