@@ -22,8 +22,12 @@
 // -- the ADMM's early exit (biconvex.cpp:111-114) makes the iteration counts differ per problem: 34 .. 100 at num_iters = 100 --
 // stores its results and takes the next unsolved problem from a device counter, instead of idling until the slowest problem of its
 // wave is done (a wave's time was the MAXIMUM over its three problems; the batch's now approaches the SUM over all problems / the
-// number of segments).  The arithmetic of a problem does not depend on which segment runs it, or when.  Addresses in this mode are
-// the arrays' own bases + 32-bit byte offsets from the problem index (the host checks that they fit).
+// number of segments).  The ITERATES of a problem do not depend on which segment runs it, or when: X, F, P, the step constants and every
+// count are the same bits.  Its segment SUMS do: a 21-lane segment lies across the DPP rows 16|5, 11|10 or 6|15 by its position in the wave,
+// so its terms are added in another order, within 2 gamma_6 of each other (gamma_6 = 6u / (1 - 6u), u = 2^-53) -- which shows in the reported
+// violation and its history, and could flip a step decision whose sum lies within that of its threshold
+// (tests/test_biconvex_gpu.py::test_result_does_not_depend_on_the_segment holds both; tests/test_lane_probe_gpu.py pins the three orders).
+// Addresses in this mode are the arrays' own bases + 32-bit byte offsets from the problem index (the host checks that they fit).
 //
 // XLDS (round 4; the build for TWO waves per SIMD, 256 registers): the FISTA loops keep y and its image in registers only; x_k and
 // ITS image rest in LDS (the problem's X / F block and an R block beside them).  An iteration reads them once -- while the segment

@@ -237,6 +237,10 @@ int set_certified_steps(int on);                     // the fp64 batch kernels' 
 // Lane-exchange self test (DPP shifts and segment sums used by the kernel).
 // out must hold 12*64 doubles.
 hipError_t launch_lane_selftest(const double *in, double *out, hipStream_t stream);
+// The lane-helper probe (lane_probe.hip; bmpc_probe_lanes): rows of 64 words a wave of `group` reads and writes (false: no such group), and
+// the launch of `waves` waves on device arrays of waves * nin * 64 and waves * nout * 64 words.
+bool lane_probe_words(int group, int *nin, int *nout);
+hipError_t launch_lane_probe(int group, const unsigned long long *in, unsigned long long *out, long waves, hipStream_t stream);
 
 // Name of the kernel symbol for a given H (for profiling / bench reports).
 const char *biconvex_kernel_name(int H, int raw);

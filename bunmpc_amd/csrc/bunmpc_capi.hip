@@ -370,6 +370,26 @@ int bmpc_selftest_lanes(void) {
     return BMPC_OK;
 }
 
+int bmpc_probe_lanes(int group, const void *in, long in_bytes, void *out, long out_bytes) {
+    int nin = 0, nout = 0;
+    if (!bunmpc::lane_probe_words(group, &nin, &nout)) return fail(BMPC_BAD_ARG, "no such group of lane helpers (BMPC_PROBE_*)");
+    if (!in || !out) return fail(BMPC_BAD_ARG, "null array");
+    const long wave_in = 512L * nin, wave_out = 512L * nout;      // (64 words of 8 bytes per row)
+    if (in_bytes < wave_in || in_bytes % wave_in != 0 || in_bytes / wave_in > (1L << 20))
+        return fail(BMPC_BAD_ARG, "in_bytes is not 1 .. 2^20 waves of this group's " + std::to_string(nin) + " rows of 64 words");
+    const long waves = in_bytes / wave_in;
+    if (out_bytes != waves * wave_out)
+        return fail(BMPC_BAD_ARG, "out_bytes is not " + std::to_string(waves) + " waves of this group's " + std::to_string(nout) + " rows of 64 words");
+    DevBuf b;
+    HIP_TRY(b.ensure((size_t)in_bytes + (size_t)out_bytes));
+    unsigned long long *din = static_cast<unsigned long long *>(b.p), *dout = din + in_bytes / 8;
+    HIP_TRY(hipMemcpy(din, in, (size_t)in_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dout, 0, (size_t)out_bytes));
+    HIP_TRY(bunmpc::launch_lane_probe(group, din, dout, waves, nullptr));
+    HIP_TRY(hipMemcpy(out, dout, (size_t)out_bytes, hipMemcpyDeviceToHost));
+    return BMPC_OK;
+}
+
 // ------------------------------------------------------------------- gait ----
 bmpc_gait_t *bmpc_gait_create(double gait_period, const double *stance_percent,
                               const double *phase_offset, int n_eff, double step_height) {

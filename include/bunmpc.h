@@ -36,6 +36,33 @@ int bmpc_device_count(int *count);           /* hipGetDeviceCount               
 int bmpc_set_device(int device);             /* hipSetDevice for the calling thread      */
 /* DPP / permlane self test of the lane exchanges the kernels rely on; 0 = pass.     */
 int bmpc_selftest_lanes(void);
+/* TEST ONLY.  The lane helpers of the centroidal kernels (bunmpc_amd/csrc/biconvex_lanes.h) called on the caller's inputs, one group of
+ * helpers per call, so that a test can hold each to a model bit for bit (tests/lanes_np.py).  in / out are HOST arrays of 64-bit
+ * words.  A wave of 64 lanes is one test case: in is [waves][NIN][64], out is [waves][NOUT][64], word [w][k][lane]; a double is its bit
+ * pattern, a float or a 32-bit integer sits in the low half of its word (high half: ignored in, zero out), a flag is 0 / 1.
+ * in_bytes = waves * NIN * 512 with waves in 1 .. 2^20, out_bytes = waves * NOUT * 512.  An unknown group, a null pointer or sizes that
+ * do not fit the group's layout: BMPC_BAD_ARG, before any device call.  "lane 0's" below: the scalar is read from word [w][k][0].
+ *   SUM64 (NIN 2: a, b doubles; NOUT 16): for L = 16, 21, 32, 64, at out 4 i .. 4 i + 3: seg_sum<L>(a); seg_sum2<L>(a, b)'s two results;
+ *       seg_sum1<L>(a).  (L = 21: the last three are meaningful at lanes 16, 32, 48 only.)
+ *   SUM32 (NIN 2: a, b floats; NOUT 9): for L = 16, 32, 64, at out 3 i .. 3 i + 2: seg_sum2_f32<L>(a, b)'s two results; seg_sum1_f32<L>(a).
+ *   SHIFT (NIN 2: a double, a float; NOUT 4): from_prev, from_next of the double; from_prev, from_next of the float.
+ *   MASK  (NIN 2: lane 0's masks m, need; NOUT 9, wave-uniform but for out 7): seg_uniform<21>(m & seg_desig<21>()); seg_covered<16>,
+ *       <32>, <64>(m, need) as flags; d0, d1 of seg_dead32(need); seg_covered32(m, d0, d1); out 7: lanes(m) as the lane's flag; the
+ *       ballot of lanes(m).
+ *   THETA (NIN 2: tol2, floor2 doubles; NOUT 1): lane j's word is screen_theta(tol2[j], floor2[j]) -- 64 wave-uniform evaluations.
+ *   ARITH (NIN 7: doubles a, b, c; flags word: low half the mask m of keep_if, bit 32 the flag ok; floats fa, fb, fc; NOUT 17):
+ *       0 keep_if(a, m); 1 keep_if(fa, m); 2 fma3(a, b, c); 3 fma3_s(lane 0's a through uniform_load, b, c); 4 clamp_box(v = a, lo = b,
+ *       hi = c); 5 clamp_box(fa, fb, fc); 6 .. 11 lds_block<6> of the record (a, b, c, a, b, c) the lane wrote to LDS, under ok;
+ *       12 ldz<double>(a, ok); 13 ldz<float>(a, ok); 14 uniform_load(b's 64 words, lane); 15 fast_div(a, b); 16 fast_div(fa, fb).
+ *   BANDED (NIN 4: g2, cv doubles; lane 0's Lh, tol2; NOUT 3, wave-uniform flags): banded_decisions' return value, retry, finished. */
+#define BMPC_PROBE_SUM64 0
+#define BMPC_PROBE_SUM32 1
+#define BMPC_PROBE_SHIFT 2
+#define BMPC_PROBE_MASK 3
+#define BMPC_PROBE_THETA 4
+#define BMPC_PROBE_ARITH 5
+#define BMPC_PROBE_BANDED 6
+int bmpc_probe_lanes(int group, const void *in, long in_bytes, void *out, long out_bytes);
 
 /* gait_planner_cpp.GaitPlanner --------------------------------------------------
  * srcpy/gait_planner/py_gait_planner.cpp:19-35 over src/gait_planner/gait_planner.cpp */

@@ -366,6 +366,40 @@ def test_three_problems_per_wave_equal_two_per_wave(oracle, hiplib, mapping, con
     assert np.array_equal(out[1]["stats"][calm], ref["stats"][calm])
 
 
+def test_result_does_not_depend_on_the_segment(hiplib, mapping):
+    """Three problems per wave: WHICH of the wave's 21-lane segments holds a problem -- and who its wave-mates are -- must not show in its
+    iterates.  Each batch is solved as it is and with one and two filler problems in front, so that every problem sits in each of the
+    three segments.  All of X, F, P, the step constants, the counts and the per-iteration trace are the same bits for every problem.  The
+    violation and its history are square roots of segment sums of non-negative fp64 partials made by the same instantiation, and a
+    21-lane sum is added in an order that depends on the segment's position in the DPP rows (16|5, 11|10, 6|15): within 2 gamma_6 of
+    each other (tests/test_lane_probe_gpu.py), halved under the root, plus two roundings: under 9u; 16u asserted."""
+    mapping("batch")
+    u = 2.0 ** -53
+    old3, olds = hiplib.bmpc_set_three_per_wave(1), hiplib.bmpc_set_work_stealing(0)
+    try:
+        for config, B in (("solo12_trot", 6), ("solo12_mixed", 7)):
+            for H in (20, 17):      # (17: idle lanes inside the segments)
+                b = problems.make_batch(config, B, H=H)
+                out = []
+                for fill in (0, 1, 2):
+                    r = bb.solve_host(b.take([B - 1] * fill + list(range(B))), num_iters=10, keep_hist=True)
+                    assert hiplib.bmpc_biconvex_last_lanes_per_problem() == 21
+                    out.append({k: v[fill:] for k, v in r.items()})
+                for other in out[1:]:
+                    for k in ("X", "F", "P", "L_x", "L_f", "stats", "trace"):
+                        assert np.array_equal(out[0][k], other[k]), (config, H, k, np.flatnonzero(np.any((out[0][k] != other[k]).reshape(B, -1), axis=1)))
+                    for k in ("hist", "dyn_viol"):
+                        x, y = out[0][k], other[k]
+                        assert np.array_equal(np.isnan(x), np.isnan(y)), (config, H, k)
+                        ran = ~np.isnan(x)
+                        rel = np.abs(x[ran] - y[ran]) / np.maximum(np.abs(y[ran]), 1e-300)
+                        print("%s H=%d %s: %d of %d values differ between two placements, at most %.2f u" % (config, H, k, (rel > 0).sum(), rel.size, rel.max() / u))
+                        assert np.all(rel <= 16 * u), (config, H, k, rel.max() / u)
+    finally:
+        hiplib.bmpc_set_three_per_wave(old3)
+        hiplib.bmpc_set_work_stealing(olds)
+
+
 @pytest.mark.parametrize("config,B,H,iters,warm", [("solo12_trot", 100, None, 10, False), ("solo12_mixed", 31, None, 10, False), ("solo12_trot", 9, 12, 4, False),
                                                    ("solo12_trot", 5, 28, 3, False), ("go2_bound", 6, 40, 3, False), ("solo12_trot", 33, None, 3, True),
                                                    ("solo12_trot", 3, 100, 2, False), ("solo12_trot", 2, 200, 1, True)])

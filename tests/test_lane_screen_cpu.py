@@ -10,6 +10,8 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import screen_rate as sr  # noqa: E402
 
+from tests import lanes_np  # noqa: E402  (theta, butterfly_sum32: the models the device is held to)
+
 
 def _partials(rng, n):
     """[n][32] non-negative partials over 40 decades around a per-row scale, with zero, denormal, inf and NaN lanes mixed in"""
@@ -24,11 +26,10 @@ def _partials(rng, n):
     return p, scale[:, 0]
 
 
-def test_a_partial_above_theta_settles_every_fp64_verdict():
-    rng = np.random.default_rng(20)
-    n = 200000
-    p, scale = _partials(rng, n)
-    # thresholds near the rows' own sizes (most of them at the largest partial, where the screen is decided), far from them, and the odd cases
+def _thresholds(rng, p, scale):
+    """(tol2, floor2) [n]: thresholds near the rows' own sizes (most of them at the largest partial, where the screen is decided), far from
+    them, and the odd cases: zero, subnormal, infinite"""
+    n = len(p)
     pmax = np.nanmax(np.where(np.isinf(p), 0.0, p), axis=1)
     near = np.where(pmax > 0, pmax, scale)
     tol2 = near * np.where(rng.random(n) < 0.5, 1.0 + rng.uniform(-1, 1, n) * 10.0 ** rng.uniform(-16, -1, n), 10.0 ** rng.uniform(-12, 4, n))
@@ -39,11 +40,19 @@ def test_a_partial_above_theta_settles_every_fp64_verdict():
     tol2[odd == 2] = 5e-324 * 3
     tol2[odd == 3] = 2.0 ** -1023      # subnormal: the relative margins round away, the screen's lower limit takes over
     floor2[odd == 4] = np.inf
-    th = sr.theta(tol2, floor2)
+    return tol2, floor2
+
+
+def test_a_partial_above_theta_settles_every_fp64_verdict():
+    rng = np.random.default_rng(20)
+    n = 200000
+    p, scale = _partials(rng, n)
+    tol2, floor2 = _thresholds(rng, p, scale)
+    th = lanes_np.theta(tol2, floor2)
     assert np.all(th >= np.maximum(tol2, floor2)) and np.all(th >= 2.0 ** -1000)
     with np.errstate(invalid="ignore"):
         hit = np.any(p > th[:, None], axis=1)
-    S = sr.butterfly_sum32(p)
+    S = lanes_np.butterfly_sum32(p)
     below, done, edge = sr.verdicts(S, tol2, floor2)
     print("rows", n, "screened", int(hit.sum()), "of them with a NaN lane", int((hit & np.isnan(S)).sum()), "with an infinite sum",
           int((hit & np.isinf(S)).sum()), "| unscreened rows below the floor", int((~hit & below).sum()), "done", int((~hit & done).sum()),
@@ -55,7 +64,7 @@ def test_a_partial_above_theta_settles_every_fp64_verdict():
     assert not (hit & edge).any()
     # the sum is at least its largest term whatever the order: the reverse butterfly and a plain left-to-right sum too
     with np.errstate(invalid="ignore", over="ignore"):
-        for T in (sr.butterfly_sum32(p[:, ::-1]), np.add.reduce(p, axis=1)):
+        for T in (lanes_np.butterfly_sum32(p[:, ::-1]), np.add.reduce(p, axis=1)):
             ok = np.isnan(T) | (T >= np.nanmax(p, axis=1))
             assert np.all(ok)
 

@@ -7,63 +7,7 @@ import math
 import numpy as np
 import pytest
 
-LANES = np.arange(64)
-
-
-def _partner(kind):
-    if kind == "xor1":
-        return LANES ^ 1
-    if kind == "xor2":
-        return LANES ^ 2
-    if kind == "half_mirror":
-        return (LANES & ~7) | (7 - (LANES & 7))
-    return (LANES & ~15) | (15 - (LANES & 15))      # row_mirror
-
-
-def _rows(v):
-    for kind in ("xor1", "xor2", "half_mirror", "mirror"):
-        v = v[_partner(kind)] + v     # v_add_f32_dpp v, v(dpp), v
-    return v
-
-
-def _swap(v, width):
-    """x = permlane{16,32}_swap(v, v); x[0] + x[1]: the two blocks of `width` lanes of each pair add"""
-    lo = (LANES // width) % 2 == 0
-    even = np.where(lo, v, v[(LANES - width) % 64])
-    odd = np.where(lo, v[(LANES + width) % 64], v)
-    return even + odd
-
-
-def _is_p(lane):
-    row = lane >> 4
-    return row == 0 or lane // 21 == (16 * row) // 21 + 1
-
-
-IS_P = np.array([_is_p(int(l)) for l in LANES])
-
-
-def seg_sum(v, lpp):
-    """the kernels' segment sum of v (64 lanes, float32 or float64) in their order of additions; valid at desig(lpp)"""
-    zero = v.dtype.type(0)
-    if lpp == 21:
-        p = _rows(np.where(IS_P, v, zero))
-        q = _rows(np.where(IS_P, zero, v))
-        bc = np.where(LANES >= 16, p[np.maximum((LANES & ~15) - 1, 0)], zero)      # row_bcast:15; row 0 keeps the old value 0
-        return bc + q
-    v = _rows(v)
-    if lpp >= 32:
-        v = _swap(v, 16)
-    if lpp >= 64:
-        v = _swap(v, 32)
-    return v
-
-
-def desig(lpp):
-    return np.array([16, 32, 48]) if lpp == 21 else np.arange(0, 64, lpp)
-
-
-def segments(lpp):
-    return [np.arange(21 * k, 21 * k + 21) for k in range(3)] if lpp == 21 else [np.arange(s, s + lpp) for s in range(0, 64, lpp)]
+from tests.lanes_np import IS_P, _partner, _rows, _swap, desig, seg_sum, segments  # noqa: F401  (the restatements: tests/lanes_np.py)
 
 
 def wide(rng, n):

@@ -16,6 +16,8 @@ import pytest
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import screen_rate as sr  # noqa: E402
 
+from tests import lanes_np  # noqa: E402  (theta, butterfly_sum32: the models the device is held to)
+
 # the kernel's own choice first (kScreenTermsX = {5}, kScreenTermsF = {8}), then the other sets DESIGN.md's table rates
 SUBSETS = {9: [(5,), (3, 5), (3, 4, 5), (0,), (0, 8)], 12: [(8,), (2,), (2, 5), (2, 5, 8, 11), (0, 11)]}
 
@@ -57,13 +59,13 @@ def _chain(d, terms):
 def _check(d, terms, tol2, floor2, label):
     nt = d.shape[-1]
     s, g = _chain(d, terms), _chain(d, range(nt))
-    th = sr.theta(tol2, floor2)
+    th = lanes_np.theta(tol2, floor2)
     assert np.all(th >= np.fmax(tol2, floor2)) and np.all(th >= 2.0 ** -1000)
     with np.errstate(invalid="ignore"):
         hit = np.any(s > th[:, None], axis=1)
         ok = np.isnan(s) | np.isnan(g) | (g >= s * (1.0 - 2.0 ** -48))      # the lemma between the two chains, lane by lane
     assert np.all(ok)
-    S = sr.butterfly_sum32(g)
+    S = lanes_np.butterfly_sum32(g)
     below, done, edge = sr.verdicts(S, tol2, floor2)
     with np.errstate(invalid="ignore"):
         full_hit = np.any(g > th[:, None], axis=1)
@@ -123,7 +125,7 @@ def test_with_a_subnormal_tolerance(nt):
     for terms in SUBSETS[nt]:
         hit, S, below, done = _check(d, terms, tol2, floor2, "subnormal tol^2")
         assert hit.sum() > n // 10 and (~hit).sum() > n // 10
-        assert np.all(sr.theta(tol2, floor2) == 2.0 ** -1000)
+        assert np.all(lanes_np.theta(tol2, floor2) == 2.0 ** -1000)
 
 
 @pytest.mark.parametrize("nt", [9, 12])
@@ -146,13 +148,13 @@ def test_one_ulp_above_theta_with_every_other_term_zero(nt):
         for _ in range(4):
             cand = np.nextafter(cand, 0.0)
         for _ in range(9):
-            tol2 = np.where((sr.theta(cand, 0.0) == target) & np.isnan(tol2), cand, tol2)
+            tol2 = np.where((lanes_np.theta(cand, 0.0) == target) & np.isnan(tol2), cand, tol2)
             cand = np.nextafter(cand, np.inf)
         found = ~np.isnan(tol2)
         assert found.sum() > n // 2, found.sum()
         d, s, tol2 = d[found], s[found], tol2[found]
         floor2 = np.where(rng.random(len(s)) < 0.5, tol2, 0.0)      # (the floor at the same place, or out of the way)
-        th = sr.theta(tol2, floor2)
+        th = lanes_np.theta(tol2, floor2)
         assert np.all(s == np.nextafter(th, np.inf))
         hit, S, below, done = _check(d, terms, tol2, floor2, "one ulp above")
         assert hit.all() and np.array_equal(S, s)
