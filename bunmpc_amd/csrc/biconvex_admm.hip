@@ -78,7 +78,7 @@ using ThisUnit = Unit<ADMM_UNIT_SHAPE, ADMM_UNIT_PRECISION, ADMM_UNIT_FEET>;
 
 template <>
 const AdmmUnit &admm_unit_of<ADMM_UNIT_SHAPE, ADMM_UNIT_PRECISION, ADMM_UNIT_FEET>() {
-    static const AdmmUnit unit = {ThisUnit::launch, scratch_bytes<ThisUnit::Insts>, loop_constants_resident_waves<ThisUnit::Insts>};
+    static const AdmmUnit unit = {ThisUnit::launch, scratch_bytes<ThisUnit::Insts>, loop_constants_resident_waves<ThisUnit::Insts>, foot_pair_phases<ThisUnit::Insts>};
     return unit;
 }
 

@@ -58,6 +58,9 @@ constexpr double kCertFloor = 2.0 * 25.0 / (kCertEta * kCertEta) * 0x1p-80;
 // (Namespace scope: a constexpr array of admm_body indexed inside a lambda would be captured by its closure.)
 [[maybe_unused]] constexpr int kScreenTermsX[] = {5};
 [[maybe_unused]] constexpr int kScreenTermsF[] = {8};
+// (wave, force phase) pairs that the loop-constants build ran two feet per lane, since the last reset (AdmmUnit::foot_pair_phases): one
+// vector atomic of lane 0 per such phase, telemetry for the tests of the eligibility rule
+[[maybe_unused]] __device__ unsigned long long g_foot_pair_phases = 0;
 
 // BQ (per-knot block-diagonal costs: raw form, fp64, one wave per SIMD): a lane holds its knot's SYMMETRIC block -- the upper triangle,
 // 45 values for X, 3E (3E + 1) / 2 for F -- where the other instantiations hold the knot's diagonal weights, loaded once per phase like
@@ -1082,10 +1085,292 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                         keep_here(wc);      // (a use that stays here: the loads are not sunk to the gradient step; one statement, one wait)
                         return kGo;
                     };
+                    // Two feet per lane ("Force loop: two feet per lane").  A swing foot -- an = sp = 0, F_0 = +0 -- stays +0
+                    // through every operation of the loop above and adds +0 to every sum.  Here the 32 lanes of a segment are re-mapped onto
+                    // UNITS: a knot, a rank and up to two of the knot's contact feet in foot order (slots); a knot with three or four contacts
+                    // takes a second unit on the lane behind its first.  Per slot the operations of iterate_k on the same operands; the six
+                    // image sums are chains over the feet in foot order, so the knot's first unit starts them from +0, hands its partial sums
+                    // to the second unit (shift_prev), which continues them with its slots and hands the finished sums back (shift_next).
+                    // Wave-uniform eligibility: the switch, at most 32 units per problem, every swing foot's F_0 the bits of +0.0.  A `done`
+                    // latch and the exit by maxit store F_{k+1} (every unit its own feet) and its image (the knot's first unit); a step
+                    // below the floor or a non-finite value at an exit stores nothing of the problems still iterating and falls through to
+                    // the loop above, which runs the phase from iteration 0 (the records still hold F_0 and its image).
+                    bool pairs_done = false;
+                    if (a.force_foot_pairs != 0 && act != 0 && maxit > 0) {
+                        keep_here(xa);      // (F_0's bits are looked at here: made in the prologue, the partial results are parked in scratch memory)
+                        unsigned cmk = 0;      // the knot's contact feet, one bit per foot
+                        unsigned f0bits = 0;      // the swing feet's F_0, every bit or'ed: +0.0 is no bit
+                        UNROLL for (int n = 0; n < E; ++n) {
+                            const bool swing = an[n] == R(0) && sp[n][0] == R(0) && sp[n][1] == R(0) && sp[n][2] == R(0);
+                            cmk |= swing ? 0u : 1u << n;
+                            unsigned w = 0;
+                            UNROLL for (int k = 0; k < 3; ++k) w |= (unsigned)__double2hiint((double)xa[3 * n + k]) | (unsigned)__double2loint((double)xa[3 * n + k]);
+                            f0bits |= swing ? w : 0u;
+                        }
+                        const bool f0ok = f0bits == 0u;
+                        const bool two = __popc(cmk) > 2;
+                        const mask_t two_m = __ballot(two);
+                        const bool fits = H + __popc((unsigned)two_m) <= 32 && H + __popc((unsigned)(two_m >> 32)) <= 32;
+                        if (fits && __ballot(!f0ok) == 0) {
+                            #pragma clang fp contract(off)
+                            // ---- the unit map, by a scatter through 64 bytes of LDS per segment (the F block of knot H's record, which has no
+                            // forces: behind the two ints of cert_count); an entry: knot | rank << 5 | contact feet << 8, 0x8000 = no unit
+                            unsigned e;
+                            {
+                                const unsigned ln = opaque_copy(lane_id()), tl = ln & 31u;
+                                const unsigned tw = ln < 32u ? (unsigned)two_m : (unsigned)(two_m >> 32);
+                                const unsigned start = tl + (unsigned)__popc(tw & ((1u << tl) - 1u));      // (<= 31 for every knot lane: `fits`)
+                                unsigned short *mp = reinterpret_cast<unsigned short *>(header() + kSegLds + (long)H * KL + 18 + 1);
+                                mp[tl] = (unsigned short)0x8000u;
+                                lds_fence();
+                                if (rvalid) {
+                                    mp[start] = (unsigned short)(tl | cmk << 8);
+                                    if (two) mp[start + 1u] = (unsigned short)(tl | 32u | cmk << 8);
+                                }
+                                lds_fence();
+                                e = mp[tl];
+                                lds_fence();
+                            }
+                            const bool uval = (e & 0x8000u) == 0u;
+                            const int mrank = (e & 32u) != 0u ? -1 : 0;
+                            const mask_t tfirst_m = __ballot(uval && mrank == 0 && __popc((e >> 8) & 15u) > 2);      // the first units of knots with two (a mask: see `lanes`)
+                            unsigned fs[2]; bool sv[2];
+                            {
+                                unsigned um = uval ? (e >> 8) & 15u : 0u;
+                                if (mrank != 0) { um &= um - 1u; um &= um - 1u; }
+                                sv[0] = um != 0u; fs[0] = sv[0] ? (unsigned)__builtin_ctz(um) : 0u; um &= um - 1u;
+                                sv[1] = um != 0u; fs[1] = sv[1] ? (unsigned)__builtin_ctz(um) : 0u;
+                            }
+                            // addresses, as byte offsets into LDS: the knot's record (its X block) and its constants; what a unit does not
+                            // have it reads from the zeros at the front (element lane mod 32 onward: at most 31 + 5 < kLdsZeros)
+                            const unsigned lnu = opaque_copy(lane_id());
+                            const unsigned zoff = 8u * (lnu & 31u);
+                            const unsigned urec = 8u * ((unsigned)(kLdsZeros + kSegLds) + lnu / 32u * (unsigned)(kSegLds + (H + 1) * KL) + (e & 31u) * (unsigned)KL);
+                            const unsigned ucon = 8u * ((unsigned)(kLdsZeros + 2 * (kSegLds + (H + 1) * KL)) + (lnu / 32u * (unsigned)(H + 1) + (e & 31u)) * (unsigned)kLoopConstLds);
+                            auto ldsp = [&](unsigned off) { return reinterpret_cast<R *>(reinterpret_cast<char *>(lds_raw) + opaque_copy(off)); };
+                            const unsigned cbk = uval ? ucon + 8u * (unsigned)NF : zoff;
+                            const unsigned cbs[2] = {sv[0] ? ucon + 24u * fs[0] : zoff, sv[1] ? ucon + 24u * fs[1] : zoff};
+                            // an, sp of the slots: the prologue's expressions on the knot's c, r, X[0..2], dt
+                            R pan[2], psp[2][3], py[6], pxa[6], pxb[6], pra[6], prb[6], pry[6], pwc[6];
+                            {
+                                const unsigned oKu = 8u * (sl_ * (unsigned)H + (uval ? e & 31u : 0u));
+                                const R dtu = ldz<R>(a.dt + wave0 * H, oKu, 0, uval);
+                                R Xu3[3];
+                                { const R *Xr = ldsp(uval ? urec : zoff); UNROLL for (int k = 0; k < 3; ++k) Xu3[k] = Xr[k]; }
+                                UNROLL for (int s = 0; s < 2; ++s) {
+                                    const unsigned oCu = oKu * (unsigned)(E * 4) + 32u * fs[s];
+                                    const R cu = ldz<R>(cnt_u, oCu, 0, sv[s]);
+                                    const R av = cu * (dtu / m);
+                                    pan[s] = sv[s] ? av : R(0);
+                                    UNROLL for (int k = 0; k < 3; ++k) {
+                                        const R ru = ldz<R>(cnt_u, oCu, 1 + k, sv[s]);
+                                        const R v = cu * (Xu3[k] - ru) * dtu;
+                                        psp[s][k] = sv[s] ? v : R(0);
+                                    }
+                                    const R *Fr = ldsp(sv[s] ? urec + 8u * 18u + 24u * fs[s] : zoff);
+                                    const R *Cs = ldsp(cbs[s]);
+                                    UNROLL for (int k = 0; k < 3; ++k) { pxa[3 * s + k] = Fr[k]; py[3 * s + k] = pxa[3 * s + k]; pwc[3 * s + k] = Cs[k]; }
+                                }
+                                const R *Rr = ldsp(uval ? urec + 8u * (unsigned)(18 + NF) : zoff);
+                                UNROLL for (int k = 0; k < 6; ++k) { pry[k] = Rr[k]; pra[k] = pry[k]; }
+                            }
+                            constexpr int kReplay = 3;
+                            // an exit: F_{k+1} and its image of the problems in m to their knots' records -- unless one of them holds a
+                            // non-finite value (false: nothing is stored, the phase is run again by the loop above)
+                            auto store_p = [&](mask_t m, const R (&xv)[6], const R (&rv)[6]) -> bool {
+                                bool bad = false;
+                                UNROLL for (int j = 0; j < 6; ++j) bad = bad || !(__builtin_fabs((double)xv[j]) < __builtin_inf()) || !(__builtin_fabs((double)rv[j]) < __builtin_inf());
+                                if ((__ballot(bad) & m) != 0) return false;
+                                if (lanes(m) && uval) {
+                                    R *Xs = ldsp(urec);
+                                    UNROLL for (int s = 0; s < 2; ++s) {
+                                        if (sv[s]) { R *Fs = Xs + 18 + 3 * fs[s]; UNROLL for (int k = 0; k < 3; ++k) Fs[k] = xv[3 * s + k]; }
+                                    }
+                                    if (mrank == 0) { UNROLL for (int k = 0; k < 6; ++k) Xs[18 + NF + k] = rv[k]; }
+                                }
+                                return true;
+                            };
+                            // an iteration that the screen does not settle: the knot's |d|^2 in the four-foot order (the first unit's chain,
+                            // continued by the second), brought to the knot's lane; from there the sums and decisions of `unsettled`
+                            auto unsettled_p = [&](const R (&xn)[6], const R (&rn)[6], int i, R g2own) -> int {
+                                R g2;
+                                {
+                                    const R gin = keep_if(from_prev(g2own), mrank);
+                                    R g = gin;
+                                    UNROLL for (int j = 0; j < 6; ++j) { const R d = xn[j] - py[j]; g = fmaR(d, d, g); }
+                                    const unsigned ln = opaque_copy(lane_id()), tl = ln & 31u;
+                                    const unsigned tw = ln < 32u ? (unsigned)two_m : (unsigned)(two_m >> 32);
+                                    const unsigned last = tl + (unsigned)__popc(tw & ((2u << tl) - 1u));      // the knot's last unit
+                                    const int src = (int)(4u * ((ln & 32u) + (last & 31u)));
+                                    const double gd = (double)g;
+                                    const int lo = __builtin_amdgcn_ds_bpermute(src, __double2loint(gd)), hi = __builtin_amdgcn_ds_bpermute(src, __double2hiint(gd));
+                                    g2 = rvalid ? (R)__hiloint2double(hi, lo) : R(0);
+                                }
+                                mask_t done = 0;
+                                mask_t unclear = ~mask_t(0);
+                                if (banded != 0) {
+                                    float gf = (float)g2;
+                                    seg_sum1_f32<LPP>(gf);
+                                    const mask_t yes = __ballot(gf < flo), no = __ballot(gf > fhi);
+                                    const mask_t dyes = __ballot(gf < t2lo), dno = __ballot(gf > t2hi);
+                                    const mask_t clear = (yes | no) & (dyes | dno) & __ballot(gf >= 1e-24f) & __ballot(gf <= 1e30f);
+                                    unclear = ~clear & act;
+                                    if (unclear == 0) {
+                                        if ((yes & act) != 0) return kReplay;
+                                        done = dyes;
+                                    }
+                                }
+                                if (unclear != 0) {
+                                    double g2s = (double)g2;
+                                    sum1(g2s);
+                                    if ((__ballot(g2s < floor2) & act) != 0) return kReplay;
+                                    done = __ballot(g2s < tol2);
+                                    if (__ballot(fabs(g2s - tol2) <= 1e-14 * tol2) != 0) done = __ballot(sqrt(g2s) < tol);
+                                }
+                                const mask_t latch = act & done;
+                                if (latch != 0) {
+                                    if (!store_p(latch, xn, rn)) return kReplay;
+                                    if ((unsigned)latch != 0u) c0 = i + 1;
+                                    if ((unsigned)(latch >> 32) != 0u) c1 = i + 1;
+                                    act &= ~done;
+                                    if (act == 0) return kAllLeft;
+                                    seg_dead32(act, dead0, dead1);
+                                }
+                                return kGo;
+                            };
+                            auto iterate_p = [&](const R (&xo)[6], const R (&ro)[6], R (&xn)[6], R (&rn)[6], int i) -> int {
+                                #pragma clang fp contract(off)
+                                const R cm = cmn;
+                                cmn = uniform_load(cmtab, min((unsigned)i + 1u, (unsigned)kMaxFistaIters - 1u));
+                                unsigned long long anycone = 0;
+                                R fr[6];
+                                UNROLL for (int s = 0; s < 2; ++s) {      // (iterate_k's gradient, step and projection, with its contractions spelled out)
+                                    const R zx = fmaR(psp[s][1], pry[5], fmaR(pan[s], pry[0], -(psp[s][2] * pry[4])));
+                                    const R zy = fmaR(-psp[s][0], pry[5], fmaR(pan[s], pry[1], psp[s][2] * pry[3]));
+                                    const R zz = fmaR(psp[s][0], pry[4], fmaR(pan[s], pry[2], -(psp[s][1] * pry[3])));
+                                    const R gx = fmaR(pwc[3 * s], py[3 * s], rho * zx), gy = fmaR(pwc[3 * s + 1], py[3 * s + 1], rho * zy);
+                                    const R gz = fmaR(pwc[3 * s + 2], py[3 * s + 2], rho * zz);
+                                    fr[3 * s] = fmaR(-gx, invL, py[3 * s]);
+                                    fr[3 * s + 1] = fmaR(-gy, invL, py[3 * s + 1]);
+                                    fr[3 * s + 2] = fmaR(-gz, invL, py[3 * s + 2]);
+                                    const R sq = fmaR(fr[3 * s], fr[3 * s], fr[3 * s + 1] * fr[3 * s + 1]);
+                                    const R fz = fr[3 * s + 2];
+                                    const bool zero = (sq * mu < -fz) || (fz < 0);
+                                    anycone |= __ballot(!zero && (sq > mu * fz));
+                                    const R keep = zero ? R(0) : R(1);
+                                    xn[3 * s] = keep * fr[3 * s];
+                                    xn[3 * s + 1] = keep * fr[3 * s + 1];
+                                    xn[3 * s + 2] = keep * fz;
+                                }
+                                if (anycone != 0) {
+                                    UNROLL for (int s = 0; s < 2; ++s) {
+                                        const R sq = fmaR(fr[3 * s], fr[3 * s], fr[3 * s + 1] * fr[3 * s + 1]);
+                                        const R fz = fr[3 * s + 2];
+                                        const bool zero = (sq * mu < -fz) || (fz < 0);
+                                        const bool cone = !zero && (sq > mu * fz);
+                                        const R k = fast_div(fmaR(mu2, sq, mu * fz), (mu2 + R(1)) * sq);
+                                        xn[3 * s] = cone ? fr[3 * s] * k : xn[3 * s];
+                                        xn[3 * s + 1] = cone ? fr[3 * s + 1] * k : xn[3 * s + 1];
+                                        xn[3 * s + 2] = cone ? fmaR(mu, sq, fz) * imu : xn[3 * s + 2];
+                                    }
+                                }
+                                {   // the image: the cross products once, the chains twice (from +0, and from the knot's first unit's partial sums)
+                                    R bk[6];
+                                    const R *Cz = reinterpret_cast<const R *>(reinterpret_cast<const char *>(lds_raw) + opaque_copy_after(cbk, xn[5]));
+                                    UNROLL for (int k = 0; k < 6; ++k) bk[k] = Cz[k];
+                                    R u[2][3];
+                                    UNROLL for (int s = 0; s < 2; ++s) {
+                                        const R vx = xn[3 * s], vy = xn[3 * s + 1], vz = xn[3 * s + 2];
+                                        u[s][0] = fmaR(psp[s][2], vy, -(psp[s][1] * vz));
+                                        u[s][1] = fmaR(psp[s][0], vz, -(psp[s][2] * vx));
+                                        u[s][2] = fmaR(psp[s][1], vx, -(psp[s][0] * vy));
+                                    }
+                                    auto chain = [&](const R (&in)[6], R (&o)[6]) {
+                                        UNROLL for (int k = 0; k < 6; ++k) o[k] = in[k];
+                                        UNROLL for (int s = 0; s < 2; ++s) {
+                                            UNROLL for (int k = 0; k < 3; ++k) { o[k] = fmaR(pan[s], xn[3 * s + k], o[k]); o[3 + k] = o[3 + k] + u[s][k]; }
+                                        }
+                                    };
+                                    const R z6[6] = {0, 0, 0, 0, 0, 0};
+                                    R p[6], pin[6], q[6], back[6];
+                                    chain(z6, p);
+                                    shift_prev(p, pin);
+                                    UNROLL for (int k = 0; k < 6; ++k) pin[k] = keep_if(pin[k], mrank);
+                                    chain(pin, q);
+                                    shift_next(q, back);
+                                    keep_here(bk);
+                                    UNROLL for (int k = 0; k < 6; ++k) rn[k] = (lanes(tfirst_m) ? back[k] : q[k]) + bk[k];
+                                }
+                                {   // the two-stage screen, on the lane's own slots: a partial over fewer terms can only miss more often
+                                    const R d2 = xn[2] - py[2];
+                                    const R sc = fmaR(d2, d2, R(0));
+                                    if (!seg_covered32(__ballot(sc > theta), dead0, dead1)) {
+                                        R g2 = 0;
+                                        UNROLL for (int j = 0; j < 6; ++j) { const R d = xn[j] - py[j]; g2 = fmaR(d, d, g2); }
+                                        if (!seg_covered32(__ballot(g2 > theta), dead0, dead1)) {
+                                            const int r = unsettled_p(xn, rn, i, g2);
+                                            if (r != kGo) return r;
+                                        }
+                                    }
+                                }
+                                { UNROLL for (int s = 0; s < 2; ++s) { const R *Cs = ldsp(cbs[s]); UNROLL for (int k = 0; k < 3; ++k) pwc[3 * s + k] = Cs[k]; } }
+                                UNROLL for (int j = 0; j < 6; ++j) py[j] = fma3_s(cm, xn[j] - xo[j], xn[j]);
+                                UNROLL for (int k = 0; k < 6; ++k) pry[k] = fmaR(cm, rn[k] - ro[k], rn[k]);
+                                keep_here(pwc);
+                                return kGo;
+                            };
+                            int pr = kGo;
+                            bool stored = true;
+                            for (int i = 0;;) {
+                                pr = iterate_p(pxa, pra, pxb, prb, i);
+                                if (pr != kGo) break;
+                                if (i + 1 >= maxit) { stored = store_p(act, pxb, prb); break; }
+                                pr = iterate_p(pxb, prb, pxa, pra, i + 1);
+                                if (pr != kGo) break;
+                                i += 2;
+                                if (i >= maxit) { stored = store_p(act, pxa, pra); break; }
+                            }
+                            lds_fence();
+                            if (pr == kReplay || !stored) {
+                                // the phase again, by the loop below: F_0 and its image from the records, the first weights and coefficient
+                                // (and the knot's an / sp, made again from the plan by the prologue's expressions: held across the loop above
+                                // they are 32 registers, which that loop then finds in scratch memory)
+                                R *rr = record_or_front(kvalid_m);
+                                {
+                                    const unsigned ph2 = opaque_zero();
+                                    const unsigned oC2 = make_off(opaque_copy(sl)).K * (unsigned)(E * 4) + ph2;
+                                    R X3[3];
+                                    UNROLL for (int k = 0; k < 3; ++k) { const R v = rr[k]; X3[k] = kvalid ? v : R(0); }
+                                    UNROLL for (int n = 0; n < E; ++n) {
+                                        const R cn = ldz<R>(cnt_u, oC2, 4 * n, rvalid);
+                                        an[n] = cn * (dt / m);
+                                        UNROLL for (int k = 0; k < 3; ++k) sp[n][k] = cn * (X3[k] - ldz<R>(cnt_u, oC2, 4 * n + 1 + k, rvalid)) * dt;
+                                    }
+                                }
+                                lds_block(rr + 18, xa, rvalid);
+                                lds_block(rr + 18 + NF, ry, rvalid);
+                                UNROLL for (int j = 0; j < NF; ++j) y[j] = xa[j];
+                                UNROLL for (int k = 0; k < 6; ++k) ra[k] = ry[k];
+                                { const R *Cz = consts(); UNROLL for (int j = 0; j < NF; ++j) wc[j] = Cz[j]; }
+                                cmn = uniform_load(cmtab, 0u);
+                                seg_dead32(act, dead0, dead1);
+                            } else {
+                                pairs_done = true;
+                                if (l0 && lnu < 32u) atomicAdd(&g_foot_pair_phases, 1ull);
+                                // (the phase is over -- neither loop below runs, i0 = maxit -- which hipcc does not see: it carried the
+                                // four-foot loop's 126 registers of state through the loop above, whose own values then went to scratch
+                                // memory.  Defined here, by no instruction, they are dead across it)
+                                auto forget = [](R &v) { asm volatile("" : "=v"(v)); };
+                                UNROLL for (int n = 0; n < E; ++n) { forget(an[n]); UNROLL for (int k = 0; k < 3; ++k) forget(sp[n][k]); }
+                                UNROLL for (int j = 0; j < NF; ++j) { forget(y[j]); forget(xa[j]); forget(wc[j]); }
+                                UNROLL for (int k = 0; k < 6; ++k) { forget(ry[k]); forget(ra[k]); }
+                            }
+                        }
+                    }
                     i0 = maxit;
                     // (where the loop ends by maxit, the problems still iterating store the last iteration's F_{k+1} and its image from the
                     // register set that iteration wrote -- at the exit itself: asked behind the loop which set that was, both stay live through it)
-                    if (act != 0 && maxit > 0) {
+                    if (!pairs_done && act != 0 && maxit > 0) {
                         for (int i = 0;;) {
                             const int r = iterate_k(xa, ra, xb, rb, i);
                             if (r != kGo) { if (r == kHandOver) i0 = i; break; }

@@ -222,3 +222,17 @@ int loop_constants_resident_waves(int H) {
     });
     return waves;
 }
+
+// (wave, force phase) pairs that the unit's loop-constants build ran two feet per lane on the current device since the last reset
+// (biconvex_admm_body.h: g_foot_pair_phases); waits for the device.  0: the unit has no such build, -1 on error
+template <typename Insts>
+long foot_pair_phases(int reset) {
+    bool has = false;
+    Insts::each([&](auto inst) { has = has || decltype(inst)::CLDS; });
+    if (!has) return 0;
+    unsigned long long n = 0;
+    const unsigned long long zero = 0;
+    if (hipMemcpyFromSymbol(&n, HIP_SYMBOL(g_foot_pair_phases), sizeof(n)) != hipSuccess) return -1;
+    if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_foot_pair_phases), &zero, sizeof(zero)) != hipSuccess) return -1;
+    return (long)n;
+}

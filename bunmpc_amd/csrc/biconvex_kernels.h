@@ -43,6 +43,8 @@ struct BatchArgs {
                                 // from the fp64 sums, no screen; 2: fp32 decisions without the screen (kernels without the screen read non-zero as 1)
     int certified_steps;        // (set by the launcher) fp64 batch kernels skip the backtracking test in phases whose step is certified: 1 force and
                                 // motion phases, 2 force phases only, 0 none
+    int force_foot_pairs;       // (set by the launcher; the eighth int: it sits where the block had padding, no other member moves) non-zero: the loop-constants
+                                // build runs an eligible certified force phase two feet per lane (biconvex_admm_body.h: "two feet per lane"); read by no other kernel
     double L0_x, L0_f;
     SolverConsts c;
     const double *cnt_plan, *dt, *x_init;
@@ -162,6 +164,12 @@ constexpr bool loop_constants_fit(int E, int H) { return H >= 1 && 8 * loop_cons
 #define BMPC_LOOP_CONSTANTS_PAY 1
 #endif
 constexpr bool kLoopConstantsPay = BMPC_LOOP_CONSTANTS_PAY != 0;
+// what mode 2 of set_force_foot_pairs ("when it pays") resolves to: "on", by the measurement in EXPERIMENTS.md ("Headline force loop: two
+// feet per lane": 2.40 -> 2.21 ms at B = 4096, H = 20, seven alternating pairs, every run below every run of the parent)
+#ifndef BMPC_FORCE_FOOT_PAIRS_PAY      // (side-by-side experiment builds: BUNMPC_EXTRA_FLAGS=-DBMPC_FORCE_FOOT_PAIRS_PAY=0)
+#define BMPC_FORCE_FOOT_PAIRS_PAY 1
+#endif
+constexpr bool kForceFootPairsPay = BMPC_FORCE_FOOT_PAIRS_PAY != 0;
 constexpr unsigned launch_grid(int B, int per_wg) { return (unsigned)((B + per_wg - 1) / per_wg); }
 
 // The kernel a batch gets.  Set by plan_launch, except the cost arrays: launch_biconvex_admm adds those.
@@ -180,6 +188,7 @@ struct AdmmUnit {
     hipError_t (*launch)(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stream);
     int (*scratch_bytes)();
     int (*loop_constants_resident_waves)(int H);      // of the unit's loop-constants build, by the occupancy query: waves one CU holds at once; 0: the unit has no such build, -1 on error
+    long (*foot_pair_phases)(int reset);              // (wave, force phase) pairs the unit's loop-constants build ran two feet per lane on the current device since the last reset; 0: no such build, -1 on error
 };
 // The combinations a unit is built for, by kShapes, and each one's accessor: every compilation of biconvex_admm.hip defines the
 // explicit specialisation it was built for, and biconvex_launch.hip's table refers to all of them.
@@ -202,6 +211,7 @@ struct DispatchKnobs {
     int exact_step_decisions = 0;      // 1: every step decision from the fp64 sums, in every centroidal kernel; 2: the headline kernel without its lane-local screen (tests)
     int certified_steps = 1;           // the fp64 batch kernels' per-phase step certificate: 0 off, 1 on, 2 force phases only
     int loop_constants_in_lds = 2;     // the headline kernel's build with loop constants in LDS and x_k in registers: 0 never, 1 whenever it fits, 2 when it pays
+    int force_foot_pairs = 2;          // ... its certified force loop two feet per lane in eligible phases: 0 never, 1 always, 2 when it pays
 };
 struct LaunchPlan {
     hipError_t status;       // hipErrorInvalidValue: a shape no kernel is built for
@@ -232,6 +242,7 @@ int set_work_stealing(int on);                       // the segment-level work-s
 int biconvex_last_lanes_per_problem();               // of the calling host thread's latest launch: 16 / 21 / 32 / 64, 0 = one problem per wave
 int set_exact_step_decisions(int on);                // 1: every step decision from the fp64 sums, in every centroidal kernel; 2: fp32 decisions without the headline kernel's lane-local screen; returns the old value
 int set_loop_constants_in_lds(int mode);             // the headline kernel's certified loops with their constants in LDS and x_k in registers: 0 never, 1 whenever it fits, 2 when it pays (default); returns the old value
+int set_force_foot_pairs(int mode);                  // the loop-constants build's certified force loop with two feet per lane where a phase is eligible: 0 never, 1 always, 2 when it pays (default); returns the old value
 int set_certified_steps(int on);                     // the fp64 batch kernels' per-phase step certificate: 0 off, 1 on (default), 2 force phases only; returns the old value
 
 // Lane-exchange self test (DPP shifts and segment sums used by the kernel).

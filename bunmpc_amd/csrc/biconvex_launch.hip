@@ -154,6 +154,7 @@ int set_latency_mapping_max_batch(int max_batch) { return set_knob(g_knobs.laten
 int set_exact_step_decisions(int on) { return set_knob(g_knobs.exact_step_decisions, on); }
 int set_certified_steps(int on) { return set_knob(g_knobs.certified_steps, on); }
 int set_loop_constants_in_lds(int mode) { return set_knob(g_knobs.loop_constants_in_lds, mode); }
+int set_force_foot_pairs(int mode) { return set_knob(g_knobs.force_foot_pairs, mode); }
 int biconvex_last_waves_per_simd() { return t_last_wpe; }
 int biconvex_last_lanes_per_problem() { return t_last_lpp; }
 const char *biconvex_last_kernel_name() { return t_last_kernel; }
@@ -232,6 +233,8 @@ hipError_t launch_biconvex_admm(const BatchArgs &args, const CostArgs &cost, int
     BatchArgs a = args;
     a.exact_step_decisions = g_knobs.exact_step_decisions;      // (every kernel with the fp32 shortcut of its step decisions; none with block or band costs)
     a.certified_steps = p.certified_steps;
+    // (read by the loop-constants build alone; mode 2, "when it pays": see kForceFootPairsPay.  Results do not depend on it)
+    a.force_foot_pairs = p.l.clds && (g_knobs.force_foot_pairs == 1 || (g_knobs.force_foot_pairs != 0 && kForceFootPairsPay)) ? 1 : 0;
     t_last_kernel = p.kernel;
     t_last_lpp = p.l.lpp;
     // (the one-problem-per-wave kernel leaves the record of the waves per SIMD what the launch before it set: tests compare whole

@@ -7,6 +7,7 @@
 //   src/gait_planner/gait_planner.cpp                                       (QuadrupedGait)
 // All numerical work of optimize() happens in biconvex_admm.hip on the GPU.
 #include "../../include/bunmpc.h"
+#include "../../include/bunmpc_foot_pairs.h"
 #include "biconvex_kernels.h"
 
 #include <cmath>
@@ -262,6 +263,8 @@ int bmpc_set_latency_mapping_max_batch(int max_batch) { return bunmpc::set_laten
 int bmpc_set_exact_step_decisions(int on) { return bunmpc::set_exact_step_decisions(on); }
 int bmpc_set_certified_steps(int on) { return bunmpc::set_certified_steps(on); }
 int bmpc_set_loop_constants_in_lds(int mode) { return bunmpc::set_loop_constants_in_lds(mode); }
+int bmpc_set_force_foot_pairs(int mode) { return bunmpc::set_force_foot_pairs(mode); }
+long bmpc_force_foot_pair_phases(int reset) { return bunmpc::admm_unit(bunmpc::kDiag, 0, 4).foot_pair_phases(reset); }
 long bmpc_loop_constants_lds_bytes(int n_eff, int n_col) { return n_col >= 1 && (n_eff == 2 || n_eff == 4) ? (long)bunmpc::loop_constants_lds_bytes(n_eff, n_col) : -1; }
 int bmpc_loop_constants_resident_waves(int n_col) {
     if (!bunmpc::loop_constants_fit(4, n_col)) return fail(BMPC_BAD_ARG, "the loop-constants build does not fit this horizon"), -1;

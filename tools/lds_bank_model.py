@@ -3,6 +3,7 @@
 with, and its verdict on where those constants lie (`consts_offset` in bunmpc_amd/csrc/biconvex_admm_body.h).
 
     python tools/lds_bank_model.py            conflict cycles per FISTA iteration, both loops, H + 1 = 17 .. 21, both layouts
+    python tools/lds_bank_model.py --units    ... of the force loop with two feet per lane, for a few contact plans
 
 The mapping (measured on MI355X, public in AMD's CDNA4 material as far as the bank count goes): LDS has 64 banks of 4 bytes.
   * `ds_read_b64` serves a wave in two groups of 32 lanes, {0..31} and {32..63}; the bank of byte address a is (a / 4) mod 64, and a
@@ -78,7 +79,52 @@ def zeros_read_are_zeros(H, layout, E=4):
     return all(e >= base or e + K_LOOP_CONST - 1 < K_LDS_ZEROS for own in (H, H - 1) for e in lane_elements(H, E, layout, own))
 
 
+# The force loop with two feet per lane ("Force loop: two feet per lane"): a lane is a unit -- a knot, a rank, up to
+# two of the knot's contact feet -- and reads, per iteration, the three weights of each of its feet (ds_read2_b64 + ds_read_b64 at the
+# foot's offset in the knot's record) and the knot's bPk (three ds_read2_b64 at offset 12); both units of a knot read the same bPk
+# (a broadcast), an empty slot and a lane without a unit read the zeros at element lane mod 32.
+def unit_iteration_conflicts(masks, H=20, E=4):
+    """conflict cycles of one iteration's constants' reads, both segments running the plan `masks` (a contact mask per force knot)"""
+    base = K_LDS_ZEROS + 2 * (K_SEG_LDS + (H + 1) * knot_lds(E))
+    units = []
+    for t, m in enumerate(masks):
+        feet = [n for n in range(4) if m >> n & 1]
+        units.append((t, feet[:2]))
+        if len(feet) > 2:
+            units.append((t, feet[2:]))
+    assert len(units) <= LPP
+    slot = [[], []]
+    bk = []
+    for lane in range(64):
+        seg, u = divmod(lane, LPP)
+        z = lane % 32
+        if u < len(units):
+            t, feet = units[u]
+            rec = base + (seg * (H + 1) + t) * K_LOOP_CONST
+            bk.append(rec + 3 * E)
+            for s in (0, 1):
+                slot[s].append(rec + 3 * feet[s] if s < len(feet) else z)
+        else:
+            bk.append(z)
+            slot[0].append(z)
+            slot[1].append(z)
+    total = 0
+    for el in slot:
+        total += sum(conflict_cycles("ds_read2_b64", [2 * (e + off) for e in el]) for off in (0, 1)) + conflict_cycles("ds_read_b64", [2 * (e + 2) for e in el])
+    total += sum(conflict_cycles("ds_read2_b64", [2 * (e + off) for e in bk]) for off in range(6))
+    return total, len(units)
+
+
 def main():
+    if "--units" in sys.argv:
+        plans = {"trot (12 knots of feet 0,3 / 1,2 alternating, 8 of four)": [9, 9, 9, 15, 15, 6, 6, 6, 15, 15, 9, 9, 9, 15, 15, 6, 6, 6, 15, 15],
+                 "two feet everywhere (0,3)": [9] * 20, "pace-like (0,2 / 1,3)": [5, 5, 5, 5, 5, 10, 10, 10, 10, 10] * 2,
+                 "three and none": [7, 0, 14, 0, 11, 0, 13, 0, 7, 0, 14, 0, 11, 0, 13, 0, 7, 0, 14, 0]}
+        print("two feet per lane: conflict cycles of the constants' reads of one certified force iteration (12 ds_read per lane)")
+        for name, masks in plans.items():
+            c, n = unit_iteration_conflicts(masks)
+            print("  %-62s %2d units: %d" % (name, n, c))
+        return 0
     print("conflict cycles per certified FISTA iteration (a full wave; in brackets: a wave whose second segment has no problem)")
     for layout in ("parent", "chosen"):
         for H in range(16, 21):
