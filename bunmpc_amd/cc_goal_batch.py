@@ -7,12 +7,29 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib_goals
+from . import _lib
+
+# the bits of `status` (include/bunmpc_goals.h)
+FEW_SWITCHES, START_AFTER_END, PAST_SCHEDULE, EVENTS_OVERFLOW = (
+    _lib._ABI.defines["BMPC_CC_" + n] for n in ("FEW_SWITCHES", "START_AFTER_END", "PAST_SCHEDULE", "EVENTS_OVERFLOW"))
+
+
+def gait_struct(gait):
+    g = _lib.CcGait()
+    g.gait_period, g.gait_dt, g.gait_horizon = gait.gait_period, gait.gait_dt, gait.gait_horizon
+    for j in range(4):
+        g.stance_percent[j], g.phase_offset[j] = gait.stance_percent[j], gait.phase_offset[j]
+    return g
+
+
+def plan_knots(episode_length, gait, sim_dt=0.001):
+    """H_cp of contact_planner.py:130, through the C-ABI (no GPU)"""
+    return _lib.lib().bmpc_cc_goal_plan_knots(int(episode_length), float(sim_dt), float(gait.gait_horizon), float(gait.gait_period), float(gait.gait_dt))
 
 
 def default_max_events(gait, episode_length, sim_dt=0.001):
     """room for every switch of a plan: each foot touches down once per gait period, plus one per foot for the ends"""
-    H = _lib_goals.plan_knots(episode_length, gait, sim_dt)
+    H = plan_knots(episode_length, gait, sim_dt)
     return max(2, 4 * (int(H * gait.gait_dt / gait.gait_period) + 2))
 
 
@@ -33,8 +50,8 @@ class _GoalTensors:
 
     def _sizes(self, d, gait, B, episode_length, goal_horizon, max_rows, max_events, sim_dt):
         d.B, d.n_eff, d.episode_length, d.goal_horizon = B, len(gait.stance_percent), episode_length, goal_horizon
-        d.max_rows, d.max_events, d.sim_dt, d.gait = max_rows, max_events, sim_dt, _lib_goals.gait_struct(gait)
-        d.n_knots = self.H = _lib_goals.plan_knots(episode_length, gait, sim_dt)
+        d.max_rows, d.max_events, d.sim_dt, d.gait = max_rows, max_events, sim_dt, gait_struct(gait)
+        d.n_knots = self.H = plan_knots(episode_length, gait, sim_dt)
         self.episode_length = episode_length
         if self.H < 1:
             raise ValueError("episode_length %d gives a plan of %d knots: nothing to plan" % (episode_length, self.H))
@@ -69,7 +86,7 @@ class DeviceCcGoals(_GoalTensors):
         B = int(np.shape(t0)[0])
         max_rows = episode_length + 1 if max_rows is None else max_rows
         max_events = default_max_events(gait, episode_length, sim_dt) if max_events is None else max_events
-        d = _lib_goals.CcGoalBatch()
+        d = _lib.CcGoalBatch()
         self._sizes(d, gait, B, episode_length, goal_horizon, max_rows, max_events, sim_dt)
         self.B = B
         self.inp = dict(t0=self._up(t0), com=self._up(com), feet0=self._up(feet0), hip_off=self._up(hip_off), v_des=self._up(v_des), w_des=self._up(w_des))
@@ -85,7 +102,7 @@ class DeviceCcGoals(_GoalTensors):
     def build(self):
         """asynchronous on torch's current stream"""
         stream = self.torch.cuda.current_stream(self.device).cuda_stream
-        _lib_goals.check(_lib_goals.lib().bmpc_cc_goal_batch_device(C.byref(self.desc), C.c_void_p(stream)))
+        _lib.check(_lib.lib().bmpc_cc_goal_batch_device(C.byref(self.desc), C.c_void_p(stream)))
         return self
 
 
@@ -101,7 +118,7 @@ class DeviceWbCcGoals(_GoalTensors):
         B = int(x.shape[0])
         max_rows = episode_length + 1 if max_rows is None else max_rows
         max_events = default_max_events(gait, episode_length, sim_dt) if max_events is None else max_events
-        d = _lib_goals.CcGoalWbBatch()
+        d = _lib.CcGoalWbBatch()
         self._sizes(d.g, gait, B, episode_length, goal_horizon, max_rows, max_events, sim_dt)
         self.B, self.dev_model = B, dev_model
         d.model = dev_model.h
@@ -124,5 +141,5 @@ class DeviceWbCcGoals(_GoalTensors):
 
     def build(self):
         stream = self.torch.cuda.current_stream(self.device).cuda_stream
-        _lib_goals.check(_lib_goals.lib().bmpc_cc_goal_wb_batch_device(C.byref(self.desc), C.c_void_p(stream)))
+        _lib.check(_lib.lib().bmpc_cc_goal_wb_batch_device(C.byref(self.desc), C.c_void_p(stream)))
         return self

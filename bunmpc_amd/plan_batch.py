@@ -2,10 +2,11 @@
 X_ter for B problems from their current CoM / feet / time / desired velocities, left in HBM for
 `bmpc_biconvex_solve_batch_device`.  Device counterpart of problems.contact_plan / centroidal_costs."""
 import ctypes as C
+import math
 
 import numpy as np
 
-from . import _lib, _lib_turn
+from . import _lib
 
 
 def gait_struct(gait, offsets_xy):
@@ -36,6 +37,17 @@ class DeviceTerrain:
         t.nx, t.ny, t.x0, t.y0, t.cell = hm.nx, hm.ny, hm.x0, hm.y0, hm.cell
         t.heights, t.sheights = self.heights.data_ptr(), hm.nx * hm.ny if hm.per_problem else 0
         self.desc = t
+
+
+def turn_struct(yaw_inertia, w_des=None):
+    """bmpc_turn_t; w_des: a device tensor (B,) of float64 (the whole-body call) or None (the centroidal-level call).  A yaw inertia
+    the C calls would refuse raises here, where the caller's argument has a name."""
+    yaw_inertia = float(yaw_inertia)
+    if not (math.isfinite(yaw_inertia) and yaw_inertia > 0.0):
+        raise ValueError("yaw_inertia must be finite and > 0, got %r" % (yaw_inertia,))
+    t = _lib.Turn()
+    t.w_des, t.yaw_inertia = None if w_des is None else w_des.data_ptr(), yaw_inertia
+    return t
 
 
 def _turn_call(fn, plan, stream):
@@ -87,13 +99,13 @@ class DevicePlan:
         for k in ("cnt_plan", "swing_time", "dt", "X_nom", "X_ter"):
             setattr(d, k, getattr(self, k).data_ptr())
         self.desc = d
-        self.turn = None if yaw_inertia is None else _lib_turn.turn_struct(yaw_inertia)
+        self.turn = None if yaw_inertia is None else turn_struct(yaw_inertia)
 
     def build(self):
         """asynchronous on torch's current stream"""
         stream = self.torch.cuda.current_stream(self.device).cuda_stream
         if self.turn is not None:
-            _lib.check(_turn_call(_lib_turn.lib().bmpc_plan_batch_turn_device, self, stream))
+            _lib.check(_turn_call(_lib.lib().bmpc_plan_batch_turn_device, self, stream))
         elif self.terrain is None:
             _lib.check(_lib.lib().bmpc_plan_batch_device(C.byref(self.desc), C.c_void_p(stream)))
         else:
@@ -155,7 +167,7 @@ class DeviceWbPlan:
         self.turn = self.w_cmd = None
         if yaw_inertia is not None:
             self.w_cmd = z(B).zero_()
-            self.turn = _lib_turn.turn_struct(yaw_inertia, self.w_cmd)
+            self.turn = turn_struct(yaw_inertia, self.w_cmd)
         self._set_commands(w_des)
 
     def _set_commands(self, w_des):
@@ -182,7 +194,7 @@ class DeviceWbPlan:
     def build(self):
         stream = self.torch.cuda.current_stream(self.device).cuda_stream
         if self.turning:
-            _lib.check(_turn_call(_lib_turn.lib().bmpc_wb_plan_batch_turn_device, self, stream))
+            _lib.check(_turn_call(_lib.lib().bmpc_wb_plan_batch_turn_device, self, stream))
         elif self.terrain is None:
             _lib.check(_lib.lib().bmpc_wb_plan_batch_device(C.byref(self.desc), C.c_void_p(stream)))
         else:

@@ -1,7 +1,7 @@
 /* bunmpc_foot_pairs.h -- the switch and the telemetry of the headline kernel's force loop with two feet per lane: the fourth header of
  * libbunmpc_hip.so.  A header of its own, as bunmpc_turn.h and bunmpc_goals.h are: the table of bunmpc.h (tests/golden/abi.json) is held
  * to its recorded size by tests/test_abi_cpu.py, so what is added to the library's interface is declared beside it.  It includes
- * nothing; bunmpc_amd/_lib_foot_pairs.py reads it with the reader of bunmpc.h.
+ * nothing; bunmpc_amd/_lib.py reads it with the reader of bunmpc.h.
  *
  * The loop-constants build of the benchmark's kernel (bmpc_set_loop_constants_in_lds in bunmpc.h; DESIGN.md section 4, "Force loop: two
  * feet per lane"): a swing foot's force is +0 throughout a certified force loop, so a force phase whose two problems need at most 32

@@ -6,7 +6,7 @@
  * (utils.py:36-102), for B problems at once and without leaving HBM.  Planner-derived goals only: the goals that the data collection
  * builds from contacts measured in the simulator (simulation.py:563-568) are not computed here.
  *
- * The header stands alone: it includes nothing and declares its own structs (bunmpc_amd/_lib_goals.py reads it with the reader of
+ * The header stands alone: it includes nothing and declares its own structs (bunmpc_amd/_lib.py reads it with the reader of
  * bunmpc.h).  Status codes and bmpc_last_error() are those of bunmpc.h; `model` is a bmpc_model_t * of bmpc_model_create.
  *
  * Per problem b, in the reference's order:

@@ -5,7 +5,7 @@
  * iterative_supervised_learning), for B problems at once on top of bmpc_plan_batch_device / bmpc_wb_plan_batch_device and their
  * terrain variants (bunmpc.h).  bunmpc_amd/cyclic_gen.py is the host mirror the tests hold these calls to, problem by problem.
  *
- * The header stands alone: it includes nothing and refers to the structs of bunmpc.h as const void * (bunmpc_amd/_lib_turn.py reads it
+ * The header stands alone: it includes nothing and refers to the structs of bunmpc.h as const void * (bunmpc_amd/_lib.py reads it
  * with the reader of bunmpc.h).  Status codes and bmpc_last_error() are those of bunmpc.h.
  *
  * Per problem b, with w = w_des[b]; the branch is on w != 0 exactly, as in the reference (a NaN takes the turning branch and gives a

@@ -13,7 +13,6 @@ and writes, per solve,
                                  (every launch covers all B problems then) after the second chunk (the first two are enqueued before the
                                  host's first look: active = B)
 The CPU test asks bmpc_ik_plan_iteration the same questions; the GPU test solves a few of them again (run())."""
-import contextlib
 import ctypes as C
 import functools
 import hashlib
@@ -78,15 +77,10 @@ def load():
         return json.load(f)["solves"]
 
 
-@contextlib.contextmanager
-def knobs(lib, values):
-    """process defaults set for the block, restored after it"""
-    old = {k: getattr(lib, "bmpc_ik_set_" + KNOB_SETTERS[k])(v) for k, v in values.items()}
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            getattr(lib, "bmpc_ik_set_" + KNOB_SETTERS[k])(v)
+def knobs(values):
+    """process defaults set for the block, restored after it: bunmpc_amd._lib.knobs by the short keys of the table"""
+    from bunmpc_amd import _lib
+    return _lib.knobs(**{"ik_" + KNOB_SETTERS[k]: v for k, v in values.items()})
 
 
 def sched_of(fields):
@@ -159,7 +153,6 @@ class IkDeviceBatch:
 
 def run(solve):
     """the solve under its knobs: (iters_run, last derivative kernel, digest)"""
-    from bunmpc_amd import _lib
     name, B, n_col, has_list, knob_values, sched = solve
-    with knobs(_lib.lib(), knob_values):
+    with knobs(knob_values):
         return IkDeviceBatch(B, n_col, has_list, sched).solve()

@@ -20,29 +20,13 @@ from bunmpc_amd import batch as bb
 from bunmpc_amd import problems
 from tests import bandq
 from tests.bandq import LF, LX
-from tests.util import K_SPREAD, rel_l2
+from tests.util import K_SPREAD, knobs, launch_record, rel_l2  # noqa: F401  (knobs: the fixture)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
 KQ = "biconvex_admm_kq_kernel"
 ALL = ("X", "F", "P", "L_x", "L_f", "stats", "hist", "trace", "dyn_viol")
 MAPPINGS = [(3, 16), (15, 16), (20, 21), (20, 32), (31, 32), (63, 64)]
-
-
-@pytest.fixture
-def knobs(hiplib):
-    """sets dispatch knobs for one test and restores every one of them afterwards"""
-    saved = []
-
-    def set_(name, value):
-        saved.append((name, getattr(hiplib, name)(value)))
-    yield set_
-    for name, old in reversed(saved):
-        getattr(hiplib, name)(old)
-
-
-def _launch(hiplib):
-    return hiplib.bmpc_biconvex_last_kernel_name().decode(), hiplib.bmpc_biconvex_last_lanes_per_problem(), hiplib.bmpc_biconvex_last_waves_per_simd()
 
 
 def _against_restatement(oracle, hiplib, knobs, config, H, lanes, mode, lam, sides="xf", may_skip=0):
@@ -53,7 +37,7 @@ def _against_restatement(oracle, hiplib, knobs, config, H, lanes, mode, lam, sid
     b, pre, rc, raw = bandq.case(oracle, config, 6, H, lam=lam, sides=sides)
     kw = dict(warm=b.warm_start(), L_x=LX, L_f=LF) if mode == "warm" else {}
     got = bb.solve_host(b, num_iters=iters, raw=raw, **kw)
-    assert _launch(hiplib) == (KQ, lanes, 1)
+    assert launch_record(hiplib) == (KQ, lanes, 1)
     retries, skipped, worst = 0, [], 0.0
     for i in range(b.B):
         kwi = dict(warm=kw["warm"], L_x=LX[i], L_f=LF[i]) if mode == "warm" else {}
@@ -121,11 +105,11 @@ def test_zero_coupling_matches_the_diagonal_kernel(oracle, hiplib, knobs, config
     zero = dict(Qx_off=np.zeros((6, b.H, 9)), Qf_off=np.zeros((6, b.H - 1, 3 * b.E)))
     kw = dict(num_iters=3, warm=b.warm_start(), L_x=LX, L_f=LF)
     ref = bb.solve_host(b, raw=raw, **kw)
-    assert _launch(hiplib)[0] == "biconvex_admm_kernel"
+    assert launch_record(hiplib)[0] == "biconvex_admm_kernel"
     assert ref["stats"][:, 3].sum() > 0 and ref["stats"][:, 4].sum() > 0
     for sides in (("Qx_off", "Qf_off"), ("Qx_off",), ("Qf_off",)):
         got = bb.solve_host(b, raw=dict(raw, **{k: zero[k] for k in sides}), **kw)
-        assert _launch(hiplib)[0] == KQ
+        assert launch_record(hiplib)[0] == KQ
         assert np.array_equal(got["stats"], ref["stats"]), sides
         assert np.array_equal(got["L_x"], ref["L_x"]) and np.array_equal(got["L_f"], ref["L_f"]), sides
         for k in "XFP":
@@ -141,13 +125,13 @@ def test_band_calls_without_coupling_are_the_plain_calls(hiplib):
     b = problems.make_batch("solo12_trot", 9)
     dev = bb.DeviceBatch(b, device="cuda:0", num_iters=3)
     dev.solve()
-    want, kernel = dev.results(), _launch(hiplib)
+    want, kernel = dev.results(), launch_record(hiplib)
     stream = C.c_void_p(torch.cuda.current_stream(dev.device).cuda_stream)
     for c in (C.byref(_lib.BandCost()), None):
         dev.X.zero_()
         _lib.check(hiplib.bmpc_biconvex_solve_batch_band_device(C.byref(dev.desc), c, stream))
         got = dev.results()
-        assert _launch(hiplib) == kernel and kernel[0] != KQ
+        assert launch_record(hiplib) == kernel and kernel[0] != KQ
         for k in ("X", "F", "P", "L_x", "L_f", "stats"):
             assert np.array_equal(got[k], want[k]), k
 
@@ -165,9 +149,9 @@ def test_a_diverging_problem_leaves_its_wave_mates_alone(oracle, hiplib, knobs, 
         bad_b.x_init[i, 2] = 1e200
         bad_raw["qx"][i] = 1e200
     clean = bb.solve_host(b, num_iters=4, raw=raw)
-    assert _launch(hiplib) == (KQ, 21, 1)
+    assert launch_record(hiplib) == (KQ, 21, 1)
     got = bb.solve_host(bad_b, num_iters=4, raw=bad_raw)
-    assert _launch(hiplib) == (KQ, 21, 1)
+    assert launch_record(hiplib) == (KQ, 21, 1)
     for i in (1, 4):
         assert got["stats"][i, 5] == 2, got["stats"][i]
         assert not np.isfinite(got["X"][i]).all()
@@ -184,7 +168,7 @@ def test_shared_coupling_equals_tiled_coupling(oracle, hiplib):
     tiled = dict(raw, Qx_off=np.repeat(rc["Qx_off"][2:3], 7, axis=0), Qf_off=np.repeat(rc["Qf_off"][2:3], 7, axis=0))
     kw = dict(num_iters=3, warm=b.warm_start(), L_x=np.resize(LX, 7), L_f=np.resize(LF, 7), keep_hist=True)
     a, t = bb.solve_host(b, raw=shared, **kw), bb.solve_host(b, raw=tiled, **kw)
-    assert _launch(hiplib)[0] == KQ
+    assert launch_record(hiplib)[0] == KQ
     for k in ALL:
         assert np.array_equal(a[k], t[k], equal_nan=True), k
     assert a["stats"][:, 3:5].sum() > 0
@@ -198,7 +182,7 @@ def test_switches_do_not_change_band_results(oracle, hiplib, knobs, knob, values
     for v in values:
         knobs(knob, v)
         out.append(bb.solve_host(b, num_iters=iters, raw=raw, warm=b.warm_start(), L_x=np.resize(LX, 12), L_f=np.resize(LF, 12), keep_hist=True))
-        assert _launch(hiplib)[0] == KQ and _launch(hiplib)[2] == 1
+        assert launch_record(hiplib)[0] == KQ and launch_record(hiplib)[2] == 1
     for k in ("X", "F", "P", "stats", "hist", "trace"):
         assert np.array_equal(out[0][k], out[1][k], equal_nan=True), k
 
@@ -214,14 +198,14 @@ def test_dispatch_of_band_batches(oracle, hiplib):
         raw = dict(Qx=rc["Qx"], qx=pre["qx"], lbx=pre["lbx"], ubx=pre["ubx"], Qf=rc["Qf"], Qx_off=rc["Qx_off"], Qf_off=rc["Qf_off"])
         for iters in (1, 30):
             got = bb.solve_host(b, num_iters=iters, raw=raw)
-            assert _launch(hiplib)[0] == KQ and _launch(hiplib)[2] == 1, (B, iters)
+            assert launch_record(hiplib)[0] == KQ and launch_record(hiplib)[2] == 1, (B, iters)
             if B == 1:
                 first[iters] = got
             else:
                 for k in ("X", "F", "P", "L_x", "L_f", "stats"):
                     assert np.array_equal(got[k][0], first[iters][k][0]), (iters, k)
         bb.solve_host(b, num_iters=1, raw={k: pre[k] for k in ("Qx", "qx", "lbx", "ubx", "Qf")})
-        assert _launch(hiplib)[0] == today, B
+        assert launch_record(hiplib)[0] == today, B
     s4, s2 = hiplib.bmpc_biconvex_band_kernel_scratch_bytes(4), hiplib.bmpc_biconvex_band_kernel_scratch_bytes(2)
     print("SCRATCH bytes per lane: four feet", s4, "two feet", s2)
     assert s4 >= 0 and s2 >= 0
@@ -233,7 +217,7 @@ def test_device_batch_carries_coupling(oracle, hiplib):
     dev = bb.DeviceBatch(b, device="cuda:0", num_iters=3, raw=raw)
     dev.solve()
     got = dev.results()
-    assert _launch(hiplib)[0] == KQ
+    assert launch_record(hiplib)[0] == KQ
     for k in ("X", "F", "P", "L_x", "L_f", "stats"):
         assert np.array_equal(got[k], host[k]), k
 
@@ -265,7 +249,7 @@ def test_dropin_takes_sparse_band_costs(oracle, hiplib, config, E):
         mp = BiconvexMP(b.m, 20, E)
         mp.set_rho(b.rho)
         got = _drive(mp, b, i, pre, sp.csr_matrix(Qx), pre["qx"][i], sp.csc_matrix(Qf), 3)
-        assert _launch(hiplib)[0] == KQ
+        assert launch_record(hiplib)[0] == KQ
         r = bandq.restatement(b, i, raw, 3, warm=b.warm_start(), L_x=LX[i], L_f=LF[i])
         print(config, i, got["stats"].tolist(), r["stats"].tolist(), {k: rel_l2(got[k], r[k]) for k in "XFP"})
         assert np.array_equal(got["stats"], r["stats"]) and got["L"] == (r["L_x"], r["L_f"])
@@ -275,12 +259,12 @@ def test_dropin_takes_sparse_band_costs(oracle, hiplib, config, E):
         fresh = BiconvexMP(b.m, 20, E)
         fresh.set_rho(b.rho)
         want = _drive(fresh, b, i, pre, pre["Qx"][i], pre["qx"][i], sp.diags(pre["Qf"][i]), 3)
-        assert _launch(hiplib)[0] != KQ
+        assert launch_record(hiplib)[0] != KQ
         # the same handle: X back to a diagonal while F keeps its coupling is still the band kernel; both diagonal: the diagonal path
         _drive(mp, b, i, pre, np.diag(pre["Qx"][i]), pre["qx"][i], None, 3)
-        assert _launch(hiplib)[0] == KQ
+        assert launch_record(hiplib)[0] == KQ
         again = _drive(mp, b, i, pre, pre["Qx"][i], pre["qx"][i], pre["Qf"][i], 3)
-        assert _launch(hiplib)[0] != KQ
+        assert launch_record(hiplib)[0] != KQ
         for k in ("X", "F", "P", "stats"):
             assert np.array_equal(again[k], want[k]), (i, k)
         assert again["L"] == want["L"]

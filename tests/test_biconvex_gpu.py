@@ -8,8 +8,8 @@ oracle itself is pinned only by its numpy twin (no reference golden vectors exis
 import numpy as np
 import pytest
 
+from bunmpc_amd import _lib, problems
 from bunmpc_amd import batch as bb
-from bunmpc_amd import problems
 from tests.util import cpu_spread, rel_l2, within_envelope
 
 pytestmark = pytest.mark.gpu
@@ -17,7 +17,6 @@ TOL = 1e-5
 
 
 def test_lane_exchange_selftest(hiplib):
-    from bunmpc_amd import _lib
     _lib.check(hiplib.bmpc_selftest_lanes())
 
 
@@ -238,7 +237,6 @@ def test_long_horizons_before_the_chaos_sets_in(oracle, hiplib, H, B, raw):
 
 
 def test_unsupported_shapes_are_refused():
-    from bunmpc_amd import _lib
     b = problems.make_batch("solo12_trot", 1, H=256)
     with pytest.raises(_lib.BmpcError) as e:
         bb.solve_host(b, num_iters=1)
@@ -269,11 +267,8 @@ def test_diverging_problem_does_not_poison_neighbours(oracle, hiplib, mapping, w
     the problems sharing its wave (one with 32-lane segments, two with 21-lane segments: "batch3") are bit-for-bit what they are
     when solved without that neighbour."""
     mapping("wave" if which == "wave" else "batch")
-    old3 = hiplib.bmpc_set_three_per_wave(1 if which == "batch3" else 0)
-    try:
+    with _lib.knobs(three_per_wave=1 if which == "batch3" else 0):
         _diverging_problem_body(oracle, hiplib, which)
-    finally:
-        hiplib.bmpc_set_three_per_wave(old3)
 
 
 def _diverging_problem_body(oracle, hiplib, which):
@@ -345,12 +340,9 @@ def test_three_problems_per_wave_equal_two_per_wave(oracle, hiplib, mapping, con
     assert 17 <= b.H + 1 <= 21
     out = {}
     for on in (1, 0):
-        old = hiplib.bmpc_set_three_per_wave(on)
-        try:
+        with _lib.knobs(three_per_wave=on):
             out[on] = bb.solve_host(b, num_iters=iters, keep_hist=True)
             assert hiplib.bmpc_biconvex_last_lanes_per_problem() == (21 if on else 32)
-        finally:
-            hiplib.bmpc_set_three_per_wave(old)
     same = np.all(out[1]["trace"] == out[0]["trace"], axis=(1, 2))
     print("%s B=%d H=%d: %d of %d problems on the same discrete path in both mappings" % (config, B, b.H, same.sum(), B))
     assert same.mean() >= (0.6 if config == "solo12_mixed" else 0.9)      # (bound / pace: the chaotic regime, where any rounding difference flips counts)
@@ -375,8 +367,7 @@ def test_result_does_not_depend_on_the_segment(hiplib, mapping):
     each other (tests/test_lane_probe_gpu.py), halved under the root, plus two roundings: under 9u; 16u asserted."""
     mapping("batch")
     u = 2.0 ** -53
-    old3, olds = hiplib.bmpc_set_three_per_wave(1), hiplib.bmpc_set_work_stealing(0)
-    try:
+    with _lib.knobs(three_per_wave=1, work_stealing=0):
         for config, B in (("solo12_trot", 6), ("solo12_mixed", 7)):
             for H in (20, 17):      # (17: idle lanes inside the segments)
                 b = problems.make_batch(config, B, H=H)
@@ -395,9 +386,6 @@ def test_result_does_not_depend_on_the_segment(hiplib, mapping):
                         rel = np.abs(x[ran] - y[ran]) / np.maximum(np.abs(y[ran]), 1e-300)
                         print("%s H=%d %s: %d of %d values differ between two placements, at most %.2f u" % (config, H, k, (rel > 0).sum(), rel.size, rel.max() / u))
                         assert np.all(rel <= 16 * u), (config, H, k, rel.max() / u)
-    finally:
-        hiplib.bmpc_set_three_per_wave(old3)
-        hiplib.bmpc_set_work_stealing(olds)
 
 
 @pytest.mark.parametrize("config,B,H,iters,warm", [("solo12_trot", 100, None, 10, False), ("solo12_mixed", 31, None, 10, False), ("solo12_trot", 9, 12, 4, False),
@@ -410,21 +398,15 @@ def test_two_waves_per_simd_build_is_bit_identical(hiplib, mapping, config, B, H
     lanes per problem, two / four waves per problem (horizons of 100 and 200 knots), partly filled waves, the chaotic mixed-gait batch, warm starts with carried step constants."""
     mapping("batch")
     b = problems.make_batch(config, B, H=H) if H else problems.make_batch(config, B)
-    old3 = hiplib.bmpc_set_three_per_wave(0)
     out = {}
-    try:
+    with _lib.knobs(three_per_wave=0):
         for mode in (1, 0):
-            old = hiplib.bmpc_set_two_waves_per_simd(mode)
-            try:
+            with _lib.knobs(two_waves_per_simd=mode):
                 r = bb.solve_host(b, num_iters=iters, keep_hist=True)
                 assert hiplib.bmpc_biconvex_last_waves_per_simd() == (2 if mode else 1)
                 if warm:      # a second call of the same solver objects: iterates and step constants carried over
                     r = bb.solve_host(b, num_iters=iters, keep_hist=True, warm=(r["X"], r["F"], r["P"]), L_x=r["L_x"], L_f=r["L_f"])
                 out[mode] = r
-            finally:
-                hiplib.bmpc_set_two_waves_per_simd(old)
-    finally:
-        hiplib.bmpc_set_three_per_wave(old3)
     for k in ("X", "F", "P", "L_x", "L_f", "stats", "trace"):
         assert np.array_equal(out[1][k], out[0][k]), k
     for k in ("hist", "dyn_viol"):
@@ -439,14 +421,11 @@ def test_three_per_wave_at_two_waves_per_simd_full_chip(oracle, hiplib):
     b = problems.make_batch("solo12_trot", B)
     out = {}
     for mode in (2, 0):
-        old = hiplib.bmpc_set_two_waves_per_simd(mode)
-        try:
+        with _lib.knobs(two_waves_per_simd=mode):
             dev = bbm.DeviceBatch(b, num_iters=10, keep_hist=True)
             dev.solve()
             out[mode] = dev.results()
             assert hiplib.bmpc_biconvex_last_lanes_per_problem() == 21 and hiplib.bmpc_biconvex_last_waves_per_simd() == (2 if mode else 1)
-        finally:
-            hiplib.bmpc_set_two_waves_per_simd(old)
     for k in ("X", "F", "P", "L_x", "L_f", "stats", "trace", "hist", "dyn_viol"):
         assert np.array_equal(out[2][k], out[0][k], equal_nan=True), k
     idx = np.arange(0, B, B // 48)[:48]
@@ -464,16 +443,11 @@ def test_work_stealing_kernel_at_two_waves_per_simd(hiplib):
     b = problems.make_batch("solo12_trot", 4099)
     out = {}
     for mode in (1, 0):
-        old = hiplib.bmpc_set_two_waves_per_simd(mode)
-        oldg = hiplib.bmpc_set_steal_grid(1536 if mode else 0)
-        try:
+        with _lib.knobs(two_waves_per_simd=mode, steal_grid=1536 if mode else 0):
             dev = bbm.DeviceBatch(b, num_iters=100, keep_hist=True)
             dev.solve()
             out[mode] = dev.results()
             assert hiplib.bmpc_biconvex_last_kernel_name().decode() == "biconvex_admm_steal_kernel" and hiplib.bmpc_biconvex_last_waves_per_simd() == mode + 1
-        finally:
-            hiplib.bmpc_set_two_waves_per_simd(old)
-            hiplib.bmpc_set_steal_grid(oldg)
     for k in ("X", "F", "P", "L_x", "L_f", "stats", "trace"):
         assert np.array_equal(out[1][k], out[0][k]), k
     assert np.allclose(out[1]["dyn_viol"], out[0]["dyn_viol"], rtol=1e-12, atol=0)
@@ -493,12 +467,9 @@ def test_two_waves_per_simd_raw_form_is_bit_identical(hiplib, mapping):
             raw["qf"] = rng.normal(0.0, 1e-3, (b.B, nf))
         out = {}
         for mode in (1, 0):
-            old = hiplib.bmpc_set_two_waves_per_simd(mode)
-            try:
+            with _lib.knobs(two_waves_per_simd=mode):
                 out[mode] = bb.solve_host(b, num_iters=4, keep_hist=True, raw=raw)
                 assert hiplib.bmpc_biconvex_last_waves_per_simd() == (2 if mode else 1)
-            finally:
-                hiplib.bmpc_set_two_waves_per_simd(old)
         for k in ("X", "F", "P", "L_x", "L_f", "stats", "trace", "hist"):
             assert np.array_equal(out[1][k], out[0][k], equal_nan=True), (with_qf, k)
 
@@ -514,8 +485,7 @@ def test_work_stealing_does_not_change_results(hiplib):
     b = problems.make_batch("solo12_trot", B)
     out = {}
     for on in (1, 0):
-        old = hiplib.bmpc_set_work_stealing(on)
-        try:
+        with _lib.knobs(work_stealing=on):
             dev = bbm.DeviceBatch(b, num_iters=100, keep_hist=True)
             dev.solve()
             out[on] = dev.results()
@@ -524,8 +494,6 @@ def test_work_stealing_does_not_change_results(hiplib):
             dev.solve()                      # a second launch: another counter of the ring, the same results
             again = dev.results()
             assert np.array_equal(again["X"], out[on]["X"]) and np.array_equal(again["stats"], out[on]["stats"])
-        finally:
-            hiplib.bmpc_set_work_stealing(old)
     n = out[1]["stats"][:, 0]
     print("work stealing: ADMM iterations min %d median %d max %d over %d problems" % (n.min(), np.median(n), n.max(), B))
     assert n.min() < 60 and n.max() == 100 and np.all(out[1]["stats"][:, 5] == 0)
@@ -538,15 +506,12 @@ def test_work_stealing_does_not_change_results(hiplib):
     # then read a problem's iterates and L from the arrays when they take it, not only at the start of the launch
     warm = {}
     for on in (1, 0):
-        old = hiplib.bmpc_set_work_stealing(on)
-        try:
+        with _lib.knobs(work_stealing=on):
             dev = bbm.DeviceBatch(b, num_iters=40)
             dev.set_warm_start(out[0]["X"], out[0]["F"], out[0]["P"], L_x=out[0]["L_x"] * 1.5, L_f=out[0]["L_f"] * 0.5)
             dev.solve()
             warm[on] = dev.results()
             assert hiplib.bmpc_biconvex_last_kernel_name().decode() == ("biconvex_admm_steal_kernel" if on else "biconvex_admm_kernel")
-        finally:
-            hiplib.bmpc_set_work_stealing(old)
     for k in ("X", "F", "P", "L_x", "L_f", "stats"):
         assert np.array_equal(warm[1][k], warm[0][k]), k
     assert len(np.unique(warm[1]["stats"][:, 0])) > 3
@@ -626,7 +591,6 @@ def test_fp32_variant_with_fp64_residual_check(oracle, config, B, H):
         r = np.linalg.norm(A @ d32["X"][i] - bf)
         assert abs(r - d32["dyn_viol"][i]) <= 1e-4 * max(r, 1e-3), (i, r, d32["dyn_viol"][i])
     # the raw cost form is fp64 only: refused with BMPC_BAD_ARG, nothing launched
-    from bunmpc_amd import _lib
     nx, nf = 9 * (b.H + 1), 12 * b.H
     raw = dict(Qx=np.ones((B, nx)), qx=np.zeros((B, nx)), lbx=np.full((B, nx), -np.inf), ubx=np.full((B, nx), np.inf),
                Qf=np.ones((B, nf)))
@@ -638,12 +602,10 @@ def test_fp32_variant_with_fp64_residual_check(oracle, config, B, H):
 @pytest.fixture
 def mapping(hiplib):
     """selects the kernel: 'batch' = one knot per lane (biconvex_admm.hip), 'wave' = one problem per wave (biconvex_latency.hip)"""
-    old = hiplib.bmpc_set_latency_mapping_max_batch(0)
-
     def choose(which):
         hiplib.bmpc_set_latency_mapping_max_batch({"batch": 0, "wave": 1 << 30}[which])
-    yield choose
-    hiplib.bmpc_set_latency_mapping_max_batch(old)
+    with _lib.knobs(latency_mapping_max_batch=0):
+        yield choose
 
 
 @pytest.mark.parametrize("config,B,H,iters", [("solo12_trot", 16, None, 10), ("solo12_trot_nominal", 1, None, 10), ("solo12_mixed", 12, None, 1),
@@ -680,11 +642,8 @@ def test_fp32_shortcut_of_the_step_decisions_changes_nothing(hiplib, mapping):
     X0, F0, P0 = b.warm_start()
 
     def run(exact):
-        old = hiplib.bmpc_set_exact_step_decisions(exact)
-        try:
+        with _lib.knobs(exact_step_decisions=exact):
             return bb.solve_host(b, num_iters=10, warm=(X0, F0, P0), L_x=Lx, L_f=Lf, keep_hist=True)
-        finally:
-            hiplib.bmpc_set_exact_step_decisions(old)
     fast, exact = run(0), run(1)
     assert hiplib.bmpc_biconvex_last_kernel_name().decode() == "biconvex_latency_kernel"
     for k in ("X", "F", "P", "L_x", "L_f", "stats", "hist", "dyn_viol"):

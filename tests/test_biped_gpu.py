@@ -10,29 +10,13 @@ import pytest
 from bunmpc_amd import _lib
 from bunmpc_amd import batch as bb
 from bunmpc_amd import problems
-from tests.util import chaos_ensemble, cpu_spread, prefix_parity, rel_l2
+from tests.util import chaos_ensemble, cpu_spread, knobs, launch_record, prefix_parity, rel_l2  # noqa: F401  (knobs: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5      # the golden fixtures' tolerance (tests/test_biconvex_gpu.py)
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FP32_MEDIAN, FP32_P95, FP32_MAX = 5e-6, 1e-5, 1e-2      # tests/test_parity_envelope_gpu.py
-
-
-@pytest.fixture
-def knobs(hiplib):
-    """sets dispatch knobs for one test and restores every one of them afterwards"""
-    saved = []
-
-    def set_(name, value):
-        saved.append((name, getattr(hiplib, name)(value)))
-    yield set_
-    for name, old in reversed(saved):
-        getattr(hiplib, name)(old)
-
-
-def _launch(hiplib):
-    return hiplib.bmpc_biconvex_last_kernel_name().decode(), hiplib.bmpc_biconvex_last_lanes_per_problem(), hiplib.bmpc_biconvex_last_waves_per_simd()
 
 
 def _parity(oracle, b, sub, iters, got, members=16, ens=None):
@@ -74,7 +58,7 @@ def test_latency_mapping_and_exact_step_decisions(oracle, hiplib, knobs, walk409
     b, sub, ens = walk4096
     small = b.slice(0, 1024)
     got = bb.solve_host(small, num_iters=10, keep_hist=True)
-    assert _launch(hiplib)[:2] == ("biconvex_latency_kernel", 0)
+    assert launch_record(hiplib)[:2] == ("biconvex_latency_kernel", 0)
     pick = sub < 1024
     _parity(oracle, small, sub[pick], 10, got, ens={k: v[pick] for k, v in ens.items()})
     b64 = problems.make_batch("biped_walk", 64)
@@ -85,7 +69,7 @@ def test_latency_mapping_and_exact_step_decisions(oracle, hiplib, knobs, walk409
     for exact in (0, 1):
         knobs("bmpc_set_exact_step_decisions", exact)
         out[exact] = bb.solve_host(b64, num_iters=10, warm=(X0, F0, P0), L_x=Lx, L_f=Lf, keep_hist=True)
-        assert _launch(hiplib)[0] == "biconvex_latency_kernel"
+        assert launch_record(hiplib)[0] == "biconvex_latency_kernel"
     for k in ("X", "F", "P", "L_x", "L_f", "stats", "trace", "hist", "dyn_viol"):
         assert np.array_equal(out[0][k], out[1][k], equal_nan=True), k
     assert out[0]["stats"][:, 3].sum() > 0 and out[0]["stats"][:, 4].sum() > 0
@@ -104,7 +88,7 @@ def test_three_and_two_problems_per_wave_both_builds(oracle, hiplib, knobs, walk
         for wpe in (1, 2):
             knobs("bmpc_set_two_waves_per_simd", 1 if wpe == 2 else 0)
             out[lpp, wpe] = bb.solve_host(b, num_iters=10, keep_hist=True)
-            assert _launch(hiplib) == ("biconvex_admm_kernel", lpp, wpe)
+            assert launch_record(hiplib) == ("biconvex_admm_kernel", lpp, wpe)
         for k in ("X", "F", "P", "L_x", "L_f", "stats", "trace", "hist", "dyn_viol"):
             assert np.array_equal(out[lpp, 1][k], out[lpp, 2][k], equal_nan=True), (lpp, k)
         _parity(oracle, b, sub, 10, out[lpp, 1], ens=ens)
@@ -125,7 +109,7 @@ def test_sixteen_and_sixty_four_lanes_both_builds(oracle, hiplib, knobs, H, lpp)
     for wpe in (1, 2):
         knobs("bmpc_set_two_waves_per_simd", 1 if wpe == 2 else 0)
         out[wpe] = bb.solve_host(b, num_iters=10, keep_hist=True)
-        assert _launch(hiplib) == ("biconvex_admm_kernel", lpp, wpe)
+        assert launch_record(hiplib) == ("biconvex_admm_kernel", lpp, wpe)
     for k in ("X", "F", "P", "L_x", "L_f", "stats", "trace", "hist", "dyn_viol"):
         assert np.array_equal(out[1][k], out[2][k], equal_nan=True), k
     _parity(oracle, b, np.arange(0, 96, 8), 10, out[1])
@@ -139,7 +123,7 @@ def test_raw_form_on_the_batch_kernel(oracle, hiplib, knobs):
     knobs("bmpc_set_latency_mapping_max_batch", 0)
     for qf in (None, 0.1 * np.ones_like(ref["Qf"])):
         got = bb.solve_host(b, num_iters=5, raw=dict(raw, qf=qf))
-        assert _launch(hiplib)[0] == "biconvex_admm_kernel"
+        assert launch_record(hiplib)[0] == "biconvex_admm_kernel"
         for i in range(b.B):
             X0, F0, P0 = b.warm_start()
             r = oracle.biconvex_solve(b.cnt_plan[i], b.dt[i], b.m, b.x_init[i], raw["Qx"][i], raw["qx"][i], raw["Qf"][i], raw["lbx"][i],
@@ -154,7 +138,7 @@ def test_fp32_harness_form(oracle, hiplib):
     b = problems.make_batch("biped_walk", B)
     ref, spread = cpu_spread(b, 10, oracle, with_numpy=False)
     got = bb.solve_host(b, num_iters=10, precision="f32")
-    assert _launch(hiplib)[:2] == ("biconvex_admm_kernel_f32", 32)
+    assert launch_record(hiplib)[:2] == ("biconvex_admm_kernel_f32", 32)
     assert np.array_equal(got["stats"][:, [0, 5]], ref["stats"][:, [0, 5]])
     err = np.maximum(rel_l2(got["X"], ref["X"]), rel_l2(got["F"], ref["F"]))
     calm = spread <= 1e-9
@@ -173,7 +157,7 @@ def test_one_problem_per_workgroup(oracle, hiplib, knobs, H, lpp):
     for wpe in (1, 2):
         knobs("bmpc_set_two_waves_per_simd", 1 if wpe == 2 else 0)
         out[wpe] = bb.solve_host(b, num_iters=3, keep_hist=True)
-        assert _launch(hiplib) == ("biconvex_admm_wg_kernel", lpp, wpe)
+        assert launch_record(hiplib) == ("biconvex_admm_wg_kernel", lpp, wpe)
     for k in ("X", "F", "P", "L_x", "L_f", "stats", "trace", "hist", "dyn_viol"):
         assert np.array_equal(out[1][k], out[2][k], equal_nan=True), k
     _parity(oracle, b, np.arange(3), 3, out[1], members=4)
@@ -190,7 +174,7 @@ def test_work_stealing_hundred_iterations(oracle, hiplib, knobs):
         dev = bbm.DeviceBatch(b, num_iters=100, keep_hist=True)
         dev.solve()
         out[on] = dev.results()
-        assert _launch(hiplib)[:2] == ("biconvex_admm_steal_kernel" if on else "biconvex_admm_kernel", 21)
+        assert launch_record(hiplib)[:2] == ("biconvex_admm_steal_kernel" if on else "biconvex_admm_kernel", 21)
     n = out[1]["stats"][:, 0]
     print("biped work stealing: ADMM iterations min %d median %d max %d" % (n.min(), np.median(n), n.max()))
     for k in ("X", "F", "P", "L_x", "L_f", "stats", "trace"):

@@ -13,7 +13,7 @@ import scipy.sparse as sp
 from bunmpc_amd import batch as bb
 from bunmpc_amd import problems
 from tests import blockq_np
-from tests.util import K_SPREAD, rel_l2
+from tests.util import K_SPREAD, knobs, launch_record, rel_l2  # noqa: F401  (knobs: the fixture)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -21,22 +21,6 @@ BQ = "biconvex_admm_bq_kernel"
 LX = np.array([2.25e6, 1e4, 1e5, 3e5, 2.25e6, 5e4])      # test_raw_form_with_backtracking's step constants: retries in both loops
 LF = np.array([506.25, 10.0, 50.0, 506.25, 20.0, 100.0])
 ALL = ("X", "F", "P", "L_x", "L_f", "stats", "hist", "trace", "dyn_viol")
-
-
-@pytest.fixture
-def knobs(hiplib):
-    """sets dispatch knobs for one test and restores every one of them afterwards"""
-    saved = []
-
-    def set_(name, value):
-        saved.append((name, getattr(hiplib, name)(value)))
-    yield set_
-    for name, old in reversed(saved):
-        getattr(hiplib, name)(old)
-
-
-def _launch(hiplib):
-    return hiplib.bmpc_biconvex_last_kernel_name().decode(), hiplib.bmpc_biconvex_last_lanes_per_problem(), hiplib.bmpc_biconvex_last_waves_per_simd()
 
 
 def _case(oracle, config, B, H=None, seed=7):
@@ -58,7 +42,7 @@ def test_block_kernel_matches_the_restatement(oracle, hiplib, knobs, config, H, 
     b, pre, blk, raw = _case(oracle, config, 6, H)
     kw = dict(warm=b.warm_start(), L_x=LX, L_f=LF) if mode == "warm" else {}
     got = bb.solve_host(b, num_iters=iters, raw=raw, **kw)
-    assert _launch(hiplib) == (BQ, lanes, 1)
+    assert launch_record(hiplib) == (BQ, lanes, 1)
     retries = 0
     for i in range(b.B):
         kwi = dict(warm=kw["warm"], L_x=LX[i], L_f=LF[i]) if mode == "warm" else {}
@@ -87,11 +71,11 @@ def test_diagonal_weights_as_blocks_match_the_diagonal_kernel(oracle, hiplib, kn
     flat = problems.block_costs(pre["Qx"], pre["qx"], pre["Qf"], b.E, yaw=0.0, lam=0.0)
     kw = dict(num_iters=3, warm=b.warm_start(), L_x=LX, L_f=LF)
     ref = bb.solve_host(b, raw=raw, **kw)
-    assert _launch(hiplib)[0] == "biconvex_admm_kernel"
+    assert launch_record(hiplib)[0] == "biconvex_admm_kernel"
     assert ref["stats"][:, 3].sum() > 0 and ref["stats"][:, 4].sum() > 0
     for sides in (("Qx_blk", "Qf_blk"), ("Qx_blk",), ("Qf_blk",)):      # a side without blocks: its diagonal, spread by the kernel
         got = bb.solve_host(b, raw=dict(raw, **{k: flat[k] for k in sides}), **kw)
-        assert _launch(hiplib)[0] == BQ
+        assert launch_record(hiplib)[0] == BQ
         assert np.array_equal(got["stats"], ref["stats"]), sides
         for k in "XFP":
             print(config, sides, k, rel_l2(got[k], ref[k]).max())
@@ -104,7 +88,7 @@ def test_shared_blocks_equal_tiled_blocks(oracle, hiplib):
     tiled = dict(raw, Qx_blk=np.repeat(blk["Qx_blk"][2:3], 7, axis=0), Qf_blk=np.repeat(blk["Qf_blk"][2:3], 7, axis=0))
     kw = dict(num_iters=3, warm=b.warm_start(), L_x=np.resize(LX, 7), L_f=np.resize(LF, 7), keep_hist=True)
     a, t = bb.solve_host(b, raw=shared, **kw), bb.solve_host(b, raw=tiled, **kw)
-    assert _launch(hiplib)[0] == BQ
+    assert launch_record(hiplib)[0] == BQ
     for k in ALL:
         assert np.array_equal(a[k], t[k], equal_nan=True), k
     assert a["stats"][:, 3:5].sum() > 0
@@ -118,7 +102,7 @@ def test_switches_do_not_change_block_results(oracle, hiplib, knobs, knob, value
     for v in values:
         knobs(knob, v)
         out.append(bb.solve_host(b, num_iters=iters, raw=raw, warm=b.warm_start(), L_x=np.resize(LX, 12), L_f=np.resize(LF, 12), keep_hist=True))
-        assert _launch(hiplib)[0] == BQ and _launch(hiplib)[2] == 1
+        assert launch_record(hiplib)[0] == BQ and launch_record(hiplib)[2] == 1
     for k in ("X", "F", "P", "stats", "hist", "trace"):
         assert np.array_equal(out[0][k], out[1][k], equal_nan=True), k
 
@@ -132,9 +116,9 @@ def test_dispatch_of_block_batches(oracle, hiplib):
         blk = problems.block_costs(pre["Qx"][:1], pre["qx"][:1], pre["Qf"][:1], b.E, yaw=0.4)
         for iters in (1, 30):
             bb.solve_host(b, num_iters=iters, raw=dict(raw, Qx_blk=blk["Qx_blk"], Qf_blk=blk["Qf_blk"]))
-            assert _launch(hiplib)[0] == BQ, (B, iters)
+            assert launch_record(hiplib)[0] == BQ, (B, iters)
         bb.solve_host(b, num_iters=1, raw=raw)
-        assert _launch(hiplib)[0] == today, B
+        assert launch_record(hiplib)[0] == today, B
     assert hiplib.bmpc_biconvex_block_kernel_scratch_bytes(4) >= 0 and hiplib.bmpc_biconvex_block_kernel_scratch_bytes(2) >= 0
 
 
@@ -144,7 +128,7 @@ def test_device_batch_carries_blocks(oracle, hiplib):
     dev = bb.DeviceBatch(b, device="cuda:0", num_iters=3, raw=raw)
     dev.solve()
     got = dev.results()
-    assert _launch(hiplib)[0] == BQ
+    assert launch_record(hiplib)[0] == BQ
     for k in ("X", "F", "P", "L_x", "L_f", "stats"):
         assert np.array_equal(got[k], host[k]), k
 
@@ -159,13 +143,13 @@ def test_block_calls_without_blocks_are_the_plain_calls(oracle, hiplib):
     b = problems.make_batch("solo12_trot", 9)
     dev = bb.DeviceBatch(b, device="cuda:0", num_iters=3)
     dev.solve()
-    want, kernel = dev.results(), _launch(hiplib)
+    want, kernel = dev.results(), launch_record(hiplib)
     stream = C.c_void_p(torch.cuda.current_stream(dev.device).cuda_stream)
     for c in (C.byref(_lib.BlockCost()), None):
         dev.X.zero_()
         _lib.check(hiplib.bmpc_biconvex_solve_batch_blocks_device(C.byref(dev.desc), c, stream))
         got = dev.results()
-        assert _launch(hiplib) == kernel and kernel[0] != BQ
+        assert launch_record(hiplib) == kernel and kernel[0] != BQ
         for k in ("X", "F", "P", "L_x", "L_f", "stats"):
             assert np.array_equal(got[k], want[k]), k
 
@@ -196,7 +180,7 @@ def test_dropin_takes_sparse_block_costs(oracle, hiplib):
         mp = BiconvexMP(b.m, 20, 4)
         mp.set_rho(b.rho)
         got = _drive(mp, b, i, pre, Qx, blk["qx"][i], Qf, 3)
-        assert _launch(hiplib)[0] == BQ
+        assert launch_record(hiplib)[0] == BQ
         r = blockq_np.solve_problem(b, i, pre, blk, 3, warm=b.warm_start(), L_x=LX[i], L_f=LF[i])
         assert np.array_equal(got["stats"], r["stats"]) and got["L"] == (r["L_x"], r["L_f"])
         assert r["stats"][3] + r["stats"][4] > 0
@@ -205,12 +189,12 @@ def test_dropin_takes_sparse_block_costs(oracle, hiplib):
         fresh = BiconvexMP(b.m, 20, 4)
         fresh.set_rho(b.rho)
         want = _drive(fresh, b, i, pre, pre["Qx"][i], pre["qx"][i], sp.diags(pre["Qf"][i]), 3)
-        assert _launch(hiplib)[0] != BQ
+        assert launch_record(hiplib)[0] != BQ
         # the same handle: X back to a diagonal while F keeps its blocks is still the block kernel; both diagonal: the diagonal path
         _drive(mp, b, i, pre, np.diag(pre["Qx"][i]), pre["qx"][i], None, 3)
-        assert _launch(hiplib)[0] == BQ
+        assert launch_record(hiplib)[0] == BQ
         again = _drive(mp, b, i, pre, pre["Qx"][i], pre["qx"][i], pre["Qf"][i], 3)
-        assert _launch(hiplib)[0] != BQ
+        assert launch_record(hiplib)[0] != BQ
         for k in ("X", "F", "P", "stats"):
             assert np.array_equal(again[k], want[k]), (i, k)
         assert again["L"] == want["L"]

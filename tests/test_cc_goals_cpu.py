@@ -1,17 +1,16 @@
 """Contact-conditioned goals without a GPU: the host path (bunmpc_amd/goals.py, bunmpc_amd/contact_planner.py) and the numpy twin
 (tests/cc_goal_np.py) against recorded outputs of the reference's own functions (tests/golden/cc_goals/cc_goals_ref.npz, written by
 tests/golden/make_golden_cc_goals.py), the twin's plan against problems.contact_plan, the second header (include/bunmpc_goals.h)
-against its recorded table and a C compiler, and the refusals of the C-ABI."""
+against its recorded table, and the refusals of the C-ABI."""
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from bunmpc_amd import _lib, _lib_goals, contact_planner, goals, problems, urdf_model
+from bunmpc_amd import _lib, cc_goal_batch, contact_planner, goals, problems, urdf_model
 from bunmpc_amd import build as hip_build
 from tests import cc_goal_np as twin
 
@@ -131,7 +130,7 @@ def test_twin_plan_equals_contact_plan(gait):
     t0, com, feet0, hip_off, v_des, w_des = plan_inputs(12, 3)
     H = twin.plan_knots(g, 100)
     # bound: 20.0 * 100 * 0.001 * 4.0 * 0.3 / 0.05 is 47.99999999999999 in fp64 and int() truncates, as in the reference
-    assert H == {"trot": 40, "bound": 47, "jump": 60}[gait] == contact_planner.plan_knots(g, 100) == _lib_goals.plan_knots(100, g)
+    assert H == {"trot": 40, "bound": 47, "jump": 60}[gait] == contact_planner.plan_knots(g, 100) == cc_goal_batch.plan_knots(100, g)
     cnt, swing = twin.raibert_plan(g, H, t0, com, feet0, hip_off, v_des, w_des)
     ref, ref_swing, _ = problems.contact_plan(g, problems.SOLO12, H, t0, np.round(com[:, :2], 3), com[:, 2], np.round(feet0, 3), v_des, w_des,
                                               hip_offsets=hip_off)
@@ -169,56 +168,32 @@ def test_end_to_end_states_are_away_from_rounding_ties():
 # ---- the second header ---------------------------------------------------------------------------------------------------------------
 
 def test_goals_header_equals_its_recorded_table():
-    """tests/golden/abi_goals.json: tools/record_abi.py's table of bunmpc_amd._lib_goals; a change of the header is re-recorded and
+    """tests/golden/abi_goals.json: tools/record_abi.py's table of include/bunmpc_goals.h; a change of the header is re-recorded and
     reviewed as a diff of the file"""
     with open(os.path.join(ROOT, "tests", "golden", "abi_goals.json")) as f:
         golden = f.read()
-    assert record_abi.dump(_lib_goals) == golden
+    assert record_abi.dump(_lib.HEADERS["bunmpc_goals.h"]) == golden
     table = json.loads(golden)
     assert len(table["functions"]) == 5 and sorted(table["structs"]) == ["bmpc_cc_gait_t", "bmpc_cc_goal_batch_t", "bmpc_cc_goal_wb_batch_t"]
 
 
 def test_the_first_header_is_untouched_by_the_second():
-    assert len(_lib._SIGS) == 164 and len(_lib._ABI.structs) == 18
-    assert not any(hasattr(_lib, n) for n in _lib_goals._NAMES.values())
-    assert not set(_lib_goals._SIGS) & set(_lib._SIGS)
-    assert _lib_goals.INCLUDE in hip_build.dependencies() and hip_build.INCLUDE in hip_build.dependencies()
+    first, goals = _lib.HEADERS["bunmpc.h"], _lib.HEADERS["bunmpc_goals.h"]
+    assert len(first.functions) == 164 and len(first.structs) == 18
+    for cname, pyname in _lib.HEADER_NAMES["bunmpc_goals.h"].items():
+        assert getattr(_lib, pyname) is goals.structs[cname] and cname not in first.structs
+    assert not set(goals.functions) & set(first.functions)
+    assert os.path.join(os.path.dirname(hip_build.INCLUDE), "bunmpc_goals.h") in hip_build.dependencies() and hip_build.INCLUDE in hip_build.dependencies()
     jobs = hip_build.compile_jobs()
     assert jobs[-1] == ("cc_goals", "cc_goals.hip", []) and all(j[1] == "biconvex_admm.hip" for j in jobs[:12])
-
-
-def test_a_c_compiler_lays_the_goal_structs_out_as_ctypes_does(tmp_path):
-    rocm_bin = os.path.dirname(os.path.realpath(hip_build.HIPCC))
-    cc = next((c for c in (os.path.join(rocm_bin, "amdclang"), os.path.join(rocm_bin, "..", "lib", "llvm", "bin", "clang")) if os.path.exists(c)), None)
-    if cc is None:
-        import shutil
-        cc = shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler on this machine")
-    want, lines = [], []
-    for cname, cls in _lib_goals._ABI.structs.items():
-        want.append("%s %d" % (cname, C.sizeof(cls)))
-        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
-        for field, _ in cls._fields_:
-            want.append("%s.%s %d %d" % (cname, field, getattr(cls, field).offset, getattr(cls, field).size))
-            lines.append('printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));' % (cname, field, cname, field, cname, field))
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "bunmpc_goals.h"\nint main(void) {\n%s\nreturn 0;\n}\n' % "\n".join(lines))
-    subprocess.check_call([cc, "-std=c99", "-Wall", "-Werror", "-I", os.path.dirname(_lib_goals.INCLUDE), "-o", str(tmp_path / "layout"), str(src)])
-    assert subprocess.check_output([str(tmp_path / "layout")], text=True).split("\n")[:-1] == want
-    for lang in ("c", "c++"):
-        subprocess.check_call([cc, "-x", lang, "-fsyntax-only", "-Wall", "-Werror", _lib_goals.INCLUDE])
-    both = tmp_path / "both.c"                           # the two headers in one translation unit
-    both.write_text('#include "bunmpc.h"\n#include "bunmpc_goals.h"\nint main(void) { return 0; }\n')
-    subprocess.check_call([cc, "-std=c99", "-fsyntax-only", "-Wall", "-Werror", "-I", os.path.dirname(_lib_goals.INCLUDE), str(both)])
 
 
 # ---- refusals through the C-ABI, no GPU ------------------------------------------------------------------------------------------------
 
 def descriptor(**kw):
-    d = _lib_goals.CcGoalBatch()
+    d = _lib.CcGoalBatch()
     d.B, d.n_eff, d.episode_length, d.goal_horizon, d.max_rows, d.max_events, d.sim_dt = 4, 4, 100, 1, 50, 32, 0.001
-    d.gait = _lib_goals.gait_struct(problems.TROT)
+    d.gait = cc_goal_batch.gait_struct(problems.TROT)
     d.n_knots = 40
     for k in ("t0", "com", "feet0", "hip_off", "v_des", "w_des", "goals", "rows", "status", "schedule", "counts"):
         setattr(d, k, 8)                                 # any non-NULL value: a refused call reads no array
@@ -235,27 +210,27 @@ def descriptor(**kw):
     (dict(B=1 << 20, max_rows=1 << 20), "2^40"),
 ])
 def test_refusals_name_the_limit(kw, word):
-    rc = _lib_goals.lib().bmpc_cc_goal_batch_device(C.byref(descriptor(**kw)), None)
+    rc = _lib.lib().bmpc_cc_goal_batch_device(C.byref(descriptor(**kw)), None)
     assert rc == _lib.BAD_ARG and word in _lib.last_error(), _lib.last_error()
 
 
 def test_refusals_of_the_whole_body_call_and_the_pure_functions():
-    lib = _lib_goals.lib()
+    lib = _lib.lib()
     assert lib.bmpc_cc_goal_batch_device(None, None) == _lib.BAD_ARG and lib.bmpc_cc_goal_wb_batch_device(None, None) == _lib.BAD_ARG
-    w = _lib_goals.CcGoalWbBatch()
+    w = _lib.CcGoalWbBatch()
     w.g = descriptor(com=None, feet0=None, hip_off=None)      # ignored by the whole-body call
     assert lib.bmpc_cc_goal_wb_batch_device(C.byref(w), None) == _lib.BAD_ARG and "null model" in _lib.last_error()
     w.g = descriptor(n_eff=3)
     assert lib.bmpc_cc_goal_wb_batch_device(C.byref(w), None) == _lib.BAD_ARG and "n_eff = 4" in _lib.last_error()
     # B = 0 is no work and no error, without a GPU
     assert lib.bmpc_cc_goal_batch_device(C.byref(descriptor(B=0)), None) == _lib.OK
-    assert lib.bmpc_cc_goal_batch_struct_size() == C.sizeof(_lib_goals.CcGoalBatch)
-    assert lib.bmpc_cc_goal_wb_batch_struct_size() == C.sizeof(_lib_goals.CcGoalWbBatch)
+    assert lib.bmpc_cc_goal_batch_struct_size() == C.sizeof(_lib.CcGoalBatch)
+    assert lib.bmpc_cc_goal_wb_batch_struct_size() == C.sizeof(_lib.CcGoalWbBatch)
     for g in GAITS.values():
         for n in (1, 7, 100, 999, 3000):
-            assert _lib_goals.plan_knots(n, g) == twin.plan_knots(g, n) == contact_planner.plan_knots(g, n)
-    assert _lib_goals.plan_knots(3000, problems.TROT) == 1200 and _lib_goals.plan_knots(3000, problems.BOUND) == 1440
-    assert _lib_goals.plan_knots(1, problems.TROT) == 0 and _lib_goals.plan_knots(999, problems.TROT) == 399      # truncated, not rounded
+            assert cc_goal_batch.plan_knots(n, g) == twin.plan_knots(g, n) == contact_planner.plan_knots(g, n)
+    assert cc_goal_batch.plan_knots(3000, problems.TROT) == 1200 and cc_goal_batch.plan_knots(3000, problems.BOUND) == 1440
+    assert cc_goal_batch.plan_knots(1, problems.TROT) == 0 and cc_goal_batch.plan_knots(999, problems.TROT) == 399      # truncated, not rounded
     assert lib.bmpc_cc_goal_plan_knots(100, 0.001, 2.0, 0.5, 0.0) == -1
 
 

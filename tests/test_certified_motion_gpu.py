@@ -11,7 +11,7 @@ import pytest
 
 from bunmpc_amd import batch as bb
 from bunmpc_amd import problems
-from tests.util import rel_l2
+from tests.util import knob_setter, launch_record, rel_l2
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import certify_rate as cr  # noqa: E402
@@ -24,18 +24,13 @@ TOL = 1e-5      # what tests/test_biconvex_gpu.py holds solo12_trot at 10 ADMM i
 
 
 @pytest.fixture
-def knobs(hiplib):
+def knobs():
     """sets dispatch knobs for one test and restores every one of them afterwards; the headline kernel is forced for every launch"""
-    saved = []
-
-    def set_(name, value):
-        saved.append((name, getattr(hiplib, name)(value)))
-    set_("bmpc_set_latency_mapping_max_batch", 0)
-    set_("bmpc_set_three_per_wave", 0)
-    set_("bmpc_set_two_waves_per_simd", 1)
-    yield set_
-    for name, old in reversed(saved):
-        getattr(hiplib, name)(old)
+    with knob_setter() as set_:
+        set_("bmpc_set_latency_mapping_max_batch", 0)
+        set_("bmpc_set_three_per_wave", 0)
+        set_("bmpc_set_two_waves_per_simd", 1)
+        yield set_
 
 
 def _switches(knobs, hiplib, solve, values=(0, 1, 2)):
@@ -44,8 +39,7 @@ def _switches(knobs, hiplib, solve, values=(0, 1, 2)):
     for v in values:
         knobs("bmpc_set_certified_steps", v)
         out[v] = solve()
-        assert (hiplib.bmpc_biconvex_last_kernel_name().decode(), hiplib.bmpc_biconvex_last_lanes_per_problem(),
-                hiplib.bmpc_biconvex_last_waves_per_simd()) == HEADLINE
+        assert launch_record(hiplib) == HEADLINE
     for v in values[1:]:
         for k in KEYS:
             assert np.array_equal(out[values[0]][k], out[v][k], equal_nan=True), (v, k)

@@ -7,22 +7,11 @@ import pytest
 
 from bunmpc_amd import batch as bb
 from bunmpc_amd import problems
+from tests.util import knobs, launch_record  # noqa: F401  (knobs: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 KEYS = ("X", "F", "P", "L_x", "L_f", "stats", "trace", "hist", "dyn_viol")
-
-
-@pytest.fixture
-def knobs(hiplib):
-    """sets dispatch knobs for one test and restores every one of them afterwards"""
-    saved = []
-
-    def set_(name, value):
-        saved.append((name, getattr(hiplib, name)(value)))
-    yield set_
-    for name, old in reversed(saved):
-        getattr(hiplib, name)(old)
 
 
 def _both(knobs, hiplib, solve):
@@ -30,8 +19,7 @@ def _both(knobs, hiplib, solve):
     for on in (0, 1):
         knobs("bmpc_set_certified_steps", on)
         out[on] = solve()
-        out[on]["kernel"] = (hiplib.bmpc_biconvex_last_kernel_name().decode(), hiplib.bmpc_biconvex_last_lanes_per_problem(),
-                             hiplib.bmpc_biconvex_last_waves_per_simd())
+        out[on]["kernel"] = launch_record(hiplib)
     assert out[0]["kernel"] == out[1]["kernel"]
     for k in KEYS:
         if k in out[0]:

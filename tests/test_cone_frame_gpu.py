@@ -17,7 +17,7 @@ from bunmpc_amd import _lib, problems
 from bunmpc_amd import batch as bb
 from bunmpc_amd.biconvex_mpc_cpp import BiconvexMP
 from tests import cone_frame_np, cone_np
-from tests.util import K_SPREAD, rel_l2
+from tests.util import K_SPREAD, knobs, launch_record, rel_l2  # noqa: F401  (knobs: the fixture)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -25,22 +25,6 @@ CONE, CONEF = "biconvex_admm_cone_kernel", "biconvex_admm_conef_kernel"
 OUT = ("X", "F", "P", "L_x", "L_f", "stats", "dyn_viol")
 EUCLID = dict(projection="euclidean")
 E3 = np.array([0.0, 0.0, 1.0])
-
-
-@pytest.fixture
-def knobs(hiplib):
-    """sets dispatch knobs for one test and restores every one of them afterwards"""
-    saved = []
-
-    def set_(name, value):
-        saved.append((name, getattr(hiplib, name)(value)))
-    yield set_
-    for name, old in reversed(saved):
-        getattr(hiplib, name)(old)
-
-
-def _launch(hiplib):
-    return hiplib.bmpc_biconvex_last_kernel_name().decode(), hiplib.bmpc_biconvex_last_lanes_per_problem(), hiplib.bmpc_biconvex_last_waves_per_simd()
 
 
 def _case(config, H):
@@ -60,7 +44,7 @@ def _solve(hiplib, knobs, config, H, lanes, form="harness", normals=None, kernel
     if normals is not False:
         cone["normals"] = nrm if normals is None else normals
     got = bb.solve_host(b, num_iters=iters, warm=warm, L_f=np.full(b.B, cone_np.L_F), raw=raw, cone=cone)
-    assert _launch(hiplib) == (kernel, lanes, 1)
+    assert launch_record(hiplib) == (kernel, lanes, 1)
     return b, mu, nrm, got
 
 
@@ -142,11 +126,11 @@ def test_null_normals_launch_the_cone_kernel(hiplib, knobs):
         else:
             _lib.check(hiplib.bmpc_biconvex_solve_batch_cone_frames_device(C.byref(dev.desc), C.byref(dev.cone), None if frame is None else C.byref(frame), stream))
         outs.append(dev.results())
-        assert _launch(hiplib) == (CONE, 32, 1)
+        assert launch_record(hiplib) == (CONE, 32, 1)
     _same(outs[1], outs[0])
     _same(outs[2], outs[0])
     host = bb.solve_host(b, num_iters=iters, warm=warm, L_f=np.full(b.B, cone_np.L_F), cone=dict(EUCLID, mu=mu, normals=None))
-    assert _launch(hiplib) == (CONE, 32, 1)
+    assert launch_record(hiplib) == (CONE, 32, 1)
     _same(host, outs[0])
 
 
@@ -184,7 +168,7 @@ def test_device_batch_carries_the_normals(hiplib, knobs):
             dev.set_warm_start(*warm, L_f=np.full(b.B, cone_np.L_F))
             dev.solve()
             got = dev.results()
-            assert _launch(hiplib) == (CONEF, 32, 1)
+            assert launch_record(hiplib) == (CONEF, 32, 1)
             _same(got, host)
 
 
@@ -218,9 +202,9 @@ def test_handle_path(hiplib, config, E):
     warm1 = tuple(w[:1] for w in warm)
     kw = dict(num_iters=iters, warm=warm1, L_f=np.full(1, cone_np.L_F), raw=raw)
     want = bb.solve_host(b, cone=dict(EUCLID, mu=mu[:1], normals=nrm[:1]), **kw)
-    assert _launch(hiplib) == (CONEF, 16, 1)
+    assert launch_record(hiplib) == (CONEF, 16, 1)
     flat = bb.solve_host(b, cone=dict(EUCLID, mu=mu[:1]), **kw)
-    assert _launch(hiplib) == (CONE, 16, 1)
+    assert launch_record(hiplib) == (CONE, 16, 1)
     assert not np.array_equal(flat["F"], want["F"])
 
     def check(got, ref, tag):
@@ -234,22 +218,22 @@ def test_handle_path(hiplib, config, E):
     mp.set_contact_normals(nrm[0])
     for again in (False, True):      # ... and the normals persist
         got = _drive(mp, b, 0, raw, warm1, iters)
-        assert _launch(hiplib) == (CONEF, 16, 1), again
+        assert launch_record(hiplib) == (CONEF, 16, 1), again
         check(got, want, again)
     mp.set_contact_normals(None)
     got = _drive(mp, b, 0, raw, warm1, iters)
-    assert _launch(hiplib) == (CONE, 16, 1)
+    assert launch_record(hiplib) == (CONE, 16, 1)
     check(got, flat, "world z")
     # set_rotation_matrix_f on its own: stored and unused
     for t in range(15):
         for n in range(E):
             mp.set_rotation_matrix_f(_frame_with_third_row(nrm[0, t, n]))
     got = _drive(mp, b, 0, raw, warm1, iters)
-    assert _launch(hiplib) == (CONE, 16, 1)
+    assert launch_record(hiplib) == (CONE, 16, 1)
     check(got, flat, "matrices unused")
     mp.use_rotation_matrices_as_contact_frames()
     got = _drive(mp, b, 0, raw, warm1, iters)
-    assert _launch(hiplib) == (CONEF, 16, 1)
+    assert launch_record(hiplib) == (CONEF, 16, 1)
     check(got, want, "rotations")
 
 
@@ -325,7 +309,7 @@ def test_kinodyn_honours_the_handle_or_refuses(hiplib):
     mp.set_friction_coefficients(mu)
     mp.set_contact_normals(nrm)
     kd.optimize(q0, np.zeros(18), 3, 1)
-    assert _launch(hiplib)[0] == CONEF
+    assert launch_record(hiplib)[0] == CONEF
     F = mp.return_opt_f()
     assert np.any(F != 0)
     _feasible(F, np.broadcast_to(mu, (H, 4)), nrm)

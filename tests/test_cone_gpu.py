@@ -17,29 +17,13 @@ from bunmpc_amd import _lib, problems
 from bunmpc_amd import batch as bb
 from bunmpc_amd.biconvex_mpc_cpp import BiconvexMP
 from tests import cone_np
-from tests.util import K_SPREAD, rel_l2
+from tests.util import K_SPREAD, knobs, launch_record, rel_l2  # noqa: F401  (knobs: the fixture)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
 CONE = "biconvex_admm_cone_kernel"
 OUT = ("X", "F", "P", "L_x", "L_f", "stats", "dyn_viol")
 EUCLID = dict(projection="euclidean")
-
-
-@pytest.fixture
-def knobs(hiplib):
-    """sets dispatch knobs for one test and restores every one of them afterwards"""
-    saved = []
-
-    def set_(name, value):
-        saved.append((name, getattr(hiplib, name)(value)))
-    yield set_
-    for name, old in reversed(saved):
-        getattr(hiplib, name)(old)
-
-
-def _launch(hiplib):
-    return hiplib.bmpc_biconvex_last_kernel_name().decode(), hiplib.bmpc_biconvex_last_lanes_per_problem(), hiplib.bmpc_biconvex_last_waves_per_simd()
 
 
 def _solve(hiplib, knobs, config, H, lanes, form):
@@ -50,7 +34,7 @@ def _solve(hiplib, knobs, config, H, lanes, form):
     if form == "raw_qf":
         raw["qf"] = cone_np.linear_force_cost(b)
     got = bb.solve_host(b, num_iters=iters, warm=warm, L_f=np.full(b.B, cone_np.L_F), raw=raw, cone=dict(EUCLID, mu=mu))
-    assert _launch(hiplib) == (CONE, lanes, 1)
+    assert launch_record(hiplib) == (CONE, lanes, 1)
     return b, mu, got
 
 
@@ -113,9 +97,9 @@ def test_strides_of_the_coefficients(hiplib, knobs, config):
              (dict(cone=dict(EUCLID), mu=0.2), dict(cone=dict(EUCLID, mu=np.full((1,) + mu.shape[1:], 0.2)), mu=7.0))]
     for one, other in pairs:
         a = bb.solve_host(b, **kw, **one)
-        assert _launch(hiplib) == (CONE, 32, 1)
+        assert launch_record(hiplib) == (CONE, 32, 1)
         t = bb.solve_host(b, **kw, **other)
-        assert _launch(hiplib) == (CONE, 32, 1)
+        assert launch_record(hiplib) == (CONE, 32, 1)
         for k in OUT:
             assert np.array_equal(a[k], t[k]), k
         assert a["stats"][:, 3].sum() > 0
@@ -126,21 +110,21 @@ def test_projection_zero_is_the_plain_call(hiplib):
     import torch
     b = problems.make_batch("solo12_mixed", 9)
     want = bb.solve_host(b, num_iters=3, mu=0.5)
-    kernel = _launch(hiplib)
+    kernel = launch_record(hiplib)
     assert kernel[0] != CONE
     got = bb.solve_host(b, num_iters=3, mu=0.5, cone=dict(projection="reference"))
-    assert _launch(hiplib) == kernel
+    assert launch_record(hiplib) == kernel
     for k in OUT:
         assert np.array_equal(got[k], want[k]), k
     dev = bb.DeviceBatch(b, device="cuda:0", num_iters=3, mu=0.5, cone=dict(projection="reference", mu=None))
     dev.solve()
     got = dev.results()
-    assert _launch(hiplib) == kernel
+    assert launch_record(hiplib) == kernel
     stream = C.c_void_p(torch.cuda.current_stream(dev.device).cuda_stream)
     dev.X.zero_()
     _lib.check(hiplib.bmpc_biconvex_solve_batch_cone_device(C.byref(dev.desc), None, stream))
     again = dev.results()
-    assert _launch(hiplib) == kernel
+    assert launch_record(hiplib) == kernel
     for k in OUT:
         assert np.array_equal(got[k], want[k]) and np.array_equal(again[k], want[k]), k
 
@@ -151,10 +135,10 @@ def test_go2_at_mu_one(hiplib):
     b = problems.make_batch("go2_bound", 4)
     assert b.H == 40
     plain = bb.solve_host(b, num_iters=2, mu=1.0)
-    assert _launch(hiplib)[0] != CONE
+    assert launch_record(hiplib)[0] != CONE
     assert np.all(plain["stats"][:, 5] == 2), plain["stats"]
     got = bb.solve_host(b, num_iters=2, mu=1.0, cone=EUCLID)
-    assert _launch(hiplib) == (CONE, 64, 1)
+    assert launch_record(hiplib) == (CONE, 64, 1)
     assert np.all(got["stats"][:, 5] == 0), got["stats"]
     _against_twin(got, [cone_np.restatement(b, i, 2, 1.0) for i in range(4)], tag="go2")
     _feasible(got["F"], np.ones((4, 40, 4)))
@@ -168,7 +152,7 @@ def test_device_batch_carries_the_cone(hiplib, knobs):
     dev.set_warm_start(*warm, L_f=np.full(b.B, cone_np.L_F))
     dev.solve()
     got = dev.results()
-    assert _launch(hiplib) == (CONE, 32, 1)
+    assert launch_record(hiplib) == (CONE, 32, 1)
     for k in OUT:
         assert np.array_equal(got[k], host[k]), k
 
@@ -192,14 +176,14 @@ def test_handle_path(hiplib, config, E):
     b, mu, warm, iters = cone_np.case(config, 15)
     raw = cone_np.raw_batch(b)
     want = bb.solve_host(b, num_iters=iters, warm=warm, L_f=np.full(b.B, cone_np.L_F), raw=raw, cone=dict(EUCLID, mu=mu))
-    assert _launch(hiplib) == (CONE, 16, 1)
+    assert launch_record(hiplib) == (CONE, 16, 1)
     mp = BiconvexMP(b.m, 15, E)
     mp.set_rho(b.rho)
     mp.set_cone_projection("euclidean")
     mp.set_friction_coefficients(mu[0])
     for again in (False, True):
         got = _drive(mp, b, 0, raw, warm, iters)
-        assert _launch(hiplib) == (CONE, 16, 1), again
+        assert launch_record(hiplib) == (CONE, 16, 1), again
         assert np.array_equal(got["stats"], want["stats"][0]) and got["L"] == (want["L_x"][0], want["L_f"][0])
         for k in "XFP":
             assert np.array_equal(got[k], want[k][0]), (again, k)
@@ -211,10 +195,10 @@ def test_handle_path(hiplib, config, E):
     scalar = bb.solve_host(b, num_iters=iters, warm=warm, L_f=np.full(b.B, cone_np.L_F), raw=raw, mu=0.2, cone=EUCLID)
     mp.set_friction_coefficients(0.2)
     got = _drive(mp, b, 0, raw, warm, iters)
-    assert _launch(hiplib)[0] == CONE and np.array_equal(got["F"], scalar["F"][0])
+    assert launch_record(hiplib)[0] == CONE and np.array_equal(got["F"], scalar["F"][0])
     mp.set_cone_projection("reference")
     _drive(mp, b, 0, raw, warm, iters)
-    assert _launch(hiplib)[0] != CONE
+    assert launch_record(hiplib)[0] != CONE
 
 
 def test_refusals_on_the_device_entry_point(hiplib):
@@ -278,7 +262,7 @@ def test_kinodyn_honours_the_handle_or_refuses(hiplib):
     mp.set_cone_projection("euclidean")
     mp.set_friction_coefficients(mu)
     kd.optimize(q0, np.zeros(18), 3, 1)
-    assert _launch(hiplib)[0] == CONE
+    assert launch_record(hiplib)[0] == CONE
     F = mp.return_opt_f()
     assert np.any(F != 0)
     _feasible(F, np.broadcast_to(mu, (H, 4)))

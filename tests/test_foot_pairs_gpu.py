@@ -5,16 +5,10 @@ pairs took the new loop: it must be 0 in mode 0 and where the eligibility rule r
 import numpy as np
 import pytest
 
-from bunmpc_amd import _lib_foot_pairs, problems
+from bunmpc_amd import problems
 from tests.test_loop_constants_gpu import KEYS, _same, _solve, knobs  # noqa: F401  (knobs: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture
-def hiplib():
-    """the library with the signatures of include/bunmpc_foot_pairs.h on it (the same handle as the session's)"""
-    return _lib_foot_pairs.lib()
 
 
 def _modes(knobs, hiplib, solve):

@@ -68,7 +68,7 @@ class hiplib_knobs:
         self.lib, self.values = lib, table_knobs(s)
 
     def bmpc_ik_plan_iteration(self, *args):
-        with rows.knobs(self.lib, self.values):
+        with rows.knobs(self.values):
             return self.lib.bmpc_ik_plan_iteration(*args)
 
 
@@ -110,10 +110,10 @@ BASE = dict(B=48, n_col=5, maxiter=40, has_list=1)
 
 def test_sched_overrides_field_by_field(hiplib):
     """bmpc_ik_sched_t through resolve_knobs: 0 = the process default, < 0 = never, n > 0 = n"""
-    with rows.knobs(hiplib, dict(spec_below=48, all_steps=48, gains_wave_below=48, express_cap=7, fused_direct=0)):
+    with rows.knobs(dict(spec_below=48, all_steps=48, gains_wave_below=48, express_cap=7, fused_direct=0)):
         s64 = dict(BASE, B=64)
         # spec_below: default 48 -> side by side at 48; never -> four per wave, one iteration per look; 10 -> only at <= 10
-        with rows.knobs(hiplib, dict(all_steps=0)):
+        with rows.knobs(dict(all_steps=0)):
             assert (plan(hiplib, BASE, 48, {}).fwd_map, plan(hiplib, BASE, 48, {}).chunk) == (2, 3)
             assert (plan(hiplib, BASE, 48, dict(spec_below=-1)).fwd_map, plan(hiplib, BASE, 1, dict(spec_below=-1)).chunk) == (0, 1)
             assert [plan(hiplib, BASE, a, dict(spec_below=10)).fwd_map for a in (11, 10, 4, 3)] == [0, 2, 2, 3]
@@ -147,7 +147,7 @@ SETTERS = [("speculative_below", 1024, 30, lambda p: p.chunk, 48, (3, 1)),      
 def test_setters_return_the_old_value_and_show_in_the_next_plan(hiplib, name, default, value, show, active, expect):
     fn = getattr(hiplib, "bmpc_ik_set_" + name)
     s = dict(BASE, B=active)
-    with rows.knobs(hiplib, dict(spec_below=48) if name != "speculative_below" else {}):
+    with rows.knobs(dict(spec_below=48) if name != "speculative_below" else {}):
         assert show(plan(hiplib, s, active, {})) == expect[0]
         assert fn(value) == default
         try:

@@ -30,7 +30,7 @@ def test_solve_agrees_with_the_plan_and_the_table(hiplib, name):
     lk = s["looks"][-1]
     if lk[1] is not None:
         out, sc = _lib.IkIterPlan(), rows.sched_of(s["sched"])
-        with rows.knobs(hiplib, {k: v for k, v in s["knobs"].items() if v != rows.DEFAULTS[k]}):
+        with rows.knobs({k: v for k, v in s["knobs"].items() if v != rows.DEFAULTS[k]}):
             assert hiplib.bmpc_ik_plan_iteration(s["B"], s["n_col"], s["maxiter"], s["has_list"], s["has_list"], lk[1], C.byref(sc), C.byref(out)) == 0
         assert out.calcdiff.kernel == (b"ik_calcdiff1_kernel" if last else b"ik_calcdiff_kernel")
     assert digest == default_digest(s["B"], s["n_col"])

@@ -13,6 +13,7 @@ from bunmpc_amd import _lib
 from bunmpc_amd import batch as bb
 from bunmpc_amd import problems
 from tests import dispatch_rows as dr
+from tests.util import knob_setter, launch_record
 
 pytestmark = pytest.mark.gpu
 
@@ -22,23 +23,14 @@ ONE_WAVE = ("biconvex_admm_kernel", 32, 1)
 
 
 @pytest.fixture
-def knobs(hiplib):
+def knobs():
     """sets dispatch knobs for one test and restores every one of them afterwards; small batches take the two-waves kernel"""
-    saved = []
-
-    def set_(name, value):
-        saved.append((name, getattr(hiplib, name)(value)))
-    set_("bmpc_set_latency_mapping_max_batch", 0)
-    set_("bmpc_set_three_per_wave", 0)
-    set_("bmpc_set_two_waves_per_simd", 1)
-    set_("bmpc_set_loop_constants_in_lds", 1)
-    yield set_
-    for name, old in reversed(saved):
-        getattr(hiplib, name)(old)
-
-
-def _launched(hiplib):
-    return (hiplib.bmpc_biconvex_last_kernel_name().decode(), hiplib.bmpc_biconvex_last_lanes_per_problem(), hiplib.bmpc_biconvex_last_waves_per_simd())
+    with knob_setter() as set_:
+        set_("bmpc_set_latency_mapping_max_batch", 0)
+        set_("bmpc_set_three_per_wave", 0)
+        set_("bmpc_set_two_waves_per_simd", 1)
+        set_("bmpc_set_loop_constants_in_lds", 1)
+        yield set_
 
 
 def _planned(hiplib, b):
@@ -65,15 +57,15 @@ def _builds(knobs, hiplib, b, solve, fits=True):
     knobs("bmpc_set_loop_constants_in_lds", 1)
     assert _planned(hiplib, b) == (1 if fits else 0)
     new = solve()
-    assert _launched(hiplib) == HEADLINE
+    assert launch_record(hiplib) == HEADLINE
     knobs("bmpc_set_loop_constants_in_lds", 0)
     assert _planned(hiplib, b) == 0
     old = solve()
-    assert _launched(hiplib) == HEADLINE
+    assert launch_record(hiplib) == HEADLINE
     _same(new, old, "the two-waves build")
     knobs("bmpc_set_two_waves_per_simd", 0)
     one = solve()
-    assert _launched(hiplib) == ONE_WAVE
+    assert launch_record(hiplib) == ONE_WAVE
     assert np.all(one["cert_phases"] == -1)
     _same(new, one, "the one-wave build", cert=False)
     knobs("bmpc_set_two_waves_per_simd", 1)

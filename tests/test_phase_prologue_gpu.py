@@ -11,7 +11,8 @@ import pytest
 
 from bunmpc_amd import batch as bb
 from bunmpc_amd import problems
-from tests.test_loop_constants_gpu import HEADLINE, KEYS, ONE_WAVE, _builds, _launched, _solve, knobs  # noqa: F401  (knobs: the fixture)
+from tests.test_loop_constants_gpu import HEADLINE, KEYS, ONE_WAVE, _builds, _solve, knobs  # noqa: F401  (knobs: the fixture)
+from tests.util import launch_record
 
 pytestmark = pytest.mark.gpu
 
@@ -64,7 +65,7 @@ def test_iterates_reset_with_step_constants_carried(hiplib, knobs):
         knobs("bmpc_set_two_waves_per_simd", two_waves)
         knobs("bmpc_set_loop_constants_in_lds", clds)
         runs[name] = solve()
-        assert _launched(hiplib) == kernel, name
+        assert launch_record(hiplib) == kernel, name
     for name in ("two waves", "one wave"):
         for k in KEYS:
             assert np.array_equal(runs["loop constants"][k], runs[name][k], equal_nan=True), (name, k)

@@ -9,6 +9,7 @@ import pytest
 
 from bunmpc_amd import batch as bb
 from bunmpc_amd import problems
+from tests.util import knob_setter, launch_record
 
 pytestmark = pytest.mark.gpu
 
@@ -18,23 +19,14 @@ ONE_WAVE = ("biconvex_admm_kernel", 32, 1)
 
 
 @pytest.fixture
-def knobs(hiplib):
+def knobs():
     """sets dispatch knobs for one test and restores every one of them afterwards; the headline kernel is forced unless a test asks for
     the one-wave build"""
-    saved = []
-
-    def set_(name, value):
-        saved.append((name, getattr(hiplib, name)(value)))
-    set_("bmpc_set_latency_mapping_max_batch", 0)
-    set_("bmpc_set_three_per_wave", 0)
-    set_("bmpc_set_two_waves_per_simd", 1)
-    yield set_
-    for name, old in reversed(saved):
-        getattr(hiplib, name)(old)
-
-
-def _launched(hiplib):
-    return (hiplib.bmpc_biconvex_last_kernel_name().decode(), hiplib.bmpc_biconvex_last_lanes_per_problem(), hiplib.bmpc_biconvex_last_waves_per_simd())
+    with knob_setter() as set_:
+        set_("bmpc_set_latency_mapping_max_batch", 0)
+        set_("bmpc_set_three_per_wave", 0)
+        set_("bmpc_set_two_waves_per_simd", 1)
+        yield set_
 
 
 def _solve(b, **kw):
@@ -56,23 +48,23 @@ def _variants(knobs, hiplib, solve, lanes=32):
     knobs("bmpc_set_certified_steps", 1)
     knobs("bmpc_set_exact_step_decisions", 0)
     base = solve()
-    assert _launched(hiplib) == two_waves
+    assert launch_record(hiplib) == two_waves
     for v in (2, 0):
         knobs("bmpc_set_certified_steps", v)
         got = solve()
-        assert _launched(hiplib) == two_waves
+        assert launch_record(hiplib) == two_waves
         assert np.all(got["cert_phases"][:, 1] == (0 if lanes == 32 else -1))      # (the motion step ran the tested loop)
         _same(base, got, "certified_steps %d" % v)
     knobs("bmpc_set_certified_steps", 1)
     knobs("bmpc_set_two_waves_per_simd", 0)
     got = solve()
-    assert _launched(hiplib) == one_wave
+    assert launch_record(hiplib) == one_wave
     _same(base, got, "one wave per SIMD")
     knobs("bmpc_set_two_waves_per_simd", 1)
     for v in (1, 2):
         knobs("bmpc_set_exact_step_decisions", v)
         got = solve()
-        assert _launched(hiplib) == two_waves
+        assert launch_record(hiplib) == two_waves
         assert np.array_equal(got["cert_phases"], base["cert_phases"])
         _same(base, got, "exact_step_decisions %d" % v)
     knobs("bmpc_set_exact_step_decisions", 0)
@@ -124,7 +116,7 @@ def test_a_diverged_wave_mate_stays_contained(hiplib, knobs, H):
         knobs("bmpc_set_exact_step_decisions", v)
         ref = _solve(clean, num_iters=10)
         got = _solve(bad, num_iters=10)
-        assert _launched(hiplib) == HEADLINE
+        assert launch_record(hiplib) == HEADLINE
         print("switch", v, "H", H, "statuses", got["stats"][:, 5].tolist(), "ADMM iterations", got["stats"][:, 0].tolist(),
               "certified phases (force, motion)", got["cert_phases"].tolist())
         assert got["stats"][:, 5].tolist() == [2, 0, 0, 2]

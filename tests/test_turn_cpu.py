@@ -1,17 +1,17 @@
-"""Turning commands without a GPU: the third header (include/bunmpc_turn.h) against its recorded table and a C compiler,
+"""Turning commands without a GPU: the third header (include/bunmpc_turn.h) against its recorded table,
 problems.make_wb_batch(w_des=...) against the single-problem harness (bunmpc_amd/cyclic_gen.py :: SoloMpcGaitGen, which restates
 abstract_cyclic_gen.py) problem by problem, a hand-checked pure-yaw state, and the refusals of the two C calls (they come before the
 first HIP call)."""
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from bunmpc_amd import _lib, _lib_turn, problems
+from bunmpc_amd import _lib, problems
+from bunmpc_amd.plan_batch import turn_struct
 from bunmpc_amd import build as hip_build
 from tests import turn_np
 
@@ -25,52 +25,26 @@ PLAN = ("cnt_plan", "swing_time", "dt", "x_init", "X_nom", "X_ter")
 # ---- 1. the third header -----------------------------------------------------------------------------------------------------------------
 
 def test_turn_header_equals_its_recorded_table():
-    """tests/golden/abi_turn.json: tools/record_abi.py's table of bunmpc_amd._lib_turn; a change of the header is re-recorded and
+    """tests/golden/abi_turn.json: tools/record_abi.py's table of include/bunmpc_turn.h; a change of the header is re-recorded and
     reviewed as a diff of the file"""
     with open(os.path.join(ROOT, "tests", "golden", "abi_turn.json")) as f:
         golden = f.read()
-    assert record_abi.dump(_lib_turn) == golden
+    assert record_abi.dump(_lib.HEADERS["bunmpc_turn.h"]) == golden
     table = json.loads(golden)
     assert sorted(table["functions"]) == ["bmpc_plan_batch_turn_device", "bmpc_turn_struct_size", "bmpc_wb_plan_batch_turn_device"]
     assert sorted(table["structs"]) == ["bmpc_turn_t"]
     for name in ("bmpc_plan_batch_turn_device", "bmpc_wb_plan_batch_turn_device"):
-        assert _lib_turn._SIGS[name] == (C.c_int, [C.c_void_p] * 5)
+        assert _lib.HEADERS["bunmpc_turn.h"].functions[name] == (C.c_int, [C.c_void_p] * 5)
 
 
 def test_the_first_two_headers_are_untouched_by_the_third():
-    from bunmpc_amd import _lib_goals
-    assert len(_lib._SIGS) == 164 and len(_lib._ABI.structs) == 18 and len(_lib_goals._SIGS) == 5
-    assert not hasattr(_lib, "Turn") and not hasattr(_lib_goals, "Turn")
-    assert not set(_lib_turn._SIGS) & (set(_lib._SIGS) | set(_lib_goals._SIGS))
-    assert _lib_turn.INCLUDE in hip_build.dependencies()
-    lib = _lib_turn.lib()                                    # every declared symbol is in the library, and the struct has its size
-    assert lib.bmpc_turn_struct_size() == C.sizeof(_lib_turn.Turn) == 16
-
-
-def test_a_c_compiler_lays_the_turn_struct_out_as_ctypes_does(tmp_path):
-    rocm_bin = os.path.dirname(os.path.realpath(hip_build.HIPCC))
-    cc = next((c for c in (os.path.join(rocm_bin, "amdclang"), os.path.join(rocm_bin, "..", "lib", "llvm", "bin", "clang")) if os.path.exists(c)), None)
-    if cc is None:
-        import shutil
-        cc = shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler on this machine")
-    want, lines = [], []
-    for cname, cls in _lib_turn._ABI.structs.items():
-        want.append("%s %d" % (cname, C.sizeof(cls)))
-        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
-        for field, _ in cls._fields_:
-            want.append("%s.%s %d %d" % (cname, field, getattr(cls, field).offset, getattr(cls, field).size))
-            lines.append('printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));' % (cname, field, cname, field, cname, field))
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "bunmpc_turn.h"\nint main(void) {\n%s\nreturn 0;\n}\n' % "\n".join(lines))
-    subprocess.check_call([cc, "-std=c99", "-Wall", "-Werror", "-I", os.path.dirname(_lib_turn.INCLUDE), "-o", str(tmp_path / "layout"), str(src)])
-    assert subprocess.check_output([str(tmp_path / "layout")], text=True).split("\n")[:-1] == want
-    for lang in ("c", "c++"):
-        subprocess.check_call([cc, "-x", lang, "-fsyntax-only", "-Wall", "-Werror", _lib_turn.INCLUDE])
-    all3 = tmp_path / "all.c"                            # the three headers in one translation unit
-    all3.write_text('#include "bunmpc.h"\n#include "bunmpc_goals.h"\n#include "bunmpc_turn.h"\nint main(void) { return 0; }\n')
-    subprocess.check_call([cc, "-std=c99", "-fsyntax-only", "-Wall", "-Werror", "-I", os.path.dirname(_lib_turn.INCLUDE), str(all3)])
+    turn, first, goals = (_lib.HEADERS[h] for h in ("bunmpc_turn.h", "bunmpc.h", "bunmpc_goals.h"))
+    assert len(first.functions) == 164 and len(first.structs) == 18 and len(goals.functions) == 5
+    assert _lib.Turn is turn.structs["bmpc_turn_t"] and "bmpc_turn_t" not in first.structs and "bmpc_turn_t" not in goals.structs
+    assert not set(turn.functions) & (set(first.functions) | set(goals.functions))
+    assert os.path.join(os.path.dirname(hip_build.INCLUDE), "bunmpc_turn.h") in hip_build.dependencies()
+    lib = _lib.lib()                                         # every declared symbol is in the library, and the struct has its size
+    assert lib.bmpc_turn_struct_size() == C.sizeof(_lib.Turn) == 16
 
 
 # ---- 2. the numpy builder against the single-problem harness --------------------------------------------------------------------------------
@@ -211,16 +185,16 @@ BAD_INERTIA = [0.0, -0.05, float("nan"), float("inf"), -float("inf")]
 
 def test_refusals_of_the_centroidal_level_call():
     keep = []
-    call = _lib_turn.lib().bmpc_plan_batch_turn_device
+    call = _lib.lib().bmpc_plan_batch_turn_device
     d, t = _plan_desc(keep), _terrain_desc(keep)
     w = np.zeros(2)
     for terrain in (None, C.byref(t)):
         for bad in BAD_INERTIA:
-            assert call(C.byref(d), terrain, None, C.byref(_lib_turn.Turn(None, bad)), None) == _lib.BAD_ARG, bad
+            assert call(C.byref(d), terrain, None, C.byref(_lib.Turn(None, bad)), None) == _lib.BAD_ARG, bad
             assert "yaw_inertia" in _lib.last_error(), _lib.last_error()
-        assert call(C.byref(d), terrain, None, C.byref(_lib_turn.Turn(w.ctypes.data, 0.05)), None) == _lib.BAD_ARG
+        assert call(C.byref(d), terrain, None, C.byref(_lib.Turn(w.ctypes.data, 0.05)), None) == _lib.BAD_ARG
         assert "bmpc_turn_t.w_des must be NULL" in _lib.last_error(), _lib.last_error()
-    turn = C.byref(_lib_turn.Turn(None, 0.05))
+    turn = C.byref(_lib.Turn(None, 0.05))
     # everything the plain calls refuse, with their messages; with a turn and without (turn == NULL is the plain call)
     for tn in (turn, None):
         assert call(None, None, None, tn, None) == _lib.BAD_ARG and "null plan descriptor" in _lib.last_error()
@@ -233,21 +207,21 @@ def test_refusals_of_the_centroidal_level_call():
     empty = _plan_desc(keep, B=0)
     assert call(C.byref(empty), None, None, turn, None) == _lib.OK and call(C.byref(empty), C.byref(t), None, turn, None) == _lib.OK
     assert call(C.byref(empty), None, None, None, None) == _lib.OK
-    assert call(C.byref(empty), None, None, C.byref(_lib_turn.Turn(None, 0.0)), None) == _lib.BAD_ARG
+    assert call(C.byref(empty), None, None, C.byref(_lib.Turn(None, 0.0)), None) == _lib.BAD_ARG
 
 
 def test_refusals_of_the_whole_body_call():
     keep = []
-    call = _lib_turn.lib().bmpc_wb_plan_batch_turn_device
+    call = _lib.lib().bmpc_wb_plan_batch_turn_device
     d, t = _wb_desc(keep), _terrain_desc(keep)
     w = np.zeros(2)
     for terrain in (None, C.byref(t)):
         for bad in BAD_INERTIA:
-            assert call(C.byref(d), terrain, None, C.byref(_lib_turn.Turn(w.ctypes.data, bad)), None) == _lib.BAD_ARG, bad
+            assert call(C.byref(d), terrain, None, C.byref(_lib.Turn(w.ctypes.data, bad)), None) == _lib.BAD_ARG, bad
             assert "yaw_inertia" in _lib.last_error(), _lib.last_error()
-        assert call(C.byref(d), terrain, None, C.byref(_lib_turn.Turn(None, 0.05)), None) == _lib.BAD_ARG
+        assert call(C.byref(d), terrain, None, C.byref(_lib.Turn(None, 0.05)), None) == _lib.BAD_ARG
         assert "bmpc_turn_t.w_des is NULL" in _lib.last_error(), _lib.last_error()
-    turn = C.byref(_lib_turn.Turn(w.ctypes.data, 0.05))
+    turn = C.byref(_lib.Turn(w.ctypes.data, 0.05))
     for tn in (turn, None):
         assert call(None, None, None, tn, None) == _lib.BAD_ARG and "null descriptor" in _lib.last_error()
         for kw, word in ((dict(ik_col=5), "sizes"), (dict(x=None), "input"), (dict(w_des=None), "output"), (dict(ik_tasks=None), "output")):
@@ -259,12 +233,12 @@ def test_refusals_of_the_whole_body_call():
             assert call(C.byref(d), C.byref(_terrain_desc(keep, **kw)), None, tn, None) == _lib.BAD_ARG and word in _lib.last_error(), kw
     empty = _wb_desc(keep, B=0)
     assert call(C.byref(empty), None, None, turn, None) == _lib.OK and call(C.byref(empty), C.byref(t), None, None, None) == _lib.OK
-    assert call(C.byref(empty), None, None, C.byref(_lib_turn.Turn(None, 0.05)), None) == _lib.BAD_ARG
+    assert call(C.byref(empty), None, None, C.byref(_lib.Turn(None, 0.05)), None) == _lib.BAD_ARG
 
 
 def test_python_layer_refuses_before_the_gpu():
     with pytest.raises(ValueError, match="yaw_inertia"):
-        _lib_turn.turn_struct(float("nan"))
+        turn_struct(float("nan"))
     with pytest.raises(ValueError, match="yaw_inertia"):
-        _lib_turn.turn_struct(0.0)
-    assert _lib_turn.turn_struct(0.05).w_des is None
+        turn_struct(0.0)
+    assert turn_struct(0.05).w_des is None

@@ -42,7 +42,7 @@ def test_whole_body_plan_with_commands(gait, terrain):
     """DeviceWbPlan(w_des=W_DES) against problems.make_wb_batch(w_des=W_DES) with the tolerances of
     tests/test_plan_gpu.py::test_whole_body_plan_on_the_device (the kinematics differ in their last bits), on flat ground and on the
     stairs, normals included; the rows without a command are the plain call's, bit for bit; turn == NULL is the plain call"""
-    from bunmpc_amd import _lib_turn
+    from bunmpc_amd import _lib
     import torch
     turn_np.assert_away_from_ties(turn_np.batch(gait).x)
     wb = turn_np.batch(gait, True, terrain)
@@ -74,7 +74,7 @@ def test_whole_body_plan_with_commands(gait, terrain):
         getattr(third, k).fill_(float("nan"))
     stream = torch.cuda.current_stream().cuda_stream
     on = third.terrain is not None
-    rc = _lib_turn.lib().bmpc_wb_plan_batch_turn_device(C.byref(third.desc), C.byref(third.terrain.desc) if on else None,
+    rc = _lib.lib().bmpc_wb_plan_batch_turn_device(C.byref(third.desc), C.byref(third.terrain.desc) if on else None,
                                                        C.c_void_p(third.normals.data_ptr()) if on else None, None, C.c_void_p(stream))
     assert rc == 0
     zeros = host(wb_plan(gait, terrain, w_des=np.zeros(B), yaw_inertia=Izz).build(), WB_OUT + WB_MID + ("normals",))
@@ -153,7 +153,7 @@ def centroidal_case(gait, n=B):
 def test_centroidal_plan_with_the_yaw_momentum_reference(gait, terrain):
     """DevicePlan(yaw_inertia=...) against contact_plan + centroidal_costs + the override (:602-607): the same bits, as
     test_turning_and_off_grid_times asks of the plain call; turn == NULL is the plain call"""
-    from bunmpc_amd import _lib_turn
+    from bunmpc_amd import _lib
     from bunmpc_amd.plan_batch import DevicePlan
     import torch
     g = turn_np.GAITS[gait][0]
@@ -180,7 +180,7 @@ def test_centroidal_plan_with_the_yaw_momentum_reference(gait, terrain):
     third = DevicePlan(terrain=hm, **inp)
     for k in PLAN_OUT:
         getattr(third, k).fill_(float("nan"))
-    rc = _lib_turn.lib().bmpc_plan_batch_turn_device(C.byref(third.desc), C.byref(third.terrain.desc) if terrain else None,
+    rc = _lib.lib().bmpc_plan_batch_turn_device(C.byref(third.desc), C.byref(third.terrain.desc) if terrain else None,
                                                     C.c_void_p(third.normals.data_ptr()) if terrain else None, None,
                                                     C.c_void_p(torch.cuda.current_stream().cuda_stream))
     assert rc == 0

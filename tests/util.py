@@ -1,4 +1,34 @@
+import contextlib
+
 import numpy as np
+import pytest
+
+
+@contextlib.contextmanager
+def knob_setter():
+    """set_(setter name, value), callable many times: each call is a bunmpc_amd._lib.knobs block that stays open until this one ends, so
+    everything is restored in reverse order.  A fixture with presets of its own sets them inside this block and yields set_."""
+    from bunmpc_amd import _lib      # here, not at import: the tools that take rel_l2 and the envelopes from this module read no header
+    keyword = {setter: k for k, setter in _lib.KNOBS.items()}
+
+    def set_(name, value):
+        if name not in keyword:
+            raise TypeError("%s is not the setter of a dispatch knob (bunmpc_amd._lib.KNOBS)" % name)
+        stack.enter_context(_lib.knobs(**{keyword[name]: value}))
+    with contextlib.ExitStack() as stack:
+        yield set_
+
+
+@pytest.fixture
+def knobs():
+    """sets dispatch knobs for one test and restores every one of them afterwards: knobs("bmpc_set_two_waves_per_simd", 1)"""
+    with knob_setter() as set_:
+        yield set_
+
+
+def launch_record(hiplib):
+    """(kernel name, lanes per problem, waves per SIMD) of the last centroidal launch"""
+    return hiplib.bmpc_biconvex_last_kernel_name().decode(), hiplib.bmpc_biconvex_last_lanes_per_problem(), hiplib.bmpc_biconvex_last_waves_per_simd()
 
 
 def rel_l2(a, b):

@@ -50,8 +50,8 @@ def interleaved(legs, args, torch):
 
 def measure(args):
     import torch
-    from bunmpc_amd import _lib_goals, problems, urdf_model
-    from bunmpc_amd.cc_goal_batch import DeviceCcGoals
+    from bunmpc_amd import problems, urdf_model
+    from bunmpc_amd.cc_goal_batch import DeviceCcGoals, plan_knots
     from bunmpc_amd.plan_batch import DevicePlan
     gait, B, L = problems.TROT, args.B, args.episode_length
     b = problems.make_batch("solo12_trot", B)
@@ -66,7 +66,7 @@ def measure(args):
         goals[name] = DeviceCcGoals(gait, L, m["t0"], com, m["feet0_raw"], hip_off, m["v_des"], m["w_des"], goal_horizon=1, max_rows=rows,
                                     want_plan=want_plan)
         legs[name] = goals[name].build
-    out = {"B": B, "episode_length": L, "plan_knots": _lib_goals.plan_knots(L, gait), "arrays": interleaved(legs, args, torch)}
+    out = {"B": B, "episode_length": L, "plan_knots": plan_knots(L, gait), "arrays": interleaved(legs, args, torch)}
     g = goals["cc_goals_rows50"]
     out["arrays"]["switches_per_problem"] = float(g.counts.sum(dim=1).double().mean())
     out["arrays"]["status_nonzero"] = int((g.status != 0).sum())
