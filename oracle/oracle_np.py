@@ -112,16 +112,18 @@ def soc_projection(v, mu):
 
 
 class Fista:
-    def __init__(self, L0, beta=1.5, mu=1.0, soc=False):
-        self.L, self.beta, self.mu, self.soc = L0, beta, mu, soc
+    """fista.cpp.  projection(y, mu): what a step applies to the gradient step; None: the problem's box bounds."""
+
+    def __init__(self, L0, beta=1.5, mu=1.0, projection=None):
+        self.L, self.beta, self.mu, self.projection = L0, beta, mu, projection
         self.n_bt = 0
 
     def step(self, p, y):
         g = p.grad(y)
         while True:
             y1 = y - g / self.L
-            if self.soc:
-                y1 = soc_projection(y1, self.mu)
+            if self.projection is not None:
+                y1 = self.projection(y1, self.mu)
             else:
                 y1 = np.maximum(np.minimum(y1, p.ub), p.lb)
             d = y1 - y
@@ -150,20 +152,22 @@ class Fista:
 
 def biconvex_solve(cnt_plan, dt, m, x_init, Qx, qx, Qf, lbx, ubx, X, F, P,
                    L_x=2.25e6, L_f=506.25, rho=5e4, num_iters=10, maxit=150, tol=1e-5,
-                   exit_tol=1e-3, beta=1.5, mu=1.0, qf=None):
-    """BiConvexMP::optimize (biconvex.cpp:80-120).  Returns dict with X,F,P,L_x,L_f,hist,stats."""
+                   exit_tol=1e-3, beta=1.5, mu=1.0, qf=None, problem=Problem, projection=soc_projection, fista=Fista):
+    """BiConvexMP::optimize (biconvex.cpp:80-120).  Returns dict with X,F,P,L_x,L_f,hist,stats.
+    The seams of the restatements built on this one (tests/blockq_np.py, tests/cone_np.py, tools/screen_rate.py): problem(Q, q, lb, ub)
+    makes the two ProblemData objects, projection(y, mu) is what the force FISTA applies, fista is the class of the two solvers."""
     cnt_plan = np.asarray(cnt_plan, float)
     H, E, _ = cnt_plan.shape
     if qf is None:
         qf = np.zeros(3 * E * H)
-    px = Problem(np.asarray(Qx, float), np.asarray(qx, float), np.asarray(lbx, float),
+    px = problem(np.asarray(Qx, float), np.asarray(qx, float), np.asarray(lbx, float),
                  np.asarray(ubx, float))
-    pf = Problem(np.asarray(Qf, float), np.asarray(qf, float))
+    pf = problem(np.asarray(Qf, float), np.asarray(qf, float))
     px.x = np.array(X, float)
     pf.x = np.array(F, float)
     P = np.array(P, float)
-    fx = Fista(L_x, beta, mu, soc=False)
-    ff = Fista(L_f, beta, mu, soc=True)
+    fx = fista(L_x, beta, mu)
+    ff = fista(L_f, beta, mu, projection)
     hist, trace, it_f, it_x, status, n_admm = [], [], 0, 0, 0, 0
     for _ in range(num_iters):
         A, b = build_A_x(px.x, cnt_plan, dt, m)

@@ -2,10 +2,8 @@
 import numpy as np
 
 from bunmpc_amd import problems
-from tests import blockq_np
+from tests import blockq_np, util
 
-LX = np.array([2.25e6, 1e4, 1e5, 3e5, 2.25e6, 5e4])      # tests/test_block_cost_gpu.py's step constants: retries in both loops
-LF = np.array([506.25, 10.0, 50.0, 506.25, 20.0, 100.0])
 MAIN = (0.5, 0.5)        # (lam_f, lam_x) of the main parity test
 STRONG = (4.0, 2.0)      # ... of the strong-weights test: cold starts backtrack twice in the force loop
 
@@ -35,9 +33,7 @@ def matrices(raw, i, E):
     return Qx, Qf
 
 
-def restatement(b, i, raw, iters, warm=None, L_x=2.25e6, L_f=506.25, sparse=True):
-    """problem i through tests/blockq_np.py (the reference's ProblemData with the whole matrix), cold or from warm = (X, F, P)"""
-    X0, F0, P0 = b.warm_start() if warm is None else warm
+def restatement(b, i, raw, iters, sparse=True, **kw):
+    """problem i through tests/blockq_np.py (the reference's ProblemData with the whole matrix); kw: util.restatement's"""
     Qx, Qf = matrices(raw, i, b.E)
-    return blockq_np.biconvex_solve(b.cnt_plan[i], b.dt[i], b.m, b.x_init[i], Qx, raw["qx"][i], Qf, raw["lbx"][i], raw["ubx"][i],
-                                    X0[i], F0[i], P0[i], sparse=sparse, L_x=L_x, L_f=L_f, rho=b.rho, mu=b.mu, num_iters=iters)
+    return util.restatement(b, i, dict(raw, Qx={i: Qx}, Qf={i: Qf}), iters, problem=blockq_np.PROBLEM[sparse], **kw)

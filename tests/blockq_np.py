@@ -1,11 +1,12 @@
 """CPU restatement of the centroidal solve with a NON-diagonal Q (test infrastructure, like oracle/oracle_np.py, which it extends):
 function::ProblemData with the whole matrix in its gradient and objective difference, problem.cpp:31-56 formula by formula.
-oracle_np's Fista, soc_projection, build_A_x, build_A_f and ADMM loop are used as they are: biconvex_solve constructs `Problem` by
-its module-level name, which is swapped for the call."""
+oracle_np's Fista, soc_projection, build_A_x, build_A_f and ADMM loop are used as they are: biconvex_solve takes the class of its two
+ProblemData objects as `problem`."""
 import numpy as np
 import scipy.sparse as sp
 
 from oracle import oracle_np
+from tests import util
 
 
 class BlockProblem(oracle_np.Problem):
@@ -33,20 +34,11 @@ class DenseBlockProblem(BlockProblem):
     sparse = False
 
 
-def biconvex_solve(cnt_plan, dt, m, x_init, Qx, qx, Qf, lbx, ubx, X, F, P, sparse=True, **kw):
-    """oracle_np.biconvex_solve with Qx (nx, nx) and Qf (nf, nf) dense square matrices"""
-    orig = oracle_np.Problem
-    oracle_np.Problem = BlockProblem if sparse else DenseBlockProblem
-    try:
-        return oracle_np.biconvex_solve(cnt_plan, dt, m, x_init, np.asarray(Qx, float), qx, np.asarray(Qf, float), lbx, ubx, X, F, P, **kw)
-    finally:
-        oracle_np.Problem = orig
+PROBLEM = {True: BlockProblem, False: DenseBlockProblem}      # by `sparse`: the problem= of oracle_np.biconvex_solve for dense square Qx, Qf
 
 
-def solve_problem(b, i, raw, blk, iters, warm=None, L_x=2.25e6, L_f=506.25, sparse=True):
-    """problem i of batch b with the raw bounds of `raw` and the block costs of `blk` (problems.block_costs), cold or from warm = (X, F, P)"""
+def solve_problem(b, i, raw, blk, iters, sparse=True, **kw):
+    """problem i of batch b with the raw bounds of `raw` and the block costs of `blk` (problems.block_costs); kw: util.restatement's"""
     from bunmpc_amd import problems
-    X0, F0, P0 = b.warm_start() if warm is None else warm
-    return biconvex_solve(b.cnt_plan[i], b.dt[i], b.m, b.x_init[i], problems.block_diag_matrix(blk["Qx_blk"][i]), blk["qx"][i],
-                          problems.block_diag_matrix(blk["Qf_blk"][i]), raw["lbx"][i], raw["ubx"][i], X0[i], F0[i], P0[i],
-                          sparse=sparse, L_x=L_x, L_f=L_f, rho=b.rho, mu=b.mu, num_iters=iters)
+    Q = dict(Qx={i: problems.block_diag_matrix(blk["Qx_blk"][i])}, Qf={i: problems.block_diag_matrix(blk["Qf_blk"][i])})
+    return util.restatement(b, i, dict(raw, qx=blk["qx"], **Q), iters, problem=PROBLEM[sparse], **kw)

@@ -1,6 +1,6 @@
 """The CPU twin of the Euclidean friction-cone projection about per-contact surface normals (bmpc_contact_frame_t) and the shared pieces
 of its tests: the projection, the normals of the cases, and the numpy restatement of the solve with it -- tests/cone_np.py's cases and
-restatement with the projection swapped."""
+restatement with this projection as its argument."""
 import functools
 
 import numpy as np
@@ -55,10 +55,7 @@ def normals(B, H, E):
 
 def restatement(b, i, iters, mu, nrm, **kw):
     """cone_np.restatement of problem i with the projection about the normals nrm (H, E, 3); "branches" as there"""
-    count = [0, 0, 0]
-    out = cone_np.restatement(b, i, iters, mu, projection=lambda v, m: project_frame(v, m, nrm, count), **kw)
-    out["branches"] = np.array(count)
-    return out
+    return cone_np.restatement(b, i, iters, mu, projection=lambda v, m, count: project_frame(v, m, nrm, count), **kw)
 
 
 @functools.lru_cache(maxsize=None)

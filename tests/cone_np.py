@@ -1,14 +1,14 @@
 """The CPU twin of the Euclidean friction-cone projection (bmpc_cone_t, projection 1) and the shared pieces of its tests: the projection
-itself, the numpy restatement of the solve with it (oracle/oracle_np.py with its projection swapped for the duration of a call), and the
-cases the CPU and the GPU tests run."""
+itself, the numpy restatement of the solve with it (oracle/oracle_np.py, which takes the force FISTA's projection as an argument), and
+the cases the CPU and the GPU tests run."""
 import functools
 
 import numpy as np
 
 from bunmpc_amd import problems
 from oracle import oracle_np
+from tests import util
 
-MAPPINGS = [(3, 16), (15, 16), (20, 21), (20, 32), (31, 32), (63, 64)]      # (H, lanes per problem)
 CONFIGS = ["solo12_trot", "biped_walk"]
 L_F = 40.0                  # the force step constant the cases start from: every case takes force-loop retries
 MU_RANGE = (0.05, 0.3)
@@ -54,26 +54,14 @@ def raw_batch(b):
     return {k: np.stack([r[k] for r in rows]) for k in rows[0]}
 
 
-def restatement(b, i, iters, mu, warm=None, L_x=2.25e6, L_f=506.25, x_init=None, qf=None, projection=project):
-    """problem i of batch b through oracle_np.biconvex_solve with oracle_np.soc_projection swapped for `projection` during the call
-    (Fista.step looks it up as a module global).  mu: a scalar or (H, E); warm = (X, F, P) of the batch or None for a cold start;
-    x_init: in place of b.x_init[i] (a cold start then begins at X = tile(x_init)).  Beside biconvex_solve's result: "branches", the
-    vectors that took the zero / inside / surface branch over the whole solve."""
-    X0, F0, P0 = b.warm_start() if warm is None else warm
-    if warm is None and x_init is not None:      # (a cold start is from the x_init of the call)
-        X0 = X0.copy()
-        X0[i] = np.tile(x_init, b.H + 1)
-    r = raw_of(b, i)
+def restatement(b, i, iters, mu, projection=project, **kw):
+    """problem i of batch b through util.restatement with `projection` (v, mu, count) applied by the force FISTA.  mu: a scalar or (H, E);
+    kw: util.restatement's.  Beside biconvex_solve's result: "branches", the vectors that took the zero / inside / surface branch over
+    the whole solve."""
     count = [0, 0, 0]
     mu = np.asarray(mu, dtype=np.float64)
-    mu_arg = float(mu) if mu.ndim == 0 else mu.reshape(-1)
-    saved = oracle_np.soc_projection
-    oracle_np.soc_projection = (lambda v, m: projection(v, m, count)) if projection is project else projection
-    try:
-        out = oracle_np.biconvex_solve(b.cnt_plan[i], b.dt[i], b.m, b.x_init[i] if x_init is None else x_init, r["Qx"], r["qx"], r["Qf"],
-                                       r["lbx"], r["ubx"], X0[i], F0[i], P0[i], L_x=L_x, L_f=L_f, rho=b.rho, num_iters=iters, mu=mu_arg, qf=qf)
-    finally:
-        oracle_np.soc_projection = saved
+    out = util.restatement(b, i, {k: {i: v} for k, v in raw_of(b, i).items()}, iters, mu=float(mu) if mu.ndim == 0 else mu.reshape(-1),
+                           projection=lambda v, m: projection(v, m, count), **kw)
     out["branches"] = np.array(count)
     return out
 

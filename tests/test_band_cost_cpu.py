@@ -9,6 +9,9 @@ import scipy.sparse as sp
 
 from bunmpc_amd import _lib, problems
 from bunmpc_amd.biconvex_mpc_cpp import classify_cost
+from tests.test_block_cost_cpu import _descriptor
+
+BAND = (_lib.BandCost, lambda H, E: dict(Qx_off=9 * H, Qf_off=3 * E * (H - 1)))
 
 
 def _band(rng, n, k, sign=1.0):
@@ -102,24 +105,6 @@ def test_rate_helper_is_psd_and_equals_the_difference_form(oracle, E):
             assert kind == "band" and np.array_equal(got[0].reshape(-1), rc[name][i]) and np.array_equal(got[1], rc[name + "_off"][i])
 
 
-def _descriptor(hiplib, keep, B=1, H=20, E=4):
-    nx, nf = 9 * (H + 1), 3 * E * H
-    d = _lib.Batch()
-    hiplib.bmpc_batch_defaults(C.byref(d))
-    d.B, d.n_col, d.n_eff, d.raw, d.cold_start = B, H, E, 1, 1
-
-    def arr(n, v=0.0):
-        a = np.full(n, v)
-        keep.append(a)
-        return a.ctypes.data
-    d.cnt_plan, d.dt, d.x_init = arr(B * H * E * 4), arr(B * H, 0.05), arr(B * 9)
-    d.Qx, d.qx, d.lbx, d.ubx, d.Qf = arr(B * nx, 1.0), arr(B * nx), arr(B * nx, -1e9), arr(B * nx, 1e9), arr(B * nf, 1.0)
-    d.X, d.F, d.P, d.L_x, d.L_f = arr(B * nx), arr(B * nf), arr(B * nx), arr(B), arr(B)
-    c = _lib.BandCost()
-    c.Qx_off, c.Qf_off = arr(9 * H), arr(3 * E * (H - 1))
-    return d, c
-
-
 def test_band_symbols_are_bound(hiplib):
     for name in ("bmpc_band_cost_struct_size", "bmpc_biconvex_solve_batch_band_device", "bmpc_biconvex_solve_batch_band_host",
                  "bmpc_biconvex_set_cost_x_band", "bmpc_biconvex_set_cost_f_band", "bmpc_biconvex_band_kernel_scratch_bytes"):
@@ -133,7 +118,7 @@ def test_band_entry_points_refuse_what_is_not_built(hiplib):
     keep = []
     for change, word in ((dict(precision=1), "fp64"), (dict(raw=0), "raw"), (dict(n_col=64), "64 knots")):
         H = change.get("n_col", 20)
-        d, c = _descriptor(hiplib, keep, H=H)
+        d, c = _descriptor(hiplib, keep, BAND, H=H)
         for k, v in change.items():
             setattr(d, k, v)
         for call in (lambda: hiplib.bmpc_biconvex_solve_batch_band_host(C.byref(d), C.byref(c)),
@@ -143,7 +128,7 @@ def test_band_entry_points_refuse_what_is_not_built(hiplib):
             assert "neighbouring knots" in msg and word in msg, msg
     # a stride that is neither shared nor a whole problem's weights
     for field in ("sQx_off", "sQf_off"):
-        d, c = _descriptor(hiplib, keep)
+        d, c = _descriptor(hiplib, keep, BAND)
         setattr(c, field, 5)
         assert hiplib.bmpc_biconvex_solve_batch_band_host(C.byref(d), C.byref(c)) == _lib.BAD_ARG
         assert "stride" in hiplib.bmpc_last_error().decode()

@@ -19,14 +19,12 @@ import scipy.sparse as sp
 from bunmpc_amd import batch as bb
 from bunmpc_amd import problems
 from tests import bandq
-from tests.bandq import LF, LX
-from tests.util import K_SPREAD, knobs, launch_record, rel_l2  # noqa: F401  (knobs: the fixture)
+from tests.test_block_cost_gpu import _drive
+from tests.util import LF, LX, MAPPINGS, TOL_FP64, assert_matches_twin, knobs, launch_record, rel_l2  # noqa: F401  (knobs: the fixture)
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-5
 KQ = "biconvex_admm_kq_kernel"
 ALL = ("X", "F", "P", "L_x", "L_f", "stats", "hist", "trace", "dyn_viol")
-MAPPINGS = [(3, 16), (15, 16), (20, 21), (20, 32), (31, 32), (63, 64)]
 
 
 def _against_restatement(oracle, hiplib, knobs, config, H, lanes, mode, lam, sides="xf", may_skip=0):
@@ -38,32 +36,13 @@ def _against_restatement(oracle, hiplib, knobs, config, H, lanes, mode, lam, sid
     kw = dict(warm=b.warm_start(), L_x=LX, L_f=LF) if mode == "warm" else {}
     got = bb.solve_host(b, num_iters=iters, raw=raw, **kw)
     assert launch_record(hiplib) == (KQ, lanes, 1)
-    retries, skipped, worst = 0, [], 0.0
-    for i in range(b.B):
-        kwi = dict(warm=kw["warm"], L_x=LX[i], L_f=LF[i]) if mode == "warm" else {}
-        r = bandq.restatement(b, i, raw, iters, **kwi)
-        bound = TOL
-        if H == 63 or may_skip:      # the two accumulation orders of the restatement itself
-            r2 = bandq.restatement(b, i, raw, iters, sparse=False, **kwi)
-            if may_skip and not np.array_equal(r["stats"], r2["stats"]):
-                print("LEFT OUT", config, H, lanes, mode, lam, "problem", i, "CPU orders disagree:", r["stats"].tolist(), r2["stats"].tolist())
-                skipped.append(i)
-                continue
-            assert np.array_equal(r["stats"], r2["stats"]), i
-            if H == 63:
-                bound = max(TOL, K_SPREAD * max(rel_l2(r2["X"], r["X"]), rel_l2(r2["F"], r["F"])))
-        err = {k: rel_l2(got[k][i], r[k]) for k in "XFP"}
-        print(config, H, lanes, mode, lam, sides, i, "stats", got["stats"][i].tolist(), r["stats"].tolist(), "L", got["L_x"][i], got["L_f"][i], "err", err, "bound", bound)
-        assert np.array_equal(got["stats"][i], r["stats"]), i
-        assert got["L_x"][i] == r["L_x"] and got["L_f"][i] == r["L_f"], i
-        for k in "XFP":
-            assert err[k] < bound, (i, k, err[k], bound)
-        if H != 63:
-            worst = max(worst, max(err.values()))
-        retries += r["stats"][3] + r["stats"][4]
-    assert len(skipped) <= may_skip, skipped
-    print("WORST", config, H, lanes, mode, lam, sides, worst)
-    return retries
+    kwi = [dict(warm=kw["warm"], L_x=LX[i], L_f=LF[i]) if mode == "warm" else {} for i in range(b.B)]
+    twins = [bandq.restatement(b, i, raw, iters, **kwi[i]) for i in range(b.B)]
+    dense = None
+    if H == 63 or may_skip:      # the two accumulation orders of the restatement itself
+        dense = [bandq.restatement(b, i, raw, iters, sparse=False, **kwi[i]) for i in range(b.B)]
+    return assert_matches_twin(got, twins, spread_of=dense if H == 63 else None, may_skip=may_skip, disagree=dense,
+                               tag="%s %d %d %s %s %s" % (config, H, lanes, mode, lam, sides))
 
 
 @pytest.mark.parametrize("mode", ["cold", "warm"])
@@ -114,7 +93,7 @@ def test_zero_coupling_matches_the_diagonal_kernel(oracle, hiplib, knobs, config
         assert np.array_equal(got["L_x"], ref["L_x"]) and np.array_equal(got["L_f"], ref["L_f"]), sides
         for k in "XFP":
             print("ZERO", config, sides, k, "max rel_l2", rel_l2(got[k], ref[k]).max(), "bits equal:", np.array_equal(got[k], ref[k]))
-            assert np.all(rel_l2(got[k], ref[k]) < TOL), (sides, k)
+            assert np.all(rel_l2(got[k], ref[k]) < TOL_FP64), (sides, k)
 
 
 def test_band_calls_without_coupling_are_the_plain_calls(hiplib):
@@ -222,21 +201,6 @@ def test_device_batch_carries_coupling(oracle, hiplib):
         assert np.array_equal(got[k], host[k]), k
 
 
-def _drive(mp, b, i, pre, Qx, qx, Qf, iters):
-    for t in range(b.H):
-        mp.set_contact_plan(b.cnt_plan[i, t], b.dt[i, t])
-    mp.set_bounds_x(pre["lbx"][i], pre["ubx"][i])
-    if Qx is not None:
-        mp.set_cost_x(Qx, qx)
-    if Qf is not None:
-        mp.set_cost_f(Qf, np.zeros(mp.nf))
-    X0, F0, P0 = b.warm_start()
-    mp.set_warm_start_vars(X0[i], F0[i], P0[i])
-    mp.set_step_constants(LX[i], LF[i])
-    mp.optimize(b.x_init[i], iters)
-    return dict(X=mp.return_opt_x(), F=mp.return_opt_f(), P=mp.return_opt_p(), stats=mp.last_stats(), L=mp.step_constants())
-
-
 @pytest.mark.parametrize("config,E", [("solo12_trot", 4), ("biped_walk", 2)])
 def test_dropin_takes_sparse_band_costs(oracle, hiplib, config, E):
     """BiconvexMP(m, 20, E) with scipy.sparse band Q_x and Q_f against the restatement; then a diagonal on the same handle: a fresh
@@ -255,7 +219,7 @@ def test_dropin_takes_sparse_band_costs(oracle, hiplib, config, E):
         assert np.array_equal(got["stats"], r["stats"]) and got["L"] == (r["L_x"], r["L_f"])
         assert r["stats"][3] + r["stats"][4] > 0
         for k in "XFP":
-            assert rel_l2(got[k], r[k]) < TOL, (i, k)
+            assert rel_l2(got[k], r[k]) < TOL_FP64, (i, k)
         fresh = BiconvexMP(b.m, 20, E)
         fresh.set_rho(b.rho)
         want = _drive(fresh, b, i, pre, pre["Qx"][i], pre["qx"][i], sp.diags(pre["Qf"][i]), 3)

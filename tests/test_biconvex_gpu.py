@@ -10,10 +10,9 @@ import pytest
 
 from bunmpc_amd import _lib, problems
 from bunmpc_amd import batch as bb
-from tests.util import cpu_spread, rel_l2, within_envelope
+from tests.util import LF, LX, TOL_FP64 as TOL, assert_matches_twin, cpu_spread, problem_args, rel_l2, within_envelope
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-5
 
 
 def test_lane_exchange_selftest(hiplib):
@@ -137,12 +136,10 @@ def test_handle_state_persists_between_solves(oracle):
     L1 = mp.step_constants()
     _drive_handle(mp, b, 0, 3, warm=False)     # continues from the previous X/F/P
     pre = oracle.solve_batch(b, num_iters=0)
-    X0, F0, P0 = b.warm_start()
-    args = (b.cnt_plan[0], b.dt[0], b.m, b.x_init[0], pre["Qx"][0], pre["qx"][0], pre["Qf"][0],
-            pre["lbx"][0], pre["ubx"][0])
-    r1 = oracle.biconvex_solve(*args, X0[0], F0[0], P0[0], L_x=2e5, L_f=40.0, rho=b.rho, num_iters=3)
+    args = problem_args(b, 0, pre)
+    r1 = oracle.biconvex_solve(*args, L_x=2e5, L_f=40.0, rho=b.rho, num_iters=3)
     assert (r1["L_x"], r1["L_f"]) == L1 and r1["stats"][3] > 0 and r1["stats"][4] > 0
-    r2 = oracle.biconvex_solve(*args, r1["X"], r1["F"], r1["P"], L_x=r1["L_x"], L_f=r1["L_f"],
+    r2 = oracle.biconvex_solve(*args[:9], r1["X"], r1["F"], r1["P"], L_x=r1["L_x"], L_f=r1["L_f"],
                                rho=b.rho, num_iters=3)
     assert rel_l2(mp.return_opt_x(), r2["X"]) < TOL and rel_l2(mp.return_opt_f(), r2["F"]) < TOL
     assert mp.step_constants() == (r2["L_x"], r2["L_f"])
@@ -155,18 +152,9 @@ def test_raw_form_with_backtracking(oracle, mapping, which):
     b = problems.make_batch("solo12_trot", 6)
     pre = oracle.solve_batch(b, num_iters=0)
     raw = {k: pre[k] for k in ("Qx", "qx", "lbx", "ubx", "Qf")}
-    Lx = np.array([2.25e6, 1e4, 1e5, 3e5, 2.25e6, 5e4])
-    Lf = np.array([506.25, 10.0, 50.0, 506.25, 20.0, 100.0])
-    X0, F0, P0 = b.warm_start()
-    got = bb.solve_host(b, num_iters=3, raw=raw, warm=(X0, F0, P0), L_x=Lx, L_f=Lf)
-    for i in range(b.B):
-        r = oracle.biconvex_solve(b.cnt_plan[i], b.dt[i], b.m, b.x_init[i], pre["Qx"][i], pre["qx"][i],
-                                  pre["Qf"][i], pre["lbx"][i], pre["ubx"][i], X0[i], F0[i], P0[i],
-                                  L_x=Lx[i], L_f=Lf[i], rho=b.rho, num_iters=3)
-        assert np.array_equal(got["stats"][i], r["stats"]), i
-        assert got["L_x"][i] == r["L_x"] and got["L_f"][i] == r["L_f"]
-        for k in "XFP":
-            assert rel_l2(got[k][i], r[k]) < TOL, (i, k)
+    got = bb.solve_host(b, num_iters=3, raw=raw, warm=b.warm_start(), L_x=LX, L_f=LF)
+    assert_matches_twin(got, [oracle.biconvex_solve(*problem_args(b, i, pre), L_x=LX[i], L_f=LF[i], rho=b.rho, num_iters=3) for i in range(b.B)],
+                        tag="raw " + which)
     assert got["stats"][:, 3:5].sum() > 0
 
 
@@ -226,8 +214,7 @@ def test_long_horizons_before_the_chaos_sets_in(oracle, hiplib, H, B, raw):
         rawd["qf"] = rng.normal(0.0, 1e-3, pre["Qf"].shape)
         X0, F0, P0 = b.warm_start()
         got = bb.solve_host(b, keep_hist=True, raw=rawd, warm=(X0, F0, P0), **kw)
-        rs = [oracle.biconvex_solve(b.cnt_plan[i], b.dt[i], b.m, b.x_init[i], rawd["Qx"][i], rawd["qx"][i], rawd["Qf"][i], rawd["lbx"][i], rawd["ubx"][i],
-                                    X0[i], F0[i], P0[i], rho=b.rho, qf=rawd["qf"][i], **kw) for i in range(B)]
+        rs = [oracle.biconvex_solve(*problem_args(b, i, rawd), rho=b.rho, qf=rawd["qf"][i], **kw) for i in range(B)]
         ref = {k: np.stack([np.asarray(r[k]) for r in rs]) for k in ("X", "F", "P", "stats", "L_x", "L_f")}
     assert hiplib.bmpc_biconvex_last_kernel_name().decode() == "biconvex_admm_wg_kernel"
     assert np.array_equal(got["stats"], ref["stats"])
@@ -659,17 +646,9 @@ def test_latency_mapping_raw_form_warm_start_and_backtracking(oracle, mapping):
     pre = oracle.solve_batch(b, num_iters=0)
     raw = {k: pre[k] for k in ("Qx", "qx", "lbx", "ubx", "Qf")}
     raw["qf"] = 0.01 * np.random.default_rng(0).standard_normal(pre["Qf"].shape)
-    Lx = np.array([2.25e6, 1e4, 1e5, 3e5, 2.25e6, 5e4])
-    Lf = np.array([506.25, 10.0, 50.0, 506.25, 20.0, 100.0])
-    X0, F0, P0 = b.warm_start()
-    got = bb.solve_host(b, num_iters=3, raw=raw, warm=(X0, F0, P0), L_x=Lx, L_f=Lf)
-    for i in range(b.B):
-        r = oracle.biconvex_solve(b.cnt_plan[i], b.dt[i], b.m, b.x_init[i], pre["Qx"][i], pre["qx"][i], pre["Qf"][i], pre["lbx"][i],
-                                  pre["ubx"][i], X0[i], F0[i], P0[i], L_x=Lx[i], L_f=Lf[i], rho=b.rho, num_iters=3, qf=raw["qf"][i])
-        assert np.array_equal(got["stats"][i], r["stats"]), i
-        assert got["L_x"][i] == r["L_x"] and got["L_f"][i] == r["L_f"]
-        for k in "XFP":
-            assert rel_l2(got[k][i], r[k]) < TOL, (i, k)
+    got = bb.solve_host(b, num_iters=3, raw=raw, warm=b.warm_start(), L_x=LX, L_f=LF)
+    assert_matches_twin(got, [oracle.biconvex_solve(*problem_args(b, i, pre), L_x=LX[i], L_f=LF[i], rho=b.rho, num_iters=3, qf=raw["qf"][i])
+                              for i in range(b.B)], tag="wave raw")
     assert got["stats"][:, 3].sum() > 0 and got["stats"][:, 4].sum() > 0
     # early exit on exit_tol, different ADMM counts inside one launch
     b2 = problems.make_batch("solo12_trot", 2)
@@ -705,7 +684,6 @@ def test_cold_start_that_carries_the_step_constants(oracle, mapping):
     (kino_dyn.cpp:83-99), FISTA's L_ carried from the call before (fista.hpp:52: it is set in the constructor only)."""
     b = problems.make_batch("solo12_trot", 5)
     pre = oracle.solve_batch(b, num_iters=0)
-    X0, F0, P0 = b.warm_start()
     for which in ("batch", "wave"):
         mapping(which)
         dev = bb.DeviceBatch(b, num_iters=3)
@@ -715,13 +693,9 @@ def test_cold_start_that_carries_the_step_constants(oracle, mapping):
         for call in range(2):
             dev.solve()
             got = dev.results()
-            for i in range(b.B):
-                r = oracle.biconvex_solve(b.cnt_plan[i], b.dt[i], b.m, b.x_init[i], pre["Qx"][i], pre["qx"][i], pre["Qf"][i], pre["lbx"][i],
-                                          pre["ubx"][i], X0[i], F0[i], P0[i], L_x=Lx[i], L_f=Lf[i], rho=b.rho, num_iters=3)
-                assert np.array_equal(got["stats"][i], r["stats"]), (which, call, i)
-                assert got["L_x"][i] == r["L_x"] and got["L_f"][i] == r["L_f"]
-                assert rel_l2(got["X"][i], r["X"]) < TOL and rel_l2(got["F"][i], r["F"]) < TOL
-                Lx[i], Lf[i] = r["L_x"], r["L_f"]
+            twins = [oracle.biconvex_solve(*problem_args(b, i, pre), L_x=Lx[i], L_f=Lf[i], rho=b.rho, num_iters=3) for i in range(b.B)]
+            assert_matches_twin(got, twins, keys="XF", tag="carry %s %d" % (which, call))
+            Lx, Lf = np.array([r["L_x"] for r in twins]), np.array([r["L_f"] for r in twins])
             if call == 0:
                 assert got["stats"][:, 3:5].sum() > 0 and np.all(got["L_x"] > 2e5)
             else:

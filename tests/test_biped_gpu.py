@@ -10,11 +10,10 @@ import pytest
 from bunmpc_amd import _lib
 from bunmpc_amd import batch as bb
 from bunmpc_amd import problems
-from tests.util import chaos_ensemble, cpu_spread, knobs, launch_record, prefix_parity, rel_l2  # noqa: F401  (knobs: the fixture)
+from tests.util import TOL_FP64 as TOL, chaos_ensemble, cpu_spread, knobs, launch_record, prefix_parity, problem_args, rel_l2  # noqa: F401  (knobs: the fixture)
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-5      # the golden fixtures' tolerance (tests/test_biconvex_gpu.py)
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FP32_MEDIAN, FP32_P95, FP32_MAX = 5e-6, 1e-5, 1e-2      # tests/test_parity_envelope_gpu.py
 
@@ -125,9 +124,7 @@ def test_raw_form_on_the_batch_kernel(oracle, hiplib, knobs):
         got = bb.solve_host(b, num_iters=5, raw=dict(raw, qf=qf))
         assert launch_record(hiplib)[0] == "biconvex_admm_kernel"
         for i in range(b.B):
-            X0, F0, P0 = b.warm_start()
-            r = oracle.biconvex_solve(b.cnt_plan[i], b.dt[i], b.m, b.x_init[i], raw["Qx"][i], raw["qx"][i], raw["Qf"][i], raw["lbx"][i],
-                                      raw["ubx"][i], X0[i], F0[i], P0[i], rho=b.rho, num_iters=5, mu=b.mu, qf=None if qf is None else qf[i])
+            r = oracle.biconvex_solve(*problem_args(b, i, raw), rho=b.rho, num_iters=5, mu=b.mu, qf=None if qf is None else qf[i])
             assert np.array_equal(got["stats"][i], r["stats"]), i
             for k in "XFP":
                 assert rel_l2(got[k][i], r[k]) < TOL, (i, k)
@@ -220,11 +217,10 @@ def test_dropin_biped_handle(oracle):
     L1 = mp.step_constants()
     _drive(mp, b, 0, 3, warm=False)            # continues from the previous X / F / P and L
     pre = oracle.solve_batch(b.take([0]), num_iters=0)
-    X0, F0, P0 = b.warm_start()
-    args = (b.cnt_plan[0], b.dt[0], b.m, b.x_init[0], pre["Qx"][0], pre["qx"][0], pre["Qf"][0], pre["lbx"][0], pre["ubx"][0])
-    r1 = oracle.biconvex_solve(*args, X0[0], F0[0], P0[0], L_x=2e5, L_f=40.0, rho=b.rho, num_iters=3, mu=b.mu)
+    args = problem_args(b, 0, pre)
+    r1 = oracle.biconvex_solve(*args, L_x=2e5, L_f=40.0, rho=b.rho, num_iters=3, mu=b.mu)
     assert (r1["L_x"], r1["L_f"]) == L1 and r1["stats"][3] > 0 and r1["stats"][4] > 0
-    r2 = oracle.biconvex_solve(*args, r1["X"], r1["F"], r1["P"], L_x=r1["L_x"], L_f=r1["L_f"], rho=b.rho, num_iters=3, mu=b.mu)
+    r2 = oracle.biconvex_solve(*args[:9], r1["X"], r1["F"], r1["P"], L_x=r1["L_x"], L_f=r1["L_f"], rho=b.rho, num_iters=3, mu=b.mu)
     assert rel_l2(mp.return_opt_x(), r2["X"]) < TOL and rel_l2(mp.return_opt_f(), r2["F"]) < TOL
     assert mp.step_constants() == (r2["L_x"], r2["L_f"])
 

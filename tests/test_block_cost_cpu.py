@@ -9,11 +9,10 @@ import scipy.sparse as sp
 
 from bunmpc_amd import _lib, problems
 from bunmpc_amd.biconvex_mpc_cpp import classify_cost
-from oracle import oracle_np
 from tests import blockq_np
-from tests.util import rel_l2
+from tests.util import TOL_FP64, rel_l2, restatement
 
-TOL = 1e-5      # the project's parity tolerance (tests/test_biconvex_gpu.py)
+BLOCKS = (_lib.BlockCost, lambda H, E: dict(Qx_blk=81 * (H + 1), Qf_blk=9 * E * E * H))
 
 
 @pytest.mark.parametrize("config", ["solo12_trot", "biped_walk"])
@@ -21,19 +20,15 @@ def test_restatement_with_diagonal_blocks_matches_the_diagonal_oracle(oracle, co
     """the new checker against the existing one: a Q that holds the diagonal alone gives the diagonal restatement's counts and iterates"""
     b = problems.make_batch(config, 2, H=20)
     pre = oracle.solve_batch(b, num_iters=0)
-    X0, F0, P0 = b.warm_start()
     for i in range(b.B):
-        args = (b.cnt_plan[i], b.dt[i], b.m, b.x_init[i])
-        kw = dict(rho=b.rho, mu=b.mu, num_iters=3)
-        rd = oracle_np.biconvex_solve(*args, pre["Qx"][i], pre["qx"][i], pre["Qf"][i], pre["lbx"][i], pre["ubx"][i], X0[i], F0[i], P0[i], **kw)
+        rd = restatement(b, i, pre, 3)
+        whole = dict(pre, Qx={i: np.diag(pre["Qx"][i])}, Qf={i: np.diag(pre["Qf"][i])})
         for sparse in (True, False):
-            rb = blockq_np.biconvex_solve(*args, np.diag(pre["Qx"][i]), pre["qx"][i], np.diag(pre["Qf"][i]), pre["lbx"][i], pre["ubx"][i],
-                                          X0[i], F0[i], P0[i], sparse=sparse, **kw)
+            rb = restatement(b, i, whole, 3, problem=blockq_np.PROBLEM[sparse])
             assert np.array_equal(rd["stats"], rb["stats"]), (i, sparse)
             for k in "XFP":
                 print(config, i, sparse, k, rel_l2(rb[k], rd[k]))
-                assert rel_l2(rb[k], rd[k]) < TOL, (i, sparse, k)
-    assert oracle_np.Problem.__name__ == "Problem"      # the swap is undone
+                assert rel_l2(rb[k], rd[k]) < TOL_FP64, (i, sparse, k)
 
 
 @pytest.mark.parametrize("E", [2, 4])
@@ -83,7 +78,8 @@ def test_structure_classification(E, form):
             classify_cost(conv(Q[:-1, :-1]), n, k, "Q")
 
 
-def _descriptor(hiplib, keep, B=1, H=20, E=4):
+def _descriptor(hiplib, keep, cost, B=1, H=20, E=4):
+    """a raw batch descriptor of zeros and ones and a cost struct cost = (class, (H, E) -> {field: doubles}); the arrays go to `keep`"""
     nx, nf = 9 * (H + 1), 3 * E * H
     d = _lib.Batch()
     hiplib.bmpc_batch_defaults(C.byref(d))
@@ -96,8 +92,9 @@ def _descriptor(hiplib, keep, B=1, H=20, E=4):
     d.cnt_plan, d.dt, d.x_init = arr(B * H * E * 4), arr(B * H, 0.05), arr(B * 9)
     d.Qx, d.qx, d.lbx, d.ubx, d.Qf = arr(B * nx, 1.0), arr(B * nx), arr(B * nx, -1e9), arr(B * nx, 1e9), arr(B * nf, 1.0)
     d.X, d.F, d.P, d.L_x, d.L_f = arr(B * nx), arr(B * nf), arr(B * nx), arr(B), arr(B)
-    c = _lib.BlockCost()
-    c.Qx_blk, c.Qf_blk = arr(81 * (H + 1)), arr(9 * E * E * H)
+    c = cost[0]()
+    for field, n in cost[1](H, E).items():
+        setattr(c, field, arr(n))
     return d, c
 
 
@@ -107,7 +104,7 @@ def test_block_entry_points_refuse_what_is_not_built(hiplib):
     keep = []
     for change, word in ((dict(precision=1), "fp64"), (dict(raw=0), "raw"), (dict(n_col=64), "64 knots")):
         H = change.get("n_col", 20)
-        d, c = _descriptor(hiplib, keep, H=H)
+        d, c = _descriptor(hiplib, keep, BLOCKS, H=H)
         for k, v in change.items():
             setattr(d, k, v)
         for call in (lambda: hiplib.bmpc_biconvex_solve_batch_blocks_host(C.byref(d), C.byref(c)),
@@ -116,12 +113,12 @@ def test_block_entry_points_refuse_what_is_not_built(hiplib):
             msg = hiplib.bmpc_last_error().decode()
             assert "block costs" in msg and word in msg, msg
     # a stride that is neither shared nor a whole problem's blocks
-    d, c = _descriptor(hiplib, keep)
+    d, c = _descriptor(hiplib, keep, BLOCKS)
     c.sQx_blk = 5
     assert hiplib.bmpc_biconvex_solve_batch_blocks_host(C.byref(d), C.byref(c)) == _lib.BAD_ARG
     assert "stride" in hiplib.bmpc_last_error().decode()
     # an asymmetric block on the host entry point and on the handle
-    d, c = _descriptor(hiplib, keep)
+    d, c = _descriptor(hiplib, keep, BLOCKS)
     keep[-2][81 * 3 + 1] = 1.0      # Qx_blk, knot 3, (0, 1)
     assert hiplib.bmpc_biconvex_solve_batch_blocks_host(C.byref(d), C.byref(c)) == _lib.BAD_ARG
     assert "not symmetric at (0, 1)" in hiplib.bmpc_last_error().decode()

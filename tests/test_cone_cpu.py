@@ -12,7 +12,7 @@ from bunmpc_amd import batch as bb
 from bunmpc_amd.biconvex_mpc_cpp import BiconvexMP
 from oracle import oracle_np
 from tests import cone_np
-from tests.util import rel_l2
+from tests.util import MAPPINGS, rel_l2, restatement
 
 
 def _draws():
@@ -71,8 +71,9 @@ def test_go2_at_mu_one():
     Euclidean projection solves every problem (ten iterations, violation 1.08 .. 1.10: the cold start's ten iterations do not converge
     under either projection -- the reference's at mu = 10 leaves the same violation)"""
     b = problems.make_batch("go2_bound", 4, H=40)
+    raw = cone_np.raw_batch(b)
     for i in range(4):
-        ref = cone_np.restatement(b, i, 10, 1.0, projection=oracle_np.soc_projection)
+        ref = restatement(b, i, raw, 10, mu=1.0)
         assert ref["stats"][5] == 2 and ref["stats"][0] == 1, ref["stats"]
         r = cone_np.restatement(b, i, 10, 1.0)
         print("go2", i, "reference", ref["stats"].tolist(), "euclidean", r["stats"].tolist(), "violation", r["hist"][-1])
@@ -84,7 +85,7 @@ def test_mixed_gaits_become_deterministic():
     its forces by 1e-3; under the Euclidean projection the counts stay and the forces move by rounding -- in fewer force iterations"""
     b = problems.make_batch("solo12_mixed", 3)
     x1 = cone_np.one_ulp(b.x_init[2])
-    ref, ref1 = (cone_np.restatement(b, 2, 10, 0.5, x_init=x, projection=oracle_np.soc_projection) for x in (None, x1))
+    ref, ref1 = (restatement(b, 2, cone_np.raw_batch(b), 10, mu=0.5, x_init=x) for x in (None, x1))
     r, r1 = (cone_np.restatement(b, 2, 10, 0.5, x_init=x) for x in (None, x1))
     print("reference", ref["stats"].tolist(), ref1["stats"].tolist(), rel_l2(ref1["F"], ref["F"]), "euclidean", r["stats"].tolist(), r1["stats"].tolist(), rel_l2(r1["F"], r["F"]))
     assert not np.array_equal(ref["stats"], ref1["stats"]) and rel_l2(ref1["F"], ref["F"]) > 1e-4
@@ -92,7 +93,7 @@ def test_mixed_gaits_become_deterministic():
     assert r["stats"][5] == 0 and r["stats"][1] < ref["stats"][1]
 
 
-@pytest.mark.parametrize("H,lanes", cone_np.MAPPINGS)
+@pytest.mark.parametrize("H,lanes", MAPPINGS)
 @pytest.mark.parametrize("config", cone_np.CONFIGS)
 def test_gpu_cases_are_well_posed(config, H, lanes):
     """the precondition of tests/test_cone_gpu.py: per problem the twin and the twin with x_init[0] moved by one ulp agree on every

@@ -16,7 +16,7 @@ from bunmpc_amd import batch as bb
 from bunmpc_amd.biconvex_mpc_cpp import BiconvexMP
 from tests import cone_frame_np, cone_np
 from tests.test_cone_cpu import _draws
-from tests.util import rel_l2
+from tests.util import MAPPINGS, rel_l2
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EUCLID = dict(projection="euclidean")
@@ -77,7 +77,7 @@ def test_projection_is_the_euclidean_projection_in_a_tilted_frame():
     assert inside.sum() > 100 and np.array_equal(p[inside].view(np.uint64), v[inside].view(np.uint64))
 
 
-@pytest.mark.parametrize("H,lanes", cone_np.MAPPINGS)
+@pytest.mark.parametrize("H,lanes", MAPPINGS)
 @pytest.mark.parametrize("config", cone_np.CONFIGS)
 def test_gpu_cases_are_well_posed(config, H, lanes):
     """the precondition of tests/test_cone_frame_gpu.py: per problem the twin and the twin with x_init[0] moved by one ulp agree on

@@ -17,13 +17,11 @@ from bunmpc_amd import _lib, problems
 from bunmpc_amd import batch as bb
 from bunmpc_amd.biconvex_mpc_cpp import BiconvexMP
 from tests import cone_frame_np, cone_np
-from tests.util import K_SPREAD, knobs, launch_record, rel_l2  # noqa: F401  (knobs: the fixture)
+from tests.test_cone_gpu import CONE, EUCLID, OUT, _drive, _solve as _solve_case
+from tests.util import MAPPINGS, assert_matches_twin, knobs, launch_record  # noqa: F401  (knobs: the fixture)
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-5
-CONE, CONEF = "biconvex_admm_cone_kernel", "biconvex_admm_conef_kernel"
-OUT = ("X", "F", "P", "L_x", "L_f", "stats", "dyn_viol")
-EUCLID = dict(projection="euclidean")
+CONEF = "biconvex_admm_conef_kernel"
 E3 = np.array([0.0, 0.0, 1.0])
 
 
@@ -32,34 +30,11 @@ def _case(config, H):
     return b, mu, warm, iters, cone_frame_np.normals(b.B, H, b.E)
 
 
-def _solve(hiplib, knobs, config, H, lanes, form="harness", normals=None, kernel=CONEF):
-    """the case through the kernel in the harness form, the raw form or the raw form with a linear force cost; normals: in place of the
-    case's"""
-    knobs("bmpc_set_three_per_wave", 1 if lanes == 21 else 0)
-    b, mu, warm, iters, nrm = _case(config, H)
-    raw = None if form == "harness" else cone_np.raw_batch(b)
-    if form == "raw_qf":
-        raw["qf"] = cone_np.linear_force_cost(b)
-    cone = dict(EUCLID, mu=mu)
-    if normals is not False:
-        cone["normals"] = nrm if normals is None else normals
-    got = bb.solve_host(b, num_iters=iters, warm=warm, L_f=np.full(b.B, cone_np.L_F), raw=raw, cone=cone)
-    assert launch_record(hiplib) == (kernel, lanes, 1)
+def _solve(hiplib, knobs, config, H, lanes, form="harness", normals=None):
+    """tests/test_cone_gpu.py's _solve about the case's normals, or about `normals` in their place"""
+    nrm = _case(config, H)[4]
+    b, mu, got = _solve_case(hiplib, knobs, config, H, lanes, form, nrm if normals is None else normals, CONEF)
     return b, mu, nrm, got
-
-
-def _against_twin(got, twin, spread_of=None, tag=""):
-    """per problem: counts and step constants equal, iterates within the bound"""
-    for i, r in enumerate(twin):
-        bound = TOL
-        if spread_of is not None:
-            bound = max(TOL, K_SPREAD * max(rel_l2(spread_of[i][k], r[k]) for k in "XF"))
-        err = {k: rel_l2(got[k][i], r[k]) for k in "XFP"}
-        print(tag, i, "stats", got["stats"][i].tolist(), r["stats"].tolist(), "L", got["L_x"][i], got["L_f"][i], "err", err, "bound", bound)
-        assert np.array_equal(got["stats"][i], r["stats"]), i
-        assert got["L_x"][i] == r["L_x"] and got["L_f"][i] == r["L_f"], i
-        for k in "XFP":
-            assert err[k] < bound, (i, k, err[k], bound)
 
 
 def _feasible(F, mu, nrm):
@@ -74,11 +49,11 @@ def _same(a, b):
         assert np.array_equal(a[k], b[k]), k
 
 
-@pytest.mark.parametrize("H,lanes", cone_np.MAPPINGS)
+@pytest.mark.parametrize("H,lanes", MAPPINGS)
 @pytest.mark.parametrize("config", cone_np.CONFIGS)
 def test_harness_form_matches_the_twin(hiplib, knobs, config, H, lanes):
     b, mu, nrm, got = _solve(hiplib, knobs, config, H, lanes)
-    _against_twin(got, cone_frame_np.twin(config, H), cone_frame_np.twin(config, H, perturbed=True) if H == 63 else None, tag="%s %d %d" % (config, H, lanes))
+    assert_matches_twin(got, cone_frame_np.twin(config, H), cone_frame_np.twin(config, H, perturbed=True) if H == 63 else None, tag="%s %d %d" % (config, H, lanes))
 
 
 @pytest.mark.parametrize("form", ["raw", "raw_qf"])
@@ -86,10 +61,10 @@ def test_harness_form_matches_the_twin(hiplib, knobs, config, H, lanes):
 @pytest.mark.parametrize("config", cone_np.CONFIGS)
 def test_raw_form_matches_the_twin(hiplib, knobs, config, H, lanes, form):
     b, mu, nrm, got = _solve(hiplib, knobs, config, H, lanes, form)
-    _against_twin(got, cone_frame_np.twin(config, H, with_qf=form == "raw_qf"), tag="%s %d %d %s" % (config, H, lanes, form))
+    assert_matches_twin(got, cone_frame_np.twin(config, H, with_qf=form == "raw_qf"), tag="%s %d %d %s" % (config, H, lanes, form))
 
 
-@pytest.mark.parametrize("H,lanes", cone_np.MAPPINGS)
+@pytest.mark.parametrize("H,lanes", MAPPINGS)
 @pytest.mark.parametrize("config", cone_np.CONFIGS)
 def test_returned_forces_lie_in_their_cones(hiplib, knobs, config, H, lanes):
     """F is a projection's output: fn >= -1e-12 and |ft| - mu fn <= 1e-12 for every foot, knot and problem"""
@@ -103,7 +78,7 @@ def test_returned_forces_lie_in_their_cones(hiplib, knobs, config, H, lanes):
 @pytest.mark.parametrize("config", cone_np.CONFIGS)
 def test_world_z_normals_are_the_cone_kernel(hiplib, knobs, config, H, lanes):
     """normals (0, 0, 1) everywhere: every output equal to the cone kernel's on the same case"""
-    b, mu, nrm, want = _solve(hiplib, knobs, config, H, lanes, normals=False, kernel=CONE)
+    b, mu, want = _solve_case(hiplib, knobs, config, H, lanes)
     for shared in (False, True):
         z = np.broadcast_to(E3, ((1 if shared else b.B), H, b.E, 3))
         got = _solve(hiplib, knobs, config, H, lanes, normals=z)[3]
@@ -170,18 +145,6 @@ def test_device_batch_carries_the_normals(hiplib, knobs):
             got = dev.results()
             assert launch_record(hiplib) == (CONEF, 32, 1)
             _same(got, host)
-
-
-def _drive(mp, b, i, raw, warm, iters):
-    for t in range(b.H):
-        mp.set_contact_plan(b.cnt_plan[i, t], b.dt[i, t])
-    mp.set_bounds_x(raw["lbx"][i], raw["ubx"][i])
-    mp.set_cost_x(raw["Qx"][i], raw["qx"][i])
-    mp.set_cost_f(raw["Qf"][i], np.zeros(mp.nf))
-    mp.set_warm_start_vars(warm[0][i], warm[1][i], warm[2][i])
-    mp.set_step_constants(2.25e6, cone_np.L_F)
-    mp.optimize(b.x_init[i], iters)
-    return dict(X=mp.return_opt_x(), F=mp.return_opt_f(), P=mp.return_opt_p(), stats=mp.last_stats(), L=mp.step_constants())
 
 
 def _frame_with_third_row(n):

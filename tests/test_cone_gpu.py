@@ -17,39 +17,26 @@ from bunmpc_amd import _lib, problems
 from bunmpc_amd import batch as bb
 from bunmpc_amd.biconvex_mpc_cpp import BiconvexMP
 from tests import cone_np
-from tests.util import K_SPREAD, knobs, launch_record, rel_l2  # noqa: F401  (knobs: the fixture)
+from tests.util import MAPPINGS, assert_matches_twin, knobs, launch_record  # noqa: F401  (knobs: the fixture)
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-5
 CONE = "biconvex_admm_cone_kernel"
 OUT = ("X", "F", "P", "L_x", "L_f", "stats", "dyn_viol")
 EUCLID = dict(projection="euclidean")
 
 
-def _solve(hiplib, knobs, config, H, lanes, form):
-    """the case through the cone kernel in the harness form, the raw form or the raw form with a linear force cost"""
+def _solve(hiplib, knobs, config, H, lanes, form="harness", normals=None, kernel=CONE):
+    """the case through `kernel` in the harness form, the raw form or the raw form with a linear force cost; normals: (B or 1, H, E, 3)
+    unit vectors for cones about them (tests/test_cone_frame_gpu.py)"""
     knobs("bmpc_set_three_per_wave", 1 if lanes == 21 else 0)
     b, mu, warm, iters = cone_np.case(config, H)
     raw = None if form == "harness" else cone_np.raw_batch(b)
     if form == "raw_qf":
         raw["qf"] = cone_np.linear_force_cost(b)
-    got = bb.solve_host(b, num_iters=iters, warm=warm, L_f=np.full(b.B, cone_np.L_F), raw=raw, cone=dict(EUCLID, mu=mu))
-    assert launch_record(hiplib) == (CONE, lanes, 1)
+    cone = dict(EUCLID, mu=mu) if normals is None else dict(EUCLID, mu=mu, normals=normals)
+    got = bb.solve_host(b, num_iters=iters, warm=warm, L_f=np.full(b.B, cone_np.L_F), raw=raw, cone=cone)
+    assert launch_record(hiplib) == (kernel, lanes, 1)
     return b, mu, got
-
-
-def _against_twin(got, twin, spread_of=None, tag=""):
-    """per problem: counts and step constants equal, iterates within the bound"""
-    for i, r in enumerate(twin):
-        bound = TOL
-        if spread_of is not None:
-            bound = max(TOL, K_SPREAD * max(rel_l2(spread_of[i][k], r[k]) for k in "XF"))
-        err = {k: rel_l2(got[k][i], r[k]) for k in "XFP"}
-        print(tag, i, "stats", got["stats"][i].tolist(), r["stats"].tolist(), "L", got["L_x"][i], got["L_f"][i], "err", err, "bound", bound)
-        assert np.array_equal(got["stats"][i], r["stats"]), i
-        assert got["L_x"][i] == r["L_x"] and got["L_f"][i] == r["L_f"], i
-        for k in "XFP":
-            assert err[k] < bound, (i, k, err[k], bound)
 
 
 def _feasible(F, mu):
@@ -59,11 +46,11 @@ def _feasible(F, mu):
     assert np.all(F[..., 2] >= 0) and worst <= 1e-12
 
 
-@pytest.mark.parametrize("H,lanes", cone_np.MAPPINGS)
+@pytest.mark.parametrize("H,lanes", MAPPINGS)
 @pytest.mark.parametrize("config", cone_np.CONFIGS)
 def test_harness_form_matches_the_twin(hiplib, knobs, config, H, lanes):
     b, mu, got = _solve(hiplib, knobs, config, H, lanes, "harness")
-    _against_twin(got, cone_np.twin(config, H), cone_np.twin(config, H, perturbed=True) if H == 63 else None, tag="%s %d %d" % (config, H, lanes))
+    assert_matches_twin(got, cone_np.twin(config, H), cone_np.twin(config, H, perturbed=True) if H == 63 else None, tag="%s %d %d" % (config, H, lanes))
 
 
 @pytest.mark.parametrize("form", ["raw", "raw_qf"])
@@ -71,10 +58,10 @@ def test_harness_form_matches_the_twin(hiplib, knobs, config, H, lanes):
 @pytest.mark.parametrize("config", cone_np.CONFIGS)
 def test_raw_form_matches_the_twin(hiplib, knobs, config, H, lanes, form):
     b, mu, got = _solve(hiplib, knobs, config, H, lanes, form)
-    _against_twin(got, cone_np.twin(config, H, with_qf=form == "raw_qf"), tag="%s %d %d %s" % (config, H, lanes, form))
+    assert_matches_twin(got, cone_np.twin(config, H, with_qf=form == "raw_qf"), tag="%s %d %d %s" % (config, H, lanes, form))
 
 
-@pytest.mark.parametrize("H,lanes", cone_np.MAPPINGS)
+@pytest.mark.parametrize("H,lanes", MAPPINGS)
 @pytest.mark.parametrize("config", cone_np.CONFIGS)
 def test_returned_forces_lie_in_their_cones(hiplib, knobs, config, H, lanes):
     """F is a projection's output: fz >= 0 and |f_xy| - mu fz <= 1e-12 for every foot, knot and problem (the twin's worst: 7e-16)"""
@@ -140,7 +127,7 @@ def test_go2_at_mu_one(hiplib):
     got = bb.solve_host(b, num_iters=2, mu=1.0, cone=EUCLID)
     assert launch_record(hiplib) == (CONE, 64, 1)
     assert np.all(got["stats"][:, 5] == 0), got["stats"]
-    _against_twin(got, [cone_np.restatement(b, i, 2, 1.0) for i in range(4)], tag="go2")
+    assert_matches_twin(got, [cone_np.restatement(b, i, 2, 1.0) for i in range(4)], tag="go2")
     _feasible(got["F"], np.ones((4, 40, 4)))
 
 

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from tests import cone_np, f32_np
-from tests.util import rel_l2
+from tests.util import problem_args, rel_l2
 from oracle import oracle_np
 
 CASE_IDS = [f32_np.case_id(c) for c in f32_np.CASES]
@@ -62,12 +62,10 @@ def test_twin_in_fp64_is_the_reference(case, regime):
     A d for the image difference and the half gradient are the reference's algebra"""
     b, s = f32_np.batch(case)[0], f32_np.settings(case, regime)
     got = f32_np.run(case, regime, dtype=np.float64)
-    X0, F0, P0 = b.warm_start() if s["warm"] is None else s["warm"]
+    raw = cone_np.raw_batch(b)
     for i in range(b.B):
-        r = cone_np.raw_of(b, i)
-        ref = oracle_np.biconvex_solve(b.cnt_plan[i], b.dt[i], b.m, b.x_init[i], r["Qx"], r["qx"], r["Qf"], r["lbx"], r["ubx"], X0[i], F0[i], P0[i],
-                                       L_x=s["L_x"][i], L_f=s["L_f"][i], rho=b.rho, num_iters=s["num_iters"], maxit=s["maxit"], tol=s["tol"],
-                                       exit_tol=s["exit_tol"], mu=b.mu)
+        ref = oracle_np.biconvex_solve(*problem_args(b, i, raw, s["warm"]), L_x=s["L_x"][i], L_f=s["L_f"][i], rho=b.rho, num_iters=s["num_iters"],
+                                       maxit=s["maxit"], tol=s["tol"], exit_tol=s["exit_tol"], mu=b.mu)
         assert np.array_equal(got["stats"][i], ref["stats"]) and np.array_equal(got["trace"][i], ref["trace"])
         assert got["L_x"][i] == ref["L_x"] and got["L_f"][i] == ref["L_f"]
         err = {k: rel_l2(got[k][i], ref[k]) for k in "XFP"}

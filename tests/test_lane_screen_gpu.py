@@ -8,13 +8,12 @@ import pytest
 
 from bunmpc_amd import batch as bb
 from bunmpc_amd import problems
-from tests.util import knob_setter, launch_record, rel_l2
+from tests.util import TOL_FP64 as TOL, knob_setter, launch_record, rel_l2      # TOL: what tests/test_biconvex_gpu.py holds solo12_trot to
 
 pytestmark = pytest.mark.gpu
 
 KEYS = ("X", "F", "P", "L_x", "L_f", "stats", "trace", "hist", "dyn_viol", "cert_phases")
 HEADLINE = ("biconvex_admm_kernel", 32, 2)
-TOL = 1e-5      # what tests/test_biconvex_gpu.py holds solo12_trot at 10 ADMM iterations to (rel-L2 against the strict oracle)
 
 
 @pytest.fixture

@@ -11,17 +11,14 @@ import pytest
 
 from bunmpc_amd import problems
 from oracle import oracle_np
-from tests.util import rel_l2
+from tests.util import problem_args, rel_l2, restatement
 
 GOLDEN = sorted(p for p in glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz"))
                 if not os.path.basename(p).startswith(("ik_", "chaos_")))          # ik_*: whole-body fixtures (tests/test_ik_twin_cpu.py); chaos_*: ensembles (below)
 
 
 def _np_solve(b, i, ref, iters):
-    X0, F0, P0 = b.warm_start()
-    return oracle_np.biconvex_solve(b.cnt_plan[i], b.dt[i], b.m, b.x_init[i], ref["Qx"][i], ref["qx"][i],
-                                    ref["Qf"][i], ref["lbx"][i], ref["ubx"][i], X0[i], F0[i], P0[i],
-                                    rho=b.rho, num_iters=iters, mu=b.mu)
+    return restatement(b, i, ref, iters)
 
 
 def test_c_matches_numpy_trot(oracle):
@@ -38,11 +35,9 @@ def test_c_matches_numpy_trot(oracle):
 def test_c_matches_numpy_with_backtracking(oracle):
     """L0 far below the Lipschitz constants forces retries in both FISTA loops (fista.cpp:20-22)."""
     b = problems.make_batch("solo12_trot", 1)
-    X0, F0, P0 = b.warm_start()
     pre = oracle.solve_batch(b, num_iters=0)
     kw = dict(L_x=1e4, L_f=10.0, rho=b.rho, num_iters=3)
-    args = (b.cnt_plan[0], b.dt[0], b.m, b.x_init[0], pre["Qx"][0], pre["qx"][0], pre["Qf"][0],
-            pre["lbx"][0], pre["ubx"][0], X0[0], F0[0], P0[0])
+    args = problem_args(b, 0, pre)
     rc = oracle.biconvex_solve(*args, **kw)
     rn = oracle_np.biconvex_solve(*args, **kw)
     assert rc["stats"][3] > 0 and rc["stats"][4] > 0

@@ -3,6 +3,8 @@ import contextlib
 import numpy as np
 import pytest
 
+from oracle import oracle_np
+
 
 @contextlib.contextmanager
 def knob_setter():
@@ -50,17 +52,64 @@ TOL_FP64 = 1e-5
 K_SPREAD = 10.0
 
 
+# ---- the CPU restatement of one problem, and the per-problem check of a kernel against it -------------------------------------
+MAPPINGS = [(3, 16), (15, 16), (20, 21), (20, 32), (31, 32), (63, 64)]      # (H, lanes per problem) of the cost-shape kernels
+LX = np.array([2.25e6, 1e4, 1e5, 3e5, 2.25e6, 5e4])      # step constants of six warm problems that force retries in both FISTA loops
+LF = np.array([506.25, 10.0, 50.0, 506.25, 20.0, 100.0])
+
+
+def problem_args(b, i, raw, warm=None, x_init=None):
+    """the positional block of oracle_np.biconvex_solve and of the C oracle's biconvex_solve for problem i of batch b: raw[k][i] its
+    cost and bound arrays (Qx, qx, Qf, lbx, ubx), warm = (X, F, P) of the batch or None for b.warm_start(); x_init: in place of
+    b.x_init[i] (a cold start then begins at X = tile(x_init))"""
+    X0, F0, P0 = b.warm_start() if warm is None else warm
+    X = X0[i] if warm is not None or x_init is None else np.tile(x_init, b.H + 1)
+    return (b.cnt_plan[i], b.dt[i], b.m, b.x_init[i] if x_init is None else x_init, raw["Qx"][i], raw["qx"][i], raw["Qf"][i],
+            raw["lbx"][i], raw["ubx"][i], X, F0[i], P0[i])
+
+
+def restatement(b, i, raw, iters, warm=None, L_x=2.25e6, L_f=506.25, x_init=None, qf=None, mu=None, problem=oracle_np.Problem,
+                projection=oracle_np.soc_projection):
+    """problem i of batch b through oracle_np.biconvex_solve, cold or from warm = (X, F, P); mu: in place of b.mu; problem and
+    projection: the seams of oracle_np.biconvex_solve (a cost shape's ProblemData, a cone's projection)"""
+    return oracle_np.biconvex_solve(*problem_args(b, i, raw, warm, x_init), L_x=L_x, L_f=L_f, rho=b.rho, num_iters=iters,
+                                    mu=b.mu if mu is None else mu, qf=qf, problem=problem, projection=projection)
+
+
+def assert_matches_twin(got, twins, spread_of=None, tol=TOL_FP64, keys="XFP", may_skip=0, disagree=None, tag=""):
+    """The batch result `got` of a kernel against twins[i], the CPU restatement of problem i: the counts and both step constants equal,
+    rel_l2 of every array of `keys` below the bound -- tol, or max(tol, K_SPREAD x the distance in X and F of spread_of[i], a second CPU
+    run of the same problem, from twins[i]).  disagree: a second CPU run per problem whose counts must equal the twin's; a problem
+    where they differ is left out and printed, and more than may_skip of them fail.  Prints what it compares; returns the twins'
+    retries (both loops) over the problems compared."""
+    retries, skipped = 0, []
+    for i, r in enumerate(twins):
+        if disagree is not None and not np.array_equal(r["stats"], disagree[i]["stats"]):
+            print("LEFT OUT", tag, "problem", i, "CPU orders disagree:", r["stats"].tolist(), disagree[i]["stats"].tolist())
+            skipped.append(i)
+            continue
+        bound = tol
+        if spread_of is not None:
+            bound = max(tol, K_SPREAD * max(rel_l2(spread_of[i][k], r[k]) for k in "XF"))
+        err = {k: rel_l2(got[k][i], r[k]) for k in keys}
+        print(tag, i, "stats", np.asarray(got["stats"][i]).tolist(), r["stats"].tolist(), "L", got["L_x"][i], got["L_f"][i], "err", err, "bound", bound)
+        assert np.array_equal(got["stats"][i], r["stats"]), i
+        assert got["L_x"][i] == r["L_x"] and got["L_f"][i] == r["L_f"], i
+        for k in keys:
+            assert err[k] < bound, (i, k, err[k], bound)
+        retries += r["stats"][3] + r["stats"][4]
+    assert len(skipped) <= may_skip, skipped
+    return retries
+
+
 def cpu_spread(b, iters, oracle, with_numpy=True, **kw):
     """strict C solution of batch b and, per problem, the largest pairwise rel-L2 distance (X and F) among the CPU restatements"""
-    from oracle import oracle_np
     ref = oracle.solve_batch(b, num_iters=iters, **kw)
     fast = oracle.solve_batch(b, num_iters=iters, fast=True, **kw)
     s = np.maximum(rel_l2(fast["X"], ref["X"]), rel_l2(fast["F"], ref["F"]))
     if with_numpy:
-        X0, F0, P0 = b.warm_start()
         for i in range(b.B):
-            rn = oracle_np.biconvex_solve(b.cnt_plan[i], b.dt[i], b.m, b.x_init[i], ref["Qx"][i], ref["qx"][i], ref["Qf"][i], ref["lbx"][i],
-                                          ref["ubx"][i], X0[i], F0[i], P0[i], rho=b.rho, num_iters=iters, mu=b.mu,
+            rn = oracle_np.biconvex_solve(*problem_args(b, i, ref), rho=b.rho, num_iters=iters, mu=b.mu,
                                           **{k: v for k, v in kw.items() if k in ("maxit", "tol", "exit_tol")})
             s[i] = max(s[i], rel_l2(rn["X"], ref["X"][i]), rel_l2(rn["F"], ref["F"][i]), rel_l2(rn["X"], fast["X"][i]), rel_l2(rn["F"], fast["F"][i]))
     return ref, s

@@ -12,14 +12,12 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from bunmpc_amd import batch as bb, problems, urdf_model      # noqa: E402
-from oracle import oracle_c, oracle_np                         # noqa: E402
-from tests.util import rel_l2                                  # noqa: E402
+from oracle import oracle_c                                    # noqa: E402
+from tests.util import rel_l2, restatement                     # noqa: E402
 
 
 def np_solve(b, i, ref, iters):
-    X0, F0, P0 = b.warm_start()
-    return oracle_np.biconvex_solve(b.cnt_plan[i], b.dt[i], b.m, b.x_init[i], ref["Qx"][i], ref["qx"][i], ref["Qf"][i], ref["lbx"][i],
-                                    ref["ubx"][i], X0[i], F0[i], P0[i], rho=b.rho, num_iters=iters, mu=b.mu)
+    return restatement(b, i, ref, iters)
 
 
 def cpu_spread(b, iters, with_np=True):

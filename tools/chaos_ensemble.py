@@ -17,7 +17,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from bunmpc_amd import problems          # noqa: E402
-from oracle import oracle_c, oracle_np    # noqa: E402
+from oracle import oracle_c               # noqa: E402
 from tests import util                    # noqa: E402
 
 # (name, config, B, H, sample stride, ADMM iterations)
@@ -41,12 +41,10 @@ def wb_dyn_batch(robot, B):
 
 
 def numpy_member(b, ref, iters):
-    X0, F0, P0 = b.warm_start()
     out = dict(X=np.empty_like(ref["X"]), F=np.empty_like(ref["F"]), hist=np.full_like(ref["hist"], np.nan),
                trace=np.full_like(ref["trace"], -1))
     for i in range(b.B):
-        r = oracle_np.biconvex_solve(b.cnt_plan[i], b.dt[i], b.m, b.x_init[i], ref["Qx"][i], ref["qx"][i], ref["Qf"][i], ref["lbx"][i],
-                                     ref["ubx"][i], X0[i], F0[i], P0[i], rho=b.rho, num_iters=iters, mu=b.mu)
+        r = util.restatement(b, i, ref, iters)
         n = len(r["hist"])
         out["X"][i], out["F"][i] = r["X"], r["F"]
         out["hist"][i, :n], out["trace"][i, :n] = r["hist"], r["trace"]

@@ -72,13 +72,13 @@ def record_solve(b, i, num_iters=10, maxit=150, tol=1e-5):
     """problem i of the batch through oracle_np.biconvex_solve with every FISTA step recorded: returns {"force": [...], "motion": [...]},
     one (squares [iterations][knots][components], floor2) per phase -- squares[k][t] sums to knot t's share of |d|^2 in iteration k"""
     from oracle import oracle_np as on
-    width = {True: 3 * b.E, False: 9}
+    width = {True: 3 * b.E, False: 9}      # keyed by "the force phase": the solver with a projection
     phases = {True: [], False: []}
 
     class Recorder(on.Fista):
         def step(self, p, y):
             y1, G = super().step(p, y)
-            d = (y1 - y).reshape(-1, width[self.soc])
+            d = (y1 - y).reshape(-1, width[self.projection is not None])
             self._rows.append(d * d)
             return y1, G
 
@@ -86,7 +86,7 @@ def record_solve(b, i, num_iters=10, maxit=150, tol=1e-5):
             self._rows = []
             fl = floor2_of(p.bPk, p.x, self.L, p.rho)
             its = super().optimize(p, maxit, tol)
-            phases[self.soc].append((np.array(self._rows), fl))
+            phases[self.projection is not None].append((np.array(self._rows), fl))
             return its
 
     sb = 0 if b.W_X.shape[0] == 1 else i
@@ -94,12 +94,8 @@ def record_solve(b, i, num_iters=10, maxit=150, tol=1e-5):
     lbx, ubx = on.create_bound_constraints(b.cnt_plan[i], b.bounds[0 if b.bounds.shape[0] == 1 else i])
     Qf = b.W_F[0 if b.W_F.shape[0] == 1 else i]
     X0, F0, P0 = b.warm_start()
-    saved, on.Fista = on.Fista, Recorder
-    try:
-        on.biconvex_solve(b.cnt_plan[i], b.dt[i], b.m, b.x_init[i], Qx, qx, Qf, lbx, ubx, X0[i], F0[i], P0[i], rho=b.rho,
-                          num_iters=num_iters, maxit=maxit, tol=tol, mu=getattr(b, "mu", 1.0))
-    finally:
-        on.Fista = saved
+    on.biconvex_solve(b.cnt_plan[i], b.dt[i], b.m, b.x_init[i], Qx, qx, Qf, lbx, ubx, X0[i], F0[i], P0[i], rho=b.rho,
+                      num_iters=num_iters, maxit=maxit, tol=tol, mu=getattr(b, "mu", 1.0), fista=Recorder)
     return {"force": phases[True], "motion": phases[False]}
 
 
