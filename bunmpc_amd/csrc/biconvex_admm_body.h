@@ -478,6 +478,40 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
         if constexpr (CLDS) return reinterpret_cast<int *>(header() + kSegLds + (long)H * KL + 18);
         else return certn;
     };
+    // CLDS: the unit map of the force loop's two feet per lane (see the force step), made ONCE per solve: it follows from the contact plan
+    // and H alone -- a foot is in contact where an = c (dt / m) is not zero -- and neither changes within a solve.  A scatter through 64
+    // bytes of LDS per segment, the F block of knot H's record behind the two ints of cert_count (the last knot has no forces: every
+    // store to an F block is a force knot's or a unit's, t < H, so nothing but this writes there until the kernel ends); an entry: knot |
+    // rank << 5 | contact feet << 8, 0x8000 = no unit.  Behind its 32 entries the segment's mask of knots with two units, which an
+    // unsettled iteration reads.  `pair_fits` (wave-uniform): at most 32 units in each of the wave's problems.
+    // (The address from the lane number counted in place, as knot_record's: header() reads `lane`, which hipcc reloads from scratch memory.)
+    [[maybe_unused]] auto unit_map = [&]() {
+        const unsigned ln = opaque_copy(lane_id());
+        return reinterpret_cast<unsigned short *>(reinterpret_cast<double *>(lds_raw) + kLdsZeros + (long)(ln / (unsigned)LPP) * (kSegLds + (long)(H + 1) * KL) + kSegLds + (long)H * KL + 18 + 1);
+    };
+    [[maybe_unused]] bool pair_fits = false;
+    if constexpr (CLDS) {
+        if (a.force_foot_pairs != 0) {
+            const double *const cnt0 = a.cnt_plan + wave0 * H * (E * 4);
+            unsigned cmk = 0;      // the knot's contact feet, one bit per foot
+            UNROLL for (int n = 0; n < E; ++n) cmk |= ldz<R>(cnt0, oK * (unsigned)(E * 4), 4 * n, rvalid) * (dt / m) == R(0) ? 0u : 1u << n;
+            const bool two = __popc(cmk) > 2;
+            const mask_t two_m = __ballot(two);
+            pair_fits = H + __popc((unsigned)two_m) <= 32 && H + __popc((unsigned)(two_m >> 32)) <= 32;
+            const unsigned ln = opaque_copy(lane_id()), tl = ln & 31u;
+            const unsigned tw = ln < 32u ? (unsigned)two_m : (unsigned)(two_m >> 32);
+            const unsigned start = tl + (unsigned)__popc(tw & ((1u << tl) - 1u));      // (<= 31 for every knot lane where the map is used: pair_fits)
+            unsigned short *mp = unit_map();
+            mp[tl] = (unsigned short)0x8000u;
+            if (tl == 0u) reinterpret_cast<unsigned *>(mp)[16] = tw;
+            lds_fence();
+            if (pair_fits && rvalid) {
+                mp[start] = (unsigned short)(tl | cmk << 8);
+                if (two) mp[start + 1u] = (unsigned short)(tl | 32u | cmk << 8);
+            }
+            lds_fence();
+        }
+    }
 
     for (int it = 0; STEAL || it < a.c.num_iters; ++it) {
         if (alive == 0) break;
@@ -1073,7 +1107,8 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                             if (!seg_covered32(__ballot(s > theta), dead0, dead1)) {
                                 R g2 = 0;
                                 UNROLL for (int j = 0; j < NF; ++j) { const R d = xn[j] - y[j]; g2 = fmaR(d, d, g2); }
-                                if (!seg_covered32(__ballot(g2 > theta), dead0, dead1)) {
+                                const mask_t own = __ballot(g2 > theta);
+                                if (!seg_covered32(own, dead0, dead1) && !seg_covered32(own | quad_screen(g2, theta), dead0, dead1)) {      // (the quad stage: biconvex_lanes.h)
                                     const int r = unsettled(xo, ro, xn, rn, i, g2);
                                     if (r != kGo) return r;
                                 }
@@ -1098,39 +1133,25 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                     bool pairs_done = false;
                     if (a.force_foot_pairs != 0 && act != 0 && maxit > 0) {
                         keep_here(xa);      // (F_0's bits are looked at here: made in the prologue, the partial results are parked in scratch memory)
-                        unsigned cmk = 0;      // the knot's contact feet, one bit per foot
+                        // what the phase itself has to show: every swing foot's F_0 the bits of +0.0, and the feet without contact in the
+                        // plan (an = 0: the map's rule) swing feet in this phase's values too -- a non-finite X makes their sp NaN, and
+                        // the wave then runs four feet per lane, where such a foot's NaNs go the way they always went
                         unsigned f0bits = 0;      // the swing feet's F_0, every bit or'ed: +0.0 is no bit
+                        bool stale = false;
                         UNROLL for (int n = 0; n < E; ++n) {
-                            const bool swing = an[n] == R(0) && sp[n][0] == R(0) && sp[n][1] == R(0) && sp[n][2] == R(0);
-                            cmk |= swing ? 0u : 1u << n;
+                            const bool off = an[n] == R(0);
+                            const bool swing = off && sp[n][0] == R(0) && sp[n][1] == R(0) && sp[n][2] == R(0);
+                            stale = stale || (off && !swing);
                             unsigned w = 0;
                             UNROLL for (int k = 0; k < 3; ++k) w |= (unsigned)__double2hiint((double)xa[3 * n + k]) | (unsigned)__double2loint((double)xa[3 * n + k]);
                             f0bits |= swing ? w : 0u;
                         }
-                        const bool f0ok = f0bits == 0u;
-                        const bool two = __popc(cmk) > 2;
-                        const mask_t two_m = __ballot(two);
-                        const bool fits = H + __popc((unsigned)two_m) <= 32 && H + __popc((unsigned)(two_m >> 32)) <= 32;
-                        if (fits && __ballot(!f0ok) == 0) {
+                        const bool f0ok = f0bits == 0u && !stale;
+                        if (pair_fits && __ballot(!f0ok) == 0) {
                             #pragma clang fp contract(off)
-                            // ---- the unit map, by a scatter through 64 bytes of LDS per segment (the F block of knot H's record, which has no
-                            // forces: behind the two ints of cert_count); an entry: knot | rank << 5 | contact feet << 8, 0x8000 = no unit
-                            unsigned e;
-                            {
-                                const unsigned ln = opaque_copy(lane_id()), tl = ln & 31u;
-                                const unsigned tw = ln < 32u ? (unsigned)two_m : (unsigned)(two_m >> 32);
-                                const unsigned start = tl + (unsigned)__popc(tw & ((1u << tl) - 1u));      // (<= 31 for every knot lane: `fits`)
-                                unsigned short *mp = reinterpret_cast<unsigned short *>(header() + kSegLds + (long)H * KL + 18 + 1);
-                                mp[tl] = (unsigned short)0x8000u;
-                                lds_fence();
-                                if (rvalid) {
-                                    mp[start] = (unsigned short)(tl | cmk << 8);
-                                    if (two) mp[start + 1u] = (unsigned short)(tl | 32u | cmk << 8);
-                                }
-                                lds_fence();
-                                e = mp[tl];
-                                lds_fence();
-                            }
+                            // ---- the lane's entry of the unit map (made in front of the ADMM loop: unit_map)
+                            const unsigned e = unit_map()[opaque_copy(lane_id()) & 31u];
+                            lds_fence();
                             const bool uval = (e & 0x8000u) == 0u;
                             const int mrank = (e & 32u) != 0u ? -1 : 0;
                             const mask_t tfirst_m = __ballot(uval && mrank == 0 && __popc((e >> 8) & 15u) > 2);      // the first units of knots with two (a mask: see `lanes`)
@@ -1199,7 +1220,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                                     R g = gin;
                                     UNROLL for (int j = 0; j < 6; ++j) { const R d = xn[j] - py[j]; g = fmaR(d, d, g); }
                                     const unsigned ln = opaque_copy(lane_id()), tl = ln & 31u;
-                                    const unsigned tw = ln < 32u ? (unsigned)two_m : (unsigned)(two_m >> 32);
+                                    const unsigned tw = reinterpret_cast<const unsigned *>(unit_map())[16];      // (the segment's knots with two units)
                                     const unsigned last = tl + (unsigned)__popc(tw & ((2u << tl) - 1u));      // the knot's last unit
                                     const int src = (int)(4u * ((ln & 32u) + (last & 31u)));
                                     const double gd = (double)g;
@@ -1307,7 +1328,8 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                                     if (!seg_covered32(__ballot(sc > theta), dead0, dead1)) {
                                         R g2 = 0;
                                         UNROLL for (int j = 0; j < 6; ++j) { const R d = xn[j] - py[j]; g2 = fmaR(d, d, g2); }
-                                        if (!seg_covered32(__ballot(g2 > theta), dead0, dead1)) {
+                                        const mask_t own = __ballot(g2 > theta);
+                                        if (!seg_covered32(own, dead0, dead1) && !seg_covered32(own | quad_screen(g2, theta), dead0, dead1)) {      // (a quad of units: as sound)
                                             const int r = unsettled_p(xn, rn, i, g2);
                                             if (r != kGo) return r;
                                         }
@@ -1935,7 +1957,8 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                             if (!seg_covered32(__ballot(s > theta), dead0, dead1)) {
                                 R g2 = 0;      // stage 2: the whole partial, with the bits it always had
                                 UNROLL for (int l = 0; l < 9; ++l) { const R d = xn[l] - y[l]; g2 = fmaR(d, d, g2); }
-                                if (!seg_covered32(__ballot(g2 > theta), dead0, dead1)) {
+                                const mask_t own = __ballot(g2 > theta);
+                                if (!seg_covered32(own, dead0, dead1) && !seg_covered32(own | quad_screen(g2, theta), dead0, dead1)) {      // stage 3: the lane's quad (biconvex_lanes.h)
                                     const int r = unsettled(xo, ro, xn, rn, i, g2);
                                     if (r != kGo) return r;
                                 }

@@ -237,6 +237,29 @@ __device__ __forceinline__ bool seg_covered32(mask_t have, unsigned d0, unsigned
     return (t0 < t1 ? t0 : t1) != 0u;
 }
 
+// ---- a stage between the lane's whole partial and the segment sum (the loop-constants build's certified loops): the partial summed
+// over the lane's DPP quad, in fp32 -- one conversion and two DPP-fused v_add_f32.  Near a loop's exit the squared step is spread over
+// the knots and no single lane is above theta, while four neighbouring knots together still are.  An aligned quad lies inside one
+// power-of-two segment, its partials are non-negative, so the exact quad sum Q is at most the exact segment sum, and the segment sum
+// as the kernel adds it (fp64, five levels, non-negative terms) is at least Q (1 - 2^-50).  The fp32 value q over-estimates Q by at
+// most (1 + 2^-24)^3 in the normal range (a conversion and two additions, each rounded to nearest), plus four conversions' 2^-150 of
+// absolute error below it; flushing a subnormal only lowers q.  With the threshold theta (1 + 2^-20) rounded to fp32 (at least
+// theta (1 + 2^-21)) and no smaller than 2^-100, q above it means Q > theta (1 + 2^-22), hence a segment sum above
+// max(tol^2, floor2) (1 + 2^-40), clear of the floor, of tol^2 and of the band around it: what one lane above theta settles
+// (tests/test_quad_screen_cpu.py holds the margin against exact rational sums).  theta = +inf gives +inf: nothing settles.  A NaN
+// partial makes its quad's q NaN, which is above nothing.
+constexpr double kQuadScreenMargin = 1.0 + 0x1p-20;
+__device__ __forceinline__ float quad_theta_f32(double theta) { return __builtin_fmaxf((float)(theta * kQuadScreenMargin), 0x1p-100f); }
+__device__ __forceinline__ float quad_sum_f32(double g2) {
+    float q = (float)g2;
+    q += dpp_mov<DPP_QUAD_XOR1>(q);
+    q += dpp_mov<DPP_QUAD_XOR2>(q);
+    return q;
+}
+// the lanes whose quad settles their segment's iteration (made on a miss of the lane-local stages only, threshold included: three
+// instructions there against a scalar register held across the loop)
+__device__ __forceinline__ mask_t quad_screen(double g2, double theta) { return __ballot(quad_sum_f32(g2) > quad_theta_f32(theta)); }
+
 // The two decisions of a FISTA step -- retry (cv > (L/2) g2) and exit (g2 < tol^2) -- from WAVE sums of g2 and cv taken in fp32:
 // 4 DPP-fused v_add_f32 per value, one v_permlane16_swap that leaves the sums of g2 in rows 0 / 2 and of cv in rows 1 / 3, one
 // v_permlane32_swap, two v_readlane: 19 instructions against the 36 of the fp64 butterfly (seg_sum2<64>).  The fp32 sums of

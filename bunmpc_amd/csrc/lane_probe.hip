@@ -153,6 +153,20 @@ __global__ __launch_bounds__(64) void lane_probe_kernel(int group, const word_t 
     }
 }
 
+// The quad stage of the certified loops' screen (quad_sum_f32, quad_theta_f32, quad_screen), in a kernel of its own: lane_probe_kernel and
+// its seven groups stay the instructions they were.  NIN 2: the lane's partial g2 and a theta per lane, doubles; NOUT 3: quad_sum_f32(g2)
+// and quad_theta_f32(theta) as floats, and the ballot of quad_screen(g2, theta) (every lane writes the wave's word).
+constexpr int kQuadProbeIn = 2, kQuadProbeOut = 3;
+__global__ __launch_bounds__(64) void quad_probe_kernel(const word_t *in_all, word_t *out_all) {
+    const int lane = threadIdx.x;
+    const word_t *in = in_all + (size_t)blockIdx.x * 64 * kQuadProbeIn;
+    word_t *out = out_all + (size_t)blockIdx.x * 64 * kQuadProbeOut + lane;
+    const double g2 = as_double(in[lane]), theta = as_double(in[64 + lane]);
+    out[0] = bits(quad_sum_f32(g2));
+    out[64] = bits(quad_theta_f32(theta));
+    out[128] = quad_screen(g2, theta);
+}
+
 }  // namespace
 
 bool lane_probe_words(int group, int *nin, int *nout) {
@@ -167,3 +181,25 @@ hipError_t launch_lane_probe(int group, const unsigned long long *in, unsigned l
 }
 
 }  // namespace bunmpc
+
+// TEST ONLY, and in no header of include/: the tables of those headers are held to their recorded sizes, and bmpc_probe_lanes to its seven
+// groups, by tests/test_abi_cpu.py and tests/test_lane_probe_cpu.py, so the probe of the quad stage has an entry point of its own that
+// tests/test_quad_screen_gpu.py binds by name.  in / out are HOST arrays of 64-bit words laid out as bmpc_probe_lanes lays them out:
+// in [waves][2][64], out [waves][3][64] (quad_probe_kernel above).  BMPC_BAD_ARG before any device call, as there.
+extern "C" int bmpc_probe_quad_screen(const void *in, long in_bytes, void *out, long out_bytes) {
+    using namespace bunmpc;
+    const long wave_in = 512L * kQuadProbeIn, wave_out = 512L * kQuadProbeOut;
+    if (!in || !out || in_bytes < wave_in || in_bytes % wave_in != 0 || in_bytes / wave_in > (1L << 20)) return BMPC_BAD_ARG;
+    const long waves = in_bytes / wave_in;
+    if (out_bytes != waves * wave_out) return BMPC_BAD_ARG;
+    unsigned long long *din = nullptr;
+    if (hipMalloc(reinterpret_cast<void **>(&din), (size_t)(in_bytes + out_bytes)) != hipSuccess) return BMPC_DEVICE_ERROR;
+    unsigned long long *dout = din + in_bytes / 8;
+    bool ok = hipMemcpy(din, in, (size_t)in_bytes, hipMemcpyHostToDevice) == hipSuccess && hipMemset(dout, 0, (size_t)out_bytes) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(quad_probe_kernel, dim3((unsigned)waves), dim3(64), 0, nullptr, din, dout);
+        ok = hipGetLastError() == hipSuccess && hipMemcpy(out, dout, (size_t)out_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    (void)hipFree(din);
+    return ok ? BMPC_OK : BMPC_DEVICE_ERROR;
+}

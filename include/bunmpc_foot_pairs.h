@@ -18,7 +18,10 @@ extern "C" {
  * force loop: two feet per lane": B = 4096, n_col = 20, 2.40 -> 2.21 ms) resolves to "in every eligible phase".  Returns the old value. */
 int bmpc_set_force_foot_pairs(int mode);
 /* Telemetry: how many (wave, force phase) pairs ran that loop on the current device since the last reset (reset != 0: the count is
- * returned and set to 0).  A wave counts a phase only if both its problems were eligible.  Waits for the device; -1 on error. */
+ * returned and set to 0).  A wave counts a phase only if both its problems were eligible.  A wave that holds a non-finite iterate -- a
+ * diverged wave-mate's, dead or alive, its last knot's included -- is not eligible in that phase or any later one: it counts nothing from
+ * there on, at every horizon (before the unit map was made once per solve such a wave could still count phases at horizons below 20
+ * knots).  Outputs do not depend on which loop ran.  Waits for the device; -1 on error. */
 long bmpc_force_foot_pair_phases(int reset);
 
 #ifdef __cplusplus

@@ -12,7 +12,7 @@ settles both decisions ("no") and keeps the sum clear of the 1e-14 band around t
 A wave-iteration is screened when every problem of the wave that still iterates has such a lane; then the wave takes no sum at all.
 
     python tools/screen_rate.py [--config solo12_trot] [--B 24] [--waves 12] [--num-iters 10] [--per-wave 2]
-                                [--terms force=2 motion=3,5 ...]
+                                [--terms force=2 motion=3,5 ...] [--quad]
 
 solves the problems of `waves` waves spread evenly over the config's batch of B (a wave: per-wave consecutive problems, as the kernel
 takes them) with oracle_np, every FISTA step recorded knot by knot, and prints, per step, the wave-iterations and the share of them
@@ -99,10 +99,21 @@ def record_solve(b, i, num_iters=10, maxit=150, tol=1e-5):
     return {"force": phases[True], "motion": phases[False]}
 
 
-def wave_rate(records, which, tol=1e-5, terms=None):
+def quad_settles(row, th):
+    """does the quad stage settle a problem?  The knots' partials [knots] on lanes 0 .. (knot t on lane t, the lanes past the last knot
+    hold zeros), through the numpy model the kernel's helpers are held to bit for bit (tests/quad_screen_np.py: the fp32 sum of each
+    aligned group of four lanes against float(theta (1 + 2^-20)))"""
+    from tests import quad_screen_np
+    v = np.zeros(32)
+    v[:len(row)] = row
+    return bool(np.any(quad_screen_np.quad_screen(v, th)))
+
+
+def wave_rate(records, which, tol=1e-5, terms=None, quad=False):
     """(screened, total) wave-iterations of one wave: records = [record_solve(...)] of its problems.  Per phase the wave runs as many
     iterations as its longest problem; theta takes the largest floor of the problems that run the phase; an iteration is screened
-    when every problem still iterating has a knot above theta.  terms: the components whose squares are summed (default: all)."""
+    when every problem still iterating has a knot above theta.  terms: the components whose squares are summed (default: all).
+    quad: a problem also counts as settled when the quad stage settles it (quad_settles)."""
     hit = total = 0
     cols = slice(None) if terms is None else list(terms)
     for k in range(max(len(r[which]) for r in records)):
@@ -110,16 +121,16 @@ def wave_rate(records, which, tol=1e-5, terms=None):
         th = theta(tol * tol, max(fl for _, fl in ph))
         for it in range(max(len(p) for p, _ in ph)):
             live = [p[it][:, cols].sum(1) for p, _ in ph if it < len(p)]
-            hit += all(bool(np.any(row > th)) for row in live)
+            hit += all(bool(np.any(row > th)) or (quad and quad_settles(row, th)) for row in live)
             total += 1
     return hit, total
 
 
-def rates_of(recs, which, per_wave=2, tol=1e-5, terms=None):
+def rates_of(recs, which, per_wave=2, tol=1e-5, terms=None, quad=False):
     """(screened, total) wave-iterations of one step over recorded solves taken per_wave at a time"""
     hit = total = 0
     for w in range(0, len(recs), per_wave):
-        h, n = wave_rate(recs[w:w + per_wave], which, tol, terms)
+        h, n = wave_rate(recs[w:w + per_wave], which, tol, terms, quad)
         hit, total = hit + h, total + n
     return hit, total
 
@@ -154,6 +165,7 @@ def main():
     ap.add_argument("--num-iters", type=int, default=10)
     ap.add_argument("--per-wave", type=int, default=2)
     ap.add_argument("--terms", nargs="+", default=[], metavar="STEP=I,J", help="stage-1 term sets of the two-stage screen to rate, e.g. force=2 motion=3,5")
+    ap.add_argument("--quad", action="store_true", help="also rate a stage on the fp32 sum of the lane's DPP quad (knot t on lane t: the four-feet layout)")
     args = ap.parse_args()
     term_sets = parse_terms(args.terms)
     b = problems.make_batch(args.config, args.B)
@@ -165,6 +177,14 @@ def main():
         hit, total = rates_of(recs, which, args.per_wave)
         print("%-12s %-6s %d problems in waves of %d: %6d wave-iterations, %6d screened (%.1f %%), %.1f per wave"
               % (args.config, which, len(idx), args.per_wave, total, hit, 100.0 * hit / max(total, 1), total / max(1, -(-len(idx) // args.per_wave))))
+    if args.quad:      # a further stage between the lane's whole partial and the segment sum: the partial summed over the lane's DPP quad.
+        # Knot t on lane t: the motion loop's layout and the four-feet force loop's.  The force loop with two feet per lane sums quads of
+        # UNITS (per-unit partials of up to two feet, 26 .. 28 lanes): its rate is not this one, and is not modelled here.
+        for which in ("force", "motion"):
+            hit, total = rates_of(recs, which, args.per_wave)
+            hq, _ = rates_of(recs, which, args.per_wave, quad=True)
+            print("%-12s %-6s quad stage: %6d of the %6d unsettled wave-iterations settled; unsettled share %.1f %% -> %.1f %%"
+                  % (args.config, which, hq - hit, total - hit, 100.0 * (total - hit) / max(total, 1), 100.0 * (total - hq) / max(total, 1)))
     width = {"force": 3 * b.E, "motion": 9}
     for which, terms in term_sets:
         hit, total = rates_of(recs, which, args.per_wave, terms=terms)
