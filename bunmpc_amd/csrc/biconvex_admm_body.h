@@ -62,6 +62,47 @@ constexpr double kCertFloor = 2.0 * 25.0 / (kCertEta * kCertEta) * 0x1p-80;
 // vector atomic of lane 0 per such phase, telemetry for the tests of the eligibility rule
 [[maybe_unused]] __device__ unsigned long long g_foot_pair_phases = 0;
 
+// MATES (a launch geometry of the loop-constants build: DESIGN.md section 9 item 4).  The two waves that share a SIMD do not share it
+// evenly: at equal priority the older one issues nearly unimpeded, finishes early, and the younger runs its remainder alone at about
+// two thirds of the pair's throughput (profiles/simd_mates_step0.txt).  With one-wave workgroups the mates are grid indices i and
+// i + 1024 and cannot see each other; here a workgroup is EIGHT waves -- two per SIMD of its CU -- each with its own two problems,
+// (block x 8 + wave) x 2 + segment, and its own LDS area of loop_constants_lds_bytes, and behind the eight areas a mailbox of 16 words:
+// [0 .. 8) the SIMD a wave runs on (HW_REG_HW_ID, read once at entry; published in front of the kernel's one barrier), [8 .. 16) the
+// phase a wave has entered, counted from 1 (0: none yet; kMateDone: its solve is over).  A wave's mate is the one other wave of the
+// workgroup with its SIMD number; a wave that finds none, or several, takes no further part.  At the head of every force and motion
+// phase a wave publishes its count n and reads its mate's m: m >= n and the mate still solving -- the mate is level or ahead -- it
+// raises its priority (s_setprio 1), otherwise it lowers it (0).  Priority outranks age, so the wave behind takes the issue slots until
+// it has caught up: a phase or two later the roles swap.  The mailbox decides priorities only -- stale or wrong words cost time, never a
+// result -- and nothing is added inside the FISTA loops.  BatchArgs::force_foot_pairs carries the switch in bit 1 (bit 0: two feet per
+// lane): off, the geometry runs without the rule (every wave at priority 0).
+constexpr int kMateDone = 0x7fffffff;
+template <bool MATES, typename A>
+__device__ __forceinline__ constexpr decltype(auto) wave_lds(A &all, unsigned offset) {
+    if constexpr (MATES) return static_cast<double *>(all + offset);
+    else return (all);
+}
+#ifdef BMPC_SIMD_STAMPS
+// The diagnostic build of tools/simd_mates_stamps.py alone (the shipped kernels execute no stamp): when a wave
+// of the loop-constants build starts and ends and where it runs, 8 words per wave of BatchArgs::simd_stamps -- [0] the 100 MHz clock at
+// entry, [1] HW_REG_HW_ID (register 4: wave slot, SIMD, CU, shader array and engine) | HW_REG_XCC_ID (register 20) << 32, [2] the
+// shader clock at entry, [3] and [4] the two clocks at exit.  Written by lane 0 at once: nothing is held across the kernel, and no
+// output is computed from a stamp.
+__device__ __forceinline__ void simd_stamp(unsigned long long *stamps, bool entry) {
+    if (!stamps) return;
+    unsigned long long *w = stamps + 8 * ((size_t)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64);
+    const unsigned long long rt = __builtin_amdgcn_s_memrealtime(), clk = __builtin_amdgcn_s_memtime();
+    if ((threadIdx.x & 63) != 0) return;
+    if (entry) {
+        w[0] = rt;
+        w[1] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | 31 << 11) | (unsigned long long)__builtin_amdgcn_s_getreg(20 | 31 << 11) << 32;
+        w[2] = clk;
+    } else {
+        w[3] = rt;
+        w[4] = clk;
+    }
+}
+#endif
+
 // BQ (per-knot block-diagonal costs: raw form, fp64, one wave per SIMD): a lane holds its knot's SYMMETRIC block -- the upper triangle,
 // 45 values for X, 3E (3E + 1) / 2 for F -- where the other instantiations hold the knot's diagonal weights, loaded once per phase like
 // them.  Q y is a lane-local mat-vec and d'Q d a lane-local quadratic form, both accumulated row by row with the columns in increasing
@@ -110,7 +151,7 @@ constexpr int sym_index(int n, int r, int c) { return r <= c ? r * n - r * (r - 
 // which projection -- one value, so a variant cannot be two shapes at once -- and with it which argument struct the variant's arrays
 // come in (Extra; kDiag: an empty one).  What a shape's kernels are built for is asserted here from the shape's row of kShapes, the
 // table the launches, plan_launch and the C-ABI read as well.
-template <typename R_, int LPP_, int E_, bool RAW_, bool HASQF_, bool STEAL_ = false, bool XLDS_ = false, int WAVES_ = 1, CostShape SHAPE_ = kDiag, bool CLDS_ = false>
+template <typename R_, int LPP_, int E_, bool RAW_, bool HASQF_, bool STEAL_ = false, bool XLDS_ = false, int WAVES_ = 1, CostShape SHAPE_ = kDiag, bool CLDS_ = false, bool MATES_ = false>
 struct AdmmCfg {
     using R = R_;
     using Extra = ShapeExtra<SHAPE_>;
@@ -123,6 +164,8 @@ struct AdmmCfg {
     static constexpr bool BAND = !MW && !STEAL && XLDS && !RAW && LPP == 32 && E == 4 && FP64;      // (the headline kernel: see "fp32 step decisions" in the body)
     static constexpr bool CLDS = CLDS_;      // (the headline kernel with its certified loops' constants in LDS: see CLDS in the body)
     static_assert(!CLDS || BAND, "loop constants in LDS: a build of the headline kernel");
+    static constexpr bool MATES = MATES_;    // (its waves in workgroups of eight, SIMD-mates keeping level: see MATES in the body)
+    static_assert(!MATES || CLDS, "SIMD-mate workgroups: a geometry of the loop-constants build");
     static_assert(!kShapes[SHAPE_].fp64_only || FP64, "this cost shape: fp64 only");
     static_assert(!kShapes[SHAPE_].raw_only || RAW, "this cost shape: raw form only");
     static_assert(LPP * WAVES <= kShapes[SHAPE_].max_knots, "this cost shape: more lanes per problem than it has kernels for");
@@ -135,14 +178,28 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
     constexpr int LPP = C::LPP, E = C::E, WAVES = C::WAVES;
     [[maybe_unused]] constexpr bool RAW = C::RAW, HASQF = C::HASQF, STEAL = C::STEAL, XLDS = C::XLDS, BQ = C::BQ, KQ = C::KQ, CONE = C::CONE, FRAME = C::FRAME, MW = C::MW, PARK = C::PARK;
     [[maybe_unused]] const auto &bq = ex, &kq = ex;      // (the names the BQ and the KQ / CONE / FRAME code reads its arrays by)
-    extern __shared__ double lds_raw[];
+    [[maybe_unused]] constexpr bool MATES = C::MATES;
+    extern __shared__ double lds_all[];
+    // MATES: the wave's number in its workgroup and the doubles of one wave's LDS area -- wave-uniform, scalar registers
+    // (every MATES line under `if constexpr`: the other instantiations compile what they compiled without it)
+    [[maybe_unused]] unsigned wg_wave = 0, wave_doubles = 0;
+    if constexpr (MATES) {
+        wg_wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        wave_doubles = (unsigned)(loop_constants_lds_bytes(C::E, a.H) / sizeof(double));
+    }
+    // the wave's LDS: the array itself (a reference that no lambda has to capture) or, MATES, the wave's area in it
+    decltype(auto) lds_raw = wave_lds<MATES>(lds_all, MATES ? wg_wave * wave_doubles : 0u);
+    auto wave_ix = [&]() -> long { if constexpr (MATES) return (long)blockIdx.x * 8 + (long)wg_wave; else return (long)blockIdx.x; };
+#ifdef BMPC_SIMD_STAMPS
+    if constexpr (C::CLDS) simd_stamp(a.simd_stamps, true);
+#endif
     constexpr int NF = 3 * E;           // force variables per knot
     constexpr int NB = RAW ? 9 : 3;     // bounded components per knot
     const int lane = threadIdx.x & 63, wv = MW ? (int)(threadIdx.x >> 6) : 0;
     const int t = MW ? (int)threadIdx.x : lane % LPP;           // knot owned by this lane
     const int seg = MW ? 0 : lane / LPP;
     const int H = a.H;
-    long prob = MW ? (long)blockIdx.x : (long)blockIdx.x * (64 / LPP) + seg;      // (STEAL: the segment's FIRST problem)
+    long prob = MW ? (long)blockIdx.x : wave_ix() * (64 / LPP) + seg;      // (STEAL: the segment's FIRST problem)
     // STEAL: the lane's place in its segment decides what it owns; whether the segment has a problem at all is the `alive` mask's business
     const bool pvalid = seg < 64 / LPP && (STEAL || prob < a.B);      // (LPP = 21: lane 63 belongs to no segment)
     const bool kvalid = pvalid && t <= H;  // owns knot t (X block t)
@@ -281,7 +338,10 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
     // are unconditional -- straight-line code in which base + offset folds into the instruction, instead of some sixty
     // exec-masked blocks each needing the address as a 64-bit register pair -- and what a lane has no business with is
     // replaced by zero after the load (ldz).  Stores stay conditional.
-    const long wave0 = STEAL ? 0L : (MW ? (long)blockIdx.x : (long)blockIdx.x * (64 / LPP));
+    // (MATES: a wave of the last workgroup whose problems all lie beyond B -- one-wave workgroups have no such wave -- runs the prologue's
+    // unconditional loads on the batch's first problems; no lane of it is pvalid, so it stores nothing and leaves the ADMM loop at once)
+    const long wave0 = STEAL ? 0L : (MW ? (long)blockIdx.x : [&]() -> long {
+        if constexpr (MATES) { const long w = wave_ix() * (64 / LPP); return w < a.B ? w : 0L; } else return wave_ix() * (64 / LPP); }());
     unsigned sl = STEAL ? (unsigned)(pvalid && prob < a.B ? prob : 0) : (pvalid ? (unsigned)seg : 0u);      // STEAL: the problem index itself
     const unsigned tk = (unsigned)(t <= H ? t : H), tr = (unsigned)(t < H ? t : H - 1);
     struct Off { unsigned X, PI, F, K, P9; };
@@ -301,7 +361,40 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
     const double *const xinit_u = a.x_init + wave0 * 9;
 
     if (lane < kLdsZeros) zeros[lane] = R(0);
+    // MATES: the mailbox behind the eight waves' areas; every wave of the workgroup -- one whose problems lie beyond B too -- publishes its
+    // SIMD in front of the barrier, meets the barrier, and then looks for the one other wave with the same number
+    [[maybe_unused]] unsigned my_simd = 0;
+    if constexpr (MATES) {
+        int *const mailbox = reinterpret_cast<int *>(lds_all + 8u * wave_doubles);
+        my_simd = (unsigned)__builtin_amdgcn_s_getreg(4 | 4 << 6 | 1 << 11);      // HW_REG_HW_ID bits 5:4
+        if (lane == 0) { mailbox[wg_wave] = (int)my_simd; mailbox[8 + wg_wave] = 0; }
+    }
     __syncthreads();
+    [[maybe_unused]] int mate = -1;      // the mate's number in the workgroup (wave-uniform); -1: none, or the rule is off
+    if constexpr (MATES) {
+        if ((a.force_foot_pairs & 2) != 0) {
+            const int *const mailbox = reinterpret_cast<const int *>(lds_all + 8u * wave_doubles);
+            int found = 0;
+            UNROLL for (int w = 0; w < 8; ++w) {
+                const unsigned id = (unsigned)__builtin_amdgcn_readfirstlane(mailbox[w]);
+                if ((unsigned)w != wg_wave && id == my_simd) { mate = w; ++found; }
+            }
+            if (found != 1) mate = -1;
+        }
+    }
+    // ... and at the head of a phase, the n-th of the solve counted from 1 (kMateDone: behind the last): one word written, one read, one
+    // s_setprio -- see MATES above
+    [[maybe_unused]] auto mate_boundary = [&](int n) {
+        if constexpr (MATES) {
+            if (mate >= 0) {
+                int *const box = reinterpret_cast<int *>(lds_all + 8u * wave_doubles) + 8;
+                __hip_atomic_store(box + wg_wave, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);      // (every lane the same word: no exec mask to make)
+                const int m = __builtin_amdgcn_readfirstlane(__hip_atomic_load(box + mate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+                if (m >= n && m != kMateDone) __builtin_amdgcn_s_setprio(1);
+                else __builtin_amdgcn_s_setprio(0);
+            }
+        }
+    };
     const double *const cmtab = a.cmtab;      // (wave-uniform reads.  The loop-constants build takes them through the scalar cache, uniform_load; as plain
                                               // loads, everywhere else, hipcc makes them per-lane global loads of one address)
 
@@ -491,7 +584,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
     };
     [[maybe_unused]] bool pair_fits = false;
     if constexpr (CLDS) {
-        if (a.force_foot_pairs != 0) {
+        if ((MATES ? (a.force_foot_pairs & 1) : a.force_foot_pairs) != 0) {      // (MATES: bit 1 is the rule's switch)
             const double *const cnt0 = a.cnt_plan + wave0 * H * (E * 4);
             unsigned cmk = 0;      // the knot's contact feet, one bit per foot
             UNROLL for (int n = 0; n < E; ++n) cmk |= ldz<R>(cnt0, oK * (unsigned)(E * 4), 4 * n, rvalid) * (dt / m) == R(0) ? 0u : 1u << n;
@@ -521,6 +614,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
 
         // =================================================================== F step
         {
+            if constexpr (MATES) mate_boundary(2 * it + 1);
             if (PARK) park_x();
             const unsigned ph = opaque_zero();      // see opaque_zero (biconvex_lanes.h): the inputs are re-read in each phase
             // XLDS: ... and their offsets re-made from the problem's index (hoisted out of the ADMM loop they were a dozen registers
@@ -1131,7 +1225,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
                     // below the floor or a non-finite value at an exit stores nothing of the problems still iterating and falls through to
                     // the loop above, which runs the phase from iteration 0 (the records still hold F_0 and its image).
                     bool pairs_done = false;
-                    if (a.force_foot_pairs != 0 && act != 0 && maxit > 0) {
+                    if ((MATES ? (a.force_foot_pairs & 1) : a.force_foot_pairs) != 0 && act != 0 && maxit > 0) {
                         keep_here(xa);      // (F_0's bits are looked at here: made in the prologue, the partial results are parked in scratch memory)
                         // what the phase itself has to show: every swing foot's F_0 the bits of +0.0, and the feet without contact in the
                         // plan (an = 0: the map's rule) swing feet in this phase's values too -- a non-finite X makes their sp NaN, and
@@ -1426,6 +1520,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
 
         // =================================================================== X step
         {
+            if constexpr (MATES) mate_boundary(2 * it + 2);
             if (PARK) park_f();
             const unsigned ph = opaque_zero();
             const unsigned sl_ = XLDS ? opaque_copy(sl) : sl;
@@ -2115,6 +2210,7 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
             }
         }
     }
+    if constexpr (MATES) mate_boundary(kMateDone);      // (the solve is over: the mate keeps no priority against a wave that only stores its results)
     if constexpr (CLDS) {     // ---- results, with the record's address and the offsets made here (held from the kernel's start they are registers -- or scratch reloads -- of every phase)
         const R *re = record_or_front(kvalid_m);
         const double *He = header();
@@ -2136,6 +2232,9 @@ __device__ __forceinline__ void admm_body(const BatchArgs &a, const typename C::
             }
             if (a.cert_phases) { int *o = a.cert_phases + (wave0 + sle) * 2; const int *cn = cert_count(); o[0] = cn[0]; o[1] = cn[1]; }
         }
+#ifdef BMPC_SIMD_STAMPS
+        simd_stamp(a.simd_stamps, false);
+#endif
     } else
     if (!STEAL) {     // ---- results: one pass from LDS to the output blocks
         if (kvalid) { UNROLL for (int l = 0; l < 9; ++l) at(Xu, oX)[l] = (double)Xg[l]; }

@@ -28,6 +28,12 @@ template <int E>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void biconvex_admm_clds_kernel(const BatchArgs a) {
     admm_body<AdmmCfg<double, 32, E, false, false, false, true, 1, kDiag, true>>(a);
 }
+// ... and that build in workgroups of EIGHT waves, two per SIMD of a CU, each with its own two problems and its own LDS area: the waves
+// that share a SIMD see each other and keep level (biconvex_admm_body.h: MATES)
+template <int E>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void biconvex_admm_clds_mates_kernel(const BatchArgs a) {
+    admm_body<AdmmCfg<double, 32, E, false, false, false, true, 1, kDiag, true, true>>(a);
+}
 // horizons of 64 .. 255 knots: one problem per workgroup of WAVES waves (biconvex_admm_body.h: WAVES)
 template <int E, int WAVES, bool RAW, bool HASQF, int WPE>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void biconvex_admm_wg_kernel(const BatchArgs a) {
@@ -72,13 +78,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 
 // One instantiation of a unit: its kernel and the plan that takes it -- lanes per problem (above 64: the workgroup kernel of LPP / 64
 // waves), form (0 harness, 1 raw, 2 raw with qf), AdmmLaunch::w2 and ::steal.
-template <auto K, int LPP_, int FORM, bool W2 = false, bool STEAL_ = false, bool CLDS_ = false>
+template <auto K, int LPP_, int FORM, bool W2 = false, bool STEAL_ = false, bool CLDS_ = false, bool MATES_ = false>
 struct Inst {
     static constexpr auto kernel = K;
     static constexpr int LPP = LPP_;
-    static constexpr bool STEAL = STEAL_, CLDS = CLDS_;
+    static constexpr bool STEAL = STEAL_, CLDS = CLDS_, MATES = MATES_;
     static bool planned(const BatchArgs &a, const AdmmLaunch &l) {
-        return l.lpp == LPP && l.steal == STEAL && l.w2 == W2 && l.clds == CLDS && (a.raw ? (a.qf ? 2 : 1) : 0) == FORM;
+        return l.lpp == LPP && l.steal == STEAL && l.w2 == W2 && l.clds == CLDS && l.mates == MATES && (a.raw ? (a.qf ? 2 : 1) : 0) == FORM;
     }
 };
 // f(std::integral_constant<int, V>) for every V of a list
@@ -102,6 +108,7 @@ struct AdmmInsts {
         v(Inst<&biconvex_admm_steal_kernel<E, 1>, 21, 0, false, true>{});
         v(Inst<&biconvex_admm_steal_kernel<E, 2>, 21, 0, true, true>{});
         if constexpr (E == 4) v(Inst<&biconvex_admm_clds_kernel<E>, 32, 0, true, false, true>{});
+        if constexpr (E == 4) v(Inst<&biconvex_admm_clds_mates_kernel<E>, 32, 0, true, false, true, true>{});
     }
 };
 // fp32 (the units built without the SLP vectoriser): harness form, 16 / 32 / 64 lanes per problem
@@ -160,6 +167,22 @@ hipError_t launch_inst(const BatchArgs &a, const AdmmLaunch &l, hipStream_t stre
             }
         }
         hipLaunchKernelGGL(kernel, dim3(launch_grid(a.B, 1)), dim3(I::LPP), launch_lds_bytes(elem, 1, E, a.H, (size_t)(I::LPP / 64) * 40), stream, a);
+    } else if constexpr (I::MATES) {
+        // eight waves' areas and the mailbox: more than the 64 KB a kernel may take without asking, raised once per device as above
+        if (!loop_constants_fit(E, a.H)) return hipErrorInvalidValue;
+        static std::mutex lock;
+        static bool raised[16] = {};
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return hipErrorInvalidDevice;
+        {
+            std::lock_guard<std::mutex> hold(lock);
+            if (!raised[dev]) {
+                const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                if (attr != hipSuccess) return attr;
+                raised[dev] = true;
+            }
+        }
+        hipLaunchKernelGGL(kernel, dim3(launch_grid(a.B, 16)), dim3(512), simd_mates_lds_bytes(E, a.H), stream, a);
     } else if constexpr (I::CLDS) {
         if (!loop_constants_fit(E, a.H)) return hipErrorInvalidValue;
         hipLaunchKernelGGL(kernel, dim3(launch_grid(a.B, 2)), dim3(64), loop_constants_lds_bytes(E, a.H), stream, a);
@@ -214,7 +237,7 @@ int loop_constants_resident_waves(int H) {
     int waves = 0;
     Insts::each([&](auto inst) {
         using I = decltype(inst);
-        if constexpr (I::CLDS) {
+        if constexpr (I::CLDS && !I::MATES) {
             int n = 0;
             const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, I::kernel, 64, loop_constants_lds_bytes(Insts::E, H));
             waves = e == hipSuccess ? n : -1;

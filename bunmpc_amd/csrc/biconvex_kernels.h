@@ -63,6 +63,9 @@ struct BatchArgs {
         int *cert_phases;    // [B][2] {force phases, motion phases} that ran the certified loop from their first iteration, or null; written
                              // by the benchmark's instantiation alone (biconvex_admm_body.h: BAND), left as it is by every other kernel
     };
+#ifdef BMPC_SIMD_STAMPS      // (the diagnostic build of tools/simd_mates_stamps.py alone; the shipped library has no such member and executes no stamp)
+    unsigned long long *simd_stamps;      // (set by the launcher) [waves][8] or null: see simd_stamp, biconvex_admm_body.h
+#endif
 };
 
 // Per-knot block-diagonal costs (bmpc_block_cost_t): the knot's symmetric block in place of its diagonal weights, raw form, fp64, one
@@ -158,6 +161,9 @@ constexpr size_t loop_constants_extra(int H) { return 2 * (size_t)(H + 1) * kLoo
 constexpr size_t loop_constants_lds_bytes(int E, int H) { return launch_lds_bytes(sizeof(double), 2, E, H, loop_constants_extra(H)); }
 // eight such waves share a CU's 160 KB (two per SIMD): 20480 bytes each -- at four feet, k <= 21
 constexpr bool loop_constants_fit(int E, int H) { return H >= 1 && 8 * loop_constants_lds_bytes(E, H) <= 160 * 1024; }
+// ... and of a workgroup of eight such waves with the mailbox of 16 words behind them (biconvex_admm_body.h: MATES): at most 160 KB - 2432
+// bytes + 64 wherever loop_constants_fit holds
+constexpr size_t simd_mates_lds_bytes(int E, int H) { return 8 * loop_constants_lds_bytes(E, H) + 64; }
 // what mode 2 of set_loop_constants_in_lds ("when it pays") resolves to wherever the build fits: "always", by the measurement in
 // EXPERIMENTS.md ("Headline kernel: iterates in registers, loop constants in LDS": 2.82 -> 2.55 ms at B = 4096, H = 20)
 #ifndef BMPC_LOOP_CONSTANTS_PAY      // (side-by-side experiment builds: BUNMPC_EXTRA_FLAGS=-DBMPC_LOOP_CONSTANTS_PAY=0)
@@ -170,6 +176,16 @@ constexpr bool kLoopConstantsPay = BMPC_LOOP_CONSTANTS_PAY != 0;
 #define BMPC_FORCE_FOOT_PAIRS_PAY 1
 #endif
 constexpr bool kForceFootPairsPay = BMPC_FORCE_FOOT_PAIRS_PAY != 0;
+// what mode 2 of set_simd_mate_balance ("when it pays") resolves to where the batch fills the chip exactly once (biconvex_launch.hip:
+// simd_mates_pay): see EXPERIMENTS.md, "Headline kernel: SIMD-mate waves kept level"
+#ifndef BMPC_SIMD_MATES_PAY      // (side-by-side experiment builds: BUNMPC_EXTRA_FLAGS=-DBMPC_SIMD_MATES_PAY=0)
+#define BMPC_SIMD_MATES_PAY 1
+#endif
+constexpr bool kSimdMatesPay = BMPC_SIMD_MATES_PAY != 0;
+#ifndef BMPC_SIMD_MATES_RULE     // (measurements: -DBMPC_SIMD_MATES_RULE=0 is the eight-wave geometry without the rule in every mode, as mode 3 is)
+#define BMPC_SIMD_MATES_RULE 1
+#endif
+constexpr bool kSimdMatesRule = BMPC_SIMD_MATES_RULE != 0;
 constexpr unsigned launch_grid(int B, int per_wg) { return (unsigned)((B + per_wg - 1) / per_wg); }
 
 // The kernel a batch gets.  Set by plan_launch, except the cost arrays: launch_biconvex_admm adds those.
@@ -180,6 +196,8 @@ struct AdmmLaunch {
     long steal_waves;    // ... its persistent grid
     CostArgs cost;
     bool clds;           // the two-waves build with the certified loops' constants in LDS (32 lanes, four feet, harness form, fp64)
+    bool mates = false;        // ... in workgroups of eight waves (biconvex_admm_body.h: MATES)
+    bool mate_rule = false;    // ... whose SIMD-mates keep level by priority (false: the geometry alone)
 };
 // The instantiations of one cost shape, precision and foot count: one translation unit each (bunmpc_amd/build.py lists them).
 // launch: the launch plan_launch decided on (a.cmtab and, for the work-stealing kernel, a.queue set); scratch_bytes: the largest
@@ -212,6 +230,7 @@ struct DispatchKnobs {
     int certified_steps = 1;           // the fp64 batch kernels' per-phase step certificate: 0 off, 1 on, 2 force phases only
     int loop_constants_in_lds = 2;     // the headline kernel's build with loop constants in LDS and x_k in registers: 0 never, 1 whenever it fits, 2 when it pays
     int force_foot_pairs = 2;          // ... its certified force loop two feet per lane in eligible phases: 0 never, 1 always, 2 when it pays
+    int simd_mate_balance = 2;         // ... in eight-wave workgroups whose SIMD-mates keep level: 0 never, 1 wherever that build is taken, 2 when it pays, 3 as 1 without the rule (measurements)
 };
 struct LaunchPlan {
     hipError_t status;       // hipErrorInvalidValue: a shape no kernel is built for
@@ -243,6 +262,8 @@ int biconvex_last_lanes_per_problem();               // of the calling host thre
 int set_exact_step_decisions(int on);                // 1: every step decision from the fp64 sums, in every centroidal kernel; 2: fp32 decisions without the headline kernel's lane-local screen; returns the old value
 int set_loop_constants_in_lds(int mode);             // the headline kernel's certified loops with their constants in LDS and x_k in registers: 0 never, 1 whenever it fits, 2 when it pays (default); returns the old value
 int set_force_foot_pairs(int mode);                  // the loop-constants build's certified force loop with two feet per lane where a phase is eligible: 0 never, 1 always, 2 when it pays (default); returns the old value
+int set_simd_mate_balance(int mode);                 // the loop-constants build in eight-wave workgroups whose SIMD-mates keep level by priority: 0 never, 1 wherever that build is taken, 2 when it pays (default), 3 the geometry without the rule; returns the old value
+int biconvex_last_block_size();                      // threads per workgroup of the calling host thread's latest launch_biconvex_admm (0: the one-problem-per-wave kernel)
 int set_certified_steps(int on);                     // the fp64 batch kernels' per-phase step certificate: 0 off, 1 on (default), 2 force phases only; returns the old value
 
 // Lane-exchange self test (DPP shifts and segment sums used by the kernel).

@@ -92,9 +92,13 @@ int *steal_counter(hipStream_t stream) {
 DispatchKnobs g_knobs;
 // of the calling host thread's latest launch_biconvex_admm (tests of the default dispatch; profiles)
 thread_local const char *t_last_kernel = "";
-thread_local int t_last_lpp = 0, t_last_wpe = 1;
+thread_local int t_last_lpp = 0, t_last_wpe = 1, t_last_block = 0;
 
 int set_knob(int &knob, int value) { const int old = knob; knob = value; return old; }
+#ifdef BMPC_SIMD_STAMPS
+// the diagnostic build's stamp buffer (bmpc_simd_stamps_buffer, at the end of this file): the caller's device array, or null
+unsigned long long *g_simd_stamps = nullptr;
+#endif
 
 // Horizons of 17..21 knots: 32-lane segments (two problems per wave) or 21-lane segments (three per wave), whichever
 // finishes the batch sooner.  The kernel runs one wave per SIMD; a wave of three problems takes ~8 % longer than a wave of two
@@ -123,6 +127,17 @@ bool two_per_simd_pays(const BatchArgs &a, int per_wave, long simds, const Dispa
 bool loop_constants_pay(const BatchArgs &a, int n_eff, const DispatchKnobs &kn) {
     if (kn.loop_constants_in_lds == 0 || (kn.loop_constants_in_lds != 1 && !kLoopConstantsPay)) return false;
     return n_eff == 4 && !a.raw && a.precision == 0 && loop_constants_fit(n_eff, a.H);
+}
+
+// The loop-constants build in workgroups of eight waves whose SIMD-mates keep level (biconvex_admm_body.h: MATES).  Mode 1 (and 3, the
+// geometry without the rule): wherever that build is taken.  Mode 2, "when it pays": where the batch fills the chip exactly once at
+// two waves per SIMD -- as many workgroups of 16 problems as the device has CUs (an MI355X: 4081 <= B <= 4096); fewer would leave whole
+// CUs empty where one-wave workgroups spread over all of them, more would each wait for a whole CU to drain -- and kSimdMatesPay says
+// so.  Results do not depend on it.
+bool simd_mates_pay(const BatchArgs &a, long simds, const DispatchKnobs &kn) {
+    if (kn.simd_mate_balance == 0 || simd_mates_lds_bytes(4, a.H) > 160 * 1024) return false;
+    if (kn.simd_mate_balance == 1 || kn.simd_mate_balance == 3) return true;
+    return kSimdMatesPay && ((long)a.B + 15) / 16 == simds / 4;
 }
 
 // The units' accessors at 4 * shape + 2 * precision + (two feet), null where kShapes[shape] builds no unit.  Made from kShapes alone: a
@@ -155,6 +170,8 @@ int set_exact_step_decisions(int on) { return set_knob(g_knobs.exact_step_decisi
 int set_certified_steps(int on) { return set_knob(g_knobs.certified_steps, on); }
 int set_loop_constants_in_lds(int mode) { return set_knob(g_knobs.loop_constants_in_lds, mode); }
 int set_force_foot_pairs(int mode) { return set_knob(g_knobs.force_foot_pairs, mode); }
+int set_simd_mate_balance(int mode) { return set_knob(g_knobs.simd_mate_balance, mode); }
+int biconvex_last_block_size() { return t_last_block; }
 int biconvex_last_waves_per_simd() { return t_last_wpe; }
 int biconvex_last_lanes_per_problem() { return t_last_lpp; }
 const char *biconvex_last_kernel_name() { return t_last_kernel; }
@@ -191,6 +208,8 @@ LaunchPlan plan_launch(const BatchArgs &a, CostShape shape, int n_eff, long simd
         p.l.lpp = lpp;
         p.l.w2 = diag && two_per_simd_pays(a, 64 / lpp, simds, kn);
         p.l.clds = p.l.w2 && lpp == 32 && loop_constants_pay(a, n_eff, kn);
+        p.l.mates = p.l.clds && simd_mates_pay(a, simds, kn);
+        p.l.mate_rule = p.l.mates && kn.simd_mate_balance != 3 && kSimdMatesRule;
         return p;
     };
     if (k <= 16) return segments(16);
@@ -235,8 +254,10 @@ hipError_t launch_biconvex_admm(const BatchArgs &args, const CostArgs &cost, int
     a.certified_steps = p.certified_steps;
     // (read by the loop-constants build alone; mode 2, "when it pays": see kForceFootPairsPay.  Results do not depend on it)
     a.force_foot_pairs = p.l.clds && (g_knobs.force_foot_pairs == 1 || (g_knobs.force_foot_pairs != 0 && kForceFootPairsPay)) ? 1 : 0;
+    if (p.l.mate_rule) a.force_foot_pairs |= 2;      // (bit 1, read by the eight-wave geometry alone: its SIMD-mates keep level)
     t_last_kernel = p.kernel;
     t_last_lpp = p.l.lpp;
+    t_last_block = p.latency ? 0 : (p.l.mates ? 512 : (p.l.lpp > 64 ? p.l.lpp : 64));
     // (the one-problem-per-wave kernel leaves the record of the waves per SIMD what the launch before it set: tests compare whole
     // (name, lanes, waves) records between consecutive launches, and bmpc_biconvex_plan_launch reports 0 for such a plan)
     if (p.latency) return launch_biconvex_latency(a, n_eff, stream);
@@ -244,6 +265,9 @@ hipError_t launch_biconvex_admm(const BatchArgs &args, const CostArgs &cost, int
     a.cmtab = momentum_table(stream);
     if (!a.cmtab) return hipErrorOutOfMemory;
     if (p.l.steal && !(a.queue = steal_counter(stream))) return hipErrorOutOfMemory;
+#ifdef BMPC_SIMD_STAMPS
+    a.simd_stamps = g_simd_stamps;
+#endif
     p.l.cost = cost;
     if (cost.shape == kBand && a.H < 2) { p.l.cost.f = nullptr; p.l.cost.sf = 0; }      // (one force knot: no pair)
     return admm_unit(cost.shape, a.precision, n_eff).launch(a, p.l, stream);
@@ -260,4 +284,19 @@ const char *biconvex_kernel_name(int H, int raw) {
     return k <= 16 ? "biconvex_admm_kernel<double, 16" : (k <= 21 && g_knobs.three_per_wave == 1 ? "biconvex_admm_kernel<double, 21" : (k <= 32 ? "biconvex_admm_kernel<double, 32" : "biconvex_admm_kernel<double, 64"));
 }
 
+#ifdef BMPC_SIMD_STAMPS
+void set_simd_stamps(unsigned long long *buf) { g_simd_stamps = buf; }
+#endif
+
 }  // namespace bunmpc
+
+// Exported, declared in no header of include/ (as bmpc_probe_quad_screen is): the switch of the eight-wave geometry and, for its tests,
+// the block size of the calling thread's latest launch.  tests/test_simd_mates_gpu.py and tools/simd_mates_stamps.py bind them.
+extern "C" int bmpc_set_simd_mate_balance(int mode) { return bunmpc::set_simd_mate_balance(mode); }
+extern "C" int bmpc_biconvex_last_block_size(void) { return bunmpc::biconvex_last_block_size(); }
+
+#ifdef BMPC_SIMD_STAMPS
+// The diagnostic build alone (BUNMPC_EXTRA_FLAGS=-DBMPC_SIMD_STAMPS, tools/simd_mates_stamps.py): a device array of 8 words per wave of
+// the next launches of the loop-constants build, or null for none.  The caller sizes it for the batch's waves.
+extern "C" void bmpc_simd_stamps_buffer(void *device_words) { bunmpc::set_simd_stamps(static_cast<unsigned long long *>(device_words)); }
+#endif
