@@ -70,9 +70,10 @@ def compile_jobs():
              ["-DADMM_UNIT_SHAPE=" + shape, "-DADMM_UNIT_PRECISION=%d" % precision, "-DADMM_UNIT_FEET=%d" % feet] +
              (_FP32_ADMM_FLAGS if precision else _FP64_ADMM_FLAGS)) for shape, precision, feet in units]
     # biconvex_launch.hip: host code and two helper kernels, which are held to the code the fp64 units' flags give them; lane_probe.hip: the
-    # lane helpers of biconvex_lanes.h behind bmpc_probe_lanes, compiled as the fp64 units compile them
+    # lane helpers of biconvex_lanes.h behind bmpc_probe_lanes, compiled as the fp64 units compile them; lie_probe.hip: the SE(3) primitives
+    # of rbd_device.h behind bmpc_probe_lie, contracted as ik_ddp.hip contracts them
     others = {"biconvex_launch.hip": _FP64_ADMM_FLAGS, "lane_probe.hip": _FP64_ADMM_FLAGS, "biconvex_latency.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], "bunmpc_capi.hip": [],
-              "ik_ddp.hip": ["-ffp-contract=on"], "bunmpc_ik_capi.hip": [], "plan_gen.hip": [], "id_ctrl.hip": [], "perturb.hip": [],
+              "ik_ddp.hip": ["-ffp-contract=on"], "lie_probe.hip": ["-ffp-contract=on"], "bunmpc_ik_capi.hip": [], "plan_gen.hip": [], "id_ctrl.hip": [], "perturb.hip": [],
               "cc_goals.hip": []}
     return jobs + [(src[:-len(".hip")], src, flags) for src, flags in others.items()]
 

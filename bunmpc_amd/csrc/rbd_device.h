@@ -57,7 +57,8 @@ RBD_D void sincos_fast(double x, double &s, double &c) {
     c = ((n + 1) & 2) ? -cc : cc;
 }
 
-// coefficients a = sin t / t, b = (1 - cos t)/t^2, c = (t - sin t)/t^3
+// coefficients a = sin t / t, b = (1 - cos t)/t^2, c = (t - sin t)/t^3.  b as a^2 / (1 + cos t) where cos t > 0: 1 - cos t loses eps / t^2
+// of its digits, which b K (jexp3, the V of exp6) shows as eps / t.  (t - sin t loses as much, but c only ever multiplies K^2.)
 RBD_D void abc(double t2, double &a, double &b, double &c) {
     if (t2 < 1e-6) {
         a = 1.0 - t2 / 6.0 + t2 * t2 / 120.0;
@@ -67,7 +68,7 @@ RBD_D void abc(double t2, double &a, double &b, double &c) {
         const double t = sqrt(t2);
         double st, ct;
         sincos_fast(t, st, ct);
-        a = st / t; b = (1.0 - ct) / t2; c = (t - st) / (t2 * t);
+        a = st / t; b = ct > 0.0 ? a * a / (1.0 + ct) : (1.0 - ct) / t2; c = (t - st) / (t2 * t);
     }
 }
 RBD_D void exp3(const double *w, double *R) {
@@ -86,31 +87,44 @@ RBD_D void exp6(const double *nu, double *R, double *p) {
     R[0] += 1.0; R[4] += 1.0; R[8] += 1.0; V[0] += 1.0; V[4] += 1.0; V[8] += 1.0;
     mat3vec(V, nu, p);
 }
+// Beyond 2 pi / 3 (cos t < -1/2) the antisymmetric part v = 2 sin t a fades and t / (2 sin t) multiplies its rounding: the axis comes from
+// the symmetric part instead, (R + R^T)/2 = cos t I + (1 - cos t) a a^T, solved for a a^T exactly (not taken as (R + I)/2, which is
+// a a^T only at pi), its sign from v; at pi itself v = 0 and the sign is free.  Below the cut the arithmetic is what it always was.
 RBD_D void log3(const double *R, double *w) {
     const double v[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
     const double nv = sqrt(dot3(v, v));
-    const double t = atan2(0.5 * nv, 0.5 * (R[0] + R[4] + R[8] - 1.0));
+    const double c = 0.5 * (R[0] + R[4] + R[8] - 1.0);
+    const double t = atan2(0.5 * nv, c);
     double f;
     if (t < 1e-3) f = 0.5 * (1.0 + t * t / 6.0 + 7.0 * t * t * t * t / 360.0);
-    else if (3.141592653589793 - t < 1e-6) {  // near pi: axis from the symmetric part
-        const double A[3] = {0.5 * (R[0] + 1.0), 0.5 * (R[4] + 1.0), 0.5 * (R[8] + 1.0)};
-        int k = A[0] >= A[1] ? (A[0] >= A[2] ? 0 : 2) : (A[1] >= A[2] ? 1 : 2);
-        double ax[3] = {0.25 * (R[k] + R[3 * k]), 0.25 * (R[3 + k] + R[3 * k + 1]), 0.25 * (R[6 + k] + R[3 * k + 2])};
-        ax[k] = A[k];
-        const double s = 1.0 / sqrt(A[k]);
-        double sg = (ax[0] * v[0] + ax[1] * v[1] + ax[2] * v[2]) < 0 ? -1.0 : 1.0;
-        for (int i = 0; i < 3; ++i) w[i] = sg * t * ax[i] * s;
+    else if (c < -0.5) {
+        const double ic = 1.0 / (1.0 - c);
+        const double A[3] = {(R[0] - c) * ic, (R[4] - c) * ic, (R[8] - c) * ic};      // a_i^2
+        const int k = A[0] >= A[1] ? (A[0] >= A[2] ? 0 : 2) : (A[1] >= A[2] ? 1 : 2);
+        const double ak = sqrt(A[k]), s = 0.5 * ic / ak;
+        double ax[3] = {s * (R[k] + R[3 * k]), s * (R[3 + k] + R[3 * k + 1]), s * (R[6 + k] + R[3 * k + 2])};
+        ax[k] = ak;
+        const double sg = (ax[0] * v[0] + ax[1] * v[1] + ax[2] * v[2]) < 0 ? -t : t;
+        for (int i = 0; i < 3; ++i) w[i] = sg * ax[i];
         return;
     } else { double st, ct; sincos_fast(t, st, ct); f = t / (2.0 * st); }
     w[0] = f * v[0]; w[1] = f * v[1]; w[2] = f * v[2];
 }
-RBD_D double beta_of(double t2) {
-    if (t2 < 1e-6) return 1.0 / 12.0 + t2 / 720.0 + t2 * t2 / 30240.0;
-    const double t = sqrt(t2);
-    double st, ct;
-    sincos_fast(t, st, ct);
-    return 1.0 / t2 - st / (2.0 * t * (1.0 - ct));
+// beta = 1/t^2 - cot(t/2) / (2 t), the K^2 coefficient of V^-1 and the w w^T coefficient of jlog3, and diag = (t/2) cot(t/2) = 1 - beta t^2.
+// From the half angle: 1/t^2 - sin t / (2 t (1 - cos t)) cancels to eps / t^4 (1e-4 of beta at t = 1e-3).  The series to t^6 below
+// t = 1e-2: its next term is 2e-24.
+RBD_D double beta_of(double t2, double &diag) {
+    if (t2 < 1e-4) {
+        diag = 1.0 - t2 * (1.0 / 12.0 + t2 * (1.0 / 720.0 + t2 * (1.0 / 30240.0)));
+        return 1.0 / 12.0 + t2 * (1.0 / 720.0 + t2 * (1.0 / 30240.0 + t2 * (1.0 / 1209600.0)));
+    }
+    const double h = 0.5 * sqrt(t2);
+    double sh, ch;
+    sincos_fast(h, sh, ch);
+    diag = h * ch / sh;
+    return (1.0 - diag) / t2;
 }
+RBD_D double beta_of(double t2) { double diag; return beta_of(t2, diag); }
 RBD_D void log6(const double *R, const double *p, double *nu) {
     double K[9], K2[9];
     log3(R, nu + 3);
@@ -123,9 +137,8 @@ RBD_D void log6(const double *R, const double *p, double *nu) {
 }
 RBD_D void jlog3(const double *w, double *J) {
     const double t2 = dot3(w, w);
-    double alpha, diag;
-    if (t2 < 1e-6) { alpha = 1.0 / 12.0 + t2 / 720.0 + t2 * t2 / 30240.0; diag = 0.5 * (2.0 - t2 / 6.0 - t2 * t2 / 360.0); }
-    else { const double t = sqrt(t2); double st, ct; sincos_fast(t, st, ct); const double s1c = st / (1.0 - ct); alpha = 1.0 / t2 - s1c / (2.0 * t); diag = 0.5 * t * s1c; }
+    double diag;
+    const double alpha = beta_of(t2, diag);
     double K[9]; skew3(w, K);
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) J[3 * i + j] = alpha * w[i] * w[j] + 0.5 * K[3 * i + j];
     J[0] += diag; J[4] += diag; J[8] += diag;
@@ -137,14 +150,15 @@ RBD_D void jexp3(const double *w, double *J) {
     for (int i = 0; i < 9; ++i) J[i] = -b * K[i] + c * K2[i];
     J[0] += 1.0; J[4] += 1.0; J[8] += 1.0;
 }
-// Barfoot's Q block of the left SE(3) Jacobian, xi = (rho, phi)
+// Barfoot's Q block of the left SE(3) Jacobian, xi = (rho, phi).  Its coefficients from their series below t = 1/2 (seven terms: the next
+// is under 1e-17 of the first): the closed forms cancel to eps / t^2, 2 eps / t^4 and 3 eps / t^4 of their values.
 RBD_D void q_left(const double *rho, const double *phi, double *Q) {
     const double t2 = dot3(phi, phi);
     double c1, c2, c3;
-    if (t2 < 1e-4) {
-        c1 = 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0;
-        c2 = 1.0 / 24.0 - t2 / 720.0 + t2 * t2 / 40320.0;
-        c3 = 1.0 / 120.0 - t2 / 2520.0 + t2 * t2 / 120960.0;
+    if (t2 < 0.25) {
+        c1 = 1.0 / 6.0 - t2 * (1.0 / 120.0 - t2 * (1.0 / 5040.0 - t2 * (1.0 / 362880.0 - t2 * (1.0 / 39916800.0 - t2 * (1.0 / 6227020800.0 - t2 * (1.0 / 1307674368000.0))))));
+        c2 = 1.0 / 24.0 - t2 * (1.0 / 720.0 - t2 * (1.0 / 40320.0 - t2 * (1.0 / 3628800.0 - t2 * (1.0 / 479001600.0 - t2 * (1.0 / 87178291200.0 - t2 * (1.0 / 20922789888000.0))))));
+        c3 = 1.0 / 120.0 - t2 * (1.0 / 2520.0 - t2 * (1.0 / 120960.0 - t2 * (1.0 / 9979200.0 - t2 * (1.0 / 1245404160.0 - t2 * (1.0 / 217945728000.0 - t2 * (1.0 / 50812489728000.0))))));
     } else {
         const double t = sqrt(t2);
         double st, ct;

@@ -531,8 +531,16 @@ class WholeBodyBatch:
 def _log3_batch(R):
     v = np.stack([R[:, 2, 1] - R[:, 1, 2], R[:, 0, 2] - R[:, 2, 0], R[:, 1, 0] - R[:, 0, 1]], axis=1)
     t = np.arctan2(0.5 * np.linalg.norm(v, axis=1), 0.5 * (np.trace(R, axis1=1, axis2=2) - 1.0))
-    f = np.where(t < 1e-3, 0.5 * (1 + t * t / 6), t / (2 * np.sin(np.where(t < 1e-3, 1.0, t))))
-    return f[:, None] * v
+    f = np.where(t < 1e-3, 0.5 * (1 + t * t / 6 + 7 * t ** 4 / 360), t / (2 * np.sin(np.where(t < 1e-3, 1.0, t))))
+    w = f[:, None] * v
+    c = 0.5 * (np.trace(R, axis1=1, axis2=2) - 1.0)
+    for b in np.nonzero(c < -0.5)[0]:      # beyond 2 pi / 3 the axis from the symmetric part, as rbd::log3 takes it: a a^T = (sym R - c I)/(1 - c)
+        d = (np.diag(R[b]) - c[b]) / (1.0 - c[b])
+        k = int(np.argmax(d))
+        ax = 0.5 * (R[b][:, k] + R[b][k, :]) / ((1.0 - c[b]) * np.sqrt(d[k]))
+        ax[k] = np.sqrt(d[k])
+        w[b] = (-t[b] if ax @ v[b] < 0 else t[b]) * ax
+    return w
 
 
 def make_wb_batch(model, B, first=0, seed=None, gait=TROT, ik=TROT_IK, ik_hor_ratio=0.5, wb=None, height_map=None, w_des=None):

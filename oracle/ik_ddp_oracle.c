@@ -93,15 +93,15 @@ static void so3_log(const double *R, double *w) {
     if (t < 1e-4) {
         const double f = 0.5 * (1.0 + t * t / 6.0);
         w[0] = f * v[0]; w[1] = f * v[1]; w[2] = f * v[2];
-    } else if (M_PI - t < 1e-6) {     /* rotation by ~pi: the axis from the symmetric part */
-        double A[9];
-        for (int i = 0; i < 9; ++i) A[i] = 0.5 * R[i];
-        A[0] += 0.5; A[4] += 0.5; A[8] += 0.5;
+    } else if (c < -0.5) {     /* beyond 2 pi / 3, where 1 / sin t starts to cost: a a^T = (sym R - c I) / (1 - c), exactly */
+        const double A[3] = {(R[0] - c) / (1.0 - c), (R[4] - c) / (1.0 - c), (R[8] - c) / (1.0 - c)};
         int k = 0;
-        if (A[4] > A[0]) k = 1;
-        if (A[8] > A[4 * k]) k = 2;
-        const double n = sqrt(A[4 * k]);
-        double ax[3] = {A[k] / n, A[3 + k] / n, A[6 + k] / n};
+        if (A[1] > A[0]) k = 1;
+        if (A[2] > A[k]) k = 2;
+        const double n = sqrt(A[k]);
+        double ax[3];
+        for (int i = 0; i < 3; ++i) ax[i] = 0.5 * (R[3 * i + k] + R[3 * k + i]) / ((1.0 - c) * n);
+        ax[k] = n;
         if (dot3(ax, v) < 0) { ax[0] = -ax[0]; ax[1] = -ax[1]; ax[2] = -ax[2]; }
         w[0] = t * ax[0]; w[1] = t * ax[1]; w[2] = t * ax[2];
     } else {

@@ -18,26 +18,46 @@ def skew(v):
 
 
 # ------------------------------------------------------------------ SO(3) / SE(3) ---
-def exp3(w):
-    t2 = w @ w
+def _abc(t2):
+    """a = sin t / t, b = (1 - cos t)/t^2, c = (t - sin t)/t^3.  b as a^2/(1 + cos t) where cos t > 0: 1 - cos t loses
+    eps/t^2 of its digits, and b K (jexp3, the V of exp6) shows it as eps/t."""
+    if t2 < 1e-6:
+        return 1.0 - t2 / 6.0 + t2 * t2 / 120.0, 0.5 - t2 / 24.0 + t2 * t2 / 720.0, 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0
     t = np.sqrt(t2)
-    if t < 1e-3:
-        a, b = 1.0 - t2 / 6.0 + t2 * t2 / 120.0, 0.5 - t2 / 24.0 + t2 * t2 / 720.0
-    else:
-        a, b = np.sin(t) / t, (1.0 - np.cos(t)) / t2
+    st, ct = np.sin(t), np.cos(t)
+    a = st / t
+    return a, (a * a / (1.0 + ct) if ct > 0.0 else (1.0 - ct) / t2), (t - st) / (t2 * t)
+
+
+def _beta(t2):
+    """beta = 1/t^2 - cot(t/2)/(2 t), the K^2 coefficient of V^-1 and the w w^T coefficient of jlog3; with it d = (t/2) cot(t/2) = 1 - beta t^2.
+    Half-angle form: 1/t^2 - sin t/(2 t (1 - cos t)) cancels to eps/t^4."""
+    if t2 < 1e-4:
+        return (1.0 / 12.0 + t2 * (1.0 / 720.0 + t2 * (1.0 / 30240.0 + t2 / 1209600.0)),
+                1.0 - t2 * (1.0 / 12.0 + t2 * (1.0 / 720.0 + t2 / 30240.0)))
+    h = 0.5 * np.sqrt(t2)
+    d = h * np.cos(h) / np.sin(h)
+    return (1.0 - d) / t2, d
+
+
+def exp3(w):
+    a, b, _ = _abc(w @ w)
     K = skew(w)
     return np.eye(3) + a * K + b * (K @ K)
 
 
 def log3(R):
     v = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
-    t = np.arctan2(0.5 * np.linalg.norm(v), (np.trace(R) - 1.0) / 2.0)   # accurate near 0, unlike arccos
+    c = (np.trace(R) - 1.0) / 2.0
+    t = np.arctan2(0.5 * np.linalg.norm(v), c)   # accurate near 0, unlike arccos
     if t < 1e-3:
         return 0.5 * v * (1.0 + t * t / 6.0 + 7.0 * t ** 4 / 360.0)
-    if np.pi - t < 1e-6:  # near pi: from the symmetric part
-        A = (R + np.eye(3)) / 2.0
-        k = np.argmax(np.diag(A))
-        ax = A[:, k] / np.sqrt(A[k, k])
+    if c < -0.5:  # beyond 2 pi / 3, where 1 / sin t starts to cost: a a^T = (sym R - c I)/(1 - c), exactly
+        d = (np.diag(R) - c) / (1.0 - c)
+        k = np.argmax(d)
+        ak = np.sqrt(d[k])
+        ax = 0.5 * (R[:, k] + R[k, :]) / ((1.0 - c) * ak)
+        ax[k] = ak
         if ax @ v < 0:
             ax = -ax
         return t * ax
@@ -47,63 +67,43 @@ def log3(R):
 def exp6(nu):
     """nu = (v, w) -> (R, p): p = V(w) v"""
     v, w = nu[:3], nu[3:]
-    t2 = w @ w
-    t = np.sqrt(t2)
-    if t < 1e-3:
-        b, c = 0.5 - t2 / 24.0 + t2 * t2 / 720.0, 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0
-    else:
-        b, c = (1.0 - np.cos(t)) / t2, (t - np.sin(t)) / (t2 * t)
+    a, b, c = _abc(w @ w)
     K = skew(w)
-    V = np.eye(3) + b * K + c * (K @ K)
-    return exp3(w), V @ v
+    K2 = K @ K
+    return np.eye(3) + a * K + b * K2, (np.eye(3) + b * K + c * K2) @ v
 
 
 def log6(R, p):
     w = log3(R)
-    t2 = w @ w
-    t = np.sqrt(t2)
     K = skew(w)
-    if t < 1e-3:
-        beta = 1.0 / 12.0 + t2 / 720.0 + t2 * t2 / 30240.0
-    else:
-        beta = 1.0 / t2 - np.sin(t) / (2.0 * t * (1.0 - np.cos(t)))
-    Vinv = np.eye(3) - 0.5 * K + beta * (K @ K)
+    Vinv = np.eye(3) - 0.5 * K + _beta(w @ w)[0] * (K @ K)
     return np.concatenate([Vinv @ p, w])
 
 
 def jlog3(w):
     """d log3(R exp3(d)) / d d at d = 0 (right Jacobian of log)"""
-    t2 = w @ w
-    t = np.sqrt(t2)
-    if t < 1e-3:
-        alpha, diag = 1.0 / 12.0 + t2 / 720.0 + t2 * t2 / 30240.0, 0.5 * (2.0 - t2 / 6.0 - t2 * t2 / 360.0)
-    else:
-        s1c = np.sin(t) / (1.0 - np.cos(t))
-        alpha, diag = 1.0 / t2 - s1c / (2.0 * t), 0.5 * t * s1c
+    alpha, diag = _beta(w @ w)
     return alpha * np.outer(w, w) + diag * np.eye(3) + 0.5 * skew(w)
 
 
 def jexp3(w):
     """right Jacobian of exp3: exp3(w + d) = exp3(w) exp3(jexp3(w) d)"""
-    t2 = w @ w
-    t = np.sqrt(t2)
-    if t < 1e-3:
-        b, c = 0.5 - t2 / 24.0 + t2 * t2 / 720.0, 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0
-    else:
-        b, c = (1.0 - np.cos(t)) / t2, (t - np.sin(t)) / (t2 * t)
+    _, b, c = _abc(w @ w)
     K = skew(w)
     return np.eye(3) - b * K + c * (K @ K)
 
 
 def _q_left(rho, phi):
-    """Barfoot's Q block of the left SE(3) Jacobian for xi = (rho, phi)"""
+    """Barfoot's Q block of the left SE(3) Jacobian for xi = (rho, phi).  Its three coefficients from their series below t = 1/2
+    (seven terms: the next is under 1e-17 of the first): the closed forms cancel to eps/t^2, 2 eps/t^4 and 3 eps/t^4."""
     t2 = phi @ phi
-    t = np.sqrt(t2)
     P, Rh = skew(phi), skew(rho)
-    if t < 1e-2:
-        c1, c2, c3 = (1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0, 1.0 / 24.0 - t2 / 720.0 + t2 * t2 / 40320.0,
-                      1.0 / 120.0 - t2 / 2520.0 + t2 * t2 / 120960.0)
+    if t2 < 0.25:
+        c1 = 1.0 / 6.0 - t2 * (1.0 / 120.0 - t2 * (1.0 / 5040.0 - t2 * (1.0 / 362880.0 - t2 * (1.0 / 39916800.0 - t2 * (1.0 / 6227020800.0 - t2 / 1307674368000.0)))))
+        c2 = 1.0 / 24.0 - t2 * (1.0 / 720.0 - t2 * (1.0 / 40320.0 - t2 * (1.0 / 3628800.0 - t2 * (1.0 / 479001600.0 - t2 * (1.0 / 87178291200.0 - t2 / 20922789888000.0)))))
+        c3 = 1.0 / 120.0 - t2 * (1.0 / 2520.0 - t2 * (1.0 / 120960.0 - t2 * (1.0 / 9979200.0 - t2 * (1.0 / 1245404160.0 - t2 * (1.0 / 217945728000.0 - t2 / 50812489728000.0)))))
     else:
+        t = np.sqrt(t2)
         st, ct = np.sin(t), np.cos(t)
         c1 = (t - st) / (t2 * t)
         c2 = (t2 + 2.0 * ct - 2.0) / (2.0 * t2 * t2)

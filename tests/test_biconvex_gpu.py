@@ -77,7 +77,7 @@ def test_hundred_admm_iterations(oracle):
 
 
 GOLDEN = sorted(p for p in __import__("glob").glob(__import__("os").path.join(__import__("os").path.dirname(__file__), "golden", "*.npz"))
-                if not __import__("os").path.basename(p).startswith(("ik_", "chaos_")))   # ik_*: whole-body fixtures (tests/test_ik_gpu.py); chaos_*: CPU ensembles
+                if not __import__("os").path.basename(p).startswith(("ik_", "chaos_", "lie_")))   # ik_*: whole-body fixtures (tests/test_ik_gpu.py); chaos_*: CPU ensembles; lie_*: tests/test_lie_ref_gpu.py
 
 
 @pytest.mark.parametrize("path", GOLDEN, ids=[__import__("os").path.basename(p)[:-4] for p in GOLDEN])

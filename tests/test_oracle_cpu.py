@@ -14,7 +14,7 @@ from oracle import oracle_np
 from tests.util import problem_args, rel_l2, restatement
 
 GOLDEN = sorted(p for p in glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz"))
-                if not os.path.basename(p).startswith(("ik_", "chaos_")))          # ik_*: whole-body fixtures (tests/test_ik_twin_cpu.py); chaos_*: ensembles (below)
+                if not os.path.basename(p).startswith(("ik_", "chaos_", "lie_")))          # ik_*: whole-body fixtures (tests/test_ik_twin_cpu.py); chaos_*: ensembles (below); lie_*: tests/test_lie_ref_cpu.py
 
 
 def _np_solve(b, i, ref, iters):
