@@ -108,9 +108,11 @@ class DeviceBatch:
     create_cost_F / create_bound_constraints itself) or, with raw=, the raw form."""
 
     def __init__(self, batch, device="cuda", num_iters=10, maxit=150, tol=1e-5, exit_tol=1e-3,
-                 beta=1.5, mu=None, keep_hist=False, precision="f64", plan=None, raw=None, cone=None):
+                 beta=1.5, mu=None, keep_hist=False, precision="f64", plan=None, raw=None, cone=None, plan_bounds=False):
         """plan: a plan_batch.DevicePlan whose tensors (cnt_plan, dt, X_nom, X_ter, x_init) are used in place of the
         batch's host arrays -- inputs built on the GPU never leave HBM.
+        plan_bounds: the plan carries the kinematic bounds too, per problem and knot (plan.bounds (B, H, 6), sbounds = 6 H: an
+        acyclic_batch.DeviceAcyclicPlan, whose bounds come from the motion's table); False: the batch's host array.
         raw: dict(Qx, qx, lbx, ubx, Qf[, qf][, Qx_blk][, Qf_blk]) -- the raw cost / bound form (solve_host explains it); with
         Qx_blk / Qf_blk the per-knot block costs, through bmpc_biconvex_solve_batch_blocks_device; with Qx_off / Qf_off the costs
         between neighbouring knots, through bmpc_biconvex_solve_batch_band_device
@@ -140,7 +142,11 @@ class DeviceBatch:
         self.blocks = None
         self.band = None
         if raw is None:
-            self.t.update(W_X=up(batch.W_X), W_X_ter=up(batch.W_X_ter), W_F=up(batch.W_F), bounds=up(batch.bounds))
+            if plan_bounds and (plan is None or tuple(plan.bounds.shape) != (B, H, 6)):
+                raise ValueError("plan_bounds needs a plan with bounds (%d, %d, 6)" % (B, H))
+            self.t.update(W_X=up(batch.W_X), W_X_ter=up(batch.W_X_ter), W_F=up(batch.W_F), bounds=plan.bounds if plan_bounds else up(batch.bounds))
+        elif plan_bounds:
+            raise ValueError("plan_bounds is for the harness form: the raw form takes lbx / ubx")
         else:
             for k in ("X_nom", "X_ter"):
                 del self.t[k]
@@ -192,7 +198,7 @@ class DeviceBatch:
             setattr(d, k, v.data_ptr())
         if raw is None:
             d.sW_X, d.sW_X_ter = _stride(batch.W_X), _stride(batch.W_X_ter)
-            d.sW_F, d.sbounds = _stride(batch.W_F), _stride(batch.bounds)
+            d.sW_F, d.sbounds = _stride(batch.W_F), 6 * H if plan_bounds else _stride(batch.bounds)
         d.X, d.F, d.P = self.X.data_ptr(), self.F.data_ptr(), self.P.data_ptr()
         d.L_x, d.L_f = self.L_x.data_ptr(), self.L_f.data_ptr()
         d.dyn_viol, d.stats = self.dyn_viol.data_ptr(), self.stats.data_ptr()

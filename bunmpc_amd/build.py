@@ -74,7 +74,7 @@ def compile_jobs():
     # of rbd_device.h behind bmpc_probe_lie, contracted as ik_ddp.hip contracts them
     others = {"biconvex_launch.hip": _FP64_ADMM_FLAGS, "lane_probe.hip": _FP64_ADMM_FLAGS, "biconvex_latency.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], "bunmpc_capi.hip": [],
               "ik_ddp.hip": ["-ffp-contract=on"], "lie_probe.hip": ["-ffp-contract=on"], "bunmpc_ik_capi.hip": [], "plan_gen.hip": [], "id_ctrl.hip": [], "perturb.hip": [],
-              "cc_goals.hip": []}
+              "acyclic_plan.hip": [], "cc_goals.hip": []}
     return jobs + [(src[:-len(".hip")], src, flags) for src, flags in others.items()]
 
 
@@ -93,9 +93,10 @@ def object_path(job, flags):
 
 
 def dependencies():
-    """every source of a job, every header of csrc/, the public header, every other header beside it (bunmpc_goals.h) and this file
-    (the flags live here)"""
+    """every source of a job, every header of csrc/, the public header, every other header beside it (bunmpc_goals.h) or under ext/
+    (bunmpc_acyclic.h) and this file (the flags live here)"""
     beside = sorted(h for h in glob.glob(os.path.join(os.path.dirname(INCLUDE), "*.h")) if h != INCLUDE)
+    beside += sorted(glob.glob(os.path.join(os.path.dirname(INCLUDE), "ext", "*.h")))
     return (sorted({os.path.join(CSRC, src) for _, src, _ in compile_jobs()}) + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [INCLUDE] + beside +
             [os.path.abspath(__file__)])
 

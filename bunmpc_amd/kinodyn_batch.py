@@ -12,17 +12,22 @@ from .inverse_kinematics_cpp import as_device_model
 
 class KinoDynDeviceBatch:
     def __init__(self, wb, model, device="cuda", num_iters=10, maxit=150, ddp_maxiter=100, plan=None, use_active_list=True, schedule=None,
-                 keep_hist=False, cone=None):
+                 keep_hist=False, cone=None, plan_costs=False):
         """plan: a plan_batch.DeviceWbPlan whose tensors replace the host-built centroidal inputs and IK task blocks of
         `wb` (weights and regularisation references still come from wb).  schedule: dict of bmpc_ik_sched_t fields for this
         batch's DDP loops (0 = process default, < 0 = never), e.g. {"gains_wave_below": -1}; no effect on results.  cone: the dict
         batch.DeviceBatch takes (projection, mu, normals -- numpy arrays or a device tensor such as plan.normals): the centroidal stage
-        runs through the cone entry points (bmpc_kinodyn_solve_batch_cone_device); None: bmpc_kinodyn_solve_batch_device"""
+        runs through the cone entry points (bmpc_kinodyn_solve_batch_cone_device); None: bmpc_kinodyn_solve_batch_device.
+        plan_costs: the plan (an acyclic_batch.DeviceAcyclicPlan) also carries what a motion's time tables give per problem and per
+        node: the kinematic bounds (B, H, 6), an IK dt of its own (dt_ik: no first-knot rule) and the regularisation state_w
+        (B, T + 1, 36), x_reg (B, T + 1, 37), ctrl_w (B, T, 18) -- batch strides (T + 1) 36, (T + 1) 37, T 18, node strides 36, 37, 18.
+        False: dt from the plan's dt, bounds and regularisation from wb, one vector per batch or problem"""
         import torch
         self.torch = torch
         self.wb = wb
         self.dm = as_device_model(model)
-        self.dyn = DeviceBatch(wb.dyn, device=device, num_iters=num_iters, maxit=maxit, plan=plan, keep_hist=keep_hist, cone=cone)
+        self.dyn = DeviceBatch(wb.dyn, device=device, num_iters=num_iters, maxit=maxit, plan=plan, keep_hist=keep_hist, cone=cone,
+                               plan_bounds=plan_costs)
         self.device = self.dyn.device
         B, T = wb.dyn.B, wb.ik_T
         f64 = torch.float64
@@ -32,8 +37,15 @@ class KinoDynDeviceBatch:
 
         self.x = up(wb.x) if plan is None else plan.x
         self.tasks = up(wb.ik_tasks) if plan is None else plan.ik_tasks
-        self.state_w, self.ctrl_w, self.x_reg = up(wb.state_w), up(wb.ctrl_w), up(wb.x_reg)
-        self.dt_ik = up(wb.dyn.dt[:, :T]) if plan is None else plan.dt[:, :T].contiguous()
+        if plan_costs:
+            self.state_w, self.ctrl_w, self.x_reg, self.dt_ik = plan.state_w, plan.ctrl_w, plan.x_reg, plan.dt_ik
+            for name, a, shape in (("state_w", self.state_w, (B, T + 1, 36)), ("x_reg", self.x_reg, (B, T + 1, 37)), ("ctrl_w", self.ctrl_w, (B, T, 18)),
+                                   ("dt_ik", self.dt_ik, (B, T))):
+                if tuple(a.shape) != shape or a.dtype != f64 or not a.is_contiguous():
+                    raise ValueError("plan.%s: expected a contiguous float64 tensor of shape %s, got %s %s" % (name, shape, a.dtype, tuple(a.shape)))
+        else:
+            self.state_w, self.ctrl_w, self.x_reg = up(wb.state_w), up(wb.ctrl_w), up(wb.x_reg)
+            self.dt_ik = up(wb.dyn.dt[:, :T]) if plan is None else plan.dt[:, :T].contiguous()
         lib = _lib.lib()
         self.ws_doubles = lib.bmpc_ik_workspace_doubles(T)
         off = (C.c_long * 8)()
@@ -52,8 +64,12 @@ class KinoDynDeviceBatch:
         ik.B, ik.n_col, ik.maxiter, ik.model = B, T, ddp_maxiter, self.dm.h
         ik.x0, ik.dt, ik.tasks = self.x.data_ptr(), self.dt_ik.data_ptr(), self.tasks.data_ptr()
         ik.state_w, ik.x_reg, ik.ctrl_w = self.state_w.data_ptr(), self.x_reg.data_ptr(), self.ctrl_w.data_ptr()
-        ik.s_state_w = 0 if wb.state_w.shape[0] == 1 else 36
-        ik.s_ctrl_w = 0 if wb.ctrl_w.shape[0] == 1 else 18
+        if plan_costs:
+            ik.s_state_w, ik.s_x_reg, ik.s_ctrl_w = (T + 1) * 36, (T + 1) * 37, T * 18
+            ik.sn_state_w, ik.sn_x_reg, ik.sn_ctrl_w = 36, 37, 18
+        else:
+            ik.s_state_w = 0 if wb.state_w.shape[0] == 1 else 36
+            ik.s_ctrl_w = 0 if wb.ctrl_w.shape[0] == 1 else 18
         ik.ws, ik.active = self.ws.data_ptr(), self.active.data_ptr()
         ik.active_list = self.active_list.data_ptr() if use_active_list else None
         ik.iters_run = C.addressof(self.iters_run)

@@ -6,9 +6,13 @@ field its name, offset, size and type name), as canonical JSON.  It imports bunm
 library nor a GPU and runs on any commit -- the table is recorded on the commit BEFORE a change to the binding and compared after it
 (tests/test_abi_cpu.py).  A deliberate ABI change is re-recorded with this tool and shows up as a diff of the file.
 
-    python tools/record_abi.py [--header bunmpc.h] [--out tests/golden/abi.json]"""
+A header under include/ext/ is bound by a module of its own, bunmpc_amd/_lib_<name>.py for include/ext/bunmpc_<name>.h, whose table is its
+ABI: --ext bunmpc_acyclic.h --out tests/golden/abi_acyclic.json.
+
+    python tools/record_abi.py [--header bunmpc.h | --ext bunmpc_acyclic.h] [--out tests/golden/abi.json]"""
 import argparse
 import ctypes
+import importlib
 import json
 import os
 import sys
@@ -35,11 +39,16 @@ def dump(abi):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--header", default="bunmpc.h")
+    ap.add_argument("--ext", help="a header of include/ext/ in place of --header")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "abi.json"))
     args = ap.parse_args()
     sys.path.insert(0, ROOT)
-    from bunmpc_amd import _lib
-    text = dump(_lib.HEADERS[args.header])
+    if args.ext:
+        abi = importlib.import_module("bunmpc_amd._lib_" + args.ext[len("bunmpc_"):-len(".h")]).ABI
+    else:
+        from bunmpc_amd import _lib
+        abi = _lib.HEADERS[args.header]
+    text = dump(abi)
     with open(args.out, "w") as f:
         f.write(text)
     table = json.loads(text)
