@@ -74,7 +74,7 @@ def compile_jobs():
     # of rbd_device.h behind bmpc_probe_lie, contracted as ik_ddp.hip contracts them
     others = {"biconvex_launch.hip": _FP64_ADMM_FLAGS, "lane_probe.hip": _FP64_ADMM_FLAGS, "biconvex_latency.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], "bunmpc_capi.hip": [],
               "ik_ddp.hip": ["-ffp-contract=on"], "lie_probe.hip": ["-ffp-contract=on"], "bunmpc_ik_capi.hip": [], "plan_gen.hip": [], "id_ctrl.hip": [], "perturb.hip": [],
-              "dataset.hip": [], "acyclic_plan.hip": [], "cc_goals.hip": []}
+              "dataset.hip": [], "contact_log.hip": [], "acyclic_plan.hip": [], "cc_goals.hip": []}
     return jobs + [(src[:-len(".hip")], src, flags) for src, flags in others.items()]
 
 

@@ -115,6 +115,14 @@ class DeviceDatabase:
             keep = keep.index_fill(0, out["rejected"].to(torch.long), 0)
         return self.append(out["states"], out["actions"], vc_goals=out["vc_goals"], cc_goals=cc, rows=rows, keep=keep, drop_nonfinite=drop_nonfinite)
 
+    def append_episodes(self, states, actions, vc_goals, log):
+        """logged episodes: states (B, T, 43), actions (B, T, 12), vc_goals (B, T, 5) and a built contact_log.DeviceContactLog -- the
+        leading log.rows[b] rows of every group with the measured goals, nothing of an episode with a nonzero status (the reference
+        returns nothing for those).  Does not synchronise."""
+        R = log.goals.shape[1]      # max_rows <= T
+        return self.append(states[:, :R], actions[:, :R], vc_goals=vc_goals[:, :R], cc_goals=log.goals, rows=log.rows,
+                           keep=(log.status == 0).to(self.torch.int32))
+
     def _header(self):
         h = self.header.cpu()
         return int(h[0]), int(h[1]), int(h[2])
