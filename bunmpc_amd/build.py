@@ -49,6 +49,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # -amdgpu-disable-clustered-low-occupancy-reschedule.
 _FP64_ADMM_FLAGS = ["-mllvm", "-amdgpu-use-amdgpu-trackers", "-mllvm", "-amdgpu-disable-unclustered-high-rp-reschedule"]
 _FP32_ADMM_FLAGS = ["-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]
+# policy.hip: its fp32 results are held to a numpy twin in every bit, subnormal inputs, weights and sums included.  So, spelled out
+# against whatever a toolchain's defaults or BUNMPC_EXTRA_FLAGS' neighbours may be: fp32 subnormals are kept (the matrix cores' A and
+# B operands and the VALU honour the kernel's denormal mode), no fast-math (a NaN must stay a NaN through the ReLU, fmaf must stay one
+# rounding), and no product is fused into a sum that the source does not fuse (fp64 normalisation, tau, err; the host packer's s and t).
+_POLICY_FLAGS = ["-fno-gpu-flush-denormals-to-zero", "-fno-fast-math", "-ffp-contract=off"]
 # The centroidal units: biconvex_admm.hip compiled once per (cost shape, precision, feet), told which by three defines.  Every
 # combination that a row of kShapes (biconvex_kernels.h) allows is listed here and nowhere else: biconvex_launch.hip's table refers to
 # the accessor of each, so a library without one of them does not load.  A unit of its own per combination so that each is built with its
@@ -74,7 +79,7 @@ def compile_jobs():
     # of rbd_device.h behind bmpc_probe_lie, contracted as ik_ddp.hip contracts them
     others = {"biconvex_launch.hip": _FP64_ADMM_FLAGS, "lane_probe.hip": _FP64_ADMM_FLAGS, "biconvex_latency.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], "bunmpc_capi.hip": [],
               "ik_ddp.hip": ["-ffp-contract=on"], "lie_probe.hip": ["-ffp-contract=on"], "bunmpc_ik_capi.hip": [], "plan_gen.hip": [], "id_ctrl.hip": [], "perturb.hip": [],
-              "dataset.hip": [], "contact_log.hip": [], "acyclic_plan.hip": [], "cc_goals.hip": []}
+              "dataset.hip": [], "contact_log.hip": [], "policy.hip": _POLICY_FLAGS, "acyclic_plan.hip": [], "cc_goals.hip": []}
     return jobs + [(src[:-len(".hip")], src, flags) for src, flags in others.items()]
 
 
