@@ -29,6 +29,53 @@ def _scalar(v):
     return float(np.asarray(v, dtype=np.float64).reshape(-1)[0])
 
 
+def host_tables(plan, nq, nv):
+    """The time tables of `plan` as the host arrays of a bmpc_acyclic_plan_t ({field: array}, the row counts are their lengths) and
+    state_end; ValueError, with the field named, for a list that is empty, too long or of the wrong width.  numpy only.
+
+    State and control regularisation: the lists of one group need not be equally long (the reference's rearing_jump.py has three rows of
+    state_wt, two of state_reg and state_scale).  Inside the table, row k of each list holds where state_scale[k]'s window does,
+    k < len(state_reg); past state_reg's end every list gives its OWN last row (abstract_acyclic_gen.py:232-254; the control lists the
+    same way on len(ctrl_scale) and ctrl_scale's end, :267-289).  The device walks ONE row index per group, so the rows are packed to
+    that: the n in-table rows, their windows cut at the end, and one more row [end, +inf) made of each list's last row.  A time below the
+    end can only match a row it matched before; a time at or past it only the added row, which is also the last one, the row the device
+    takes past the end and for a NaN time."""
+    n_col = int(plan.n_col)
+
+    def table(a, shape, name):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.ndim != len(shape) or any(n is not None and n != m for n, m in zip(shape, a.shape)):
+            raise ValueError("%s: expected shape (%s), got %s" % (name, ", ".join("n" if n is None else "%d" % n for n in shape), a.shape))
+        if not 1 <= a.shape[0] <= _lib_acyclic.MAX_PHASES and shape[0] is None:
+            raise ValueError("%s: between 1 and %d rows, got %d" % (name, _lib_acyclic.MAX_PHASES, a.shape[0]))
+        return a
+
+    def packed(lead, scale, end, lists):
+        n = len(lists[lead])
+        if n > _lib_acyclic.MAX_PHASES - 1:
+            raise ValueError("%s: at most %d rows (one more is added for the times past the end), got %d" % (lead, _lib_acyclic.MAX_PHASES - 1, n))
+        for name, a in lists.items():
+            if len(a) < n:
+                raise ValueError("%s: %d rows, fewer than %s's %d" % (name, len(a), lead, n))
+        out = {"tab_" + name: np.concatenate([a[:n], a[-1:]]) for name, a in lists.items()}
+        out["tab_" + scale][:n, 2] = np.minimum(out["tab_" + scale][:n, 2], end)
+        out["tab_" + scale][n, 1:] = end, np.inf
+        return out
+
+    h = dict(dt_arr=table(np.asarray(plan.dt_arr, dtype=np.float64)[:n_col], (n_col,), "dt_arr"),      # (plan_cartwheel.py lists n_col + 1)
+             tab_cnt_plan=table(plan.cnt_plan, (None, 4, 6), "cnt_plan"), tab_X_nom=table(plan.X_nom, (None, 11), "X_nom"),
+             tab_X_ter=table(plan.X_ter, (9,), "X_ter"), tab_bounds=table(plan.bounds, (None, 8), "bounds"))
+    if isinstance(plan.swing_wt, (np.ndarray, list)):      # None or a scalar: no swing tasks (:204)
+        h["tab_swing_wt"] = table(plan.swing_wt, (None, 4, 6), "swing_wt")
+    state_reg = table(plan.state_reg, (None, nq + nv + 2), "state_reg")
+    state_end = float(state_reg[-1, -1])
+    h.update(packed("state_reg", "state_scale", state_end, dict(state_reg=state_reg[:, :nq + nv], state_wt=table(plan.state_wt, (None, 2 * nv + 2), "state_wt")[:, :2 * nv],
+                                                                state_scale=table(plan.state_scale, (None, 3), "state_scale"))))
+    ctrl_scale = table(plan.ctrl_scale, (None, 3), "ctrl_scale")
+    h.update(packed("ctrl_scale", "ctrl_scale", float(ctrl_scale[-1, -1]), dict(ctrl_wt=table(plan.ctrl_wt, (None, nv + 2), "ctrl_wt")[:, :nv], ctrl_scale=ctrl_scale)))
+    return {k: np.ascontiguousarray(a) for k, a in h.items()}, state_end
+
+
 class DeviceMotionTable:
     """An ACyclicMotionParams-shaped object (motions/weight_abstract.py; the reference's own motions/acyclic/*.py work as they are)
     uploaded once: every time table as one device tensor, the row counts and scalars on the host."""
@@ -40,33 +87,8 @@ class DeviceMotionTable:
         self.dm = as_device_model(model)
         nq, nv = self.dm.model.nq, self.dm.model.nv
         self.n_col = int(plan.n_col)
-
-        def table(a, shape, name):
-            a = np.ascontiguousarray(a, dtype=np.float64)
-            if a.ndim != len(shape) or any(n is not None and n != m for n, m in zip(shape, a.shape)):
-                raise ValueError("%s: expected shape (%s), got %s" % (name, ", ".join("n" if n is None else "%d" % n for n in shape), a.shape))
-            if not 1 <= a.shape[0] <= _lib_acyclic.MAX_PHASES and shape[0] is None:
-                raise ValueError("%s: between 1 and %d rows, got %d" % (name, _lib_acyclic.MAX_PHASES, a.shape[0]))
-            return a
-
-        h = dict(dt_arr=table(np.asarray(plan.dt_arr, dtype=np.float64)[:self.n_col], (self.n_col,), "dt_arr"),
-                 tab_cnt_plan=table(plan.cnt_plan, (None, 4, 6), "cnt_plan"), tab_X_nom=table(plan.X_nom, (None, 11), "X_nom"),
-                 tab_X_ter=table(plan.X_ter, (9,), "X_ter"), tab_bounds=table(plan.bounds, (None, 8), "bounds"))
-        swing = isinstance(plan.swing_wt, (np.ndarray, list))      # a scalar: no swing tasks (:205)
-        if swing:
-            h["tab_swing_wt"] = table(plan.swing_wt, (None, 4, 6), "swing_wt")
-        state_reg = table(plan.state_reg, (None, nq + nv + 2), "state_reg")
-        h["tab_state_reg"] = np.ascontiguousarray(state_reg[:, :nq + nv])
-        h["tab_state_wt"] = np.ascontiguousarray(table(plan.state_wt, (None, 2 * nv + 2), "state_wt")[:, :2 * nv])
-        h["tab_state_scale"] = table(plan.state_scale, (None, 3), "state_scale")
-        h["tab_ctrl_wt"] = np.ascontiguousarray(table(plan.ctrl_wt, (None, nv + 2), "ctrl_wt")[:, :nv])
-        h["tab_ctrl_scale"] = table(plan.ctrl_scale, (None, 3), "ctrl_scale")
-        if not len(h["tab_state_reg"]) == len(h["tab_state_wt"]) == len(h["tab_state_scale"]):
-            raise ValueError("state_reg, state_wt and state_scale: one row per phase each")
-        if len(h["tab_ctrl_wt"]) != len(h["tab_ctrl_scale"]):
-            raise ValueError("ctrl_wt and ctrl_scale: one row per phase each")
-        self.host = h
-        self.state_end = float(state_reg[-1, -1])
+        h, self.state_end = host_tables(plan, nq, nv)
+        self.host, swing = h, "tab_swing_wt" in h
         self.counts = dict(n_cnt=len(h["tab_cnt_plan"]), n_x=len(h["tab_X_nom"]), n_b=len(h["tab_bounds"]), n_sw=len(h["tab_swing_wt"]) if swing else 0,
                            n_s=len(h["tab_state_scale"]), n_c=len(h["tab_ctrl_scale"]))
         self.cnt_wt, self.cent_wt = _scalar(plan.cnt_wt), (_scalar(plan.cent_wt[0]), _scalar(plan.cent_wt[1]))
@@ -155,7 +177,10 @@ def hold_on_device(knots, dt, size, max_rows=None, step=0.001, out=None, rows=No
     B, n, w = knots.shape
     knots, dt = knots.contiguous(), dt.contiguous()
     if max_rows is None:
-        max_rows = max(int((dt[:, :size] / step).to(torch.int64).sum(dim=1).max()), 1)
+        # the kernel's hold_count on the host, in numpy: torch divides a device tensor by a scalar as a multiply by its reciprocal,
+        # and (k / 1000) * (1 / 0.001) is k where the correctly rounded (k / 1000) / 0.001 is just below it (k = 43, 51, 59, ...)
+        q = dt[:, :size].cpu().numpy() / step
+        max_rows = max(int(np.where(q >= 1.0, np.minimum(q, 1073741824.0), 0.0).astype(np.int64).sum(axis=1).max()), 1)
     if out is None:
         out = torch.zeros((B, max_rows, w), dtype=torch.float64, device=knots.device)
         rows = torch.zeros(B, dtype=torch.int32, device=knots.device)

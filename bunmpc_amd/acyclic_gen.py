@@ -138,10 +138,12 @@ class SoloAcyclicGen:
                                     self.ik.add_position_tracking_task_single(self.ee_frame_id[j], p.swing_wt[k][j][1:4],
                                                                               p.swing_wt[k][j][0], "swing_0" + self.eff_names[j], i)
                             break
-        # state regularisation, node by node (terminal = node T)
+        # state regularisation, node by node (terminal = node T).  The three lists need not be equally long (rearing_jump.py: three
+        # rows of state_wt, two of state_reg and state_scale): inside the table row k of each, k from the loop over len(state_reg)
+        # with the window of state_scale[k] (:232-244); past state_reg's end each list's OWN last row (:246-254)
         for i, ft in enumerate(self._knot_times(t, T + 1, T - 1)):
             self.dt_arr[min(i, T - 1)] = p.dt_arr[min(i, T - 1)]
-            k_sel = len(p.state_reg) - 1 if not make_cyclic else None
+            k_sel = -1 if not make_cyclic else None
             if ft < p.state_reg[-1][-1]:
                 k_sel = None
                 for k in range(len(p.state_reg)):
@@ -155,9 +157,10 @@ class SoloAcyclicGen:
                 self.ik.add_state_regularization_cost_single(i, p.state_scale[k_sel][0], "xReg", wts, ref)
             else:
                 self.ik.add_state_regularization_cost(0, i, p.state_scale[k_sel][0], "xReg", wts, ref, True)
-        # control regularisation (note the reference passes ctrl_wt[k][0] as the weight of the running nodes, :262,277)
+        # control regularisation, the same way on ctrl_scale's rows and end (:267-289; note the reference passes ctrl_wt[k][0] as
+        # the weight of the running nodes, :271,283)
         for i, ft in enumerate(self._knot_times(t, p.n_col + 1, p.n_col - 1)):
-            k_sel = len(p.ctrl_scale) - 1 if not make_cyclic else None
+            k_sel = -1 if not make_cyclic else None
             if ft < p.ctrl_scale[-1][-1]:
                 k_sel = None
                 for k in range(len(p.ctrl_scale)):

@@ -1,7 +1,9 @@
 """The twin of the device-side acyclic plan (include/ext/bunmpc_acyclic.h): bunmpc_amd.acyclic_gen.SoloAcyclicGen itself, driven with
 recording stand-ins for its solver objects, and what they receive packed into the arrays of bmpc_acyclic_plan_t -- so the spec the
 device is held to is the mirror's own code, call by call.  No GPU.  Also hold_np, the zero-order-hold expansion of its optimize, and
-hop_plan, the synthetic motion table of the tests (our own numbers, in the shape of motions/weight_abstract.py::ACyclicMotionParams)."""
+hop_plan, the synthetic motion table of the tests (our own numbers, in the shape of motions/weight_abstract.py::ACyclicMotionParams).
+The mirror itself is held to a recording of the reference's generator on the reference's own tables (tests/golden/acyclic/acyclic_ref.npz):
+pack_table / unpack_table / ref_cases read and write that file's tables and cases."""
 import types
 
 import numpy as np
@@ -152,8 +154,22 @@ class _Kd:
     def return_dyn(self): return self.mp
 
 
-def plan_np(model, plan, x, t, t0):
-    """the arrays of bmpc_acyclic_plan_t for one problem, from SoloAcyclicGen.create_contact_plan / create_costs"""
+def _shared_last_row(plan):
+    """the planted fault: `plan` as the rule "row len(state_reg) - 1 of state_wt, state_reg and state_scale past the end" (and row
+    len(ctrl_scale) - 1 of the control lists) sees it.  Inside a table only rows below that count are read, so cutting the longer
+    lists to it changes nothing but what each list's last row is."""
+    cut = types.SimpleNamespace(**vars(plan))
+    ns, nc = len(plan.state_reg), len(plan.ctrl_scale)
+    cut.state_wt, cut.state_scale, cut.ctrl_wt, cut.ctrl_reg = plan.state_wt[:ns], plan.state_scale[:ns], plan.ctrl_wt[:nc], plan.ctrl_reg[:nc]
+    return cut
+
+
+def plan_np(model, plan, x, t, t0, fault=None):
+    """the arrays of bmpc_acyclic_plan_t for one problem, from SoloAcyclicGen.create_contact_plan / create_costs.  `fault` (None in
+    every checker) plants one fault for the test that shows the recording has teeth: "shared_last_row"."""
+    assert fault in (None, "shared_last_row")
+    if fault == "shared_last_row":
+        plan = _shared_last_row(plan)
     gen = SoloAcyclicGen(model, model)
     kd = _Kd(plan.n_col)
     gen._make_kd = lambda: kd
@@ -175,6 +191,75 @@ def plan_batch_np(model, plan, x, t, t0):
     out = {k: np.stack([r[k] for r in rows]) for k in rows[0]}
     out["x"] = np.array(x, dtype=np.float64)
     return out
+
+
+# ---- the recording of the reference's generator (tests/golden/acyclic/acyclic_ref.npz, written by tests/golden/make_golden_acyclic.py) ----
+
+REF_TABLES = ("plan_jump", "rearing", "rearing_jump", "plan_cartwheel", "plan_hifive")
+# the time tables of an ACyclicMotionParams: lists of rows, each list with a row count of its own
+TABLE_LISTS = ("plan_freq", "cnt_plan", "X_nom", "bounds", "state_reg", "state_wt", "state_scale", "ctrl_wt", "ctrl_reg", "ctrl_scale", "kp", "kd")
+TABLE_VECTORS = ("dt_arr", "W_X", "W_X_ter", "W_F", "X_ter", "cent_wt")
+TABLE_SCALARS = ("rho", "cnt_wt")
+SWING_NONE, SWING_SCALAR, SWING_LIST = 0, 1, 2
+STATE_NOMINAL, STATE_PERTURBED, STATE_PLACED = 0, 1, 2      # states(); PLACED: the perturbed state at the reference's initial base position
+# what the reference's create_contact_plan / create_costs hand the solver objects, in plan_np's layout, and what the tests compare
+REF_OUTPUTS = ("cnt_plan", "dt", "dt_ik", "X_nom", "X_ter", "bounds", "ik_tasks", "state_w", "x_reg", "ctrl_w", "frames")
+# int((k / 1000) / 0.001) == k - 1 in IEEE double: the intervals at which a hold count that is not a correctly rounded division differs
+HOLD_EDGES_MS = (43, 51, 59, 71, 86, 87)
+
+
+def pack_table(plan):
+    """every field of an ACyclicMotionParams as arrays {field: array}: the lists with `<field>_rows`, swing_wt with a flag"""
+    out = dict(n_col=np.int64(plan.n_col), robot_name=np.array(plan.robot_name), motion_name=np.array(plan.motion_name))
+    for k in TABLE_LISTS:
+        out[k] = np.array([np.asarray(r, dtype=np.float64) for r in getattr(plan, k)], dtype=np.float64)
+        out[k + "_rows"] = np.int64(len(getattr(plan, k)))
+    for k in TABLE_VECTORS:
+        out[k] = np.asarray(getattr(plan, k), dtype=np.float64)
+    for k in TABLE_SCALARS:
+        out[k] = np.float64(getattr(plan, k))
+    sw = plan.swing_wt
+    if isinstance(sw, (np.ndarray, list)):
+        out["swing_wt_kind"], out["swing_wt"], out["swing_wt_rows"] = np.int64(SWING_LIST), np.asarray(sw, dtype=np.float64), np.int64(len(sw))
+    else:
+        out["swing_wt_kind"], out["swing_wt_rows"] = np.int64(SWING_NONE if sw is None else SWING_SCALAR), np.int64(0)
+        out["swing_wt"] = np.float64(0.0 if sw is None else sw)
+    return out
+
+
+def unpack_table(z, name):
+    """the table `name` of the recording as an ACyclicMotionParams-shaped object, from the file alone"""
+    g = lambda k: z["%s__%s" % (name, k)]      # noqa: E731
+    p = types.SimpleNamespace(n_col=int(g("n_col")), robot_name=str(g("robot_name")), motion_name=str(g("motion_name")))
+    for k in TABLE_LISTS:
+        rows = g(k)
+        assert rows.shape[0] == int(g(k + "_rows"))
+        setattr(p, k, [np.array(r) for r in rows])
+    for k in TABLE_VECTORS:
+        setattr(p, k, np.array(g(k)))
+    for k in TABLE_SCALARS:
+        setattr(p, k, float(g(k)))
+    kind = int(g("swing_wt_kind"))
+    p.swing_wt = None if kind == SWING_NONE else float(g("swing_wt")) if kind == SWING_SCALAR else [np.array(r) for r in g("swing_wt")]
+    return p
+
+
+def ref_cases(z, name):
+    """the recorded cases of one table: x (B, 37), t (B,), t0 (B,), the recorded x_init (B, 9) -- an INPUT of the recording, from
+    oracle/rbd_np.py, not the reference's -- and the arrays the reference's solver objects received"""
+    g = lambda k: z["%s__%s" % (name, k)]      # noqa: E731
+    return dict(x=g("x"), t=g("t"), t0=g("t0"), kind=g("state_kind"), x_init=g("x_init"), size=g("size"), ref={k: g("out_" + k) for k in REF_OUTPUTS})
+
+
+def hold_edge_problems():
+    """the dt rows of the hold's edge intervals (B = 8, 12 intervals): one problem per edge value as dt[0], one with all six in a
+    row, one with 0.04 -- and seeded knots (8, 13, 37)"""
+    dt = np.full((len(HOLD_EDGES_MS) + 2, 12), 0.05)
+    for b, k in enumerate(HOLD_EDGES_MS):
+        dt[b, 0] = k / 1000
+    dt[len(HOLD_EDGES_MS), 3:3 + len(HOLD_EDGES_MS)] = [k / 1000 for k in HOLD_EDGES_MS]
+    dt[len(HOLD_EDGES_MS) + 1, :] = 0.04
+    return np.random.default_rng(8687).normal(size=(len(dt), 13, 37)), dt
 
 
 def hold_np(knots, dt, size, max_rows=None, step=0.001):
