@@ -53,6 +53,7 @@ _FP32_ADMM_FLAGS = ["-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-
 # against whatever a toolchain's defaults or BUNMPC_EXTRA_FLAGS' neighbours may be: fp32 subnormals are kept (the matrix cores' A and
 # B operands and the VALU honour the kernel's denormal mode), no fast-math (a NaN must stay a NaN through the ReLU, fmaf must stay one
 # rounding), and no product is fused into a sum that the source does not fuse (fp64 normalisation, tau, err; the host packer's s and t).
+# policy_train.hip (the training step) is held to its twin in the same way, operation by operation, and takes the same flags.
 _POLICY_FLAGS = ["-fno-gpu-flush-denormals-to-zero", "-fno-fast-math", "-ffp-contract=off"]
 # The centroidal units: biconvex_admm.hip compiled once per (cost shape, precision, feet), told which by three defines.  Every
 # combination that a row of kShapes (biconvex_kernels.h) allows is listed here and nowhere else: biconvex_launch.hip's table refers to
@@ -79,7 +80,7 @@ def compile_jobs():
     # of rbd_device.h behind bmpc_probe_lie, contracted as ik_ddp.hip contracts them
     others = {"biconvex_launch.hip": _FP64_ADMM_FLAGS, "lane_probe.hip": _FP64_ADMM_FLAGS, "biconvex_latency.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], "bunmpc_capi.hip": [],
               "ik_ddp.hip": ["-ffp-contract=on"], "lie_probe.hip": ["-ffp-contract=on"], "bunmpc_ik_capi.hip": [], "plan_gen.hip": [], "id_ctrl.hip": [], "perturb.hip": [],
-              "dataset.hip": [], "contact_log.hip": [], "policy.hip": _POLICY_FLAGS, "acyclic_plan.hip": [], "cc_goals.hip": []}
+              "dataset.hip": [], "contact_log.hip": [], "policy.hip": _POLICY_FLAGS, "policy_train.hip": _POLICY_FLAGS, "acyclic_plan.hip": [], "cc_goals.hip": []}
     return jobs + [(src[:-len(".hip")], src, flags) for src, flags in others.items()]
 
 

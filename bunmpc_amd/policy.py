@@ -1,4 +1,4 @@
-"""The policy network, inference only (include/ext/bunmpc_policy.h): the reference's `GoalConditionedPolicyNet`
+"""The policy network's forward pass (include/ext/bunmpc_policy.h): the reference's `GoalConditionedPolicyNet`
 (`ISL/examples/iterative_algorithm/networks.py`) in eval() mode as one kernel launch on rows that are device tensors already -- the `x` of
 `DeviceDatabase.batch(index)`, or the states and goals of a batch of rollouts with the normalisation of `simulation.py:1702-1710` folded in:
 
@@ -8,7 +8,8 @@
     action, tau = policy.act(states, goals, norm=DevicePolicy.norm_of(db), q=q, v=v, kp=2.0, kd=0.1, action_type="pd_target")
     err = policy.l1_rows(x, y)                                         # (n,) the rows' summands of nn.L1Loss(reduction="sum")
 
-`host_forward` is the same function in numpy and the specification: the device result equals it in every bit.  Training is not here."""
+`host_forward` is the same function in numpy and the specification: the device result equals it in every bit.  The training step, and this class on the
+weights being trained, are bunmpc_amd/policy_train.py::DeviceTrainer."""
 import ctypes as C
 import re
 
@@ -218,6 +219,18 @@ def unpack(dims, image):
 
 # ---- the device ------------------------------------------------------------------------------------------------------------------------
 
+def device_rows(device, name, t, width, n=None):
+    """(address, row stride) of a float64 tensor (n, width) on `device` (a torch.device with its index, as a tensor's .device is) whose
+    rows are contiguous; any row stride >= width is used in place.  The argument check of DevicePolicy and of policy_train.DeviceTrainer."""
+    if str(t.dtype) != "torch.float64" or t.device != device:
+        raise ValueError("%s: a float64 tensor on %s is expected, got %s on %s" % (name, device, t.dtype, t.device))
+    if t.dim() != 2 or t.shape[1] != width or (n is not None and t.shape[0] != n):
+        raise ValueError("%s: expected shape (%s, %d), got %s" % (name, "n" if n is None else n, width, tuple(t.shape)))
+    if t.shape[0] > 1 and (t.stride(1) != 1 or t.stride(0) < width):
+        raise ValueError("%s: rows must be contiguous and not overlap: strides %s" % (name, tuple(t.stride())))
+    return t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else width)
+
+
 class DevicePolicy:
     def __init__(self, net, device="cuda"):
         import torch
@@ -228,15 +241,7 @@ class DevicePolicy:
         self.tile = _lib_policy.lib().bmpc_policy_tile()
 
     def _rows(self, name, t, width, n=None):
-        """(address, row stride) of a float64 device tensor (n, width) whose rows are contiguous; any row stride >= width is used in place"""
-        torch = self.torch
-        if t.dtype != torch.float64 or t.device != self.packed.device:
-            raise ValueError("%s: a float64 tensor on %s is expected, got %s on %s" % (name, self.packed.device, t.dtype, t.device))
-        if t.dim() != 2 or t.shape[1] != width or (n is not None and t.shape[0] != n):
-            raise ValueError("%s: expected shape (%s, %d), got %s" % (name, "n" if n is None else n, width, tuple(t.shape)))
-        if t.shape[0] > 1 and (t.stride(1) != 1 or t.stride(0) < width):
-            raise ValueError("%s: rows must be contiguous and not overlap: strides %s" % (name, tuple(t.stride())))
-        return t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else width)
+        return device_rows(self.packed.device, name, t, width, n)
 
     def _launch(self, r):
         if r.n:      # (empty tensors have no address to pass)
